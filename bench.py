@@ -8,12 +8,16 @@ One "step" = one loop body of sync_distributed_train (run_mode.py:180-186):
 `value` = env transitions per second over the whole job (W*T*K*N / wall), measured between
 barrier + torch.cuda.synchronize() brackets, max over ranks.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (for N>1 the driver launches it with torch.distributed.run, one rank per GPU; ranks are
 data-parallel learners: own envs, own minibatches, one RCCL all-reduce of the flat gradient per
 minibatch -> "weak" scaling, global batch = N x 256.)
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = one timed step).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy: rollout_* (its
+transitions), network_* (the parameters after its updates), result_* (learn()'s statistics).
+
+Extra objects on the JSON line (`repeats` always; the others with --full only):
   roofline      the learner's dominant MFMA kernel: flops per launch / its average launch duration, measured live
                 with HIP events on the launch stream (20 back-to-back launches per event pair, so the pair's own
                 ~4 us does not have to be subtracted); `rocprof_avg_us` is the average of the same kernel in the
@@ -50,9 +54,15 @@ import torch
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: FP32 matrix peak
 PROF_REPEAT = 20
+REFERENCE_PRESENT = False  # the CPU legs time the ports (oracle/*_port.py); the reference tree itself is never read here
 
 
-def parse():
+# what only `--full` runs: every measurement after the timed PPO steps
+FULL_ONLY = ("no_roofline", "no_variants", "no_rainbow", "no_hopper", "no_dqn", "no_ppo_atari", "no_apex", "no_cpu_baseline")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
@@ -80,7 +90,17 @@ def parse():
     ap.add_argument("--dqn-steps", type=int, default=3000)
     ap.add_argument("--no-variants", action="store_true", help="skip the PPO side runs (one timestep per exchange; Python collector)")
     ap.add_argument("--repeats", type=int, default=5, help="the timed steps are also reported as this many consecutive chunks (median / min / max)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline PPO steps: roofline pass, acting figures, PPO variants, the "
+                                                       "Rainbow / Hopper / DQN / PPO-Atari / Ape-X legs and the CPU baselines (each still off with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed (its rollout, the "
+                                                                        "network after its updates, its learn() statistics) as DIR/<name>.npy (rank 0)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:  # a plain run: set up, warm up, time the steps, print the line -- nothing else
+        for k in FULL_ONLY:
+            setattr(a, k, True)
+    return a
 
 
 # ------------------------------------------------------------------------------------------------- CPU baselines
@@ -165,10 +185,10 @@ def cpu_baseline(iters, W, T):
         "unit": "env_transitions/s",
         "cores": cores if best is seq else max(cores, W),
         "kind": "port",
-        # the reference tree only exists in the build container (never on a GPU box): what is timed here is the port, which
-        # tests/test_oracle_golden.py pins to the reference's own learn() (losses / weights 1e-6) and oracle/time_reference_vs_port.py
-        # times side by side with the REAL reference where that tree exists (profiles/r03_cpu_reference_vs_port.json)
-        "reference_present": os.path.isdir("/root/reference"),
+        # bench.py never reads the reference tree: what is timed here is the port, which tests/test_oracle_golden.py pins to the
+        # reference's own learn() (losses / weights 1e-6) and oracle/time_reference_vs_port.py times side by side with the REAL
+        # reference where that tree exists (profiles/r03_cpu_reference_vs_port.json)
+        "reference_present": REFERENCE_PRESENT,
         "sample": f"{iters} sync iterations of config.ppo.cartpole (W={W}, T={T}, 3 epochs x 4 minibatches of 256) per variant; value = the faster "
                   f"variant ({'actor processes' if best is procs else 'sequential in-process workers'}): collect {best['collect_ms']:.1f} ms + learn {best['learn_ms']:.1f} ms per iteration",
         "learner_updates_per_s": best["learner_updates_per_s"],
@@ -203,7 +223,7 @@ def rainbow_cpu_reference(updates=8, warm=2):
     for _ in range(updates):
         ag.learn()
     dt = time.perf_counter() - t0
-    return {"value": updates / dt, "unit": "updates/s", "ms_per_update": dt / updates * 1e3, "cores": cores, "kind": "port", "reference_present": os.path.isdir("/root/reference"),
+    return {"value": updates / dt, "unit": "updates/s", "ms_per_update": dt / updates * 1e3, "cores": cores, "kind": "port", "reference_present": REFERENCE_PRESENT,
             "sample": f"{updates} Rainbow.learn() calls (B=32, (4,84,84) uint8, N=1e6 sum tree, {fill} stored), torch CPU {cores} threads"}
 
 
@@ -227,7 +247,7 @@ def hopper_cpu_reference(W=32, T=2048, B=2048, epochs=10):
     t0 = time.perf_counter()
     ag.learn()
     dt = time.perf_counter() - t0
-    return {"value": M / dt, "unit": "transitions/s", "s_per_learn": dt, "cores": cores, "kind": "port", "reference_present": os.path.isdir("/root/reference"),
+    return {"value": M / dt, "unit": "transitions/s", "s_per_learn": dt, "cores": cores, "kind": "port", "reference_present": REFERENCE_PRESENT,
             "sample": f"one PPO.learn() over {M} transitions (W={W}, T={T}), {epochs} epochs x {M // B} minibatches of {B}, S=11, A=3 continuous, hidden 512, torch CPU {cores} threads"}
 
 
@@ -260,7 +280,7 @@ def rainbow_single_mode_cpu(env_steps=48, warm=8):
             n_learn += 1
         state = nxt
     dt = time.perf_counter() - t0
-    return {"value": env_steps / dt, "unit": "env_steps/s", "learner_updates_per_s": n_learn / dt, "cores": cores, "kind": "port", "reference_present": os.path.isdir("/root/reference"),
+    return {"value": env_steps / dt, "unit": "env_steps/s", "learner_updates_per_s": n_learn / dt, "cores": cores, "kind": "port", "reference_present": REFERENCE_PRESENT,
             "sample": f"{env_steps} env steps of the single-mode loop (act B=1 + interact_callback + process; {n_learn} learn() calls), torch CPU {cores} threads"}
 
 
@@ -334,7 +354,7 @@ def dqn_leg(local_rank, steps, want_cpu):
             pstate, n_learn = single_mode_steps(port, penv, pstate, 2100, n)
             dt = time.perf_counter() - t0
             out["cpu_reference"] = {"value": n / dt, "unit": "env_steps/s", "learner_updates_per_s": n_learn / dt, "us_per_step": dt / n * 1e6, "cores": cores, "kind": "port",
-                                    "reference_present": os.path.isdir("/root/reference"),
+                                    "reference_present": REFERENCE_PRESENT,
                                     "sample": f"{n} steps of the same loop on oracle/dqn_port.py (pinned to the reference's learn() by the dqn_h512 fixture), torch CPU {cores} threads"}
             out["x_cpu_reference"] = out["value"] / out["cpu_reference"]["value"]
         except Exception as e:
@@ -782,10 +802,11 @@ class _Ahead:
 
 
 def _self_launch(n):
-    """`python bench.py --gpus N` without a launcher (RANK unset): re-exec under torch.distributed.run, one rank per GPU, rendezvous
-    on 127.0.0.1 at a free port -- the same command line the driver's launcher form uses (the old assert died before
-    touching a GPU when the driver issued `--gpus 8` the way it issues `--gpus 1`)."""
+    """`python bench.py --gpus N` without a launcher (RANK unset): run torch.distributed.run as a child process, one rank per GPU,
+    rendezvous on 127.0.0.1 at a free port -- the same command line the driver's launcher form uses (the old assert died
+    before touching a GPU when the driver issued `--gpus 8` the way it issues `--gpus 1`) -- and leave with its exit status."""
     import socket
+    import subprocess
 
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -795,7 +816,37 @@ def _self_launch(n):
            os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # this pool's hosts only support dmabuf IPC (RCCL needs it across processes)
-    os.execvpe(cmd[0], cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
+
+
+def last_step_outputs(agent, n_rows):
+    """What the timed path computed in its last step, as host arrays: the rollout it collected (rows 0 .. n_rows of the agent's rollout
+    store: learn() only rewinds the store), the network's parameters after the step's updates.  A rollout too large for the dump's budget
+    is thinned to a fixed, seeded sample of its rows."""
+    net = {f"network_{k}": v.detach().float().cpu().numpy() for k, v in agent.network.state_dict().items()}
+    store = agent.memory._store
+    rows = np.arange(n_rows)
+    row_bytes = sum(4 * int(np.prod(store.column(k).shape[1:])) for k in store.names)
+    budget = DUMP_MAX_BYTES // 2 - sum(v.nbytes for v in net.values())
+    if n_rows * row_bytes > budget:
+        rows = np.sort(np.random.RandomState(0).choice(n_rows, budget // row_bytes, replace=False))
+    idx = torch.from_numpy(rows).to(store.device)
+    roll = {f"rollout_{k}": store.column(k)[:n_rows].index_select(0, idx).float().cpu().numpy() for k in store.names}
+    return {**roll, **net}
+
+
+def write_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array: float32 / float64 only, at most DUMP_MAX_BYTES in all."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    bad = {k: str(v.dtype) for k, v in arrays.items() if v.dtype not in (np.float32, np.float64)}
+    if bad:
+        raise ValueError(f"--dump-outputs writes float32 / float64 arrays only: {bad}")
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes is over the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def main():
@@ -950,9 +1001,14 @@ def main():
         out["repeats"] = {"n": len(chunk_ms), "steps_each": [m1 - m0 for m0, m1 in zip([0] + marks[:-1], marks)], "ms_per_step": [round(v, 4) for v in chunk_ms],
                           "median_ms_per_step": med, "min_ms_per_step": min(chunk_ms), "max_ms_per_step": max(chunk_ms), "median_value": world * W * T / (med * 1e-3),
                           "note": "consecutive chunks of the ONE timed region (rank 0 host clock); `value` is the whole region"}
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {**last_step_outputs(agent, W * T), **{f"result_{k}": np.float64(v) for k, v in out["last_result"].items()}})
     variants = {}
 
     def emit():
+        if not args.full:
+            print(json.dumps(out))
+            return
         # the secondary legs' headline numbers once more, compact and LAST on the line: a truncated tail still carries them
         leg = lambda k, f: (out.get(k) or {}).get(f)
         cpu_v = out["cpu_baseline"]["value"] if out.get("cpu_baseline") else None
@@ -991,7 +1047,7 @@ def main():
         threading.Thread(target=watchdog, daemon=True).start()
         return done
 
-    legs_done = guard(float(os.environ.get("JH_BENCH_LEGS_TIMEOUT", "1500")), "legs_error", "a leg after the timed region did not finish in time; the line is printed with what had finished") if world > 1 else None
+    legs_done = guard(float(os.environ.get("JH_BENCH_LEGS_TIMEOUT", "1500")), "legs_error", "a leg after the timed region did not finish in time; the line is printed with what had finished") if world > 1 and args.full else None
     act_us = None
     if hasattr(collector, "stats"):
         st = collector.stats()
@@ -1050,7 +1106,7 @@ def main():
         out["roofline_kernels"] = {k: e for k, e in entries.items() if k != dom}
         out["kernel_us_per_learn"] = {k: round(v, 1) for k, v in sorted(per_learn.items(), key=lambda kv: -kv[1])}
         out["event_timing"] = {"launches_per_event_pair": PROF_REPEAT, "other_kernels_avg_us_incl_event_pair": {k: round(v[1] / v[0] * 1e3, 2) for k, v in prof.items() if v[2] == 0}}
-    if rank == 0 and act_us is not None:
+    if rank == 0 and act_us is not None and args.full:
         rp, src = rocprof_avg_us("jh_act_persist_kernel")
         out["acting"] = {"kernel": "jh_act_persist_kernel", "launches_per_step": 1, "host_us_per_timestep": act_us, "us_per_step": act_us * T,
                          "share_of_step": act_us * T / (ms_per_step * 1e3), "rocprof_avg_us": rp,

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_emits_one_contract_json_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--cpu-baseline-iters", "2", "--rainbow-updates", "20", "--rainbow-filled", "8192",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2", "--cpu-baseline-iters", "2", "--rainbow-updates", "20", "--rainbow-filled", "8192",
                           "--apex-actors", "16", "--apex-updates", "60", "--hopper-iters", "1", "--dqn-steps", "300"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -82,3 +82,29 @@ def test_bench_emits_one_contract_json_line():
     sh = hp["per_gpu_share_of_8"]
     assert "error" not in sh, sh
     assert sh["env_transitions_per_s"] > 0 and "W=4" in sh["workload"] and lg["hopper_per_gpu_share_of_8_env_transitions_s"] == sh["env_transitions_per_s"]
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes the last timed step's rollout, network and statistics."""
+    import numpy as np
+
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "env_transitions/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 8 * 128 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6 and sum(d["repeats"]["steps_each"]) == 3
+    assert not {"roofline", "acting", "variants", "rainbow", "hopper", "dqn", "ppo_atari", "apex", "cpu_baseline", "legs"} & set(d)
+    arrays = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert all(f.endswith(".npy") for f in os.listdir(dump)) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)) for a in arrays.values())
+    assert arrays["rollout_state"].shape == arrays["rollout_next_state"].shape == (8 * 128, 4)
+    assert arrays["rollout_action"].shape == arrays["rollout_reward"].shape == arrays["rollout_done"].shape == (8 * 128, 1)
+    assert set(np.unique(arrays["rollout_action"])) <= {0.0, 1.0} and set(np.unique(arrays["rollout_done"])) <= {0.0, 1.0}
+    assert sum(a.size for k, a in arrays.items() if k.startswith("network_")) == (4 * 512 + 512) + (512 * 512 + 512) + (512 * 2 + 2) + (512 + 1)
+    assert {k[len("result_"):]: float(a) for k, a in arrays.items() if k.startswith("result_")} == d["last_result"]

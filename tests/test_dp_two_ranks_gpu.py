@@ -249,7 +249,7 @@ def test_bench_two_ranks_on_one_gpu_plumbing(tmp_path, launcher, strong):
     env = dict(os.environ, JH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    args = ["--gpus", "2", "--steps", "3", "--warmup", "2", "--no-rainbow", "--no-roofline", "--no-cpu-baseline", "--hopper-iters", "1",
+    args = ["--gpus", "2", "--full", "--steps", "3", "--warmup", "2", "--no-rainbow", "--no-roofline", "--no-cpu-baseline", "--hopper-iters", "1",
             "--apex-actors", "16", "--apex-updates", "240", "--apex-buffer", "200000", "--apex-prefill", "4000"] + (["--strong"] if strong else [])
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
@@ -279,7 +279,7 @@ def test_bench_two_ranks_prints_the_line_when_a_late_leg_hangs():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-rainbow", "--no-hopper", "--no-roofline", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "2", "--no-rainbow", "--no-hopper", "--no-roofline", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

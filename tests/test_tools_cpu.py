@@ -87,7 +87,7 @@ def test_vs_exact_allows_what_fp32_itself_cannot_do_better_and_nothing_more():
         T.vs_exact(exact + 2e-5, exact, exact.clone(), 1e-5, "comparator exact: only the tolerance is left")
 
 
-def test_hopper_cpu_reference_runs_the_ports_learner_at_the_legs_shapes():
+def _bench():
     spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
     b = importlib.util.module_from_spec(spec)
     argv, sys.argv = sys.argv, ["bench.py"]
@@ -95,6 +95,11 @@ def test_hopper_cpu_reference_runs_the_ports_learner_at_the_legs_shapes():
         spec.loader.exec_module(b)
     finally:
         sys.argv = argv
+    return b
+
+
+def test_hopper_cpu_reference_runs_the_ports_learner_at_the_legs_shapes():
+    b = _bench()
     threads = torch.get_num_threads()
     try:
         r = b.hopper_cpu_reference(W=2, T=64, B=32, epochs=2)
@@ -102,3 +107,47 @@ def test_hopper_cpu_reference_runs_the_ports_learner_at_the_legs_shapes():
         torch.set_num_threads(threads)
     assert r["kind"] == "port" and r["unit"] == "transitions/s" and r["value"] > 0 and abs(r["value"] * r["s_per_learn"] - 128) < 1e-6 * 128
     assert "2 epochs x 4 minibatches of 32" in r["sample"]
+
+
+def test_bench_plain_run_leaves_every_other_measurement_to_full():
+    b = _bench()
+    plain = b.parse(["--steps", "7", "--warmup", "2"])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert all(getattr(plain, k) for k in b.FULL_ONLY)
+    full = b.parse(["--full", "--no-dqn", "--dump-outputs", "out"])
+    assert full.full and full.no_dqn and full.dump_outputs == "out" and not any(getattr(full, k) for k in b.FULL_ONLY if k != "no_dqn")
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            b.parse(bad)
+
+
+def test_bench_dump_writes_float_arrays_within_the_budget(tmp_path):
+    b = _bench()
+    arrays = {"rollout_state": np.arange(12, dtype=np.float32).reshape(3, 4), "result_loss": np.float64(0.25)}
+    b.write_outputs(str(tmp_path / "d"), arrays)
+    assert sorted(os.listdir(tmp_path / "d")) == ["result_loss.npy", "rollout_state.npy"]
+    back = np.load(tmp_path / "d" / "rollout_state.npy")
+    assert back.dtype == np.float32 and np.array_equal(back, arrays["rollout_state"]) and float(np.load(tmp_path / "d" / "result_loss.npy")) == 0.25
+    with pytest.raises(ValueError):
+        b.write_outputs(str(tmp_path / "e"), {"action": np.zeros(3, np.int64)})
+    with pytest.raises(ValueError):
+        b.write_outputs(str(tmp_path / "f"), {"big": np.zeros(b.DUMP_MAX_BYTES // 8 + 1, np.float64)})
+    assert not os.path.exists(tmp_path / "e") and not os.path.exists(tmp_path / "f")
+
+
+def test_bench_dump_thins_a_rollout_over_the_budget_to_a_seeded_sample(monkeypatch):
+    """last_step_outputs on a stand-in agent (host tensors): the whole rollout when it fits, the same fixed sample of rows on every call when not."""
+    from types import SimpleNamespace
+
+    b = _bench()
+    cols = {"state": torch.arange(400.0).reshape(100, 4), "action": torch.arange(100, dtype=torch.int64).reshape(100, 1), "done": torch.ones(100, 1, dtype=torch.uint8)}
+    store = SimpleNamespace(names=list(cols), device=torch.device("cpu"), column=cols.__getitem__)
+    agent = SimpleNamespace(memory=SimpleNamespace(_store=store), network=torch.nn.Linear(3, 2))
+    whole = b.last_step_outputs(agent, 60)
+    assert np.array_equal(whole["rollout_state"], cols["state"][:60].numpy()) and whole["rollout_action"].dtype == np.float32
+    assert whole["network_weight"].shape == (2, 3) and whole["rollout_done"].shape == (60, 1)
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 2 * (32 + 40 * 24))  # the network's 32 bytes + 40 rows of 24 bytes, in half the budget
+    a, c = b.last_step_outputs(agent, 60), b.last_step_outputs(agent, 60)
+    rows = a["rollout_action"][:, 0].astype(int)
+    assert len(rows) == 40 and np.all(np.diff(rows) > 0) and rows.max() < 60 and np.array_equal(a["rollout_state"], c["rollout_state"])
+    assert np.array_equal(a["rollout_state"], cols["state"].numpy()[rows])
