@@ -1,14 +1,14 @@
-// Native sync-mode rollout collection for PPO (discrete policy on CartPole, continuous policy on the synthetic
-// control env) -- the whole of
-// DistributedManager.run + Actor.run (manager/distributed_manager.py:26-31,76-92) for W workers and
-// T steps in ONE call, no Python per step:
-//   for t in 0..T-1:
-//     jh_pponet_act_discrete      -> observations into device-mapped pinned memory, ONE launch (fused
-//                                    MLP forward, partial heads + per-tile flags written back into
-//                                    pinned memory), host polls the flags and samples the actions
-//     jh_cartpole_step            -> host physics for all W envs, auto-reset
-//     transition (s, a, r, s', d) -> pinned staging slab of the rollout store, worker-major
-//   one hipMemcpyAsync per column moves the W*T transitions into the GPU-resident store.
+// Native sync-mode rollout collection for PPO: DistributedManager.run + Actor.run (manager/distributed_manager.py:26-31,76-92)
+// for W host envs (behind a jh_env_vtbl) and T timesteps in ONE call, no Python per step.  A run is
+//   run_prepare  staging rows of the rollout store, the capture slab, the persistent acting kernel (jh_persist.hip)
+//   run_loop     the collector's persistent form, fixed when it is created:
+//                  run_loop_lookahead  forkable envs with two actions: two timesteps per exchange with the kernel
+//                  run_loop_split      32 rows of a built-in env: two independent exchanges of 16 per timestep
+//                  run_loop_exchange   otherwise: one exchange of the W rows per timestep
+//                then run_loop_per_launch, one acting launch per timestep, for the timesteps the form did not complete (all of
+//                them when the kernel is unavailable, the rest when it gave up)
+//   run_commit   ONE launch moves the staged rows, the captured heads / values and the ride-along copies to the device
+// The forms share the per-timestep bookkeeping (sampling, capture, transition rows, error handling), not their schedules.
 // Weights never leave HBM (the acting network IS the learner's), so BaseAgent.sync_out / sync_in
 // (core/agent/base.py:75-85) and the per-iteration state_dict broadcast disappear.
 #include <chrono>
@@ -26,7 +26,6 @@ void jh_persist_publish_rows(jh_persist* p, int r0, int r1, const float* h_obs, 
 int jh_persist_collect_range(jh_persist* p, int r0, int n_rows, unsigned tag, float* h_heads);
 int jh_persist_collect(jh_persist* p, int W, unsigned tag, float* h_heads);
 int jh_persist_collect_rows(jh_persist* p, const int* rows, int n_rows, unsigned tag, float* h_heads);
-int jh_persist_heads(const jh_persist* p);
 void jh_persist_abort(jh_persist* p);
 bool jh_persist_gave_up(const jh_persist* p);
 void jh_persist_dump_debug(jh_persist* p, int T);
@@ -45,8 +44,7 @@ struct Level {  // 2^k W forked envs: row 2 i + a = env i of the level above aft
   }
 };
 // dst rows 2 i + a <- src row i stepped with action a (auto-reset included: the row then holds the reset state)
-// -> the env table's first error (jh_env_vtbl: obs / step return a negative JH_ERR_* and the run stops -- ADVICE r5: the speculative
-// steps dropped it, and a failing user env kept feeding stale rows into the store)
+// -> the env table's first error (jh_env_vtbl: obs / step return a negative JH_ERR_* and the run stops)
 inline int fork_step(const jh_env_vtbl& vt, Level& dst, const void* src, int n_src) {
   for (int i = 0; i < n_src; ++i) { vt.copy_row(dst.env, 2 * i, src, i); vt.copy_row(dst.env, 2 * i + 1, src, i); }
   int rc = vt.step(dst.env, 0, 2 * n_src, dst.act.data(), dst.next.data(), dst.rw.data(), dst.dn.data());
@@ -66,25 +64,27 @@ inline void copy_level_row(const jh_env_vtbl& vt, Level& d, int di, const Level&
 struct jh_collector {
   jh_ctx* ctx = nullptr;
   jh_pponet* net = nullptr;
-  // the host envs behind a table of functions (include/jorldy_hip.h: jh_env_vtbl; round 5): the two built-in envs
+  // the host envs behind a table of functions (include/jorldy_hip.h: jh_env_vtbl): the two built-in envs
   // (jh_cartpole_*, jh_control_*) are two such tables, a C user plugs any other with jh_collector_create_env
   jh_env_vtbl vt{};
   void* env = nullptr;
   jh_store* store = nullptr;
   int W = 0, S = 0, A = 0;
+  int no = 0;  // raw heads per row of `heads`, the acting kernel's layout: A logits | A mu + A log_std, then V
   bool cont = false;
   int col_state = 0, col_action = 1, col_reward = 2, col_next = 3, col_done = 4;
   std::vector<float> obs, next_obs, reward, heads, act_f;
   std::vector<int64_t> act_i;
   std::vector<uint8_t> done;
-  double dbg_publish = 0.0, dbg_wait = 0.0;  // JH_COLLECT_DEBUG
+  bool dbg = false, dbg_persist = false;     // JH_COLLECT_DEBUG, JH_PERSIST_DEBUG (read at creation)
+  double dbg_publish = 0.0, dbg_wait = 0.0;  // JH_COLLECT_DEBUG, run_loop_exchange
   long dbg_n = 0;
   jh_persist* persist = nullptr;  // null: one launch per timestep
   int mode = 1;                   // 1: persistent acting kernel (default), 0: launch per step (JH_COLLECT_PERSISTENT=0)
   // lookahead = 2 (discrete two-action envs that can be forked on the host, 3 W <= 32 rows): every PCIe round trip carries each
   // env's state AND both successor states, and serves two timesteps (run_loop_lookahead).  1: one timestep per round trip.
   int lookahead = 1;
-  // round 6: 32 rows of an env that steps row ranges (the built-in envs) are exchanged as two INDEPENDENT halves of 16 (run_loop_split): one half's round
+  // 32 rows of an env that steps row ranges (the built-in envs) are exchanged as two INDEPENDENT halves of 16 (run_loop_split): one half's round
   // trip through the acting kernel runs under the other half's sampling, env steps and bookkeeping.  JH_COLLECT_SPLIT=0: one exchange of 32 rows.
   bool split = false;
   Level lv[4];  // L1, L2, L3 and the one-step exchange's scratch level
@@ -131,6 +131,9 @@ static int collector_create(jh_ctx* ctx, jh_pponet* net, const jh_env_vtbl* vt, 
   jh_collector* c = new jh_collector();
   c->ctx = ctx; c->net = net; c->vt = *vt; c->env = env; c->store = store; c->W = W; c->S = S; c->A = A; c->cont = cont;
   c->col_state = cols[0]; c->col_action = cols[1]; c->col_reward = cols[2]; c->col_next = cols[3]; c->col_done = cols[4];
+  c->no = (cont ? 2 * A : A) + 1;
+  c->dbg = getenv("JH_COLLECT_DEBUG") != nullptr;
+  c->dbg_persist = getenv("JH_PERSIST_DEBUG") != nullptr;
   if (const char* e = getenv("JH_COLLECT_PERSISTENT")) c->mode = atoi(e);
   if (c->mode == 1 && W <= 32 && W * S <= 512) {  // jh_persist.hip: two row tiles of 16, up to four poll instructions of 128 observation granules
     if (jh_persist_create(net, &c->persist) != JH_OK) c->persist = nullptr;  // unsupported width: one launch per step
@@ -158,7 +161,7 @@ static int collector_create(jh_ctx* ctx, jh_pponet* net, const jh_env_vtbl* vt, 
   c->act_f.resize((size_t)A * W);
   c->reward.resize(W);
   c->done.resize(W);
-  c->heads.resize(16 * (size_t)W);
+  c->heads.resize((size_t)c->no * W);
   run_state_alloc(c);
   *out = c;
   return JH_OK;
@@ -292,9 +295,17 @@ struct RunState {
   bool active = false, cap = false, persistent = false, early = false;
   int T = 0, steps = 0;
   int64_t n = 0;
-  void* cols[16] = {};
+  // the store's staging columns: state, next state, reward, done, action (int64 for a discrete policy, float [A] for a continuous one)
+  float *st = nullptr, *ns = nullptr, *rw = nullptr;
+  uint8_t* dn = nullptr;
+  int64_t* ac_i = nullptr;
+  float* ac_f = nullptr;
   jh_pinned_slab* cap_slab = nullptr;
   float *ch0 = nullptr, *ch1 = nullptr, *cv = nullptr, *cnv = nullptr;
+  // test hook (tests/test_agents_gpu.py): JH_COLLECT_TEST_STALL="<timestep>,<half>" makes run_loop_split sit idle for 0.35 s in front of
+  // that half's read, which is what a stalled environment looks like to the acting kernel (it gives up after ~0.2 s without
+  // observations): exercises the hand-over to one launch per step
+  int stall_t = -1, stall_h = -1;
 };
 static RunState& run_state(jh_collector* c) { return *static_cast<RunState*>(c->run); }
 static void run_state_alloc(jh_collector* c) { c->run = new RunState(); }
@@ -349,8 +360,16 @@ static int run_prepare(jh_collector* c, int T, hipStream_t st) {
   r.n = (int64_t)W * T;
   r.cap = c->cap_v && c->cap_rows == r.n;
   r.steps = collector_steps(c, T);
-  int rc = jh_store_stage_begin(c->store, r.n, r.cols);
+  if (const char* e = getenv("JH_COLLECT_TEST_STALL")) (void)sscanf(e, "%d,%d", &r.stall_t, &r.stall_h);
+  void* cols[16] = {};
+  int rc = jh_store_stage_begin(c->store, r.n, cols);
   if (rc) return rc;
+  r.st = (float*)cols[c->col_state];
+  r.ns = (float*)cols[c->col_next];
+  r.rw = (float*)cols[c->col_reward];
+  r.dn = (uint8_t*)cols[c->col_done];
+  r.ac_i = (int64_t*)cols[c->col_action];
+  r.ac_f = (float*)cols[c->col_action];
   // captured block in pinned, device-mapped memory: [h0 n*A | h1 n*A (continuous) | value n | next_value n]
   if (r.cap) {
     const size_t fl = (size_t)r.n * A * (c->cont ? 2 : 1) + 2 * (size_t)r.n;
@@ -378,133 +397,140 @@ static int run_prepare(jh_collector* c, int T, hipStream_t st) {
   return JH_OK;
 }
 
-static int run_loop_lookahead(jh_collector* c, int training, hipStream_t stream_h, int* t_done);
-static int run_loop_split(jh_collector* c, int training, hipStream_t stream_h, int* t_done);
+// ---- the per-timestep bookkeeping the forms below share (their schedules differ, so each form keeps its own loop)
+using Clock = std::chrono::steady_clock;
+static double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
 
-// The host loop.  Returns the first error; the caller commits either way.
-static int run_loop(jh_collector* c, int training, hipStream_t stream_h) {
-  RunState& r = run_state(c);
-  const int W = c->W, S = c->S, A = c->A, T = r.T, steps = T + (r.cap ? 1 : 0);
-  const bool cap = r.cap;
-  int t_begin = 0;
-  if (r.persistent && c->lookahead == 2) {
-    const int rc_la = run_loop_lookahead(c, training, stream_h, &t_begin);
-    if (rc_la != JH_OK || t_begin >= steps) return rc_la;
-    // the acting kernel gave up in the middle of the run: finish the remaining timesteps with one launch per step (below)
-    r.persistent = false;
-  } else if (r.persistent && c->split) {
-    const int rc_sp = run_loop_split(c, training, stream_h, &t_begin);
-    if (rc_sp != JH_OK || t_begin >= steps) return rc_sp;
-    r.persistent = false;  // (the same)
+// host seconds spent acting at timestep t (jh_collector_stats / _stats_detail): the first timestep and the value-only query are also
+// counted on their own
+static void count_act(jh_collector* c, const RunState& r, int t, double dt) {
+  c->t_act += dt;
+  if (t == r.T) c->t_extra += dt;
+  else if (t == 0) c->t_first += dt;
+}
+
+// the sampled action of row w in the collector's per-timestep buffers: int64 (discrete) or float [A] (continuous)
+static const void* act_of(const jh_collector* c, int w) {
+  return c->cont ? (const void*)(c->act_f.data() + (size_t)c->A * w) : (const void*)(c->act_i.data() + w);
+}
+
+// a_t of row w from its raw heads z, under the current sampling step (net->act_ctr)
+static void sample_row(jh_collector* c, const float* z, int w, int training) {
+  if (c->cont) jh_sample_continuous(c->net, z, w, training, c->act_f.data() + (size_t)w * c->A);
+  else c->act_i[w] = jh_sample_discrete(c->net, z, w, training);
+}
+
+// acting-time capture of row w at timestep t from its raw heads z: V(state_t) is also V(next_state_{t-1}) (masked by done_{t-1} in
+// GAE); the value-only query (t == T) contributes only that
+static void capture_row(const jh_collector* c, const RunState& r, int w, int t, const float* z) {
+  if (!r.cap) return;
+  const int A = c->A;
+  const float v = z[c->no - 1];
+  if (t > 0) r.cnv[(size_t)w * r.T + (t - 1)] = v;
+  if (t == r.T) return;
+  const size_t row = (size_t)w * r.T + t;
+  r.cv[row] = v;
+  memcpy(r.ch0 + row * A, z, sizeof(float) * A);
+  if (c->cont) memcpy(r.ch1 + row * A, z + A, sizeof(float) * A);
+}
+
+// transition (s, a, r, s', d) into staging row w * T + t (worker-major: w0 t0..tT-1, w1 ...  distributed_manager.py:30)
+static void store_row(const jh_collector* c, const RunState& r, int w, int t, const float* s, const float* s_next, const void* a, float rw, uint8_t dn) {
+  const int S = c->S, A = c->A;
+  const size_t row = (size_t)w * r.T + t;
+  memcpy(r.st + S * row, s, sizeof(float) * S);
+  memcpy(r.ns + S * row, s_next, sizeof(float) * S);
+  if (c->cont) memcpy(r.ac_f + A * row, a, sizeof(float) * A);
+  else r.ac_i[row] = *(const int64_t*)a;
+  r.rw[row] = rw;
+  r.dn[row] = dn;
+}
+
+// env rows w0 .. w1-1 take their sampled actions; their transitions go to the staging rows of timestep t.  -> the env's status
+static int step_rows(jh_collector* c, const RunState& r, int w0, int w1, int t) {
+  const int rc = c->vt.step(c->env, w0, w1, act_of(c, 0), c->next_obs.data(), c->reward.data(), c->done.data());
+  if (rc) return rc;
+  const size_t S = (size_t)c->S;
+  for (int w = w0; w < w1; ++w) store_row(c, r, w, t, &c->obs[S * w], &c->next_obs[S * w], act_of(c, w), c->reward[w], c->done[w]);
+  return JH_OK;
+}
+
+// One acting launch (jh_pponet_act_*) over rows r0 .. r0+n-1 of c->obs.  The launch samples those rows into c->act_* under ITS row
+// keys 0 .. n-1 and counts a sampling step; their raw heads go to c->heads in the persistent kernel's per-row layout
+static int act_launch(jh_collector* c, int r0, int n, int training, hipStream_t st) {
+  const int A = c->A, no = c->no;
+  std::vector<float> mu((size_t)n * A), ls((size_t)n * A), v(n);
+  const float* obs = c->obs.data() + (size_t)r0 * c->S;
+  const int rc = c->cont ? jh_pponet_act_continuous(c->net, n, obs, c->act_f.data() + (size_t)r0 * A, mu.data(), ls.data(), v.data(), training, (jh_stream)st)
+                         : jh_pponet_act_discrete(c->net, n, obs, c->act_i.data() + r0, mu.data(), v.data(), training, (jh_stream)st);
+  if (rc) return rc;
+  for (int k = 0; k < n; ++k) {  // [n][A] mu | [n][A] log_std | [n] V  ->  per row [mu A | log_std A | V]
+    float* z = c->heads.data() + (size_t)(r0 + k) * no;
+    memcpy(z, &mu[(size_t)k * A], sizeof(float) * A);
+    if (c->cont) memcpy(z + A, &ls[(size_t)k * A], sizeof(float) * A);
+    z[no - 1] = v[k];
   }
-  jh_stream stream = (jh_stream)stream_h;
-  int rc = JH_OK;
-  float *ch0 = r.ch0, *ch1 = r.ch1, *cv = r.cv, *cnv = r.cnv;
-  float* st = (float*)r.cols[c->col_state];
-  int64_t* ac_i = (int64_t*)r.cols[c->col_action];
-  float* ac_f = (float*)r.cols[c->col_action];
-  float* rw = (float*)r.cols[c->col_reward];
-  float* ns = (float*)r.cols[c->col_next];
-  uint8_t* dn = (uint8_t*)r.cols[c->col_done];
-  bool persistent = r.persistent;
-  const int no = c->persist ? jh_persist_heads(c->persist) : 0;  // policy heads + value
-  const int n_pol = c->cont ? 2 * A : A;
-  std::vector<float> val(W), lg((size_t)W * 2 * A);
-  for (int t = t_begin; t < steps; ++t) {
+  return JH_OK;
+}
+
+// An env error inside a persistent form: stop the acting kernel (it would poll for ~0.2 s otherwise) and return the env's status -- the
+// caller's commit carries the abort value, nothing of this run reaches the store
+static int env_failed(jh_collector* c, int rc) {
+  jh_persist_abort(c->persist);
+  return rc;
+}
+
+// The persistent acting kernel gave up at timestep t (no observations for ~0.2 s; it exits by itself).  JH_OK: the stream is drained,
+// *t_done = t and the run finishes with one launch per step -- impossible when the commit launch and the learner are already queued
+// behind the kernel on this stream (jh_collector_begin)
+static int kernel_gave_up(jh_collector* c, const RunState& r, int t, hipStream_t st, int* t_done) {
+  jh_persist_abort(c->persist);
+  if (r.early)
+    return jh_fail(JH_ERR_STATE, "the persistent acting kernel gave up at step %d of a run whose commit was enqueued ahead (jh_collector_begin): "
+                                 "no observations for ~0.2 s; use jh_collector_run for environments that may stall", t);
+  JH_HIP(hipStreamSynchronize(st));
+  *t_done = t;
+  return JH_OK;
+}
+
+// ---- the persistent forms.  Each returns the first error, or JH_OK with *t_done = the timesteps it completed (incl. the value-only
+// query of a capturing run): all of them, or fewer when the kernel gave up.
+
+// One exchange of the W rows per timestep.
+static int run_loop_exchange(jh_collector* c, int training, hipStream_t st, int* t_done) {
+  RunState& r = run_state(c);
+  const int W = c->W, T = r.T, steps = T + (r.cap ? 1 : 0);
+  for (int t = 0; t < steps; ++t) {
     const bool extra = t == T;  // capture: one value-only query of the states the rollout ended in
     // current state of every env (reset state where it just finished)
-    rc = c->vt.obs(c->env, 0, W, c->obs.data());
-    if (rc) {
-      if (persistent) jh_persist_abort(c->persist);
-      return rc;
+    int rc = c->vt.obs(c->env, 0, W, c->obs.data());
+    if (rc) return env_failed(c, rc);
+    const auto t0 = Clock::now();
+    const unsigned tag = jh_persist_publish(c->persist, W, c->obs.data());
+    const auto tp = c->dbg ? Clock::now() : t0;
+    rc = jh_persist_collect(c->persist, W, tag, c->heads.data());
+    if (c->dbg) {  // JH_COLLECT_DEBUG: publish / wait + read of an exchange, summed per collector (printed every 4th run below)
+      c->dbg_publish += secs(t0, tp);
+      c->dbg_wait += secs(tp, Clock::now());
+      c->dbg_n += 1;
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    if (persistent) {
-      static const bool dbg1 = getenv("JH_COLLECT_DEBUG") != nullptr;
-      const auto d0 = dbg1 ? std::chrono::steady_clock::now() : t0;
-      const unsigned tag = jh_persist_publish(c->persist, W, c->obs.data());
-      const auto d1 = dbg1 ? std::chrono::steady_clock::now() : t0;
-      rc = jh_persist_collect(c->persist, W, tag, c->heads.data());
-      if (dbg1) {  // JH_COLLECT_DEBUG=1: publish / wait + read of an exchange, summed per collector (printed every 16th run below)
-        const auto d2 = std::chrono::steady_clock::now();
-        c->dbg_publish += std::chrono::duration<double>(d1 - d0).count();
-        c->dbg_wait += std::chrono::duration<double>(d2 - d1).count();
-        c->dbg_n += 1;
-      }
-      if (rc) {  // the kernel gave up (it exits by itself)
-        jh_persist_abort(c->persist);
-        if (r.early)  // the commit launch and the learner are already queued behind it on this stream: no per-step launches possible
-          return jh_fail(JH_ERR_STATE, "the persistent acting kernel gave up at step %d of a run whose commit was enqueued ahead (jh_collector_begin): "
-                                       "no observations for ~0.2 s; use jh_collector_run for environments that may stall", t);
-        JH_HIP(hipStreamSynchronize(stream_h));  // finish this rollout with per-step launches
-        persistent = false;
-      } else {
-        for (int w = 0; w < W; ++w) {
-          const float* hz = c->heads.data() + (size_t)w * no;
-          if (!extra) {
-            if (c->cont) jh_sample_continuous(c->net, hz, w, training, c->act_f.data() + (size_t)w * A);
-            else c->act_i[w] = jh_sample_discrete(c->net, hz, w, training);
-          }
-          memcpy(lg.data() + (size_t)w * n_pol, hz, sizeof(float) * n_pol);
-          val[w] = hz[no - 1];
-        }
-        if (!extra) c->net->act_ctr += 1;
-      }
-    }
-    if (!persistent) {
-      if (r.early) return jh_fail(JH_ERR_STATE, "jh_collector_begin needs the persistent acting kernel (W <= 32, W * S <= 512, JH_COLLECT_PERSISTENT != 0)");
-      // (the per-step launch samples even for the value-only query; its actions are not used)
-      rc = c->cont ? jh_pponet_act_continuous(c->net, W, c->obs.data(), c->act_f.data(), lg.data(), lg.data() + (size_t)W * A, val.data(), training, stream)
-                   : jh_pponet_act_discrete(c->net, W, c->obs.data(), c->act_i.data(), lg.data(), val.data(), training, stream);
-      if (rc) return rc;
-      if (extra) c->net->act_ctr -= 1;  // the value-only query must not consume a sampling step: same action stream with and without capture
-      if (c->cont) {  // [W][A] mu | [W][A] log_std  ->  per-row [mu A | log_std A] like the persistent path
-        std::vector<float> tmp(lg);
-        for (int w = 0; w < W; ++w) {
-          memcpy(lg.data() + (size_t)w * 2 * A, tmp.data() + (size_t)w * A, sizeof(float) * A);
-          memcpy(lg.data() + (size_t)w * 2 * A + A, tmp.data() + (size_t)W * A + (size_t)w * A, sizeof(float) * A);
-        }
-      }
-    }
-    if (cap) {
-      for (int w = 0; w < W; ++w) {
-        if (t > 0) cnv[(size_t)w * T + (t - 1)] = val[w];  // V(next_state_{t-1}) = V(state_t)  (masked by done_{t-1} in GAE)
-        if (!extra) {
-          const size_t row = (size_t)w * T + t;
-          cv[row] = val[w];
-          memcpy(ch0 + row * A, lg.data() + (size_t)w * n_pol, sizeof(float) * A);
-          if (c->cont) memcpy(ch1 + row * A, lg.data() + (size_t)w * n_pol + A, sizeof(float) * A);
-        }
-      }
-    }
-    if (extra) {
-      const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      c->t_act += dt;
-      c->t_extra += dt;
-      break;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    if (t == 0) c->t_first += std::chrono::duration<double>(t1 - t0).count();
-    rc = c->vt.step(c->env, 0, W, c->cont ? (const void*)c->act_f.data() : (const void*)c->act_i.data(), c->next_obs.data(), c->reward.data(), c->done.data());
-    if (rc) {
-      if (persistent) jh_persist_abort(c->persist);
-      return rc;
-    }
+    if (rc) return kernel_gave_up(c, r, t, st, t_done);
     for (int w = 0; w < W; ++w) {
-      const size_t row = (size_t)w * T + t;  // worker-major: w0 t0..tT-1, w1 ...  (distributed_manager.py:30)
-      memcpy(st + S * row, c->obs.data() + (size_t)S * w, sizeof(float) * S);
-      memcpy(ns + S * row, c->next_obs.data() + (size_t)S * w, sizeof(float) * S);
-      if (c->cont) memcpy(ac_f + A * row, c->act_f.data() + (size_t)A * w, sizeof(float) * A);
-      else ac_i[row] = c->act_i[w];
-      rw[row] = c->reward[w];
-      dn[row] = c->done[w];
+      const float* z = c->heads.data() + (size_t)w * c->no;
+      if (!extra) sample_row(c, z, w, training);
+      capture_row(c, r, w, t, z);
     }
-    const auto t2 = std::chrono::steady_clock::now();
-    c->t_act += std::chrono::duration<double>(t1 - t0).count();
-    c->t_env += std::chrono::duration<double>(t2 - t1).count();
+    if (!extra) c->net->act_ctr += 1;
+    const auto t1 = Clock::now();
+    count_act(c, r, t, secs(t0, t1));
+    if (extra) break;
+    rc = step_rows(c, r, 0, W, t);
+    if (rc) return env_failed(c, rc);
+    c->t_env += secs(t1, Clock::now());
     c->steps += 1;
   }
-  if (persistent && getenv("JH_PERSIST_DEBUG") && (c->runs % 16) == 15) jh_persist_dump_debug(c->persist, T);
+  *t_done = steps;
+  if (c->dbg_persist && (c->runs % 16) == 15) jh_persist_dump_debug(c->persist, T);
   if (c->dbg_n > 0 && (c->runs % 4) == 3) {
     fprintf(stderr, "[jh_collect] one timestep per exchange, per step: publish %.2f us, wait + read of the heads %.2f us (sampling + bookkeeping + env step: the rest of act / env)\n",
             c->dbg_publish / c->dbg_n * 1e6, c->dbg_wait / c->dbg_n * 1e6);
@@ -514,115 +540,66 @@ static int run_loop(jh_collector* c, int training, hipStream_t stream_h) {
   return JH_OK;
 }
 
-
-// ---- split: the 32 rows of a timestep as two INDEPENDENT exchanges of 16 (round 6).
+// ---- split: the 32 rows of a timestep as two INDEPENDENT exchanges of 16.
 // One timestep of config.ppo.mujoco's 32 workers was exchange (19.4 us: publication, PCIe polling, 3.9 us of kernel, 48 KB of partial heads back, the host's
 // sampling) + env steps and bookkeeping (11 us), one after the other.  The acting kernel's two row tiles are two sets of workgroups that never talk to each
 // other, so with tags per row tile (jh_persist.hip: PersistArgs::split) the host runs them out of phase: while half A's observations are on their way through
 // the kernel, the host samples, steps and stores half B, publishes B's next observations, and only then comes back for A's heads.  Nothing is speculated: the
 // same rows go through the same arithmetic (a row's position inside its tile is unchanged), the sampling stream is keyed by (seed, timestep, row), every env
 // row advances on its own state -- the rollout, the captured heads / values and every stored transition are bit-identical to the one-exchange path (tested).
-// *t_done: timesteps completed (incl. the value-only query); < steps only when the kernel gave up (the caller finishes with one launch per step).
-static int run_loop_split(jh_collector* c, int training, hipStream_t stream_h, int* t_done) {
+static int run_loop_split(jh_collector* c, int training, hipStream_t st, int* t_done) {
   RunState& r = run_state(c);
-  const int W = c->W, S = c->S, A = c->A, T = r.T, steps = T + (r.cap ? 1 : 0), HR = 16;
-  const bool cap = r.cap;
-  float *ch0 = r.ch0, *ch1 = r.ch1, *cv = r.cv, *cnv = r.cnv;
-  float* st = (float*)r.cols[c->col_state];
-  int64_t* ac_i = (int64_t*)r.cols[c->col_action];
-  float* ac_f = (float*)r.cols[c->col_action];
-  float* rw = (float*)r.cols[c->col_reward];
-  float* ns = (float*)r.cols[c->col_next];
-  uint8_t* dn = (uint8_t*)r.cols[c->col_done];
-  const int no = jh_persist_heads(c->persist);
+  const int W = c->W, T = r.T, steps = T + (r.cap ? 1 : 0), HR = 16;
   const unsigned base = jh_persist_seq(c->persist);  // the kernel's tags are base + 1 .. base + steps, for each half on its own
   bool dead = false;  // the kernel gave up while half 1 of a timestep was owed: that half is finished by hand, then the per-step path takes over
-  // test hook (tests/test_agents_gpu.py): JH_COLLECT_TEST_STALL="<timestep>,<half>" makes the host sit idle for 0.35 s in front of that half's read, which is what a
-  // stalled environment looks like to the acting kernel (it gives up after ~0.2 s without observations): exercises the hand-over to one launch per step
-  int stall_t = -1, stall_h = -1;
-  if (const char* e = getenv("JH_COLLECT_TEST_STALL")) (void)sscanf(e, "%d,%d", &stall_t, &stall_h);
-  *t_done = 0;
   int rc = c->vt.obs(c->env, 0, W, c->obs.data());
-  if (rc) { jh_persist_abort(c->persist); return rc; }
+  if (rc) return env_failed(c, rc);
   for (int h = 0; h < 2; ++h) jh_persist_publish_rows(c->persist, h * HR, (h + 1) * HR, c->obs.data(), base + 1);
   for (int t = 0; t < steps; ++t) {
     const bool extra = t == T;  // capture: one value-only query of the states the rollout ended in
     for (int h = 0; h < 2; ++h) {
       const int r0 = h * HR, r1 = r0 + HR;
-      const auto t0 = std::chrono::steady_clock::now();
-      if (t == stall_t && h == stall_h) {
+      const auto t0 = Clock::now();
+      if (t == r.stall_t && h == r.stall_h) {
         // (the OTHER half's workgroups are the ones starved: this half's observations are out already)
-        while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.35) {}
+        while (secs(t0, Clock::now()) < 0.35) {}
       }
-      rc = jh_persist_collect_range(c->persist, r0, HR, base + (unsigned)t + 1, c->heads.data() + (size_t)r0 * no);
-      if (rc) {  // the kernel gave up (it exits by itself)
-        jh_persist_abort(c->persist);
-        if (r.early)
-          return jh_fail(JH_ERR_STATE, "the persistent acting kernel gave up at step %d of a run whose commit was enqueued ahead (jh_collector_begin): "
-                                       "no observations for ~0.2 s; use jh_collector_run for environments that may stall", t);
-        JH_HIP(hipStreamSynchronize(stream_h));
-        if (h == 0) { *t_done = t; return JH_OK; }  // both halves stand at step t: the per-step path takes over from here
+      rc = jh_persist_collect_range(c->persist, r0, HR, base + (unsigned)t + 1, c->heads.data() + (size_t)r0 * c->no);
+      if (rc) {
+        rc = kernel_gave_up(c, r, t, st, t_done);
+        if (rc || h == 0) return rc;  // (both halves stand at step t: the per-step path takes over from here)
         // half 1 of step t is still owed (half 0 has moved on): its raw heads from one launch over its 16 rows, sampled below with the rows' own stream keys
-        std::vector<float> mu((size_t)HR * A), ls((size_t)HR * A), vv(HR);
-        std::vector<float> af((size_t)HR * A);
-        std::vector<int64_t> ai(HR);
         const uint64_t ctr = c->net->act_ctr;
-        rc = c->cont ? jh_pponet_act_continuous(c->net, HR, c->obs.data() + (size_t)r0 * S, af.data(), mu.data(), ls.data(), vv.data(), 0, (jh_stream)stream_h)
-                     : jh_pponet_act_discrete(c->net, HR, c->obs.data() + (size_t)r0 * S, ai.data(), mu.data(), vv.data(), 0, (jh_stream)stream_h);
+        rc = act_launch(c, r0, HR, 0, st);
         if (rc) return rc;
         c->net->act_ctr = ctr;  // (the launch counted a sampling step; this timestep's count comes below)
         dead = true;
-        for (int k = 0; k < HR; ++k) {
-          float* hz = c->heads.data() + (size_t)(r0 + k) * no;
-          memcpy(hz, mu.data() + (size_t)k * A, sizeof(float) * A);
-          if (c->cont) memcpy(hz + A, ls.data() + (size_t)k * A, sizeof(float) * A);
-          hz[no - 1] = vv[k];
-        }
       }
       for (int w = r0; w < r1; ++w) {
-        const float* hz = c->heads.data() + (size_t)w * no;
-        if (!extra) {
-          if (c->cont) jh_sample_continuous(c->net, hz, w, training, c->act_f.data() + (size_t)w * A);
-          else c->act_i[w] = jh_sample_discrete(c->net, hz, w, training);
-        }
-        if (cap) {
-          const float val = hz[no - 1];
-          if (t > 0) cnv[(size_t)w * T + (t - 1)] = val;  // V(next_state_{t-1}) = V(state_t)  (masked by done_{t-1} in GAE)
-          if (!extra) {
-            const size_t row = (size_t)w * T + t;
-            cv[row] = val;
-            memcpy(ch0 + row * A, hz, sizeof(float) * A);
-            if (c->cont) memcpy(ch1 + row * A, hz + A, sizeof(float) * A);
-          }
-        }
+        const float* z = c->heads.data() + (size_t)w * c->no;
+        if (!extra) sample_row(c, z, w, training);
+        capture_row(c, r, w, t, z);
       }
       if (h == 1 && !extra) c->net->act_ctr += 1;  // one sampling step per TIMESTEP: both halves drew under the same counter
-      const auto t1 = std::chrono::steady_clock::now();
-      c->t_act += std::chrono::duration<double>(t1 - t0).count();
-      if (extra) { c->t_extra += std::chrono::duration<double>(t1 - t0).count(); continue; }
-      if (t == 0) c->t_first += std::chrono::duration<double>(t1 - t0).count();
-      rc = c->vt.step(c->env, r0, r1, c->cont ? (const void*)c->act_f.data() : (const void*)c->act_i.data(), c->next_obs.data(), c->reward.data(), c->done.data());
-      if (rc) { jh_persist_abort(c->persist); return rc; }
-      for (int w = r0; w < r1; ++w) {
-        const size_t row = (size_t)w * T + t;  // worker-major: w0 t0..tT-1, w1 ...  (distributed_manager.py:30)
-        memcpy(st + S * row, c->obs.data() + (size_t)S * w, sizeof(float) * S);
-        memcpy(ns + S * row, c->next_obs.data() + (size_t)S * w, sizeof(float) * S);
-        if (c->cont) memcpy(ac_f + A * row, c->act_f.data() + (size_t)A * w, sizeof(float) * A);
-        else ac_i[row] = c->act_i[w];
-        rw[row] = c->reward[w];
-        dn[row] = c->done[w];
-      }
+      const auto t1 = Clock::now();
+      count_act(c, r, t, secs(t0, t1));
+      if (extra) continue;
+      rc = step_rows(c, r, r0, r1, t);
+      if (rc) return env_failed(c, rc);
       if (t + 1 < steps && !dead) {  // this half's next observations (the reset state where an episode just ended) go out NOW: their round trip runs under the other half's work
         rc = c->vt.obs(c->env, r0, r1, c->obs.data());
-        if (rc) { jh_persist_abort(c->persist); return rc; }
+        if (rc) return env_failed(c, rc);
         jh_persist_publish_rows(c->persist, r0, r1, c->obs.data(), base + (unsigned)t + 2);
       }
-      c->t_env += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+      c->t_env += secs(t1, Clock::now());
     }
     if (!extra) c->steps += 1;
-    *t_done = t + 1;
-    if (dead) return JH_OK;
+    if (dead) {
+      *t_done = t + 1;
+      return JH_OK;
+    }
   }
+  *t_done = steps;
   return JH_OK;
 }
 
@@ -643,22 +620,11 @@ static int run_loop_split(jh_collector* c, int training, hipStream_t stream_h, i
 // rollout, the captured heads / values and every stored transition are bit-identical to the one-step-per-exchange path
 // (tests/test_agents_gpu.py: lookahead vs JH_COLLECT_LOOKAHEAD=1); what changes is that the GPU also evaluates the successor that
 // was not taken (8 wasted rows per exchange) and the host steps env copies that are thrown away.
-// *t_done: timesteps (incl. the value-only query) completed; < steps only when the kernel gave up.
-static int run_loop_lookahead(jh_collector* c, int training, hipStream_t stream_h, int* t_done) {
+static int run_loop_lookahead(jh_collector* c, int training, hipStream_t st, int* t_done) {
   RunState& r = run_state(c);
-  const int W = c->W, S = c->S, T = r.T, steps = T + (r.cap ? 1 : 0);
-  const bool cap = r.cap;
+  const int W = c->W, S = c->S, T = r.T, steps = T + (r.cap ? 1 : 0), no = c->no;
   void* e = c->env;
   const jh_env_vtbl& vt = c->vt;
-  float *ch0 = r.ch0, *cv = r.cv, *cnv = r.cnv;
-  float* st = (float*)r.cols[c->col_state];
-  int64_t* ac_i = (int64_t*)r.cols[c->col_action];
-  float* rw = (float*)r.cols[c->col_reward];
-  float* ns = (float*)r.cols[c->col_next];
-  uint8_t* dn = (uint8_t*)r.cols[c->col_done];
-  const int no = jh_persist_heads(c->persist);  // A logits + value
-  const int A = c->A;
-  // the levels' buffers live in the collector (they were re-allocated on every run)
   Level &L1 = c->lv[0], &L2 = c->lv[1], &L3 = c->lv[2], &tmp = c->lv[3];
   L1.env = c->spec; L2.env = c->spec2; L3.env = c->spec3;
   L1.init(2 * W, S); L2.init(4 * W, S); L3.init(8 * W, S);
@@ -666,50 +632,33 @@ static int run_loop_lookahead(jh_collector* c, int training, hipStream_t stream_
   std::vector<int> pick(W);
   std::vector<int64_t> a0(W), a1(W);
   int t = 0;
-  *t_done = 0;
-  // JH_COLLECT_DEBUG=1: where the host's time per exchange goes (ns, summed over the run, printed every 16th run): fork = stepping the
+  // JH_COLLECT_DEBUG: where the host's time per exchange goes (summed over the run, printed every 16th run): fork = stepping the
   // speculative copies, wait = polling for the root rows' heads, sample = both samplings + the chosen successors' heads,
   // publish = assembling and publishing the next exchange, book = transitions / captured heads / moving the envs on
-  static const bool dbg = getenv("JH_COLLECT_DEBUG") != nullptr;
+  const bool dbg = c->dbg;
   double d_fork = 0, d_wait = 0, d_sample = 0, d_publish = 0, d_book = 0;
   int n_ex = 0;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   // rows 0 .. W-1: the envs' current states; rows W + 2 w + a: the state env w acts on next if it takes action a now
-  // an env error anywhere in this loop: stop the acting kernel (it would poll for ~0.2 s otherwise) and return the error -- the caller's
-  // commit carries the abort value, nothing of this run reaches the store
-  auto env_failed = [&](int rc_env) {
-    jh_persist_abort(c->persist);
-    return rc_env;
-  };
-  int rc_env = fork_step(vt, L1, e, W);
-  if (!rc_env) rc_env = vt.obs(e, 0, W, pub.data());
-  if (rc_env) return env_failed(rc_env);
+  int rc = fork_step(vt, L1, e, W);
+  if (!rc) rc = vt.obs(e, 0, W, pub.data());
+  if (rc) return env_failed(c, rc);
   memcpy(pub.data() + (size_t)W * S, L1.obs.data(), sizeof(float) * (size_t)2 * W * S);
-  auto t0 = std::chrono::steady_clock::now();
+  auto t0 = Clock::now();
   unsigned tag = jh_persist_publish(c->persist, 3 * W, pub.data());
   while (t < steps) {
     const bool extra = t == T;
     const bool two = !extra && t + 1 < T;
     const int t_next = t + (two ? 2 : 1);
-    const auto q0 = dbg ? now() : std::chrono::steady_clock::time_point();
+    const auto q0 = dbg ? Clock::now() : Clock::time_point();
     if (!extra) {  // the GPU is busy for ~5 us: run the env model two levels further meanwhile
-      rc_env = fork_step(vt, L2, L1.env, 2 * W);
-      if (!rc_env && two && t_next < steps) rc_env = fork_step(vt, L3, L2.env, 4 * W);
-      if (rc_env) return env_failed(rc_env);
+      rc = fork_step(vt, L2, L1.env, 2 * W);
+      if (!rc && two && t_next < steps) rc = fork_step(vt, L3, L2.env, 4 * W);
+      if (rc) return env_failed(c, rc);
     }
-    const auto q1 = dbg ? now() : q0;
-    int rc = jh_persist_collect_rows(c->persist, nullptr, W, tag, hz.data());
-    const auto q2 = dbg ? now() : q0;
-    if (rc) {  // the kernel gave up (it exits by itself)
-      jh_persist_abort(c->persist);
-      if (r.early)
-        return jh_fail(JH_ERR_STATE, "the persistent acting kernel gave up at step %d of a run whose commit was enqueued ahead (jh_collector_begin): "
-                                     "no observations for ~0.2 s; use jh_collector_run for environments that may stall", t);
-      JH_HIP(hipStreamSynchronize(stream_h));
-      *t_done = t;
-      return JH_OK;  // the caller finishes the run with one launch per step
-    }
+    const auto q1 = dbg ? Clock::now() : q0;
+    rc = jh_persist_collect_rows(c->persist, nullptr, W, tag, hz.data());
+    const auto q2 = dbg ? Clock::now() : q0;
+    if (rc) return kernel_gave_up(c, r, t, st, t_done);
     if (!extra) {
       for (int w = 0; w < W; ++w) {
         a0[w] = jh_sample_discrete(c->net, hz.data() + (size_t)w * no, w, training);
@@ -723,7 +672,7 @@ static int run_loop_lookahead(jh_collector* c, int training, hipStream_t stream_
         c->net->act_ctr += 1;
       }
     }
-    const auto t1 = std::chrono::steady_clock::now();
+    const auto t1 = Clock::now();
     if (dbg) { d_fork += secs(q0, q1); d_wait += secs(q1, q2); d_sample += secs(q2, t1); ++n_ex; }
     // ---- the next exchange first: its rows are already computed; everything else happens while the GPU works on it
     unsigned tag_next = 0;
@@ -740,54 +689,28 @@ static int run_loop_lookahead(jh_collector* c, int training, hipStream_t stream_
           memcpy(&pub_next[(size_t)S * (W + 2 * w)], &L2.obs[(size_t)S * 2 * k1], sizeof(float) * 2 * S);
         }
       }
-      t0_next = std::chrono::steady_clock::now();
+      t0_next = Clock::now();
       tag_next = jh_persist_publish(c->persist, 3 * W, pub_next.data());
     }
-    const auto q3 = dbg ? now() : t1;
+    const auto q3 = dbg ? Clock::now() : t1;
     if (dbg) d_publish += secs(t1, q3);
     // ---- bookkeeping of this exchange: captured heads / values, transitions, the envs move on
-    if (cap) {
-      for (int w = 0; w < W; ++w) {
-        const float* z = hz.data() + (size_t)w * no;
-        if (t > 0) cnv[(size_t)w * T + (t - 1)] = z[no - 1];  // V(next_state_{t-1}) = V(state_t)  (masked by done_{t-1} in GAE)
-        if (!extra) {
-          const size_t row = (size_t)w * T + t;
-          cv[row] = z[no - 1];
-          memcpy(ch0 + row * A, z, sizeof(float) * A);
-          if (two) {
-            const float* z2 = hz2.data() + (size_t)w * no;
-            cnv[row] = z2[no - 1];
-            cv[row + 1] = z2[no - 1];
-            memcpy(ch0 + (row + 1) * A, z2, sizeof(float) * A);
-          }
-        }
-      }
+    for (int w = 0; w < W; ++w) {
+      capture_row(c, r, w, t, hz.data() + (size_t)w * no);
+      if (two) capture_row(c, r, w, t + 1, hz2.data() + (size_t)w * no);
     }
+    count_act(c, r, t, secs(t0, t1));
     if (extra) {
-      const double dt = std::chrono::duration<double>(t1 - t0).count();
-      c->t_act += dt;
-      c->t_extra += dt;
       t = t_next;
       break;
     }
-    if (t == 0) c->t_first += std::chrono::duration<double>(t1 - t0).count();
     if (!two) { tmp.env = L3.env; tmp.init(2 * W, S); }  // one-step exchange: L3 is free, the successors move up through it
     for (int w = 0; w < W; ++w) {
       const int k1 = 2 * w + (int)a0[w];
-      size_t row = (size_t)w * T + t;  // worker-major (distributed_manager.py:30)
-      memcpy(st + S * row, pub.data() + (size_t)S * w, sizeof(float) * S);
-      memcpy(ns + S * row, &L1.next[(size_t)S * k1], sizeof(float) * S);
-      ac_i[row] = a0[w];
-      rw[row] = L1.rw[k1];
-      dn[row] = L1.dn[k1];
+      store_row(c, r, w, t, &pub[(size_t)S * w], &L1.next[(size_t)S * k1], &a0[w], L1.rw[k1], L1.dn[k1]);
       if (two) {
         const int k2 = 2 * k1 + (int)a1[w];
-        row += 1;
-        memcpy(st + S * row, &L1.obs[(size_t)S * k1], sizeof(float) * S);
-        memcpy(ns + S * row, &L2.next[(size_t)S * k2], sizeof(float) * S);
-        ac_i[row] = a1[w];
-        rw[row] = L2.rw[k2];
-        dn[row] = L2.dn[k2];
+        store_row(c, r, w, t + 1, &L1.obs[(size_t)S * k1], &L2.next[(size_t)S * k2], &a1[w], L2.rw[k2], L2.dn[k2]);
         vt.copy_row(e, w, L2.env, k2);
         if (t_next < steps) {  // (L1's rows of env w are read above before they are overwritten)
           copy_level_row(vt, L1, 2 * w, L3, 2 * k2);
@@ -802,10 +725,9 @@ static int run_loop_lookahead(jh_collector* c, int training, hipStream_t stream_
     if (!two)
       for (int i = 0; i < 2 * W; ++i) copy_level_row(vt, L1, i, tmp, i);
     c->steps += two ? 2 : 1;
-    const auto t2 = std::chrono::steady_clock::now();
+    const auto t2 = Clock::now();
     if (dbg) d_book += secs(q3, t2);
-    c->t_act += std::chrono::duration<double>(t1 - t0).count();
-    c->t_env += std::chrono::duration<double>(t2 - t1).count();
+    c->t_env += secs(t1, t2);
     t = t_next;
     tag = tag_next;
     t0 = t0_next;
@@ -815,8 +737,48 @@ static int run_loop_lookahead(jh_collector* c, int training, hipStream_t stream_
   if (dbg && n_ex > 0 && (c->runs % 16) == 15)
     fprintf(stderr, "[jh_collect] host us per exchange (%d exchanges): fork %.2f  wait %.2f  sample %.2f  publish %.2f  book %.2f\n", n_ex, d_fork / n_ex * 1e6,
             d_wait / n_ex * 1e6, d_sample / n_ex * 1e6, d_publish / n_ex * 1e6, d_book / n_ex * 1e6);
-  if (getenv("JH_PERSIST_DEBUG") && (c->runs % 16) == 15) jh_persist_dump_debug(c->persist, collector_steps(c, T));
+  if (c->dbg_persist && (c->runs % 16) == 15) jh_persist_dump_debug(c->persist, collector_steps(c, T));
   return JH_OK;
+}
+
+// One acting launch per timestep from timestep t_begin on: the whole run when the persistent acting kernel is unavailable, the rest of
+// it when the kernel gave up.  No acting kernel is running here, so an env error is returned as it is.
+static int run_loop_per_launch(jh_collector* c, int training, hipStream_t st, int t_begin) {
+  RunState& r = run_state(c);
+  if (r.early) return jh_fail(JH_ERR_STATE, "jh_collector_begin needs the persistent acting kernel (W <= 32, W * S <= 512, JH_COLLECT_PERSISTENT != 0)");
+  const int W = c->W, T = r.T, steps = T + (r.cap ? 1 : 0);
+  for (int t = t_begin; t < steps; ++t) {
+    const bool extra = t == T;
+    int rc = c->vt.obs(c->env, 0, W, c->obs.data());
+    if (rc) return rc;
+    const auto t0 = Clock::now();
+    rc = act_launch(c, 0, W, training, st);  // (it samples even for the value-only query; its actions are not used)
+    if (rc) return rc;
+    if (extra) c->net->act_ctr -= 1;  // the value-only query must not consume a sampling step: same action stream with and without capture
+    for (int w = 0; w < W; ++w) capture_row(c, r, w, t, c->heads.data() + (size_t)w * c->no);
+    const auto t1 = Clock::now();
+    count_act(c, r, t, secs(t0, t1));
+    if (extra) break;
+    rc = step_rows(c, r, 0, W, t);
+    if (rc) return rc;
+    c->t_env += secs(t1, Clock::now());
+    c->steps += 1;
+  }
+  return JH_OK;
+}
+
+// The host loop: the collector's persistent form, then one launch per step for the timesteps it did not complete.  Returns the first
+// error; the caller commits either way.
+static int run_loop(jh_collector* c, int training, hipStream_t st) {
+  RunState& r = run_state(c);
+  int t = 0;
+  if (r.persistent) {
+    const int rc = c->lookahead == 2 ? run_loop_lookahead(c, training, st, &t)
+                   : c->split        ? run_loop_split(c, training, st, &t)
+                                     : run_loop_exchange(c, training, st, &t);
+    if (rc) return rc;
+  }
+  return t < r.T + (r.cap ? 1 : 0) ? run_loop_per_launch(c, training, st, t) : JH_OK;
 }
 
 // Collect T steps from every env and append the W*T transitions (worker-major) to the store.
