@@ -446,8 +446,10 @@ __global__ void __launch_bounds__(256) jh_mlp_heads_bwd_dh_kernel(int B, int H, 
                                                                   const float* __restrict__ dv2, const float* __restrict__ mix, int ov, PpoFinish fin) {
   const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int h4 = H >> 2;
-  if (i4 >= (int64_t)B * h4) return;
-  const int b = (int)(i4 / h4), k = 4 * (int)(i4 - (int64_t)b * h4);
+  // lanes past the end stay until the loss partials are reduced (below): they read row 0 and store nothing
+  const bool on = i4 < (int64_t)B * h4;
+  if (!on && !(dv2 && fin.partial)) return;
+  const int b = on ? (int)(i4 / h4) : 0, k = on ? 4 * (int)(i4 - (int64_t)b * h4) : 0;
   float gv[8];
   float4 w[8];
 #pragma unroll
@@ -458,13 +460,18 @@ __global__ void __launch_bounds__(256) jh_mlp_heads_bwd_dh_kernel(int B, int H, 
   if (dv2) {  // the one-launch loss (jh_ppo_onepass_kernel) left both critic branches' value gradients: slot `ov` is the value head
     float w1, w2;
     const float g2 = dv2[b];
-    if (fin.partial) {  // ... and its workgroups' partials (nb <= 64): every wave reduces them in the two-pass order (the same bits everywhere), workgroup 0 writes the statistics
+    if (fin.partial) {
+      // ... and its workgroups' partials (nb <= 64): every wave reduces them in the two-pass order (the same bits everywhere), workgroup 0 writes the statistics.
+      // A 64-lane shuffle tree with partial j in lane j: ALL lanes of the wave take part.  The lanes past the end used to return first, and a grid whose
+      // last wave is partial (B H / 4 % 64 != 0: H = 16 / 32 / 64 / 128 at ragged B) lost their partials -- that wave's rows took {w1, w2} of truncated sums
+      // (tests/test_ppo_update_rows_gpu.py, the "tail" cases)
       float t[6];
       ppo_reduce_partials_wave(fin.partial, fin.nb, t);
       ppo_finish_stats(t[0], t[1], t[2], t[3], t[4], t[5], fin.B, fin.ent_count, fin.vf, fin.ent, w1, w2, (blockIdx.x == 0 && threadIdx.x == 0) ? fin.stats : nullptr);
     } else {
       w1 = mix[0]; w2 = mix[1];
     }
+    if (!on) return;
 #pragma unroll
     for (int o = 0; o < 8; ++o)
       if (o == ov) gv[o] = w1 * gv[o] + w2 * g2;  // jh_ppo_critic_select_kernel's expression

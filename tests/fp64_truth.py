@@ -189,3 +189,42 @@ def grad_vs_exact(ours, exact, ref32, tol, what, rows=None):
     e_ref = float(np.abs(pick(ref32) - ex).max()) / scale if ref32 is not None else 0.0
     margins.leq(e_ours, max(tol, 2.0 * e_ref), f"{what} |ours - fp64| / max|fp64| (reference fp32: {e_ref:.2e})")
     return e_ours, e_ref
+
+
+def ppo_update_float64(module, cont, x, action, adv, ret, v_old, lp_old, eps, vf, ent):
+    """ONE whole PPO minibatch update (core/agent/ppo.py:122-165 restated, as ppo_head_grads_float64 is, composed with the mirror module's
+    raw()) with torch autograd on the CPU in the module's own dtype: float64 for the truth, `as32(module)` for the torch-CPU-fp32 comparator
+    the criterion above needs.  x [B, S] and the other arguments are the minibatch's GATHERED rows (any float dtype; action [B, A] continuous,
+    [B, 1] discrete; lp_old [B, A] / [B, 1]).  Test infrastructure, not the product.
+      -> heads   tuple of detached raw heads, (logits, v) or (mu_raw, log_std_raw, v)
+         stats   {loss, actor, critic, entropy, max_ratio, min_prob, c1, c2} as Python floats (entropy = entropy_loss = -mean H)
+         grads   {parameter name: d(loss)/d(parameter)}, state_dict order
+         rows    per-row quantities for conditions on the inputs: {ratio [B], dv = v - v_old [B], g_c1, g_c2: d(c1)/dv, d(c2)/dv [B]}"""
+    dt = next(module.parameters()).dtype
+    c = lambda a: torch.as_tensor(a).detach().cpu().to(dt)
+    for p in module.parameters():
+        p.grad = None
+    x, adv, ret, v_old, lp_old = c(x), c(adv).reshape(-1, 1), c(ret).reshape(-1, 1), c(v_old).reshape(-1, 1), c(lp_old)
+    heads = module.raw(x)
+    v = heads[-1]
+    if cont:
+        mu_raw, ls_raw = heads[0], heads[1]
+        m = torch.distributions.Normal(torch.clamp(mu_raw, -5.0, 5.0), torch.tanh(ls_raw).exp())
+        # (the action clamp happens on fp32 tensors in the reference: see ppo_head_grads_float64)
+        a_cl = torch.clamp(torch.as_tensor(action).detach().cpu().float(), -1 + 1e-7, 1 - 1e-7).to(dt)
+        log_prob = m.log_prob(torch.atanh(a_cl))
+    else:
+        m = torch.distributions.Categorical(torch.exp(torch.log_softmax(heads[0], dim=-1)))
+        log_prob = m.log_prob(torch.as_tensor(action).detach().cpu().reshape(-1).long()).unsqueeze(-1)
+    ratio = (log_prob - lp_old.reshape(log_prob.shape)).sum(1, keepdim=True).exp()
+    actor = -torch.min(ratio * adv, torch.clamp(ratio, 1 - eps, 1 + eps) * adv).mean()
+    v_clip = v_old + torch.clamp(v - v_old, -eps, eps)
+    c1, c2 = torch.nn.functional.mse_loss(v, ret), torch.nn.functional.mse_loss(v_clip, ret)
+    critic = torch.max(c1, c2)
+    entropy = -m.entropy().mean()
+    loss = actor + vf * critic + ent * entropy
+    g_c1, g_c2 = (torch.autograd.grad(t, v, retain_graph=True)[0].reshape(-1) for t in (c1, c2))
+    loss.backward()
+    stats = {"loss": loss, "actor": actor, "critic": critic, "entropy": entropy, "max_ratio": ratio.max(), "min_prob": log_prob.exp().min(), "c1": c1, "c2": c2}
+    return (tuple(h.detach() for h in heads), {k: float(t.detach()) for k, t in stats.items()}, {k: p.grad.detach().clone() for k, p in module.named_parameters()},
+            {"ratio": ratio.detach().reshape(-1), "dv": (v - v_old).detach().reshape(-1), "g_c1": g_c1, "g_c2": g_c2})

@@ -45,7 +45,7 @@ def _truth(a2, b2, epi, bias, aux):
     return want, float((np.abs(a64) @ np.abs(b64)).max()) + 1e-9, a64
 
 
-def test_tgemm_dense_random_shapes_modes_and_epilogues_match_torch():
+def test_tgemm_dense_random_shapes_modes_and_epilogues_match_float64():
     """The GEMM engine under every value-network layer, on 80 random problems: ragged M / N / K (not multiples of
     the 64 x 64 x 32 tile, of 4, or of anything), all four dense operand layouts, row strides that do and do not
     allow 16-byte loads, every epilogue, fused row sums, shapes that do and do not split K."""
@@ -109,7 +109,7 @@ def _dma_cases(seed, label, reps=3, every=1):
             margins.lt(rs_err, 2e-6, f"rowsum dma {label} case {case} M{M} N{N} K{K}")
 
 
-def test_tgemm_dense_lds_dma_shapes_all_layouts_match_torch():
+def test_tgemm_dense_lds_dma_shapes_all_layouts_match_float64():
     """Problems the LDS-DMA kernel takes (K % 32 == 0, 16-byte pieces, x-contiguous extents % 4 == 0; tiles that are and are not
     full, K ranges that do and do not split, one to three chunk buffers' worth of K) in all four dense layouts, with every epilogue
     and the fused row sums."""
