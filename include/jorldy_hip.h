@@ -284,6 +284,29 @@ int jh_value_act(jh_ctx* ctx, int32_t N, int32_t A, int32_t K, const float* d_lo
                  const float* h_eps, const double* h_u, const int64_t* h_rand_action, int64_t* d_action,
                  float* d_q_taken, float* d_q_all, jh_stream stream);
 
+/* ------------------------------------------------------------------ QR-DQN
+ * Pairwise quantile-Huber loss, forward and backward to the online quantiles (core/agent/qrdqn.py:60-95, logits2Q
+ * qrdqn.py:112-115).  d_logit / d_next_logit_online / d_target_logit float32 [B][A][N] = online(s), online(s'), target(s');
+ * d_action / d_reward / d_done float32 [B] (actions clamped into [0, A)); d_tau float32 [N], the quantile midpoints as the
+ * host's torch.arange gives them (qrdqn.py:26-31; 1 - tau is formed in fp32 as the reference forms inv_tau).  With
+ * P[i] = logit[b][action[b]][i], a* = first maximum over a of mean_i next_logit_online[b][a][i] (the online net selects, the
+ * target net evaluates; there is no other form) and T[j] = reward + (1 - done) * gamma * target_logit[b][a*][j]:
+ * e = T[j] - P[i], loss = 1 / (B N) * sum_b sum_j sum_i (e < 0 ? 1 - tau[i] : tau[i]) * smooth_l1(e, beta 1).
+ * Outputs: d_grad_logit float32 [B][A][N] = d loss / d logit, every entry written (zero outside the taken action's row);
+ * d_stats float32[8] = {loss, max_Q, max_logit, min_logit, 0, mark, 0, mark}: max_Q over the quantile means of d_logit, max / min
+ * over d_logit itself, the payload fenced before the arrival marks [5], [7] (0.f) as jh_c51_loss leaves them.
+ * 1 <= N <= 256.  Two launches, no floating-point atomics: the same inputs give the same bits, eagerly or replayed in a graph.      */
+int jh_qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online,
+               const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done,
+               const float* d_tau, float gamma, float* d_grad_logit, float* d_stats, jh_stream stream);
+
+/* QRDQN.act (core/agent/qrdqn.py:33-47) for R actor rows in one call: jh_value_act with Q = mean of the N quantiles
+ * (qrdqn.py:112-115) in place of the expectation over a support.  d_logits float32 [R][A][N]; the host's epsilon draws as in
+ * jh_value_act (all three NULL: greedy); d_action int64[R] (first maximum), d_q_taken float32[R] (NULL ok; written and fenced
+ * before the action, so a host that waits on device-mapped actions finds it in place), d_q_all float32[R][A] (NULL ok).    */
+int jh_quantile_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
+                    const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream);
+
 /* ------------------------------------------------------------------ native policy-value MLP
  * The encoder of the PPO configs (core/network/head.py:6-18 MLP head + policy_value.py:8-57):
  * S -> H relu -> H relu -> {A logits | A mu, A log_std} + value, as hand-written kernels

@@ -160,12 +160,17 @@ class NativeValueNetMixin:
         nz = torch.randn(net.noise_len, device=net.device) if (net.kind == "rainbow" and is_train) else None
         net.forward(a["x_dev"], 0, nz, out=a["logits"])
         a["am"].np[:] = -1  # arrival marks (actions are >= 0)
-        ops.value_act(a["logits"].view(N, A, K), float(getattr(self, "v_min", 0.0)), float(getattr(self, "v_max", 0.0)), out=(a["act_dev"], a["q_dev"]))
+        self._act_kernel(a["logits"].view(N, A, K), (a["act_dev"], a["q_dev"]))
         if L.load().jh_host_wait_words(L.ptr(a["words"]), L.ptr(a["marks"]), N, 0xFFFFFFFF, 5.0) != 0:
             torch.cuda.current_stream(self.device).synchronize()
             if (a["am"].np < 0).any():
                 raise RuntimeError("act(): the actions never arrived (failed launch?)")
         return a["am"].np.reshape(N, 1).copy()
+
+    def _act_kernel(self, logits, out):
+        """Outputs [N, A, K] -> greedy actions and their Q in `out` (device-mapped).  Default: Q values (K = 1) or the expectation of
+        K atoms on linspace(v_min, v_max, K); an agent that reads its outputs otherwise overrides this (QRDQN: quantile means)."""
+        ops.value_act(logits, float(getattr(self, "v_min", 0.0)), float(getattr(self, "v_max", 0.0)), out=out)
 
     def _set_native_hyper(self, d, steps):
         if self._opt_name == "adam":

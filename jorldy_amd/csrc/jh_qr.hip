@@ -1,0 +1,209 @@
+// Quantile-regression DQN (core/agent/qrdqn.py), the two parts that are specific to the algorithm:
+//   jh_qr_loss       pairwise quantile-Huber loss, forward and backward to the online quantiles,
+//                    online net selects / target net evaluates                 (qrdqn.py:60-95)
+//   jh_quantile_act  epsilon-greedy acting on the mean of the quantiles         (qrdqn.py:33-47, 112-115)
+// No floating-point atomics: every sum has a fixed order, so two runs (and a graph replay) give the same bits.
+#include "jh_common.h"
+
+struct QrArgs {
+  int B, A, N;
+  const float *logit, *next_logit, *target_logit, *action, *reward, *done, *tau;
+  float gamma;
+  float *grad, *stats, *partial;  // partial [B][4] = {sum_j sum_i w * huber, max Q, max logit, min logit} of a sample
+};
+
+// Mean of one row of N quantiles on one wave (torch.mean(_logits, dim=-1), qrdqn.py:114): every lane returns it.
+// rmx / rmn: the row's largest / smallest entry.
+__device__ __forceinline__ float qr_row_mean(const float* __restrict__ z, int N, int lane, float& rmx, float& rmn) {
+  float s = 0.f;
+  rmx = -3.4e38f;
+  rmn = 3.4e38f;
+  for (int k = lane; k < N; k += 64) {
+    const float v = z[k];
+    s += v;
+    rmx = fmaxf(rmx, v);
+    rmn = fminf(rmn, v);
+  }
+  rmx = jh_wave_max(rmx);
+  rmn = jh_wave_min(rmn);
+  return jh_wave_sum(s) / (float)N;
+}
+
+// One workgroup of 256 threads per sample (N <= 256: thread i owns prediction quantile i).
+// LDS: [N] Bellman image of the target quantiles, [A] selector means, [4][3] per-wave statistics, [16] reduction.
+// Every thread stays to the end: the work of threads i >= N is predicated, not skipped (block reduction at the end).
+__global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int b = blockIdx.x, A = a.A, N = a.N;
+  float* s_T = smem;           // [N]
+  float* s_qsel = s_T + N;     // [A]
+  float* s_stat = s_qsel + A;  // [4][3]
+  float* s_red = s_stat + 12;  // [16]
+  int act = (int)a.action[b];
+  act = act < 0 ? 0 : (act >= A ? A - 1 : act);
+  const float r = a.reward[b], dn = a.done[b];
+  // what phase 3 keeps in registers, requested ahead of the reductions of phase 1
+  const bool own = tid < N;
+  const int ti = own ? tid : N - 1;
+  const float P = a.logit[((size_t)b * A + act) * N + ti];
+  const float tau = a.tau[ti];
+  const float inv_tau = 1.f - tau;  // qrdqn.py:31
+  // ---- phase 1: quantile means of online(s) (statistics) and online(s') (selector), action rows strided over the waves
+  float maxq = -3.4e38f, maxl = -3.4e38f, minl = 3.4e38f;
+  for (int aa = wid; aa < A; aa += 4) {
+    float rmx, rmn, x0, x1;
+    const float q = qr_row_mean(a.logit + ((size_t)b * A + aa) * N, N, lane, rmx, rmn);
+    maxq = fmaxf(maxq, q);
+    maxl = fmaxf(maxl, rmx);
+    minl = fminf(minl, rmn);
+    const float q2 = qr_row_mean(a.next_logit + ((size_t)b * A + aa) * N, N, lane, x0, x1);
+    if (lane == 0) s_qsel[aa] = q2;
+    if (aa != act) {  // the rows of the actions not taken: zero gradient (net.backward reads all of it)
+      float* g = a.grad + ((size_t)b * A + aa) * N;
+      for (int k = lane; k < N; k += 64) g[k] = 0.f;
+    }
+  }
+  if (lane == 0) { s_stat[wid * 3 + 0] = maxq; s_stat[wid * 3 + 1] = maxl; s_stat[wid * 3 + 2] = minl; }
+  __syncthreads();
+  // ---- a* = first maximum of the online net's means at s' (qrdqn.py:76); every thread walks the same A values
+  int best = 0;
+  float bq = -3.4e38f;
+  for (int aa = 0; aa < A; ++aa) {
+    const float q = s_qsel[aa];
+    if (q > bq) { bq = q; best = aa; }
+  }
+  // ---- phase 2: theta_target = reward + (1 - done) * gamma * target(s')[a*]  (qrdqn.py:79-81, in torch's order of operations)
+  if (own) s_T[tid] = r + ((1.f - dn) * a.gamma) * a.target_logit[((size_t)b * A + best) * N + tid];
+  __syncthreads();
+  // ---- phase 3: thread i walks the targets j; e = T[j] - P[i], smooth_l1 (beta 1), weight tau[i] / 1 - tau[i] by the sign of e
+  float ls = 0.f, gs = 0.f;
+  for (int j = 0; j < N; ++j) {
+    const float e = s_T[j] - P;  // the same LDS word for every lane: a broadcast
+    const float ae = fabsf(e);
+    const float hub = ae < 1.f ? 0.5f * e * e : ae - 0.5f;
+    const float w = e < 0.f ? inv_tau : tau;
+    ls += w * hub;
+    gs += w * fminf(fmaxf(e, -1.f), 1.f);
+  }
+  if (own) a.grad[((size_t)b * A + act) * N + tid] = -gs / ((float)a.B * (float)N);
+  // ---- phase 4: the sample's loss, wave shuffle tree then the waves in order
+  const float tot = jh_block_reduce(own ? ls : 0.f, s_red, JhAdd(), 0.f);
+  if (tid == 0) {
+    float mq = -3.4e38f, ml = -3.4e38f, nl = 3.4e38f;
+    const int nw = A < 4 ? A : 4;  // waves that saw at least one action row
+    for (int w = 0; w < nw; ++w) {
+      mq = fmaxf(mq, s_stat[w * 3 + 0]);
+      ml = fmaxf(ml, s_stat[w * 3 + 1]);
+      nl = fminf(nl, s_stat[w * 3 + 2]);
+    }
+    float* p = a.partial + 4 * (size_t)b;
+    p[0] = tot; p[1] = mq; p[2] = ml; p[3] = nl;
+  }
+}
+
+// Sum of the per-sample partials in a fixed order -> d_stats, payload fenced before the arrival marks (as jh_c51_finish_kernel).
+__global__ void __launch_bounds__(256) jh_qr_finish_kernel(QrArgs a) {
+  __shared__ float s_red[16];
+  float sl = 0.f, mq = -3.4e38f, ml = -3.4e38f, nl = 3.4e38f;
+  for (int b = threadIdx.x; b < a.B; b += 256) {
+    sl += a.partial[4 * (size_t)b];
+    mq = fmaxf(mq, a.partial[4 * (size_t)b + 1]);
+    ml = fmaxf(ml, a.partial[4 * (size_t)b + 2]);
+    nl = fminf(nl, a.partial[4 * (size_t)b + 3]);
+  }
+  sl = jh_block_reduce(sl, s_red, JhAdd(), 0.f);
+  mq = jh_block_reduce(mq, s_red, JhMax(), -3.4e38f);
+  ml = jh_block_reduce(ml, s_red, JhMax(), -3.4e38f);
+  nl = jh_block_reduce(nl, s_red, JhMin(), 3.4e38f);
+  if (threadIdx.x == 0 && a.stats) {
+    a.stats[0] = sl / ((float)a.B * (float)a.N);  // qrdqn.py:91: mean over (b, j) of the sum over i
+    a.stats[1] = mq;
+    a.stats[2] = ml;
+    a.stats[3] = nl;
+    a.stats[4] = 0.f;
+    a.stats[6] = 0.f;
+    __threadfence_system();  // payload before the arrival marks [5], [7] (mapped host memory, jh_host_wait_marks)
+    a.stats[5] = a.stats[7] = 0.f;
+  }
+}
+
+JH_EXPORT int jh_qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online,
+                         const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done,
+                         const float* d_tau, float gamma, float* d_grad_logit, float* d_stats, jh_stream stream) {
+  JH_ARG(ctx && d_logit && d_next_logit_online && d_target_logit && d_action && d_reward && d_done && d_tau && d_grad_logit);
+  JH_ARG(B >= 1 && A >= 1 && N >= 1 && N <= 256);
+  hipStream_t st = jh_s(stream);
+  void* scratch = nullptr;
+  int rc = jh_ctx_scratch(ctx, sizeof(float) * 4 * (size_t)B, &scratch);
+  if (rc) return rc;
+  QrArgs a{};
+  a.B = B; a.A = A; a.N = N;
+  a.logit = d_logit; a.next_logit = d_next_logit_online; a.target_logit = d_target_logit; a.action = d_action;
+  a.reward = d_reward; a.done = d_done; a.tau = d_tau; a.gamma = gamma; a.grad = d_grad_logit; a.stats = d_stats;
+  a.partial = (float*)scratch;
+  const size_t lds = sizeof(float) * ((size_t)N + (size_t)A + 12 + 16);
+  JH_ARG(lds <= 64 * 1024);
+  JH_LAUNCH(jh_qr_block_kernel, dim3(B), dim3(256), lds, st, a);
+  JH_LAUNCH_CHECK();
+  JH_LAUNCH(jh_qr_finish_kernel, dim3(1), dim3(256), 0, st, a);
+  JH_LAUNCH_CHECK();
+  return JH_OK;
+}
+
+// QRDQN.act for R actor rows in one call: one wave per row, Q = mean of the N quantiles, first maximum like torch.argmax,
+// epsilon-greedy with the host's draws (jh_value_act's rules), q_taken fenced before the action.
+// Every lane of a wave stays through the shuffles: rows beyond R read row R - 1 and write nothing.
+__global__ void __launch_bounds__(256) jh_quantile_act_kernel(int R, int A, int N, const float* __restrict__ logits, const float* __restrict__ eps,
+                                                              const double* __restrict__ u, const int64_t* __restrict__ rand_action,
+                                                              int64_t* __restrict__ action, float* __restrict__ q_taken, float* __restrict__ q_all) {
+  const int lane = threadIdx.x & 63;
+  const int row0 = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const bool live = row0 < R;
+  const int row = live ? row0 : R - 1;
+  float best = -3.4e38f, q_rand = 0.f;
+  int best_a = 0;
+  int ra = rand_action ? (int)rand_action[row] : 0;
+  ra = ra < 0 ? 0 : (ra >= A ? A - 1 : ra);
+  for (int a = 0; a < A; ++a) {
+    float rmx, rmn;
+    const float q = qr_row_mean(logits + ((size_t)row * A + a) * N, N, lane, rmx, rmn);
+    if (q_all && live && lane == 0) q_all[(size_t)row * A + a] = q;
+    if (q > best) { best = q; best_a = a; }
+    if (a == ra) q_rand = q;
+  }
+  if (live && lane == 0) {
+    const bool explore = eps && u && u[row] < (double)eps[row];
+    if (q_taken) {
+      q_taken[row] = explore ? q_rand : best;
+      __threadfence_system();
+    }
+    action[row] = explore ? ra : best_a;
+  }
+}
+
+JH_EXPORT int jh_quantile_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
+                              const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream) {
+  JH_ARG(ctx && d_logits && d_action);
+  JH_ARG(R > 0 && A > 0 && N > 0);
+  JH_ARG((h_eps == nullptr) == (h_u == nullptr) && (h_eps == nullptr) == (h_rand_action == nullptr));
+  hipStream_t st = jh_s(stream);
+  const float* d_eps = nullptr;
+  const double* d_u = nullptr;
+  const int64_t* d_ra = nullptr;
+  jh_pinned_slab* slab = nullptr;
+  if (h_eps) {  // the draws ride in a pinned, device-mapped slab the kernel reads in place
+    const size_t o_u = ((sizeof(float) * (size_t)R + 255) & ~(size_t)255), o_r = o_u + ((sizeof(double) * (size_t)R + 255) & ~(size_t)255);
+    int rc = jh_ctx_slab(ctx, o_r + sizeof(int64_t) * (size_t)R + 256, &slab);
+    if (rc) return rc;
+    memcpy(slab->host, h_eps, sizeof(float) * (size_t)R);
+    memcpy((char*)slab->host + o_u, h_u, sizeof(double) * (size_t)R);
+    memcpy((char*)slab->host + o_r, h_rand_action, sizeof(int64_t) * (size_t)R);
+    d_eps = (const float*)slab->dev;
+    d_u = (const double*)((char*)slab->dev + o_u);
+    d_ra = (const int64_t*)((char*)slab->dev + o_r);
+  }
+  JH_LAUNCH(jh_quantile_act_kernel, dim3((R + 3) / 4), dim3(256), 0, st, R, A, N, d_logits, d_eps, d_u, d_ra, d_action, d_q_taken, d_q_all);
+  JH_LAUNCH_CHECK();
+  return slab ? jh_ctx_slab_release(ctx, slab, st) : JH_OK;
+}

@@ -816,6 +816,38 @@ def c51_loss(logit, target_logit, action, reward, done, v_min, v_max, gamma, nex
     return g, prio, kl, stats
 
 
+def qr_loss(logit, next_logit_online, target_logit, action, reward, done, tau, gamma, stats=None):
+    """jh_qr_loss (qrdqn.py:60-95): logit / next_logit_online / target_logit [B, A, N], action / reward / done [B] (or [B, 1]),
+    tau float32 [N] on the device.  Returns (grad_logit [B, A, N], stats f32[8] = {loss, max_Q, max_logit, min_logit, 0, mark, 0, mark})."""
+    z = _f32(logit)
+    B, A, N = (int(v) for v in z.shape)
+    zn, zt, t = _f32(next_logit_online), _f32(target_logit), _f32(tau).reshape(-1)
+    assert tuple(zn.shape) == (B, A, N) and tuple(zt.shape) == (B, A, N) and t.numel() == N and t.device == z.device
+    a, r, d = _f32(action).reshape(-1), _f32(reward).reshape(-1), _f32(done).reshape(-1)
+    assert a.numel() == B and r.numel() == B and d.numel() == B
+    g = torch.empty_like(z)
+    if stats is None:
+        stats = torch.empty(8, dtype=torch.float32, device=z.device)
+    L.check(L.load().jh_qr_loss(L.ctx(_dev(z)), B, A, N, L.ptr(z), L.ptr(zn), L.ptr(zt), L.ptr(a), L.ptr(r), L.ptr(d), L.ptr(t), float(gamma), L.ptr(g), L.ptr(stats),
+                                L.stream_ptr()))
+    return g, stats
+
+
+def quantile_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_all=False):
+    """jh_quantile_act: network outputs [R, A, N] (N quantiles per action, Q = their mean) -> (action int64 [R], q_taken float32 [R],
+    q_all | None) on the device.  eps / u / rand_action as in value_act."""
+    lg = _f32(logits)
+    R, A, N = (int(v) for v in lg.shape)
+    dev = lg.device
+    act, q = (torch.empty(R, dtype=torch.int64, device=dev), torch.empty(R, dtype=torch.float32, device=dev)) if out is None else out
+    q_all = torch.empty(R, A, dtype=torch.float32, device=dev) if want_q_all else None
+    if eps is not None:
+        eps, u, rand_action = (np.ascontiguousarray(eps, dtype=np.float32), np.ascontiguousarray(u, dtype=np.float64), np.ascontiguousarray(rand_action, dtype=np.int64))
+        assert eps.size == R and u.size == R and rand_action.size == R
+    L.check(L.load().jh_quantile_act(L.ctx(_dev(lg)), R, A, N, L.ptr(lg), L.ptr(eps), L.ptr(u), L.ptr(rand_action), L.ptr(act), L.ptr(q), L.ptr(q_all), L.stream_ptr()))
+    return act, q, q_all
+
+
 # ============================================================================= host collector
 class CartPoleVec:
     """W synthetic CartPole-v1 envs stepped in one native call (jh_cartpole_*)."""
