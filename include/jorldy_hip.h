@@ -258,6 +258,22 @@ int jh_td_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t n_step, int32_t flags,
                const float* d_reward, const float* d_done, const float* d_weights, float gamma, float alpha,
                float* d_grad_q, float* d_prio, float* d_stats, jh_stream stream);
 
+/* ------------------------------------------------------------------ Munchausen DQN
+ * core/agent/m_dqn.py:29-59 with agent/utils.py:29-39, forward and backward to Q(s).  d_q / d_q_target / d_q_next_target
+ * float32 [B][A] = online(s), target(s), target(s'); d_action / d_reward / d_done float32 [B] (actions clamped into [0, A)).
+ * Per row, with the row maximum subtracted before every exp:
+ *   log-policy  lp = d_q_target[a] - (max + tau * log(sum_k exp((d_q_target[k] - max) / tau)))
+ *   soft value  V  = sum_k pi_k * (x_k - tau * log pi_k),  x = d_q_next_target, pi = softmax((x - max) / tau)
+ *   target      y  = reward + alpha * clamp(lp, l_0, 0) + (1 - done) * gamma * V
+ *   loss = mean_b smooth_l1(d_q[b][a] - y, beta 1)
+ * Outputs: d_grad_q [B][A] = d loss / d d_q, every entry written (clamp(q - y, -1, 1) / B at the taken action, zero elsewhere);
+ * d_stats float32[4] = {loss, max over b of the TAKEN q, mean of alpha * clamp(lp, l_0, 0), mark}: the payload is fenced before
+ * the arrival mark [3] (0.f), as jh_td_loss leaves it.  tau > 0, l_0 <= 0; A == 1 is legal (lp is exactly 0, V is x itself).
+ * At most two launches, no floating-point atomics: the same inputs give the same bits, eagerly or replayed in a graph.        */
+int jh_mdqn_loss(jh_ctx* ctx, int32_t B, int32_t A, const float* d_q, const float* d_q_target, const float* d_q_next_target,
+                 const float* d_action, const float* d_reward, const float* d_done, float gamma, float alpha, float tau, float l_0,
+                 float* d_grad_q, float* d_stats, jh_stream stream);
+
 /* ------------------------------------------------------------------ C51 / Rainbow
  * Categorical n-step projection + cross-entropy, forward and backward to the online
  * logits (rainbow.py:167-239, c51.py:68-109, logits2Q rainbow.py:285-292).  flags: */
@@ -547,6 +563,14 @@ int jh_rbnet_forward_keep(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t
  * NULL) -> d_logits [3][B][A][K] = online(state), online(next_state), target(next_state)                */
 int jh_rbnet_learn_forward(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits,
                            jh_stream stream);
+/* The three forwards of Munchausen DQN's learn() (m_dqn.py:31-38): d_x as above -> d_logits [3][B][A][K] = online(state),
+ * target(state), target(next_state).  The online trunk runs over B rows and the target trunk over 2B, in as many launches as
+ * jh_rbnet_learn_forward; jh_rbnet_backward continues from it in the same way.  Kinds 1 and 2 (a noisy network: JH_ERR_ARG); d_noise
+ * is ignored.  The target network's activation buffers hold max_batch rows unless jh_rbnet_reserve_target_rows(n, rows) grew them
+ * (rows <= 2 * max_batch; allocates, so: once, outside any stream capture); without room for 2B rows: JH_ERR_STATE.            */
+int jh_rbnet_reserve_target_rows(jh_rbnet* n, int32_t rows);
+int jh_rbnet_learn_forward_m(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits,
+                             jh_stream stream);
 /* jh_rbnet_learn_forward in two halves + the part that does not depend on the batch (rainbow.py:160-186: the three forwards of learn()):
  *   jh_rbnet_prepare_noise  W = mu + sig * eps of the three noisy weight sets (network/utils.py:55-86) for the draw d_noise [3][noise_len]
  *                           -- may run on another stream while the trunk runs (a 12-us launch off the critical path)

@@ -83,6 +83,7 @@ _PROTOS = {
     "jh_value_act": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_td_loss": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp]),
     "jh_c51_loss": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "jh_mdqn_loss": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "jh_qr_loss": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
     "jh_quantile_act": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_pponet_param_count": (_i64, [_i32, _i32, _i32, _i32]),
@@ -130,6 +131,8 @@ _PROTOS = {
     "jh_rbnet_forward": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "jh_rbnet_forward_keep": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "jh_rbnet_learn_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "jh_rbnet_learn_forward_m": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "jh_rbnet_reserve_target_rows": (C.c_int, [_vp, _i32]),
     "jh_rbnet_prepare_noise": (C.c_int, [_vp, _vp, _vp]),
     "jh_rbnet_learn_trunk": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "jh_rbnet_learn_heads": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),

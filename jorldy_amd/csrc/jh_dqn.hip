@@ -140,6 +140,100 @@ JH_EXPORT int jh_td_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t n_step, int3
   return JH_OK;
 }
 
+// ============================================================================ Munchausen DQN
+// m_dqn.py:29-59 with agent/utils.py:29-39: one lane per row like jh_td_loss_kernel, the same per-block partials
+// {sum of loss terms, max taken q, sum of Munchausen terms} and the same finish launch (jh_td_finish_kernel).
+struct MdqnArgs {
+  int B, A;
+  const float *q, *qt, *qnt, *action, *reward, *done;
+  float gamma, alpha, tau, l_0;
+  float *grad_q, *stats, *partial;
+};
+
+__global__ void __launch_bounds__(256) jh_mdqn_loss_kernel(MdqnArgs a) {
+  __shared__ float s_red[16];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool on = i < a.B;
+  float lterm = 0.f, qa = -3.4e38f, mun = 0.f;
+  if (on) {
+    int act = (int)a.action[i];
+    act = act < 0 ? 0 : (act >= a.A ? a.A - 1 : act);
+    const float* q = a.q + (size_t)i * a.A;
+    const float* qt = a.qt + (size_t)i * a.A;
+    const float* qnt = a.qnt + (size_t)i * a.A;
+    qa = q[act];
+    // ---- Munchausen term: stable_scaled_log_softmax(target(s), tau)[action], clipped to [l_0, 0]   (m_dqn.py:38-42, 47)
+    float m = qt[0];
+    for (int k = 1; k < a.A; ++k) m = fmaxf(m, qt[k]);
+    float se = 0.f;
+    for (int k = 0; k < a.A; ++k) se += expf((qt[k] - m) / a.tau);
+    const float lp = qt[act] - (m + a.tau * logf(se));
+    mun = a.alpha * fminf(fmaxf(lp, a.l_0), 0.f);
+    // ---- soft value of target(s'): sum_a pi (q - tau log pi)   (m_dqn.py:44-50)
+    float mn = qnt[0];
+    for (int k = 1; k < a.A; ++k) mn = fmaxf(mn, qnt[k]);
+    float sn = 0.f;
+    for (int k = 0; k < a.A; ++k) sn += expf((qnt[k] - mn) / a.tau);  // the row maximum of (x - max) / tau is 0: log_softmax subtracts nothing more
+    const float lsn = logf(sn);
+    const float tau_lse = mn + a.tau * lsn;
+    float ent = 0.f;
+    for (int k = 0; k < a.A; ++k) {
+      const float x = qnt[k];
+      const float pi = expf((x - mn) / a.tau - lsn);  // exp(log_softmax(y / tau))   utils.py:36-39
+      ent += pi * (x - (x - tau_lse));                // next_target_q - next_log_policy
+    }
+    const float r = a.reward[i], d = a.done[i];
+    const float y = (r + mun) + (1.f - d) * a.gamma * ent;  // m_dqn.py:52-56
+    const float diff = qa - y, ad = fabsf(diff);
+    lterm = ad < 1.f ? 0.5f * diff * diff : ad - 0.5f;  // smooth_l1, beta = 1
+    const float g = (ad < 1.f ? diff : (diff > 0.f ? 1.f : -1.f)) * (1.f / (float)a.B);
+    float* gq = a.grad_q + (size_t)i * a.A;
+    for (int k = 0; k < a.A; ++k) gq[k] = (k == act) ? g : 0.f;
+  }
+  const float s_l = jh_block_reduce(lterm, s_red, JhAdd(), 0.f);
+  const float m_q = jh_block_reduce(qa, s_red, JhMax(), -3.4e38f);
+  const float s_m = jh_block_reduce(mun, s_red, JhAdd(), 0.f);
+  if (threadIdx.x == 0) {
+    if (gridDim.x == 1) {
+      if (a.stats) {
+        a.stats[0] = s_l / (float)a.B;
+        a.stats[1] = m_q;
+        a.stats[2] = s_m / (float)a.B;
+        __threadfence_system();  // payload before the arrival mark, as jh_td_loss_kernel
+        a.stats[3] = 0.f;
+      }
+    } else {
+      float* p = a.partial + 3 * (size_t)blockIdx.x;
+      p[0] = s_l; p[1] = m_q; p[2] = s_m;
+    }
+  }
+}
+
+JH_EXPORT int jh_mdqn_loss(jh_ctx* ctx, int32_t B, int32_t A, const float* d_q, const float* d_q_target, const float* d_q_next_target,
+                           const float* d_action, const float* d_reward, const float* d_done, float gamma, float alpha, float tau, float l_0,
+                           float* d_grad_q, float* d_stats, jh_stream stream) {
+  JH_ARG(ctx && d_q && d_q_target && d_q_next_target && d_action && d_reward && d_done && d_grad_q && d_stats);
+  JH_ARG(B > 0 && A > 0);
+  JH_ARG(tau > 0.f && l_0 <= 0.f);
+  MdqnArgs a{};
+  a.B = B; a.A = A; a.q = d_q; a.qt = d_q_target; a.qnt = d_q_next_target; a.action = d_action; a.reward = d_reward; a.done = d_done;
+  a.gamma = gamma; a.alpha = alpha; a.tau = tau; a.l_0 = l_0; a.grad_q = d_grad_q; a.stats = d_stats;
+  const int nb = (B + 255) / 256;
+  if (nb > 1) {
+    void* scratch = nullptr;
+    int rc = jh_ctx_scratch(ctx, sizeof(float) * 3 * (size_t)nb, &scratch);
+    if (rc) return rc;
+    a.partial = (float*)scratch;
+  }
+  JH_LAUNCH(jh_mdqn_loss_kernel, dim3(nb), dim3(256), 0, jh_s(stream), a);
+  JH_LAUNCH_CHECK();
+  if (nb > 1) {
+    JH_LAUNCH(jh_td_finish_kernel, dim3(1), dim3(256), 0, jh_s(stream), nb, B, a.partial, d_stats);
+    JH_LAUNCH_CHECK();
+  }
+  return JH_OK;
+}
+
 // ============================================================================ C51 / Rainbow
 // torch.linspace(v_min, v_max, K) in float32 (symmetric form used by ATen)
 __device__ __forceinline__ float support_z(int k, int K, float v_min, float v_max) {

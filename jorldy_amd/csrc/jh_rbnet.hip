@@ -642,6 +642,7 @@ struct jh_rbnet {
   int raw_heads = 0;    // the last learn_heads left xa / xv uncombined (jh_rbnet_learn_heads_raw): jh_rbnet_c51_step combines them
   int dx_ready = 0;     // dxa / dxv already hold the gradient pulled through the dueling combine (jh_rbnet_c51_step)
   int pend_parts = 0;   // conv1 weight-gradient partials not yet summed into the bucket (jh_rbnet_backward_deferred): their count
+  int tgt_rows = 0;     // rows the target slot's activation buffers (act1 / act2 / feat / h [1]) hold: maxB, or what jh_rbnet_reserve_target_rows asked for
   std::vector<void*> owned;
 };
 
@@ -748,6 +749,7 @@ JH_EXPORT int jh_rbnet_create(jh_ctx* ctx, int32_t kind, int32_t head_cnn, int32
     return rc;
   }
   n->params = d_params; n->target = d_target; n->grads = d_grads; n->m = d_m; n->v = d_v;
+  n->tgt_rows = max_batch;
   const NoisyDims& d = n->nd;
   const int H = hidden;
   const size_t B = (size_t)max_batch;
@@ -1150,6 +1152,67 @@ JH_EXPORT int jh_rbnet_learn_forward(jh_rbnet* n, const void* d_x, int32_t x_dty
   int rc = jh_rbnet_learn_trunk(n, d_x, x_dtype, B, stream);
   if (rc) return rc;
   return jh_rbnet_learn_heads(n, B, d_noise, d_logits, stream);
+}
+
+// Munchausen DQN's learn() (agent/m_dqn.py:31-38) evaluates the TARGET network on both halves of the batch: its slot then holds 2B rows
+// where every other agent needs B.  Grown on request only (through the net's own allocator, once, at construction of the agent: nothing
+// allocates inside a captured learn()); the buffers it replaces are released.  rows <= 2 * max_batch: what the im2col tables cover.
+JH_EXPORT int jh_rbnet_reserve_target_rows(jh_rbnet* n, int32_t rows) {
+  JH_ARG(n != nullptr);
+  JH_ARG(rows > 0 && rows <= 2 * n->maxB);
+  if (rows <= n->tgt_rows) return JH_OK;
+  JH_HIP(hipSetDevice(n->ctx->device));
+  JH_HIP(hipDeviceSynchronize());  // nothing in flight reads the buffers that go
+  const size_t R = (size_t)rows;
+  float* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
+  float** old[4] = {&n->act1[1], &n->act2[1], &n->feat[1], &n->h[1]};
+  const size_t floats[4] = {n->cnn ? R * n->P1 * 32 : 0, n->cnn ? R * n->P2 * 64 : 0, R * n->F, R * n->hidden};
+  int rc = JH_OK;
+  for (int i = 0; i < 4 && !rc; ++i)
+    if (floats[i]) rc = rb_alloc(n, (void**)&fresh[i], floats[i] * sizeof(float), true);
+  if (rc) return rc;  // what was allocated stays owned by the net and goes with it; the old buffers are still in place
+  for (int i = 0; i < 4; ++i) {
+    if (!floats[i]) continue;
+    for (size_t k = 0; k < n->owned.size(); ++k)
+      if (n->owned[k] == (void*)*old[i]) {
+        (void)hipFree(n->owned[k]);
+        n->owned.erase(n->owned.begin() + (long)k);
+        break;
+      }
+    *old[i] = fresh[i];
+  }
+  n->tgt_rows = rows;
+  return JH_OK;
+}
+
+// The three forwards of M_DQN.learn (agent/m_dqn.py:31-38): d_x = [state; next_state] as for jh_rbnet_learn_forward,
+//   logits[0] = online(state)   logits[1] = target(state)   logits[2] = target(next_state)
+// The online trunk runs over the B state rows, the target trunk over all 2B rows, in the same grouped launches as jh_rbnet_learn_forward's
+// (two jobs per layer).  The online activations of the state rows sit at the start of slot 0 as after jh_rbnet_learn_forward:
+// jh_rbnet_backward continues from here unchanged.
+JH_EXPORT int jh_rbnet_learn_forward_m(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits, jh_stream stream) {
+  JH_ARG(n && d_x && d_logits);
+  if (n->noisy) return jh_fail(JH_ERR_ARG, "jh_rbnet_learn_forward_m: kinds discrete_q_network and dueling only (a noisy network has no Munchausen agent)");
+  (void)d_noise;
+  JH_ARG(B > 0 && B <= n->maxB);
+  JH_ARG(x_dtype == JH_U8 || x_dtype == JH_F32);
+  if (n->tgt_rows < 2 * B)
+    return jh_fail(JH_ERR_STATE, "jh_rbnet_learn_forward_m: the target slot holds %d rows, 2 * B = %d needed (jh_rbnet_reserve_target_rows)", n->tgt_rows, 2 * B);
+  TrunkJob tj[2] = {{n->params, d_x, B, 0}, {n->target, d_x, 2 * B, 1}};
+  int rc = rb_trunk(n, tj, 2, x_dtype == JH_U8, jh_s(stream));
+  if (rc) return rc;
+  n->last_x = d_x; n->last_x_u8 = x_dtype == JH_U8; n->last_B = B;
+  const size_t lsz = (size_t)B * n->NA;
+  float* const* sin = n->has_l ? n->h : n->feat;  // what the streams read
+  HeadJob hj[3] = {{n->params, nullptr, sin[0], d_logits},
+                   {n->target, nullptr, sin[1], d_logits + lsz},
+                   {n->target, nullptr, sin[1] + (size_t)B * n->in1, d_logits + 2 * lsz}};
+  rc = rb_heads(n, hj, 3, B, jh_s(stream));
+  if (rc) return rc;
+  n->last_noise = nullptr;
+  n->raw_heads = 0;
+  n->dx_ready = 0;
+  return JH_OK;
 }
 
 static int rb_noisy_grad(jh_rbnet* n, hipStream_t st) {

@@ -833,6 +833,23 @@ def qr_loss(logit, next_logit_online, target_logit, action, reward, done, tau, g
     return g, stats
 
 
+def mdqn_loss(q, q_target, q_next_target, action, reward, done, gamma, alpha, tau, l_0, stats=None):
+    """jh_mdqn_loss (m_dqn.py:29-59): q / q_target / q_next_target [B, A] = online(s), target(s), target(s'), action / reward / done [B]
+    (or [B, 1]).  Returns (grad_q [B, A], stats f32[4] = {loss, max taken Q, mean Munchausen term, mark})."""
+    q = _f32(q)
+    B, A = (int(v) for v in q.shape)
+    qt, qn = _f32(q_target), _f32(q_next_target)
+    assert tuple(qt.shape) == (B, A) and tuple(qn.shape) == (B, A)
+    a, r, d = _f32(action).reshape(-1), _f32(reward).reshape(-1), _f32(done).reshape(-1)
+    assert a.numel() == B and r.numel() == B and d.numel() == B
+    g = torch.empty_like(q)
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.float32, device=q.device)
+    L.check(L.load().jh_mdqn_loss(L.ctx(_dev(q)), B, A, L.ptr(q), L.ptr(qt), L.ptr(qn), L.ptr(a), L.ptr(r), L.ptr(d), float(gamma), float(alpha), float(tau), float(l_0),
+                                  L.ptr(g), L.ptr(stats), L.stream_ptr()))
+    return g, stats
+
+
 def quantile_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_all=False):
     """jh_quantile_act: network outputs [R, A, N] (N quantiles per action, Q = their mean) -> (action int64 [R], q_taken float32 [R],
     q_all | None) on the device.  eps / u / rand_action as in value_act."""
@@ -1086,6 +1103,18 @@ class RainbowNet:
         """x_all = [state; next_state] (2B rows), noise [3, noise_len] (rainbow; else None) -> out [3, B, A, K]."""
         assert x_all.is_contiguous() and (noise is None or noise.is_contiguous()) and out.is_contiguous() and int(x_all.shape[0]) == 2 * B
         L.check(self.lib.jh_rbnet_learn_forward(self.h, L.ptr(x_all), self._xdt(x_all), int(B), L.ptr(noise), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def reserve_target_rows(self, rows):
+        """Room for `rows` (<= 2 * max_batch) rows in the target network's activation buffers (jh_rbnet_reserve_target_rows): `learn_forward_m`
+        needs 2B.  Allocates: call it once, outside any graph capture."""
+        L.check(self.lib.jh_rbnet_reserve_target_rows(self.h, int(rows)))
+
+    def learn_forward_m(self, x_all, B, noise, out):
+        """x_all = [state; next_state] (2B rows) -> out [3, B, A, K] = online(state), target(state), target(next_state) (jh_rbnet_learn_forward_m);
+        `backward` continues from it as after `learn_forward`.  q / dueling networks; `noise` is ignored."""
+        assert x_all.is_contiguous() and out.is_contiguous() and int(x_all.shape[0]) == 2 * B
+        L.check(self.lib.jh_rbnet_learn_forward_m(self.h, L.ptr(x_all), self._xdt(x_all), int(B), L.ptr(noise), L.ptr(out), L.stream_ptr()))
         return out
 
     def prepare_noise(self, noise):
