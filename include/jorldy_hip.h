@@ -323,6 +323,60 @@ int jh_qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logi
 int jh_quantile_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
                     const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream);
 
+/* ------------------------------------------------------------------ IQN
+ * The implicit quantile network with an MLP head (core/network/iqn.py:9-47) and what IQN.learn() / act() do around it
+ * (core/agent/iqn.py:60-146).  With S inputs, width H (H % 4 == 0), E cosine features, N samples per row (1 <= N <= 256), A actions:
+ *   feat = relu(head.l(x)) [rows][H], psi = relu(state_embed(feat)) [rows][H]                         (iqn.py:28-29)
+ *   cos_term[r][n][i] = cos(tau[r][n] * i_pi[i]), i_pi = arange(0, E) * pi as FLOAT32; the product is rounded to float32 before
+ *   the cosine (iqn.py:14, 40-47), phi = relu(sample_embed(cos_term)) [rows][N][H], embed = psi[:, None, :] * phi,
+ *   relu(l1), relu(l2), q -> [rows][N][A]                                                              (iqn.py:31-38)
+ * tau is the CALLER's draw (uniform in [tau_min, tau_max], iqn.py:41-45).  Parameters live in caller-owned flat fp32 buckets as
+ * jh_rbnet's do; jh_iqnnet_segment describes the layout (rows x cols, row-major [out][in] = the reference's own, 16-byte aligned):
+ *   0 head.l.weight [H][S]  1 head.l.bias   2 state_embed.weight [H][H]  3 bias   4 sample_embed.weight [H][E]  5 bias
+ *   6 l1.weight [H][H]  7 bias   8 l2.weight [H][H]  9 bias   10 q.weight [A][H]  11 q.bias
+ * Every dense contraction is a launch of the tile engine (jh_tgemm_dense's kernel).                                           */
+typedef struct jh_iqnnet jh_iqnnet;
+int64_t jh_iqnnet_param_count_for(int32_t state_size, int32_t hidden, int32_t embedding_dim, int32_t num_sample, int32_t action_size);
+int jh_iqnnet_create(jh_ctx* ctx, int32_t state_size, int32_t hidden, int32_t embedding_dim, int32_t num_sample, int32_t action_size,
+                     int32_t max_batch, float* d_params, float* d_target, float* d_grads, float* d_m, float* d_v, jh_iqnnet** out);
+void jh_iqnnet_destroy(jh_iqnnet* n);
+int32_t jh_iqnnet_segment_count(void);
+int jh_iqnnet_segment(const jh_iqnnet* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols);
+/* torch.optim.Adam's (lr, beta1, beta2, eps) and step counter; every config.iqn.* uses Adam */
+int jh_iqnnet_set_hyper(jh_iqnnet* n, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream);
+int jh_iqnnet_set_lr(jh_iqnnet* n, double lr, jh_stream stream);
+int jh_iqnnet_sync_target(jh_iqnnet* n, jh_stream stream);
+/* network(x) with the draws d_tau [rows][N]: rows <= max_batch, which 0 online / 1 target -> d_logits [rows][N][A]            */
+int jh_iqnnet_forward(jh_iqnnet* n, int32_t which, const float* d_x, int32_t rows, const float* d_tau, float* d_logits, jh_stream stream);
+/* The three forwards of IQN.learn() (iqn.py:90, 100, 103), each with its own draw: d_x = [state; next_state] (2B rows),
+ * d_tau [3][B][N] -> d_logits [3][B][N][A] = online(state), online(next_state), target(next_state); every layer is one grouped
+ * launch for the online rows and the target rows.  The activations of online(state) stay in place for jh_iqnnet_backward.     */
+int jh_iqnnet_learn_forward(jh_iqnnet* n, const float* d_x, int32_t B, const float* d_tau, float* d_logits, jh_stream stream);
+/* loss.backward() (iqn.py:128) given d(loss)/d(online(state) output) [B][N][A] (from jh_iqn_loss); fills d_grads              */
+int jh_iqnnet_backward(jh_iqnnet* n, const float* d_g, jh_stream stream);
+/* [clip_grad_norm_(max_norm) when max_norm > 0,] torch.optim.Adam's step (iqn.py:129); advances the step counter              */
+int jh_iqnnet_optim_step(jh_iqnnet* n, float max_norm, jh_stream stream);
+/* The network's elementwise steps on their own (tests): the cosine features d_out [rows][E] of d_tau [rows] (iqn.py:46); the
+ * Hadamard product d_out [B][N][H] = d_psi [B][H] * d_phi [B][N][H] (iqn.py:34) and its backward through both relus (iqn.py:29, 32):
+ * d_grad_phi_pre = d_grad_embed * psi * (phi > 0), d_grad_psi_pre [B][H] = (sum over n, in a fixed order, of d_grad_embed * phi) * (psi > 0). */
+int jh_iqn_cos_features(jh_ctx* ctx, int64_t rows, int32_t E, const float* d_tau, float* d_out, jh_stream stream);
+int jh_iqn_hadamard(jh_ctx* ctx, int32_t B, int32_t N, int32_t H, const float* d_psi, const float* d_phi, float* d_out, jh_stream stream);
+int jh_iqn_hadamard_backward(jh_ctx* ctx, int32_t B, int32_t N, int32_t H, const float* d_grad_embed, const float* d_psi, const float* d_phi,
+                             float* d_grad_phi_pre, float* d_grad_psi_pre, jh_stream stream);
+/* jh_qr_loss on the network's [B][N][A] layout with tau per sample (iqn.py:89-121): d_logit / d_next_logit_online / d_target_logit
+ * float32 [B][N][A]; d_tau float32 [B][N], the draw of the FIRST forward (1 - tau formed in fp32 as iqn.py:120 does).  With
+ * P[i] = logit[b][i][action[b]], a* = first maximum over a of mean_n next_logit_online[b][n][a] (iqn.py:106, 142-146) and
+ * T[j] = reward + (1 - done) * gamma * target_logit[b][j][a*]: e = T[j] - P[i],
+ * loss = 1 / (B N) * sum_b sum_j sum_i (e < 0 ? 1 - tau[b][i] : tau[b][i]) * smooth_l1(e, beta 1).
+ * d_grad_logit float32 [B][N][A], every entry written (zero for the actions not taken); d_stats float32[8] as jh_qr_loss leaves
+ * them.  1 <= N <= 256.  Two launches, no floating-point atomics: the same inputs give the same bits, eagerly or replayed.      */
+int jh_iqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online,
+                const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done, const float* d_tau,
+                float gamma, float* d_grad_logit, float* d_stats, jh_stream stream);
+/* IQN.act (iqn.py:60-76) for R actor rows: jh_quantile_act's rules on d_logits float32 [R][N][A] (Q = mean over the N samples). */
+int jh_iqn_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
+               const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream);
+
 /* ------------------------------------------------------------------ native policy-value MLP
  * The encoder of the PPO configs (core/network/head.py:6-18 MLP head + policy_value.py:8-57):
  * S -> H relu -> H relu -> {A logits | A mu, A log_std} + value, as hand-written kernels

@@ -86,6 +86,23 @@ _PROTOS = {
     "jh_mdqn_loss": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "jh_qr_loss": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
     "jh_quantile_act": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_iqnnet_param_count_for": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "jh_iqnnet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _pp]),
+    "jh_iqnnet_destroy": (None, [_vp]),
+    "jh_iqnnet_segment_count": (_i32, []),
+    "jh_iqnnet_segment": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
+    "jh_iqnnet_set_hyper": (C.c_int, [_vp, _f64, _f64, _f64, _f64, _i64, _vp]),
+    "jh_iqnnet_set_lr": (C.c_int, [_vp, _f64, _vp]),
+    "jh_iqnnet_sync_target": (C.c_int, [_vp, _vp]),
+    "jh_iqnnet_forward": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "jh_iqnnet_learn_forward": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "jh_iqnnet_backward": (C.c_int, [_vp, _vp, _vp]),
+    "jh_iqnnet_optim_step": (C.c_int, [_vp, _f32, _vp]),
+    "jh_iqn_cos_features": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    "jh_iqn_hadamard": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "jh_iqn_hadamard_backward": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_iqn_loss": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "jh_iqn_act": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_pponet_param_count": (_i64, [_i32, _i32, _i32, _i32]),
     "jh_pponet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_uint64, _pp]),
     "jh_pponet_destroy": (None, [_vp]),

@@ -34,11 +34,11 @@ class DQN(NativeValueNetMixin, BaseAgent):
         self.graph_with_collective = os.environ.get("JH_GRAPH_DP", "1") == "1"
         self.action_size = action_size
         self.action_type = "discrete"
-        require_native(backend, network, head, state_size, hidden_size, optim_config)
+        self._require_native(backend, network, head, state_size, hidden_size, optim_config)
         self.backend = "native"
         self._net = None
         self._init_native(network, state_size, action_size, 1, hidden_size, head, batch_size, optim_config,
-                          Network(network, state_size, action_size, D_hidden=hidden_size, head=head))
+                          self._initial_net(network, state_size, action_size, hidden_size, head))
         self.gamma = gamma
         self.epsilon = epsilon_init
         self.epsilon_init = epsilon_init
@@ -71,6 +71,14 @@ class DQN(NativeValueNetMixin, BaseAgent):
         # trunk.  On this stack a fork / join inside a hipGraph costs more than the 42 us it hides: Rainbow 2 969 -> 2 655 updates/s, Ape-X
         # 988 -> 967 (two alternating pairs each, round 4).  Default: one stream, one chain.
         self._overlap = os.environ.get("JH_LEARN_OVERLAP", "0") == "1"
+
+    def _require_native(self, backend, network, head, state_size, hidden_size, optim_config):
+        """What this agent's network may be; an agent with a network of its own (IQN) overrides it together with _initial_net / _init_native."""
+        require_native(backend, network, head, state_size, hidden_size, optim_config)
+
+    def _initial_net(self, network, state_size, action_size, hidden_size, head):
+        """The parameter container whose initialisation the native network imports."""
+        return Network(network, state_size, action_size, D_hidden=hidden_size, head=head)
 
     @torch.no_grad()
     def act(self, state, training=True):

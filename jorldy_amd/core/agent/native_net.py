@@ -101,11 +101,17 @@ class NativeValueNetMixin:
     """Agent-side plumbing of the native backend (state kept on the agent: _net, _opt_name, _optim_config,
     _lr0, _lr_now, _adam_steps)."""
 
+    _net_view = NativeNet  # what `agent.network` / `agent.target_network` are; an agent whose network is called differently (IQN) sets its own
+
+    def _build_native_net(self, network, state_size, action_size, num_support, hidden_size, head, batch_size, noise_type):
+        """The engine object behind the agent: ops.RainbowNet for the DQN family and Rainbow; ops.IQNNet presents the same surface."""
+        return ops.RainbowNet(state_size, action_size, num_support, hidden_size, head, batch_size, self.device, kind=_KIND_OF[network], noise_type=noise_type)
+
     def _init_native(self, network, state_size, action_size, num_support, hidden_size, head, batch_size, optim_config, torch_net, noise_type="factorized"):
-        self._net = ops.RainbowNet(state_size, action_size, num_support, hidden_size, head, batch_size, self.device, kind=_KIND_OF[network], noise_type=noise_type)
+        self._net = self._build_native_net(network, state_size, action_size, num_support, hidden_size, head, batch_size, noise_type)
         self._net.import_state(torch_net.state_dict())  # the reference's initialisation (orthogonal / uniform, utils.py:89-124)
         self._net.sync_target()
-        self.network, self.target_network = NativeNet(self._net, 0), NativeNet(self._net, 1)
+        self.network, self.target_network = self._net_view(self._net, 0), self._net_view(self._net, 1)
         self._optim_config = dict(optim_config)
         self._opt_name = optim_config.get("name", "adam").lower()
         d = Optimizer(**optim_config, params=[torch.nn.Parameter(torch.zeros(1))]).defaults

@@ -9,6 +9,7 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   continuous_policy_value      core/network/policy_value.py:38-57
   dueling                      core/network/dueling.py:8-35
   rainbow                      core/network/rainbow.py:8-94 (+ utils.py:55-107 noisy linear)
+  iqn                          core/network/iqn.py:9-47
 """
 import torch
 
@@ -136,12 +137,29 @@ class Rainbow(BaseNetwork):
         orthogonal_init(self.l)
 
 
+class IQN(BaseNetwork):
+    """Implicit quantile network (iqn.py:9-24).  The reference's orthogonal_init call names sample_embed twice and state_embed never
+    (iqn.py:23): state_embed keeps nn.Linear's default initialisation, and so it does here."""
+
+    def __init__(self, D_in, D_out, D_em=64, N_sample=64, D_hidden=512, head="mlp"):
+        super().__init__(D_in, D_hidden, head)
+        self.N_sample, self.D_em = N_sample, D_em
+        self.state_embed = torch.nn.Linear(self.head.D_head_out, D_hidden)
+        self.sample_embed = torch.nn.Linear(D_em, D_hidden)
+        self.l1 = torch.nn.Linear(D_hidden, D_hidden)
+        self.l2 = torch.nn.Linear(D_hidden, D_hidden)
+        self.q = torch.nn.Linear(D_hidden, D_out)
+        orthogonal_init([self.sample_embed, self.sample_embed, self.l1, self.l2])
+        orthogonal_init(self.q, "linear")
+
+
 network_dict = {
     "discrete_q_network": DiscreteQ_Network,
     "discrete_policy_value": DiscretePolicyValue,
     "continuous_policy_value": ContinuousPolicyValue,
     "dueling": Dueling,
     "rainbow": Rainbow,
+    "iqn": IQN,
 }
 
 

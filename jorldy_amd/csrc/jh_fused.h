@@ -179,3 +179,9 @@ struct C51Duel {
 // jh_dqn.hip.  a.partial is filled in here.  duel: block kernel with the combine folded in (B <= 1024).  per: the statistics
 // launch also writes the priorities a.prio back into the tree's leaves (the climb is the caller's next launch).
 int jh_c51_run(jh_ctx* ctx, C51Args a, const C51Duel* duel, const PerDeltaArgs* per, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------- Adam on flat buckets
+// jh_rbnet.hip's optimizer kernels ([global-norm clip,] torch.optim.Adam step, step counter advanced inside) for any owner of flat fp32
+// parameter / gradient / moment buckets (jh_iqn.hip).  hyper: JH_HY_FLOATS floats; ticket: 2048 zeroed bytes; norm_partial: 256 floats.
+int jh_flat_adam_step(int64_t n_params, float* p, float* g, float* m, float* v, float* hyper, unsigned* ticket, float* norm_partial, float max_norm,
+                      hipStream_t st);

@@ -1399,3 +1399,15 @@ JH_EXPORT int jh_rbnet_optim_step(jh_rbnet* n, int32_t optimizer, float max_norm
 }
 
 JH_EXPORT int jh_rbnet_adam_step(jh_rbnet* n, jh_stream stream) { return jh_rbnet_optim_step(n, 0, 0.f, stream); }
+
+// The same optimizer kernels for another owner of flat fp32 buckets (jh_iqn.hip): [clip_grad_norm_(max_norm),] torch.optim.Adam's step.
+// hyper: JH_HY_FLOATS floats; ticket: 2048 zeroed bytes; norm_partial: 256 floats.
+int jh_flat_adam_step(int64_t n_params, float* p, float* g, float* m, float* v, float* hyper, unsigned* ticket, float* norm_partial, float max_norm, hipStream_t st) {
+  if (max_norm > 0.f) {
+    JH_LAUNCH(jh_rb_gradnorm_kernel, dim3(256), dim3(256), 0, st, n_params, g, norm_partial);
+    JH_LAUNCH_CHECK();
+  }
+  JH_LAUNCH(jh_rb_optim_kernel<0>, dim3(512), dim3(256), 0, st, n_params, p, g, m, v, hyper, ticket, norm_partial, 256, max_norm, OptFuse{});
+  JH_LAUNCH_CHECK();
+  return JH_OK;
+}

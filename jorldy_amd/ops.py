@@ -865,6 +865,67 @@ def quantile_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_al
     return act, q, q_all
 
 
+def iqn_loss(logit, next_logit_online, target_logit, action, reward, done, tau, gamma, stats=None):
+    """jh_iqn_loss (iqn.py:89-121): logit / next_logit_online / target_logit [B, N, A] as the network writes them, action / reward / done [B]
+    (or [B, 1]), tau float32 [B, N] = the draw of the forward that produced `logit`.  Returns (grad_logit [B, N, A], stats f32[8] as qr_loss)."""
+    z = _f32(logit)
+    B, N, A = (int(v) for v in z.shape)
+    zn, zt, t = _f32(next_logit_online), _f32(target_logit), _f32(tau)
+    assert tuple(zn.shape) == (B, N, A) and tuple(zt.shape) == (B, N, A) and t.numel() == B * N and t.device == z.device
+    a, r, d = _f32(action).reshape(-1), _f32(reward).reshape(-1), _f32(done).reshape(-1)
+    assert a.numel() == B and r.numel() == B and d.numel() == B
+    g = torch.empty_like(z)
+    if stats is None:
+        stats = torch.empty(8, dtype=torch.float32, device=z.device)
+    L.check(L.load().jh_iqn_loss(L.ctx(_dev(z)), B, A, N, L.ptr(z), L.ptr(zn), L.ptr(zt), L.ptr(a), L.ptr(r), L.ptr(d), L.ptr(t), float(gamma), L.ptr(g), L.ptr(stats),
+                                 L.stream_ptr()))
+    return g, stats
+
+
+def iqn_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_all=False):
+    """jh_iqn_act: network outputs [R, N, A] (N samples per row, Q = their mean) -> (action int64 [R], q_taken float32 [R], q_all | None)
+    on the device.  eps / u / rand_action as in value_act."""
+    lg = _f32(logits)
+    R, N, A = (int(v) for v in lg.shape)
+    dev = lg.device
+    act, q = (torch.empty(R, dtype=torch.int64, device=dev), torch.empty(R, dtype=torch.float32, device=dev)) if out is None else out
+    q_all = torch.empty(R, A, dtype=torch.float32, device=dev) if want_q_all else None
+    if eps is not None:
+        eps, u, rand_action = (np.ascontiguousarray(eps, dtype=np.float32), np.ascontiguousarray(u, dtype=np.float64), np.ascontiguousarray(rand_action, dtype=np.int64))
+        assert eps.size == R and u.size == R and rand_action.size == R
+    L.check(L.load().jh_iqn_act(L.ctx(_dev(lg)), R, A, N, L.ptr(lg), L.ptr(eps), L.ptr(u), L.ptr(rand_action), L.ptr(act), L.ptr(q), L.ptr(q_all), L.stream_ptr()))
+    return act, q, q_all
+
+
+def iqn_cos_features(tau, E):
+    """jh_iqn_cos_features: tau float32 [...] -> cos(tau * (arange(E) * pi as float32)) [..., E], the argument rounded to float32 (iqn.py:14, 46)."""
+    t = _f32(tau)
+    out = torch.empty(tuple(t.shape) + (int(E),), dtype=torch.float32, device=t.device)
+    L.check(L.load().jh_iqn_cos_features(L.ctx(_dev(t)), int(t.numel()), int(E), L.ptr(t), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def iqn_hadamard(psi, phi):
+    """jh_iqn_hadamard: psi [B, H], phi [B, N, H] -> psi[:, None, :] * phi (iqn.py:34)."""
+    p, f = _f32(psi), _f32(phi)
+    B, N, H = (int(v) for v in f.shape)
+    assert tuple(p.shape) == (B, H)
+    out = torch.empty_like(f)
+    L.check(L.load().jh_iqn_hadamard(L.ctx(_dev(f)), B, N, H, L.ptr(p), L.ptr(f), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def iqn_hadamard_backward(grad_embed, psi, phi):
+    """jh_iqn_hadamard_backward: the product's backward through both relus -> (d phi_pre [B, N, H], d psi_pre [B, H]); psi / phi are the
+    relu outputs of the forward."""
+    g, p, f = _f32(grad_embed), _f32(psi), _f32(phi)
+    B, N, H = (int(v) for v in f.shape)
+    assert tuple(p.shape) == (B, H) and tuple(g.shape) == (B, N, H)
+    dphi, dpsi = torch.empty_like(f), torch.empty_like(p)
+    L.check(L.load().jh_iqn_hadamard_backward(L.ctx(_dev(f)), B, N, H, L.ptr(g), L.ptr(p), L.ptr(f), L.ptr(dphi), L.ptr(dpsi), L.stream_ptr()))
+    return dphi, dpsi
+
+
 # ============================================================================= host collector
 class CartPoleVec:
     """W synthetic CartPole-v1 envs stepped in one native call (jh_cartpole_*)."""
@@ -1173,6 +1234,128 @@ class RainbowNet:
     def optim_step(self, optimizer="adam", max_norm=None):
         """[clip_grad_norm_(max_norm)] + optimizer.step(); optimizer in {"adam", "rmsprop"}."""
         L.check(self.lib.jh_rbnet_optim_step(self.h, {"adam": 0, "rmsprop": 1}[optimizer], float(max_norm or 0.0), L.stream_ptr()))
+
+
+class IQNNet:
+    """jh_iqnnet_*: the implicit quantile network with an MLP head (network/iqn.py:9-47) -- head.l, state_embed, cosine features of the
+    caller's tau draws, sample_embed, Hadamard product, l1, l2, q -- with the three learn() forwards, the backward and Adam as tile-engine
+    launches plus the elementwise kernels of jh_iqn.hip.  It presents RainbowNet's surface (flat buckets, export / import in the
+    reference's state_dict keys, set_hyper / set_lr / sync_target, forward / learn_forward / backward / optim_step), so the agents'
+    native plumbing (NativeValueNetMixin) works on it unchanged.  Outputs are [rows, N, A]; K = N.
+
+    Where RainbowNet takes a noise draw, this takes tau: `forward(x, which, tau)` with tau [rows, N], `learn_forward(x_all, B, tau, out)`
+    with tau [3, B, N].  forward() without tau draws it uniformly in `tau_range` on the device (torch.rand), or takes `tau_inject`."""
+
+    _SEG = ("head.l.weight", "head.l.bias", "state_embed.weight", "state_embed.bias", "sample_embed.weight", "sample_embed.bias", "l1.weight", "l1.bias",
+            "l2.weight", "l2.bias", "q.weight", "q.bias")
+    kind, cnn, noise_len = "iqn", False, 0
+
+    def __init__(self, state_size, action_size, embedding_dim, num_sample, hidden, max_batch, device):
+        self.lib = L.load()
+        self.device = torch.device(device)
+        self.ctx = L.ctx(self.device.index)
+        self.S, self.A, self.E, self.N, self.H, self.maxB = int(state_size), int(action_size), int(embedding_dim), int(num_sample), int(hidden), int(max_batch)
+        self.K = self.N
+        self.tau_range, self.tau_inject = (0.0, 1.0), None
+        n = int(self.lib.jh_iqnnet_param_count_for(self.S, self.H, self.E, self.N, self.A))
+        if n <= 0:
+            L.check(-2)
+        self.n_params = n
+        mk = lambda: torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.params, self.target, self.grads, self.m, self.v = mk(), mk(), mk(), mk(), mk()
+        self.h = C.c_void_p()
+        L.check(self.lib.jh_iqnnet_create(self.ctx, self.S, self.H, self.E, self.N, self.A, self.maxB, L.ptr(self.params), L.ptr(self.target), L.ptr(self.grads),
+                                          L.ptr(self.m), L.ptr(self.v), C.byref(self.h)))
+        assert int(self.lib.jh_iqnnet_segment_count()) == len(self._SEG)
+        self.seg = {}
+        for i, name in enumerate(self._SEG):
+            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
+            L.check(self.lib.jh_iqnnet_segment(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
+            self.seg[name] = (off.value, rows.value, cols.value)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.jh_iqnnet_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _pairs(self, bucket):
+        """[(reference key, view of the bucket shaped like the reference tensor)] in the order of the reference module's state_dict."""
+        out = []
+        for name in self._SEG:
+            off, rows, cols = self.seg[name]
+            v = bucket[off : off + rows * cols]
+            out.append((name, v.view(rows, cols) if name.endswith(".weight") else v))
+        return out
+
+    def export_state(self, bucket=None):
+        from collections import OrderedDict
+
+        bucket = self.params if bucket is None else bucket
+        return OrderedDict((k, v.clone()) for k, v in self._pairs(bucket))
+
+    @torch.no_grad()
+    def import_state(self, sd, bucket=None):
+        bucket = self.params if bucket is None else bucket
+        pairs = dict(self._pairs(bucket))
+        missing = [k for k in pairs if k not in sd]
+        if missing:
+            raise KeyError(f"state_dict is missing {missing}")
+        for k, v in pairs.items():
+            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
+            if tuple(src.shape) != tuple(v.shape):
+                raise ValueError(f"{k}: expected {tuple(v.shape)}, got {tuple(src.shape)}")
+            v.copy_(src)
+
+    def set_hyper(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0, centered=False):
+        L.check(self.lib.jh_iqnnet_set_hyper(self.h, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
+
+    def set_lr(self, lr):
+        L.check(self.lib.jh_iqnnet_set_lr(self.h, float(lr), L.stream_ptr()))
+
+    def sync_target(self):
+        L.check(self.lib.jh_iqnnet_sync_target(self.h, L.stream_ptr()))
+
+    def draw_tau(self, rows, lo=None, hi=None):
+        """tau [rows, N] on the device: the injected draw, or uniform in [lo, hi] (default `tau_range`) like the reference's uniform_ (iqn.py:41-45)."""
+        if self.tau_inject is not None:
+            return torch.as_tensor(self.tau_inject).to(self.device, torch.float32).reshape(rows, self.N).contiguous()
+        lo, hi = self.tau_range if lo is None else (lo, hi)
+        t = torch.rand(rows, self.N, device=self.device)
+        return t if (lo, hi) == (0.0, 1.0) else t * (hi - lo) + lo
+
+    def forward(self, x, which=0, tau=None, out=None):
+        """network(x) -> logits [rows, N, A]; rows <= max_batch.  tau [rows, N] or None (see draw_tau)."""
+        assert x.is_contiguous() and x.device == self.device and x.dtype == torch.float32
+        rows = int(x.shape[0])
+        tau = self.draw_tau(rows) if tau is None else tau
+        assert tau.is_contiguous() and tau.dtype == torch.float32 and tau.numel() == rows * self.N and tau.device == self.device
+        if out is None:
+            out = torch.empty(rows, self.N, self.A, dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.numel() == rows * self.N * self.A
+        L.check(self.lib.jh_iqnnet_forward(self.h, int(which), L.ptr(x), rows, L.ptr(tau), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def learn_forward(self, x_all, B, tau, out):
+        """x_all = [state; next_state] (2B rows), tau [3, B, N] -> out [3, B, N, A] = online(state), online(next_state), target(next_state)."""
+        assert x_all.is_contiguous() and x_all.dtype == torch.float32 and int(x_all.shape[0]) == 2 * B
+        assert tau.is_contiguous() and tau.dtype == torch.float32 and tau.numel() == 3 * B * self.N
+        assert out.is_contiguous() and out.numel() == 3 * B * self.N * self.A
+        L.check(self.lib.jh_iqnnet_learn_forward(self.h, L.ptr(x_all), int(B), L.ptr(tau), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def backward(self, g, defer=False):
+        """g = d(loss)/d(logits of online(state)) [B, N, A]."""
+        assert g.is_contiguous() and g.dtype == torch.float32
+        L.check(self.lib.jh_iqnnet_backward(self.h, L.ptr(g), L.stream_ptr()))
+
+    def optim_step(self, optimizer="adam", max_norm=None):
+        """[clip_grad_norm_(max_norm)] + Adam's step."""
+        if optimizer != "adam":
+            raise ValueError(f"IQNNet has Adam only (every config.iqn.* uses it), got {optimizer!r}")
+        L.check(self.lib.jh_iqnnet_optim_step(self.h, float(max_norm or 0.0), L.stream_ptr()))
 
 
 class StagingRing:
