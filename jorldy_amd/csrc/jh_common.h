@@ -105,6 +105,15 @@ int jh_ctx_slab(jh_ctx* ctx, size_t bytes, jh_pinned_slab** out);
 // Mark the slab busy until everything enqueued on `stream` so far has executed.
 int jh_ctx_slab_release(jh_ctx* ctx, jh_pinned_slab* slab, hipStream_t stream);
 int jh_ctx_scratch(jh_ctx* ctx, size_t bytes, void** out);
+// The host's epsilon-greedy draws of `rows` actor rows (eps float32, u float64, rand_action int64) copied into ONE slab the acting
+// kernel reads in place.  h_eps == nullptr (greedy): no slab, null pointers.  The caller launches, then releases out->slab if it is set.
+struct jh_draws {
+  jh_pinned_slab* slab;
+  const float* eps;
+  const double* u;
+  const int64_t* rand_action;
+};
+int jh_ctx_stage_draws(jh_ctx* ctx, size_t rows, const float* h_eps, const double* h_u, const int64_t* h_rand_action, jh_draws* out);
 
 // ---------------------------------------------------------------- object layouts (shared between TUs)
 struct jh_store {

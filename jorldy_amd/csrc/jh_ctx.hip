@@ -137,6 +137,22 @@ int jh_ctx_slab_release(jh_ctx* ctx, jh_pinned_slab* slab, hipStream_t stream) {
   return JH_OK;
 }
 
+int jh_ctx_stage_draws(jh_ctx* ctx, size_t rows, const float* h_eps, const double* h_u, const int64_t* h_rand_action, jh_draws* out) {
+  *out = jh_draws{nullptr, nullptr, nullptr, nullptr};
+  if (!h_eps) return JH_OK;
+  // the draws ride in a pinned, device-mapped slab the kernel reads in place; each array starts on a 256-byte boundary
+  const size_t o_u = ((sizeof(float) * rows + 255) & ~(size_t)255), o_r = o_u + ((sizeof(double) * rows + 255) & ~(size_t)255);
+  int rc = jh_ctx_slab(ctx, o_r + sizeof(int64_t) * rows + 256, &out->slab);
+  if (rc) return rc;
+  memcpy(out->slab->host, h_eps, sizeof(float) * rows);
+  memcpy((char*)out->slab->host + o_u, h_u, sizeof(double) * rows);
+  memcpy((char*)out->slab->host + o_r, h_rand_action, sizeof(int64_t) * rows);
+  out->eps = (const float*)out->slab->dev;
+  out->u = (const double*)((char*)out->slab->dev + o_u);
+  out->rand_action = (const int64_t*)((char*)out->slab->dev + o_r);
+  return JH_OK;
+}
+
 // A stream capture that failed (hipErrorStreamCaptureInvalidated) leaves its stream in the capture until somebody ends it; a caller whose
 // framework gave up half way (torch.cuda.graph.__exit__ raises out of capture_end) calls this before it reuses or abandons the stream.
 // Returns 1 when there was a capture to end, 0 when the stream was not capturing; the sticky error of the failed capture is cleared.

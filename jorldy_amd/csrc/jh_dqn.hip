@@ -821,23 +821,11 @@ JH_EXPORT int jh_value_act(jh_ctx* ctx, int32_t N, int32_t A, int32_t K, const f
   JH_ARG(N > 0 && A > 0 && K > 0);
   JH_ARG((h_eps == nullptr) == (h_u == nullptr) && (h_eps == nullptr) == (h_rand_action == nullptr));
   hipStream_t st = jh_s(stream);
-  const float* d_eps = nullptr;
-  const double* d_u = nullptr;
-  const int64_t* d_ra = nullptr;
-  jh_pinned_slab* slab = nullptr;
-  if (h_eps) {  // the draws ride in a pinned, device-mapped slab the kernel reads in place
-    const size_t o_u = ((sizeof(float) * (size_t)N + 255) & ~(size_t)255), o_r = o_u + ((sizeof(double) * (size_t)N + 255) & ~(size_t)255);
-    int rc = jh_ctx_slab(ctx, o_r + sizeof(int64_t) * (size_t)N + 256, &slab);
-    if (rc) return rc;
-    memcpy(slab->host, h_eps, sizeof(float) * (size_t)N);
-    memcpy((char*)slab->host + o_u, h_u, sizeof(double) * (size_t)N);
-    memcpy((char*)slab->host + o_r, h_rand_action, sizeof(int64_t) * (size_t)N);
-    d_eps = (const float*)slab->dev;
-    d_u = (const double*)((char*)slab->dev + o_u);
-    d_ra = (const int64_t*)((char*)slab->dev + o_r);
-  }
+  jh_draws dr;
+  int rc = jh_ctx_stage_draws(ctx, (size_t)N, h_eps, h_u, h_rand_action, &dr);
+  if (rc) return rc;
   const float dz = K > 1 ? (v_max - v_min) / (float)(K - 1) : 0.f;
-  JH_LAUNCH(jh_value_act_kernel, dim3((N + 3) / 4), dim3(256), 0, st, N, A, K, d_logits, v_min, dz, d_eps, d_u, d_ra, d_action, d_q_taken, d_q_all);
+  JH_LAUNCH(jh_value_act_kernel, dim3((N + 3) / 4), dim3(256), 0, st, N, A, K, d_logits, v_min, dz, dr.eps, dr.u, dr.rand_action, d_action, d_q_taken, d_q_all);
   JH_LAUNCH_CHECK();
-  return slab ? jh_ctx_slab_release(ctx, slab, st) : JH_OK;
+  return dr.slab ? jh_ctx_slab_release(ctx, dr.slab, st) : JH_OK;
 }

@@ -2,10 +2,9 @@
 //   jh_iqnnet_*      the network with an MLP head: x -> relu(head.l) -> psi = relu(state_embed), tau -> cos(tau * i * pi) ->
 //                    phi = relu(sample_embed), embed = psi (.) phi, relu(l1), relu(l2), q  -> [rows][N][A]; the three forwards of
 //                    learn() in shared launches, the backward of online(s), Adam (jh_rbnet's optimizer kernels on the flat buckets)
-//   jh_iqn_loss      pairwise quantile-Huber loss with per-sample tau, forward and backward to online(s)   (iqn.py:89-121)
-//   jh_iqn_act       epsilon-greedy acting on the mean over the N samples                                  (iqn.py:60-76, 142-146)
 // Every dense contraction runs on the tile engine (jh_tgemm.hip) under the call-site name "dense".  The kernels of this file are the
-// elementwise / reducing steps between them: cosine features, the Hadamard product and its backward, loss and acting.
+// elementwise steps between them: cosine features, the Hadamard product and its backward.  The loss and acting entries jh_iqn_loss /
+// jh_iqn_act are the sample-major instantiations of the quantile family's kernels in jh_qr.hip.
 // No floating-point atomics: every sum has a fixed order, so two runs (and a graph replay) give the same bits.
 #include "jh_fused.h"
 #include "jh_tgemm.h"
@@ -67,159 +66,6 @@ __global__ void __launch_bounds__(256) jh_iqn_hadamard_bwd_kernel(int N, int H4,
       acc.x += q.x; acc.y += q.y; acc.z += q.z; acc.w += q.w;
     }
     dpsi[(size_t)b * H4 + h] = make_float4(p.x > 0.f ? acc.x : 0.f, p.y > 0.f ? acc.y : 0.f, p.z > 0.f ? acc.z : 0.f, p.w > 0.f ? acc.w : 0.f);
-  }
-}
-
-// ---------------------------------------------------------------------------------- loss
-struct IqnArgs {
-  int B, A, N;
-  const float *logit, *next_logit, *target_logit, *action, *reward, *done, *tau;
-  float gamma;
-  float *grad, *stats, *partial;  // partial [B][4] = {sum_j sum_i w * huber, max Q, max logit, min logit} of a sample
-};
-
-// Mean over the N samples of action column a of one row block z [N][A] on one wave (logits2Q, iqn.py:142-146): every lane returns it.
-__device__ __forceinline__ float iqn_col_mean(const float* __restrict__ z, int N, int A, int a, int lane, float& cmx, float& cmn) {
-  float s = 0.f;
-  cmx = -3.4e38f;
-  cmn = 3.4e38f;
-  for (int k = lane; k < N; k += 64) {
-    const float v = z[(size_t)k * A + a];
-    s += v;
-    cmx = fmaxf(cmx, v);
-    cmn = fminf(cmn, v);
-  }
-  cmx = jh_wave_max(cmx);
-  cmn = jh_wave_min(cmn);
-  return jh_wave_sum(s) / (float)N;
-}
-
-// jh_qr_block_kernel's algorithm on the [B][N][A] layout with tau per sample: one workgroup of 256 threads per sample (N <= 256:
-// thread i owns prediction sample i).  LDS: [N] Bellman image of the target samples, [A] selector means, [4][3] per-wave statistics,
-// [16] reduction.  Every thread stays to the end: the work of threads i >= N is predicated, not skipped.
-__global__ void __launch_bounds__(256) jh_iqn_block_kernel(IqnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int b = blockIdx.x, A = a.A, N = a.N;
-  float* s_T = smem;           // [N]
-  float* s_qsel = s_T + N;     // [A]
-  float* s_stat = s_qsel + A;  // [4][3]
-  float* s_red = s_stat + 12;  // [16]
-  int act = (int)a.action[b];
-  act = act < 0 ? 0 : (act >= A ? A - 1 : act);
-  const float r = a.reward[b], dn = a.done[b];
-  const size_t base = (size_t)b * N * A;
-  const bool own = tid < N;
-  const int ti = own ? tid : N - 1;
-  const float P = a.logit[base + (size_t)ti * A + act];
-  const float tau = a.tau[(size_t)b * N + ti];  // the FIRST forward's draw for this sample (iqn.py:90, 96)
-  const float inv_tau = 1.f - tau;              // iqn.py:120
-  // ---- phase 1: means over the samples of online(s) (statistics) and online(s') (selector), action columns strided over the waves
-  float maxq = -3.4e38f, maxl = -3.4e38f, minl = 3.4e38f;
-  for (int aa = wid; aa < A; aa += 4) {
-    float cmx, cmn, x0, x1;
-    const float q = iqn_col_mean(a.logit + base, N, A, aa, lane, cmx, cmn);
-    maxq = fmaxf(maxq, q);
-    maxl = fmaxf(maxl, cmx);
-    minl = fminf(minl, cmn);
-    const float q2 = iqn_col_mean(a.next_logit + base, N, A, aa, lane, x0, x1);
-    if (lane == 0) s_qsel[aa] = q2;
-  }
-  // the entries of the actions not taken: zero gradient (the backward reads all of it)
-  for (int k = tid; k < N * A; k += 256)
-    if (k % A != act) a.grad[base + k] = 0.f;
-  if (lane == 0) { s_stat[wid * 3 + 0] = maxq; s_stat[wid * 3 + 1] = maxl; s_stat[wid * 3 + 2] = minl; }
-  __syncthreads();
-  // ---- a* = first maximum of the online net's means at s' (iqn.py:106); every thread walks the same A values
-  int best = 0;
-  float bq = -3.4e38f;
-  for (int aa = 0; aa < A; ++aa) {
-    const float q = s_qsel[aa];
-    if (q > bq) { bq = q; best = aa; }
-  }
-  // ---- phase 2: theta_target = reward + (1 - done) * gamma * target(s')[a*]  (iqn.py:109-111, in torch's order of operations)
-  if (own) s_T[tid] = r + ((1.f - dn) * a.gamma) * a.target_logit[base + (size_t)tid * A + best];
-  __syncthreads();
-  // ---- phase 3: thread i walks the targets j; e = T[j] - P[i], smooth_l1 (beta 1), weight tau[i] / 1 - tau[i] by the sign of e
-  float ls = 0.f, gs = 0.f;
-  for (int j = 0; j < N; ++j) {
-    const float e = s_T[j] - P;  // the same LDS word for every lane: a broadcast
-    const float ae = fabsf(e);
-    const float hub = ae < 1.f ? 0.5f * e * e : ae - 0.5f;
-    const float w = e < 0.f ? inv_tau : tau;
-    ls += w * hub;
-    gs += w * fminf(fmaxf(e, -1.f), 1.f);
-  }
-  if (own) a.grad[base + (size_t)tid * A + act] = -gs / ((float)a.B * (float)N);
-  // ---- phase 4: the sample's loss, wave shuffle tree then the waves in order
-  const float tot = jh_block_reduce(own ? ls : 0.f, s_red, JhAdd(), 0.f);
-  if (tid == 0) {
-    float mq = -3.4e38f, ml = -3.4e38f, nl = 3.4e38f;
-    const int nw = A < 4 ? A : 4;  // waves that saw at least one action column
-    for (int w = 0; w < nw; ++w) {
-      mq = fmaxf(mq, s_stat[w * 3 + 0]);
-      ml = fmaxf(ml, s_stat[w * 3 + 1]);
-      nl = fminf(nl, s_stat[w * 3 + 2]);
-    }
-    float* p = a.partial + 4 * (size_t)b;
-    p[0] = tot; p[1] = mq; p[2] = ml; p[3] = nl;
-  }
-}
-
-// Sum of the per-sample partials in a fixed order -> d_stats, payload fenced before the arrival marks (as jh_qr_finish_kernel).
-__global__ void __launch_bounds__(256) jh_iqn_finish_kernel(IqnArgs a) {
-  __shared__ float s_red[16];
-  float sl = 0.f, mq = -3.4e38f, ml = -3.4e38f, nl = 3.4e38f;
-  for (int b = threadIdx.x; b < a.B; b += 256) {
-    sl += a.partial[4 * (size_t)b];
-    mq = fmaxf(mq, a.partial[4 * (size_t)b + 1]);
-    ml = fmaxf(ml, a.partial[4 * (size_t)b + 2]);
-    nl = fminf(nl, a.partial[4 * (size_t)b + 3]);
-  }
-  sl = jh_block_reduce(sl, s_red, JhAdd(), 0.f);
-  mq = jh_block_reduce(mq, s_red, JhMax(), -3.4e38f);
-  ml = jh_block_reduce(ml, s_red, JhMax(), -3.4e38f);
-  nl = jh_block_reduce(nl, s_red, JhMin(), 3.4e38f);
-  if (threadIdx.x == 0 && a.stats) {
-    a.stats[0] = sl / ((float)a.B * (float)a.N);  // iqn.py:121: mean over (b, j) of the sum over i
-    a.stats[1] = mq;
-    a.stats[2] = ml;
-    a.stats[3] = nl;
-    a.stats[4] = 0.f;
-    a.stats[6] = 0.f;
-    __threadfence_system();  // payload before the arrival marks [5], [7] (mapped host memory, jh_host_wait_marks)
-    a.stats[5] = a.stats[7] = 0.f;
-  }
-}
-
-// IQN.act for R actor rows in one call: one wave per row, Q = mean over the N samples, first maximum like torch.argmax,
-// epsilon-greedy with the host's draws (jh_value_act's rules), q_taken fenced before the action.
-// Every lane of a wave stays through the shuffles: rows beyond R read row R - 1 and write nothing.
-__global__ void __launch_bounds__(256) jh_iqn_act_kernel(int R, int A, int N, const float* __restrict__ logits, const float* __restrict__ eps,
-                                                         const double* __restrict__ u, const int64_t* __restrict__ rand_action,
-                                                         int64_t* __restrict__ action, float* __restrict__ q_taken, float* __restrict__ q_all) {
-  const int lane = threadIdx.x & 63;
-  const int row0 = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const bool live = row0 < R;
-  const int row = live ? row0 : R - 1;
-  float best = -3.4e38f, q_rand = 0.f;
-  int best_a = 0;
-  int ra = rand_action ? (int)rand_action[row] : 0;
-  ra = ra < 0 ? 0 : (ra >= A ? A - 1 : ra);
-  for (int a = 0; a < A; ++a) {
-    float cmx, cmn;
-    const float q = iqn_col_mean(logits + (size_t)row * N * A, N, A, a, lane, cmx, cmn);
-    if (q_all && live && lane == 0) q_all[(size_t)row * A + a] = q;
-    if (q > best) { best = q; best_a = a; }
-    if (a == ra) q_rand = q;
-  }
-  if (live && lane == 0) {
-    const bool explore = eps && u && u[row] < (double)eps[row];
-    if (q_taken) {
-      q_taken[row] = explore ? q_rand : best;
-      __threadfence_system();
-    }
-    action[row] = explore ? ra : best_a;
   }
 }
 
@@ -366,21 +212,11 @@ JH_EXPORT int jh_iqnnet_segment(const jh_iqnnet* n, int32_t i, int64_t* offset, 
 
 JH_EXPORT int jh_iqnnet_set_hyper(jh_iqnnet* n, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream) {
   JH_ARG(n != nullptr);
-  jh_pinned_slab* slab = nullptr;
-  int rc = jh_ctx_slab(n->ctx, 64, &slab);
-  if (rc) return rc;
-  jh_hyper_fill((float*)slab->host, lr, beta1, beta2, eps, (double)step);
-  JH_HIP(hipMemcpyAsync(n->hyper, slab->dev, JH_HY_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, jh_s(stream)));
-  return jh_ctx_slab_release(n->ctx, slab, jh_s(stream));
+  return jh_hyper_upload(n->ctx, n->hyper, lr, beta1, beta2, eps, step, 0, jh_s(stream));
 }
 JH_EXPORT int jh_iqnnet_set_lr(jh_iqnnet* n, double lr, jh_stream stream) {
   JH_ARG(n != nullptr);
-  jh_pinned_slab* slab = nullptr;
-  int rc = jh_ctx_slab(n->ctx, 16, &slab);
-  if (rc) return rc;
-  *(float*)slab->host = (float)lr;
-  JH_HIP(hipMemcpyAsync(n->hyper, slab->dev, sizeof(float), hipMemcpyDeviceToDevice, jh_s(stream)));
-  return jh_ctx_slab_release(n->ctx, slab, jh_s(stream));
+  return jh_hyper_upload_lr(n->ctx, n->hyper, lr, jh_s(stream));
 }
 JH_EXPORT int jh_iqnnet_sync_target(jh_iqnnet* n, jh_stream stream) {
   JH_ARG(n != nullptr);
@@ -520,53 +356,4 @@ JH_EXPORT int jh_iqn_hadamard_backward(jh_ctx* ctx, int32_t B, int32_t N, int32_
   JH_ARG(ctx && d_grad_embed && d_psi && d_phi && d_grad_phi_pre && d_grad_psi_pre);
   JH_ARG(B > 0 && N > 0 && H > 0 && H % 4 == 0 && (int64_t)B * N * H < ((int64_t)1 << 31));
   return iqn_hadamard_bwd(B, N, H, d_grad_embed, d_psi, d_phi, d_grad_phi_pre, d_grad_psi_pre, jh_s(stream));
-}
-
-JH_EXPORT int jh_iqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online, const float* d_target_logit,
-                          const float* d_action, const float* d_reward, const float* d_done, const float* d_tau, float gamma, float* d_grad_logit, float* d_stats,
-                          jh_stream stream) {
-  JH_ARG(ctx && d_logit && d_next_logit_online && d_target_logit && d_action && d_reward && d_done && d_tau && d_grad_logit);
-  JH_ARG(B >= 1 && A >= 1 && N >= 1 && N <= 256);
-  hipStream_t st = jh_s(stream);
-  void* scratch = nullptr;
-  int rc = jh_ctx_scratch(ctx, sizeof(float) * 4 * (size_t)B, &scratch);
-  if (rc) return rc;
-  IqnArgs a{};
-  a.B = B; a.A = A; a.N = N;
-  a.logit = d_logit; a.next_logit = d_next_logit_online; a.target_logit = d_target_logit; a.action = d_action;
-  a.reward = d_reward; a.done = d_done; a.tau = d_tau; a.gamma = gamma; a.grad = d_grad_logit; a.stats = d_stats;
-  a.partial = (float*)scratch;
-  const size_t lds = sizeof(float) * ((size_t)N + (size_t)A + 12 + 16);
-  JH_ARG(lds <= 64 * 1024);
-  JH_LAUNCH(jh_iqn_block_kernel, dim3(B), dim3(256), lds, st, a);
-  JH_LAUNCH_CHECK();
-  JH_LAUNCH(jh_iqn_finish_kernel, dim3(1), dim3(256), 0, st, a);
-  JH_LAUNCH_CHECK();
-  return JH_OK;
-}
-
-JH_EXPORT int jh_iqn_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
-                         const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream) {
-  JH_ARG(ctx && d_logits && d_action);
-  JH_ARG(R > 0 && A > 0 && N > 0);
-  JH_ARG((h_eps == nullptr) == (h_u == nullptr) && (h_eps == nullptr) == (h_rand_action == nullptr));
-  hipStream_t st = jh_s(stream);
-  const float* d_eps = nullptr;
-  const double* d_u = nullptr;
-  const int64_t* d_ra = nullptr;
-  jh_pinned_slab* slab = nullptr;
-  if (h_eps) {  // the draws ride in a pinned, device-mapped slab the kernel reads in place
-    const size_t o_u = ((sizeof(float) * (size_t)R + 255) & ~(size_t)255), o_r = o_u + ((sizeof(double) * (size_t)R + 255) & ~(size_t)255);
-    int rc = jh_ctx_slab(ctx, o_r + sizeof(int64_t) * (size_t)R + 256, &slab);
-    if (rc) return rc;
-    memcpy(slab->host, h_eps, sizeof(float) * (size_t)R);
-    memcpy((char*)slab->host + o_u, h_u, sizeof(double) * (size_t)R);
-    memcpy((char*)slab->host + o_r, h_rand_action, sizeof(int64_t) * (size_t)R);
-    d_eps = (const float*)slab->dev;
-    d_u = (const double*)((char*)slab->dev + o_u);
-    d_ra = (const int64_t*)((char*)slab->dev + o_r);
-  }
-  JH_LAUNCH(jh_iqn_act_kernel, dim3((R + 3) / 4), dim3(256), 0, st, R, A, N, d_logits, d_eps, d_u, d_ra, d_action, d_q_taken, d_q_all);
-  JH_LAUNCH_CHECK();
-  return slab ? jh_ctx_slab_release(ctx, slab, st) : JH_OK;
 }

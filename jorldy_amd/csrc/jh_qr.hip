@@ -1,9 +1,26 @@
-// Quantile-regression DQN (core/agent/qrdqn.py), the two parts that are specific to the algorithm:
-//   jh_qr_loss       pairwise quantile-Huber loss, forward and backward to the online quantiles,
-//                    online net selects / target net evaluates                 (qrdqn.py:60-95)
-//   jh_quantile_act  epsilon-greedy acting on the mean of the quantiles         (qrdqn.py:33-47, 112-115)
+// The quantile family: what QR-DQN (core/agent/qrdqn.py) and IQN (core/agent/iqn.py) share below the network.  One loss and one
+// acting kernel, instantiated for the two layouts of a row block the networks write:
+//   jh_qr_loss       pairwise quantile-Huber loss, forward and backward to the online quantiles, online net selects / target net
+//                    evaluates; [B][A][N], tau [N] shared by the batch                (qrdqn.py:60-95)
+//   jh_iqn_loss      the same on [B][N][A] with tau [B][N], the draw of each sample   (iqn.py:89-121)
+//   jh_quantile_act  epsilon-greedy acting on the mean of the N quantiles, [R][A][N]  (qrdqn.py:33-47, 112-115)
+//   jh_iqn_act       the same on [R][N][A]                                            (iqn.py:60-76, 142-146)
 // No floating-point atomics: every sum has a fixed order, so two runs (and a graph replay) give the same bits.
 #include "jh_common.h"
+
+namespace {
+
+// Layout of one row block (the A x N values of sample / actor row b).  It decides the address of element (action a, quantile i),
+// whether tau is shared or per sample, and the shape of the loop that zeroes the gradient of the actions not taken -- nothing else.
+enum QLayout {
+  Q_ACTION_MAJOR,  // [A][N], tau [N]     (QR-DQN: the N quantiles of an action are contiguous)
+  Q_SAMPLE_MAJOR   // [N][A], tau [B][N]  (IQN: the A values of a sample are contiguous)
+};
+
+template <QLayout L>
+__device__ __forceinline__ size_t q_at(int b, int A, int N, int a, int i) {
+  return L == Q_ACTION_MAJOR ? ((size_t)b * A + a) * N + i : (size_t)b * N * A + (size_t)i * A + a;
+}
 
 struct QrArgs {
   int B, A, N;
@@ -12,14 +29,15 @@ struct QrArgs {
   float *grad, *stats, *partial;  // partial [B][4] = {sum_j sum_i w * huber, max Q, max logit, min logit} of a sample
 };
 
-// Mean of one row of N quantiles on one wave (torch.mean(_logits, dim=-1), qrdqn.py:114): every lane returns it.
-// rmx / rmn: the row's largest / smallest entry.
-__device__ __forceinline__ float qr_row_mean(const float* __restrict__ z, int N, int lane, float& rmx, float& rmn) {
+// Mean of the N quantiles of action a of row block b of z on one wave (torch.mean(_logits, dim=-1), qrdqn.py:114; logits2Q,
+// iqn.py:142-146): every lane returns it.  rmx / rmn: the largest / smallest of the N entries.
+template <QLayout L>
+__device__ __forceinline__ float qr_row_mean(const float* __restrict__ z, int b, int A, int N, int a, int lane, float& rmx, float& rmn) {
   float s = 0.f;
   rmx = -3.4e38f;
   rmn = 3.4e38f;
   for (int k = lane; k < N; k += 64) {
-    const float v = z[k];
+    const float v = z[q_at<L>(b, A, N, a, k)];
     s += v;
     rmx = fmaxf(rmx, v);
     rmn = fminf(rmn, v);
@@ -32,6 +50,7 @@ __device__ __forceinline__ float qr_row_mean(const float* __restrict__ z, int N,
 // One workgroup of 256 threads per sample (N <= 256: thread i owns prediction quantile i).
 // LDS: [N] Bellman image of the target quantiles, [A] selector means, [4][3] per-wave statistics, [16] reduction.
 // Every thread stays to the end: the work of threads i >= N is predicated, not skipped (block reduction at the end).
+template <QLayout L>
 __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -46,35 +65,44 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
   // what phase 3 keeps in registers, requested ahead of the reductions of phase 1
   const bool own = tid < N;
   const int ti = own ? tid : N - 1;
-  const float P = a.logit[((size_t)b * A + act) * N + ti];
-  const float tau = a.tau[ti];
-  const float inv_tau = 1.f - tau;  // qrdqn.py:31
-  // ---- phase 1: quantile means of online(s) (statistics) and online(s') (selector), action rows strided over the waves
+  const float P = a.logit[q_at<L>(b, A, N, act, ti)];
+  // IQN: the FIRST forward's draw for this sample (iqn.py:90, 96)
+  const float tau = a.tau[L == Q_ACTION_MAJOR ? (size_t)ti : (size_t)b * N + ti];
+  const float inv_tau = 1.f - tau;  // qrdqn.py:31, iqn.py:120
+  // ---- phase 1: quantile means of online(s) (statistics) and online(s') (selector), actions strided over the waves
   float maxq = -3.4e38f, maxl = -3.4e38f, minl = 3.4e38f;
   for (int aa = wid; aa < A; aa += 4) {
     float rmx, rmn, x0, x1;
-    const float q = qr_row_mean(a.logit + ((size_t)b * A + aa) * N, N, lane, rmx, rmn);
+    const float q = qr_row_mean<L>(a.logit, b, A, N, aa, lane, rmx, rmn);
     maxq = fmaxf(maxq, q);
     maxl = fmaxf(maxl, rmx);
     minl = fminf(minl, rmn);
-    const float q2 = qr_row_mean(a.next_logit + ((size_t)b * A + aa) * N, N, lane, x0, x1);
+    const float q2 = qr_row_mean<L>(a.next_logit, b, A, N, aa, lane, x0, x1);
     if (lane == 0) s_qsel[aa] = q2;
-    if (aa != act) {  // the rows of the actions not taken: zero gradient (net.backward reads all of it)
-      float* g = a.grad + ((size_t)b * A + aa) * N;
-      for (int k = lane; k < N; k += 64) g[k] = 0.f;
+    if constexpr (L == Q_ACTION_MAJOR) {
+      if (aa != act) {  // the rows of the actions not taken: zero gradient (net.backward reads all of it)
+        float* g = a.grad + q_at<L>(b, A, N, aa, 0);
+        for (int k = lane; k < N; k += 64) g[k] = 0.f;
+      }
     }
+  }
+  if constexpr (L == Q_SAMPLE_MAJOR) {
+    // the entries of the actions not taken, interleaved with the taken one: a flat walk, no division on the action-major path
+    float* g = a.grad + q_at<L>(b, A, N, 0, 0);
+    for (int k = tid; k < N * A; k += 256)
+      if (k % A != act) g[k] = 0.f;
   }
   if (lane == 0) { s_stat[wid * 3 + 0] = maxq; s_stat[wid * 3 + 1] = maxl; s_stat[wid * 3 + 2] = minl; }
   __syncthreads();
-  // ---- a* = first maximum of the online net's means at s' (qrdqn.py:76); every thread walks the same A values
+  // ---- a* = first maximum of the online net's means at s' (qrdqn.py:76, iqn.py:106); every thread walks the same A values
   int best = 0;
   float bq = -3.4e38f;
   for (int aa = 0; aa < A; ++aa) {
     const float q = s_qsel[aa];
     if (q > bq) { bq = q; best = aa; }
   }
-  // ---- phase 2: theta_target = reward + (1 - done) * gamma * target(s')[a*]  (qrdqn.py:79-81, in torch's order of operations)
-  if (own) s_T[tid] = r + ((1.f - dn) * a.gamma) * a.target_logit[((size_t)b * A + best) * N + tid];
+  // ---- phase 2: theta_target = reward + (1 - done) * gamma * target(s')[a*]  (qrdqn.py:79-81, iqn.py:109-111, in torch's order of operations)
+  if (own) s_T[tid] = r + ((1.f - dn) * a.gamma) * a.target_logit[q_at<L>(b, A, N, best, tid)];
   __syncthreads();
   // ---- phase 3: thread i walks the targets j; e = T[j] - P[i], smooth_l1 (beta 1), weight tau[i] / 1 - tau[i] by the sign of e
   float ls = 0.f, gs = 0.f;
@@ -86,12 +114,12 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
     ls += w * hub;
     gs += w * fminf(fmaxf(e, -1.f), 1.f);
   }
-  if (own) a.grad[((size_t)b * A + act) * N + tid] = -gs / ((float)a.B * (float)N);
+  if (own) a.grad[q_at<L>(b, A, N, act, tid)] = -gs / ((float)a.B * (float)N);
   // ---- phase 4: the sample's loss, wave shuffle tree then the waves in order
   const float tot = jh_block_reduce(own ? ls : 0.f, s_red, JhAdd(), 0.f);
   if (tid == 0) {
     float mq = -3.4e38f, ml = -3.4e38f, nl = 3.4e38f;
-    const int nw = A < 4 ? A : 4;  // waves that saw at least one action row
+    const int nw = A < 4 ? A : 4;  // waves that saw at least one action
     for (int w = 0; w < nw; ++w) {
       mq = fmaxf(mq, s_stat[w * 3 + 0]);
       ml = fmaxf(ml, s_stat[w * 3 + 1]);
@@ -103,6 +131,7 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
 }
 
 // Sum of the per-sample partials in a fixed order -> d_stats, payload fenced before the arrival marks (as jh_c51_finish_kernel).
+// The partials carry no layout: one kernel for both.
 __global__ void __launch_bounds__(256) jh_qr_finish_kernel(QrArgs a) {
   __shared__ float s_red[16];
   float sl = 0.f, mq = -3.4e38f, ml = -3.4e38f, nl = 3.4e38f;
@@ -117,7 +146,7 @@ __global__ void __launch_bounds__(256) jh_qr_finish_kernel(QrArgs a) {
   ml = jh_block_reduce(ml, s_red, JhMax(), -3.4e38f);
   nl = jh_block_reduce(nl, s_red, JhMin(), 3.4e38f);
   if (threadIdx.x == 0 && a.stats) {
-    a.stats[0] = sl / ((float)a.B * (float)a.N);  // qrdqn.py:91: mean over (b, j) of the sum over i
+    a.stats[0] = sl / ((float)a.B * (float)a.N);  // qrdqn.py:91, iqn.py:121: mean over (b, j) of the sum over i
     a.stats[1] = mq;
     a.stats[2] = ml;
     a.stats[3] = nl;
@@ -128,32 +157,10 @@ __global__ void __launch_bounds__(256) jh_qr_finish_kernel(QrArgs a) {
   }
 }
 
-JH_EXPORT int jh_qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online,
-                         const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done,
-                         const float* d_tau, float gamma, float* d_grad_logit, float* d_stats, jh_stream stream) {
-  JH_ARG(ctx && d_logit && d_next_logit_online && d_target_logit && d_action && d_reward && d_done && d_tau && d_grad_logit);
-  JH_ARG(B >= 1 && A >= 1 && N >= 1 && N <= 256);
-  hipStream_t st = jh_s(stream);
-  void* scratch = nullptr;
-  int rc = jh_ctx_scratch(ctx, sizeof(float) * 4 * (size_t)B, &scratch);
-  if (rc) return rc;
-  QrArgs a{};
-  a.B = B; a.A = A; a.N = N;
-  a.logit = d_logit; a.next_logit = d_next_logit_online; a.target_logit = d_target_logit; a.action = d_action;
-  a.reward = d_reward; a.done = d_done; a.tau = d_tau; a.gamma = gamma; a.grad = d_grad_logit; a.stats = d_stats;
-  a.partial = (float*)scratch;
-  const size_t lds = sizeof(float) * ((size_t)N + (size_t)A + 12 + 16);
-  JH_ARG(lds <= 64 * 1024);
-  JH_LAUNCH(jh_qr_block_kernel, dim3(B), dim3(256), lds, st, a);
-  JH_LAUNCH_CHECK();
-  JH_LAUNCH(jh_qr_finish_kernel, dim3(1), dim3(256), 0, st, a);
-  JH_LAUNCH_CHECK();
-  return JH_OK;
-}
-
-// QRDQN.act for R actor rows in one call: one wave per row, Q = mean of the N quantiles, first maximum like torch.argmax,
+// QRDQN.act / IQN.act for R actor rows in one call: one wave per row, Q = mean of the N quantiles, first maximum like torch.argmax,
 // epsilon-greedy with the host's draws (jh_value_act's rules), q_taken fenced before the action.
 // Every lane of a wave stays through the shuffles: rows beyond R read row R - 1 and write nothing.
+template <QLayout L>
 __global__ void __launch_bounds__(256) jh_quantile_act_kernel(int R, int A, int N, const float* __restrict__ logits, const float* __restrict__ eps,
                                                               const double* __restrict__ u, const int64_t* __restrict__ rand_action,
                                                               int64_t* __restrict__ action, float* __restrict__ q_taken, float* __restrict__ q_all) {
@@ -167,7 +174,7 @@ __global__ void __launch_bounds__(256) jh_quantile_act_kernel(int R, int A, int 
   ra = ra < 0 ? 0 : (ra >= A ? A - 1 : ra);
   for (int a = 0; a < A; ++a) {
     float rmx, rmn;
-    const float q = qr_row_mean(logits + ((size_t)row * A + a) * N, N, lane, rmx, rmn);
+    const float q = qr_row_mean<L>(logits, row, A, N, a, lane, rmx, rmn);
     if (q_all && live && lane == 0) q_all[(size_t)row * A + a] = q;
     if (q > best) { best = q; best_a = a; }
     if (a == ra) q_rand = q;
@@ -182,28 +189,65 @@ __global__ void __launch_bounds__(256) jh_quantile_act_kernel(int R, int A, int 
   }
 }
 
-JH_EXPORT int jh_quantile_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
-                              const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream) {
+// The launches keep the names the profile report and DESIGN.md's kernel table know them by, one set per entry point.
+template <QLayout L>
+int qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online, const float* d_target_logit,
+            const float* d_action, const float* d_reward, const float* d_done, const float* d_tau, float gamma, float* d_grad_logit, float* d_stats,
+            jh_stream stream) {
+  JH_ARG(ctx && d_logit && d_next_logit_online && d_target_logit && d_action && d_reward && d_done && d_tau && d_grad_logit);
+  JH_ARG(B >= 1 && A >= 1 && N >= 1 && N <= 256);
+  hipStream_t st = jh_s(stream);
+  void* scratch = nullptr;
+  int rc = jh_ctx_scratch(ctx, sizeof(float) * 4 * (size_t)B, &scratch);
+  if (rc) return rc;
+  QrArgs a{};
+  a.B = B; a.A = A; a.N = N;
+  a.logit = d_logit; a.next_logit = d_next_logit_online; a.target_logit = d_target_logit; a.action = d_action;
+  a.reward = d_reward; a.done = d_done; a.tau = d_tau; a.gamma = gamma; a.grad = d_grad_logit; a.stats = d_stats;
+  a.partial = (float*)scratch;
+  const size_t lds = sizeof(float) * ((size_t)N + (size_t)A + 12 + 16);
+  JH_ARG(lds <= 64 * 1024);
+  JH_LAUNCH_NAMED(L == Q_ACTION_MAJOR ? "jh_qr_block_kernel" : "jh_iqn_block_kernel", jh_qr_block_kernel<L>, dim3(B), dim3(256), lds, st, a);
+  JH_LAUNCH_CHECK();
+  JH_LAUNCH_NAMED(L == Q_ACTION_MAJOR ? "jh_qr_finish_kernel" : "jh_iqn_finish_kernel", jh_qr_finish_kernel, dim3(1), dim3(256), 0, st, a);
+  JH_LAUNCH_CHECK();
+  return JH_OK;
+}
+
+template <QLayout L>
+int qr_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u, const int64_t* h_rand_action,
+           int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream) {
   JH_ARG(ctx && d_logits && d_action);
   JH_ARG(R > 0 && A > 0 && N > 0);
   JH_ARG((h_eps == nullptr) == (h_u == nullptr) && (h_eps == nullptr) == (h_rand_action == nullptr));
   hipStream_t st = jh_s(stream);
-  const float* d_eps = nullptr;
-  const double* d_u = nullptr;
-  const int64_t* d_ra = nullptr;
-  jh_pinned_slab* slab = nullptr;
-  if (h_eps) {  // the draws ride in a pinned, device-mapped slab the kernel reads in place
-    const size_t o_u = ((sizeof(float) * (size_t)R + 255) & ~(size_t)255), o_r = o_u + ((sizeof(double) * (size_t)R + 255) & ~(size_t)255);
-    int rc = jh_ctx_slab(ctx, o_r + sizeof(int64_t) * (size_t)R + 256, &slab);
-    if (rc) return rc;
-    memcpy(slab->host, h_eps, sizeof(float) * (size_t)R);
-    memcpy((char*)slab->host + o_u, h_u, sizeof(double) * (size_t)R);
-    memcpy((char*)slab->host + o_r, h_rand_action, sizeof(int64_t) * (size_t)R);
-    d_eps = (const float*)slab->dev;
-    d_u = (const double*)((char*)slab->dev + o_u);
-    d_ra = (const int64_t*)((char*)slab->dev + o_r);
-  }
-  JH_LAUNCH(jh_quantile_act_kernel, dim3((R + 3) / 4), dim3(256), 0, st, R, A, N, d_logits, d_eps, d_u, d_ra, d_action, d_q_taken, d_q_all);
+  jh_draws dr;
+  int rc = jh_ctx_stage_draws(ctx, (size_t)R, h_eps, h_u, h_rand_action, &dr);
+  if (rc) return rc;
+  JH_LAUNCH_NAMED(L == Q_ACTION_MAJOR ? "jh_quantile_act_kernel" : "jh_iqn_act_kernel", jh_quantile_act_kernel<L>, dim3((R + 3) / 4), dim3(256), 0, st, R, A, N,
+                  d_logits, dr.eps, dr.u, dr.rand_action, d_action, d_q_taken, d_q_all);
   JH_LAUNCH_CHECK();
-  return slab ? jh_ctx_slab_release(ctx, slab, st) : JH_OK;
+  return dr.slab ? jh_ctx_slab_release(ctx, dr.slab, st) : JH_OK;
+}
+
+}  // namespace
+
+JH_EXPORT int jh_qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online,
+                         const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done,
+                         const float* d_tau, float gamma, float* d_grad_logit, float* d_stats, jh_stream stream) {
+  return qr_loss<Q_ACTION_MAJOR>(ctx, B, A, N, d_logit, d_next_logit_online, d_target_logit, d_action, d_reward, d_done, d_tau, gamma, d_grad_logit, d_stats, stream);
+}
+JH_EXPORT int jh_iqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online,
+                          const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done,
+                          const float* d_tau, float gamma, float* d_grad_logit, float* d_stats, jh_stream stream) {
+  return qr_loss<Q_SAMPLE_MAJOR>(ctx, B, A, N, d_logit, d_next_logit_online, d_target_logit, d_action, d_reward, d_done, d_tau, gamma, d_grad_logit, d_stats, stream);
+}
+
+JH_EXPORT int jh_quantile_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
+                              const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream) {
+  return qr_act<Q_ACTION_MAJOR>(ctx, R, A, N, d_logits, h_eps, h_u, h_rand_action, d_action, d_q_taken, d_q_all, stream);
+}
+JH_EXPORT int jh_iqn_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
+                         const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream) {
+  return qr_act<Q_SAMPLE_MAJOR>(ctx, R, A, N, d_logits, h_eps, h_u, h_rand_action, d_action, d_q_taken, d_q_all, stream);
 }

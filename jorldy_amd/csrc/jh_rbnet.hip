@@ -838,25 +838,32 @@ JH_EXPORT int jh_rbnet_segment(const jh_rbnet* n, int32_t i, int64_t* offset, in
 }
 JH_EXPORT int64_t jh_rbnet_noise_len(const jh_rbnet* n) { return n ? n->nd.noise_len : -1; }
 
-JH_EXPORT int jh_rbnet_set_hyper(jh_rbnet* n, double lr, double beta1, double beta2, double eps, int64_t step, int32_t centered, jh_stream stream) {
-  JH_ARG(n != nullptr);
+int jh_hyper_upload(jh_ctx* ctx, float* d_hyper, double lr, double beta1, double beta2, double eps, int64_t step, int centered, hipStream_t st) {
   jh_pinned_slab* slab = nullptr;
-  int rc = jh_ctx_slab(n->ctx, 64, &slab);
+  int rc = jh_ctx_slab(ctx, 64, &slab);
   if (rc) return rc;
   float* h = (float*)slab->host;
   jh_hyper_fill(h, lr, beta1, beta2, eps, (double)step);
   h[JH_HY_BC1] = centered ? 1.f : 0.f;
-  JH_HIP(hipMemcpyAsync(n->hyper, slab->dev, JH_HY_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, jh_s(stream)));
-  return jh_ctx_slab_release(n->ctx, slab, jh_s(stream));
+  JH_HIP(hipMemcpyAsync(d_hyper, slab->dev, JH_HY_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return jh_ctx_slab_release(ctx, slab, st);
+}
+int jh_hyper_upload_lr(jh_ctx* ctx, float* d_hyper, double lr, hipStream_t st) {
+  jh_pinned_slab* slab = nullptr;
+  int rc = jh_ctx_slab(ctx, 16, &slab);
+  if (rc) return rc;
+  *(float*)slab->host = (float)lr;
+  JH_HIP(hipMemcpyAsync(d_hyper, slab->dev, sizeof(float), hipMemcpyDeviceToDevice, st));
+  return jh_ctx_slab_release(ctx, slab, st);
+}
+
+JH_EXPORT int jh_rbnet_set_hyper(jh_rbnet* n, double lr, double beta1, double beta2, double eps, int64_t step, int32_t centered, jh_stream stream) {
+  JH_ARG(n != nullptr);
+  return jh_hyper_upload(n->ctx, n->hyper, lr, beta1, beta2, eps, step, centered, jh_s(stream));
 }
 JH_EXPORT int jh_rbnet_set_lr(jh_rbnet* n, double lr, jh_stream stream) {
   JH_ARG(n != nullptr);
-  jh_pinned_slab* slab = nullptr;
-  int rc = jh_ctx_slab(n->ctx, 16, &slab);
-  if (rc) return rc;
-  *(float*)slab->host = (float)lr;
-  JH_HIP(hipMemcpyAsync(n->hyper, slab->dev, sizeof(float), hipMemcpyDeviceToDevice, jh_s(stream)));
-  return jh_ctx_slab_release(n->ctx, slab, jh_s(stream));
+  return jh_hyper_upload_lr(n->ctx, n->hyper, lr, jh_s(stream));
 }
 JH_EXPORT int jh_rbnet_sync_target(jh_rbnet* n, jh_stream stream) {
   JH_ARG(n != nullptr);

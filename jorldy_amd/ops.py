@@ -713,18 +713,24 @@ class NormalSource:
         return t
 
 
+def _act_buffers(R, A, dev, eps, u, rand_action, out, want_q_all):
+    """What value_act / quantile_act / iqn_act share: the outputs (act int64 [R] and q float32 [R], or the caller's `out` pair; q_all
+    float32 [R, A] when wanted) and the three host draw arrays, contiguous in the types the library reads (or all None)."""
+    act, q = (torch.empty(R, dtype=torch.int64, device=dev), torch.empty(R, dtype=torch.float32, device=dev)) if out is None else out
+    q_all = torch.empty(R, A, dtype=torch.float32, device=dev) if want_q_all else None
+    if eps is not None:
+        eps, u, rand_action = (np.ascontiguousarray(eps, dtype=np.float32), np.ascontiguousarray(u, dtype=np.float64), np.ascontiguousarray(rand_action, dtype=np.int64))
+        assert eps.size == R and u.size == R and rand_action.size == R
+    return act, q, q_all, eps, u, rand_action
+
+
 def value_act(logits, v_min=0.0, v_max=0.0, eps=None, u=None, rand_action=None, out=None, want_q_all=False):
     """jh_value_act: network outputs [N, A, K] (K = 1: Q values) -> (action int64 [N], q_taken float32 [N], q_all | None)
     on the device.  eps / u / rand_action: numpy float32 / float64 / int64 [N] (the host's epsilon-greedy draws) or
     all None for greedy."""
     lg = _f32(logits)
     N, A, K = (int(v) for v in lg.shape)
-    dev = lg.device
-    act, q = (torch.empty(N, dtype=torch.int64, device=dev), torch.empty(N, dtype=torch.float32, device=dev)) if out is None else out
-    q_all = torch.empty(N, A, dtype=torch.float32, device=dev) if want_q_all else None
-    if eps is not None:
-        eps, u, rand_action = (np.ascontiguousarray(eps, dtype=np.float32), np.ascontiguousarray(u, dtype=np.float64), np.ascontiguousarray(rand_action, dtype=np.int64))
-        assert eps.size == N and u.size == N and rand_action.size == N
+    act, q, q_all, eps, u, rand_action = _act_buffers(N, A, lg.device, eps, u, rand_action, out, want_q_all)
     L.check(L.load().jh_value_act(L.ctx(_dev(lg)), N, A, K, L.ptr(lg), float(v_min), float(v_max), L.ptr(eps), L.ptr(u), L.ptr(rand_action), L.ptr(act), L.ptr(q),
                                   L.ptr(q_all), L.stream_ptr()))
     return act, q, q_all
@@ -816,21 +822,27 @@ def c51_loss(logit, target_logit, action, reward, done, v_min, v_max, gamma, nex
     return g, prio, kl, stats
 
 
-def qr_loss(logit, next_logit_online, target_logit, action, reward, done, tau, gamma, stats=None):
-    """jh_qr_loss (qrdqn.py:60-95): logit / next_logit_online / target_logit [B, A, N], action / reward / done [B] (or [B, 1]),
-    tau float32 [N] on the device.  Returns (grad_logit [B, A, N], stats f32[8] = {loss, max_Q, max_logit, min_logit, 0, mark, 0, mark})."""
-    z = _f32(logit)
-    B, A, N = (int(v) for v in z.shape)
-    zn, zt, t = _f32(next_logit_online), _f32(target_logit), _f32(tau).reshape(-1)
-    assert tuple(zn.shape) == (B, A, N) and tuple(zt.shape) == (B, A, N) and t.numel() == N and t.device == z.device
+def _quantile_loss(entry, B, A, N, z, next_logit_online, target_logit, action, reward, done, t, gamma, stats):
+    """What qr_loss / iqn_loss share once the layout is read off `z`: the two other networks' outputs in z's shape, the [B] vectors
+    flat, the gradient and the stats block allocated, the call."""
+    zn, zt = _f32(next_logit_online), _f32(target_logit)
+    assert zn.shape == z.shape and zt.shape == z.shape and t.device == z.device
     a, r, d = _f32(action).reshape(-1), _f32(reward).reshape(-1), _f32(done).reshape(-1)
     assert a.numel() == B and r.numel() == B and d.numel() == B
     g = torch.empty_like(z)
     if stats is None:
         stats = torch.empty(8, dtype=torch.float32, device=z.device)
-    L.check(L.load().jh_qr_loss(L.ctx(_dev(z)), B, A, N, L.ptr(z), L.ptr(zn), L.ptr(zt), L.ptr(a), L.ptr(r), L.ptr(d), L.ptr(t), float(gamma), L.ptr(g), L.ptr(stats),
-                                L.stream_ptr()))
+    L.check(entry(L.ctx(_dev(z)), B, A, N, L.ptr(z), L.ptr(zn), L.ptr(zt), L.ptr(a), L.ptr(r), L.ptr(d), L.ptr(t), float(gamma), L.ptr(g), L.ptr(stats), L.stream_ptr()))
     return g, stats
+
+
+def qr_loss(logit, next_logit_online, target_logit, action, reward, done, tau, gamma, stats=None):
+    """jh_qr_loss (qrdqn.py:60-95): logit / next_logit_online / target_logit [B, A, N], action / reward / done [B] (or [B, 1]),
+    tau float32 [N] on the device.  Returns (grad_logit [B, A, N], stats f32[8] = {loss, max_Q, max_logit, min_logit, 0, mark, 0, mark})."""
+    z, t = _f32(logit), _f32(tau).reshape(-1)
+    B, A, N = (int(v) for v in z.shape)
+    assert t.numel() == N
+    return _quantile_loss(L.load().jh_qr_loss, B, A, N, z, next_logit_online, target_logit, action, reward, done, t, gamma, stats)
 
 
 def mdqn_loss(q, q_target, q_next_target, action, reward, done, gamma, alpha, tau, l_0, stats=None):
@@ -855,12 +867,7 @@ def quantile_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_al
     q_all | None) on the device.  eps / u / rand_action as in value_act."""
     lg = _f32(logits)
     R, A, N = (int(v) for v in lg.shape)
-    dev = lg.device
-    act, q = (torch.empty(R, dtype=torch.int64, device=dev), torch.empty(R, dtype=torch.float32, device=dev)) if out is None else out
-    q_all = torch.empty(R, A, dtype=torch.float32, device=dev) if want_q_all else None
-    if eps is not None:
-        eps, u, rand_action = (np.ascontiguousarray(eps, dtype=np.float32), np.ascontiguousarray(u, dtype=np.float64), np.ascontiguousarray(rand_action, dtype=np.int64))
-        assert eps.size == R and u.size == R and rand_action.size == R
+    act, q, q_all, eps, u, rand_action = _act_buffers(R, A, lg.device, eps, u, rand_action, out, want_q_all)
     L.check(L.load().jh_quantile_act(L.ctx(_dev(lg)), R, A, N, L.ptr(lg), L.ptr(eps), L.ptr(u), L.ptr(rand_action), L.ptr(act), L.ptr(q), L.ptr(q_all), L.stream_ptr()))
     return act, q, q_all
 
@@ -868,18 +875,10 @@ def quantile_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_al
 def iqn_loss(logit, next_logit_online, target_logit, action, reward, done, tau, gamma, stats=None):
     """jh_iqn_loss (iqn.py:89-121): logit / next_logit_online / target_logit [B, N, A] as the network writes them, action / reward / done [B]
     (or [B, 1]), tau float32 [B, N] = the draw of the forward that produced `logit`.  Returns (grad_logit [B, N, A], stats f32[8] as qr_loss)."""
-    z = _f32(logit)
+    z, t = _f32(logit), _f32(tau)
     B, N, A = (int(v) for v in z.shape)
-    zn, zt, t = _f32(next_logit_online), _f32(target_logit), _f32(tau)
-    assert tuple(zn.shape) == (B, N, A) and tuple(zt.shape) == (B, N, A) and t.numel() == B * N and t.device == z.device
-    a, r, d = _f32(action).reshape(-1), _f32(reward).reshape(-1), _f32(done).reshape(-1)
-    assert a.numel() == B and r.numel() == B and d.numel() == B
-    g = torch.empty_like(z)
-    if stats is None:
-        stats = torch.empty(8, dtype=torch.float32, device=z.device)
-    L.check(L.load().jh_iqn_loss(L.ctx(_dev(z)), B, A, N, L.ptr(z), L.ptr(zn), L.ptr(zt), L.ptr(a), L.ptr(r), L.ptr(d), L.ptr(t), float(gamma), L.ptr(g), L.ptr(stats),
-                                 L.stream_ptr()))
-    return g, stats
+    assert t.numel() == B * N
+    return _quantile_loss(L.load().jh_iqn_loss, B, A, N, z, next_logit_online, target_logit, action, reward, done, t, gamma, stats)
 
 
 def iqn_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_all=False):
@@ -887,12 +886,7 @@ def iqn_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_all=Fal
     on the device.  eps / u / rand_action as in value_act."""
     lg = _f32(logits)
     R, N, A = (int(v) for v in lg.shape)
-    dev = lg.device
-    act, q = (torch.empty(R, dtype=torch.int64, device=dev), torch.empty(R, dtype=torch.float32, device=dev)) if out is None else out
-    q_all = torch.empty(R, A, dtype=torch.float32, device=dev) if want_q_all else None
-    if eps is not None:
-        eps, u, rand_action = (np.ascontiguousarray(eps, dtype=np.float32), np.ascontiguousarray(u, dtype=np.float64), np.ascontiguousarray(rand_action, dtype=np.int64))
-        assert eps.size == R and u.size == R and rand_action.size == R
+    act, q, q_all, eps, u, rand_action = _act_buffers(R, A, lg.device, eps, u, rand_action, out, want_q_all)
     L.check(L.load().jh_iqn_act(L.ctx(_dev(lg)), R, A, N, L.ptr(lg), L.ptr(eps), L.ptr(u), L.ptr(rand_action), L.ptr(act), L.ptr(q), L.ptr(q_all), L.stream_ptr()))
     return act, q, q_all
 

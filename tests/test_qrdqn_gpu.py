@@ -181,6 +181,51 @@ def test_quantile_act_matches_numpy(R, N):
     assert np.array_equal(npy(out[0]), want)
 
 
+# ----------------------------------------------------------------------------------------------- one algorithm, two layouts
+# QR-DQN's entries read a row block as [A][N] with tau [N], IQN's as [N][A] with tau [B][N].  The same numbers through both give the
+# same bits: sums, first maxima and the Bellman image do not depend on where an element lies in memory.
+@pytest.mark.parametrize("B,A,N", [(1, 1, 1), (3, 2, 8), (32, 6, 65), (3, 18, 256), (255, 6, 51)])
+def test_qr_loss_and_iqn_loss_are_one_algorithm(B, A, N):
+    from jorldy_amd import ops
+
+    assert (B, A, N, "plain") in Q.SWEEP
+    d = Q.sweep_case(B, A, N, "plain")
+    tau = _tau(N)
+    am = [f32(d[k]) for k in ("logit", "next_online", "target")]
+    sm = [x.transpose(1, 2).contiguous() for x in am]
+    vec = [f32(d[k]) for k in ("action", "reward", "done")]
+    g_qr, s_qr = ops.qr_loss(*am, *vec, tau, 0.99, stats=torch.full((8,), -1.0, device="cuda"))
+    g_iqn, s_iqn = ops.iqn_loss(*sm, *vec, tau.reshape(1, N).expand(B, N).contiguous(), 0.99, stats=torch.full((8,), -2.0, device="cuda"))
+    torch.cuda.synchronize()
+    assert tuple(g_qr.shape) == (B, A, N) and tuple(g_iqn.shape) == (B, N, A)
+    assert torch.equal(g_iqn.transpose(1, 2), g_qr)
+    assert torch.equal(s_iqn, s_qr)
+
+
+@pytest.mark.parametrize("R", [1, 5])
+@pytest.mark.parametrize("N", [1, 65, 200])
+def test_quantile_act_and_iqn_act_are_one_algorithm(R, N):
+    from jorldy_amd import ops
+
+    A = 4
+    rs = np.random.RandomState(100 * R + N)
+    lg = cu(rs.randn(R, A, N).astype(np.float32))
+    lg_sm = lg.transpose(1, 2).contiguous()
+    eps = np.full(R, 0.5, np.float32)
+    u = rs.rand(R)
+    u[0] = 0.1  # at least one random row ...
+    if R > 1:
+        u[1] = 0.9  # ... and one greedy one
+    ra = rs.randint(0, A, size=R).astype(np.int64)
+    for draws in (dict(), dict(eps=eps, u=u, rand_action=ra)):
+        a_qr, q_qr, all_qr = ops.quantile_act(lg, want_q_all=True, **draws)
+        a_iqn, q_iqn, all_iqn = ops.iqn_act(lg_sm, want_q_all=True, **draws)
+        torch.cuda.synchronize()
+        assert torch.equal(a_iqn, a_qr) and torch.equal(q_iqn, q_qr) and torch.equal(all_iqn, all_qr)
+        if draws:
+            assert np.array_equal(npy(a_qr)[u < eps], ra[u < eps])
+
+
 # ----------------------------------------------------------------------------------------------- the agent
 def _agent_for(z, use_graph=True, lr=None, **over):
     from jorldy_amd.core.agent import Agent
