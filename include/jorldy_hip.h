@@ -352,6 +352,11 @@ int jh_iqnnet_forward(jh_iqnnet* n, int32_t which, const float* d_x, int32_t row
  * d_tau [3][B][N] -> d_logits [3][B][N][A] = online(state), online(next_state), target(next_state); every layer is one grouped
  * launch for the online rows and the target rows.  The activations of online(state) stay in place for jh_iqnnet_backward.     */
 int jh_iqnnet_learn_forward(jh_iqnnet* n, const float* d_x, int32_t B, const float* d_tau, float* d_logits, jh_stream stream);
+/* The forwards of M_IQN.learn() (m_iqn.py:30, 43, 50) in jh_iqnnet_learn_forward's launches: d_x = [state; next_state] (2B rows),
+ * d_tau [3][B][N] -> d_logits [3][B][N][A] = online(state) with draw 0 (the one jh_iqnnet_backward differentiates), online(state)
+ * with draw 1, target(next_state) with draw 2.  The reference's online(next_state) (m_iqn.py:40-41, 46-47) feeds nothing and is
+ * not computed: 3 B N sampled rows, as IQN's learn().                                                                          */
+int jh_iqnnet_learn_forward_m(jh_iqnnet* n, const float* d_x, int32_t B, const float* d_tau, float* d_logits, jh_stream stream);
 /* loss.backward() (iqn.py:128) given d(loss)/d(online(state) output) [B][N][A] (from jh_iqn_loss); fills d_grads              */
 int jh_iqnnet_backward(jh_iqnnet* n, const float* d_g, jh_stream stream);
 /* [clip_grad_norm_(max_norm) when max_norm > 0,] torch.optim.Adam's step (iqn.py:129); advances the step counter              */
@@ -373,6 +378,17 @@ int jh_iqn_hadamard_backward(jh_ctx* ctx, int32_t B, int32_t N, int32_t H, const
 int jh_iqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online,
                 const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done, const float* d_tau,
                 float gamma, float* d_grad_logit, float* d_stats, jh_stream stream);
+/* jh_iqn_loss's pairwise loss under the Munchausen target (m_iqn.py:29-95, agent/utils.py:29-39).  d_logit = online(state) under
+ * the first draw d_tau [B][N], d_logit_again = online(state) under a second draw, d_target_logit = target(next_state), each
+ * float32 [B][N][A].  With x = mean_n logit_again, x' = mean_n target_logit, tau_e the entropy temperature (the agent's self.tau):
+ *   lp = x[action] - (max x + tau_e log sum exp((x - max x) / tau_e)),  pi = softmax(x' / tau_e),  logpi = x' - (max x' + tau_e log sum exp(...)),
+ *   T[j] = (reward + alpha * clip(lp, l_0, 0)) + ((1 - done) * gamma) * sum_a pi[a] * (target_logit[b][j][a] - logpi[a]);
+ * loss and d_grad_logit as jh_iqn_loss.  d_stats float32[8] in jh_iqn_loss's slots: loss, max_Q (the largest mean of d_logit),
+ * max / min over d_logit_again (m_iqn.py:50 reassigns `logit` before lines 94-95 read it), marks at [5] and [7].
+ * tau_e > 0, l_0 <= 0, 1 <= N <= 256.  Two launches, no floating-point atomics: the same bits eagerly or replayed.               */
+int jh_miqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_logit_again, const float* d_target_logit,
+                 const float* d_action, const float* d_reward, const float* d_done, const float* d_tau, float gamma, float alpha, float tau_e,
+                 float l_0, float* d_grad_logit, float* d_stats, jh_stream stream);
 /* IQN.act (iqn.py:60-76) for R actor rows: jh_quantile_act's rules on d_logits float32 [R][N][A] (Q = mean over the N samples). */
 int jh_iqn_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
                const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream);

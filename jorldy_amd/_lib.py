@@ -96,12 +96,14 @@ _PROTOS = {
     "jh_iqnnet_sync_target": (C.c_int, [_vp, _vp]),
     "jh_iqnnet_forward": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "jh_iqnnet_learn_forward": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "jh_iqnnet_learn_forward_m": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "jh_iqnnet_backward": (C.c_int, [_vp, _vp, _vp]),
     "jh_iqnnet_optim_step": (C.c_int, [_vp, _f32, _vp]),
     "jh_iqn_cos_features": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "jh_iqn_hadamard": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "jh_iqn_hadamard_backward": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_iqn_loss": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "jh_miqn_loss": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "jh_iqn_act": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_pponet_param_count": (_i64, [_i32, _i32, _i32, _i32]),
     "jh_pponet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_uint64, _pp]),

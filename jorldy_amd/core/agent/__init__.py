@@ -4,11 +4,13 @@ from .base import BaseAgent
 from .dqn import DQN, ApeX, Double, Multistep, PER
 from .iqn import IQN
 from .mdqn import MDQN
+from .miqn import MIQN
 from .ppo import PPO
 from .qrdqn import QRDQN
 from .rainbow import C51, Rainbow
 
-agent_dict = {"dqn": DQN, "double": Double, "multistep": Multistep, "per": PER, "ape_x": ApeX, "c51": C51, "rainbow": Rainbow, "ppo": PPO, "qrdqn": QRDQN, "m_dqn": MDQN, "iqn": IQN}
+agent_dict = {"dqn": DQN, "double": Double, "multistep": Multistep, "per": PER, "ape_x": ApeX, "c51": C51, "rainbow": Rainbow, "ppo": PPO, "qrdqn": QRDQN, "m_dqn": MDQN, "iqn": IQN,
+              "m_iqn": MIQN}
 
 
 def Agent(name, *args, **kwargs):

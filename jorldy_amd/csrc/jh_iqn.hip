@@ -224,7 +224,7 @@ JH_EXPORT int jh_iqnnet_sync_target(jh_iqnnet* n, jh_stream stream) {
   return JH_OK;
 }
 
-// Up to two (parameter set, input rows) jobs that sit one after the other in the activation buffers: job j's rows start at row0.
+// Up to three (parameter set, input rows) jobs that sit one after the other in the activation buffers: job j's rows start at row0.
 // d_tau and d_logits cover the rows of all jobs contiguously, from row 0.  Each layer is ONE grouped launch for all jobs.
 struct IqJob {
   const float* P;
@@ -235,7 +235,7 @@ static int iq_forward(jh_iqnnet* n, const IqJob* jobs, int nj, const float* d_ta
   const int S = n->S, H = n->H, E = n->E, N = n->N, A = n->A;
   int total = 0;
   for (int j = 0; j < nj; ++j) total += jobs[j].rows;
-  TGemm g[2];
+  TGemm g[3];
   int rc;
   // head.l and state_embed on the state rows
   for (int j = 0; j < nj; ++j) {
@@ -302,7 +302,22 @@ JH_EXPORT int jh_iqnnet_learn_forward(jh_iqnnet* n, const float* d_x, int32_t B,
   return JH_OK;
 }
 
-// Backward of logits[0] = online(state) of the last jh_iqnnet_learn_forward: d_g = d(loss)/d(logits) [B][N][A]; fills the gradient
+// The three forwards M-IQN's learn() keeps (m_iqn.py:30, 43, 50; the reference's online(next_state) of line 40 feeds nothing and is
+// not run): rows [0, B): online on state with draw 0 -- where jh_iqnnet_backward expects the activations it differentiates --,
+// rows [B, 2B): online on state again with draw 1, rows [2B, 3B): target on next_state with draw 2.  The second job runs the state
+// trunk (head.l, state_embed) again rather than sharing job 0's: 1 / N of the sampled work, and every job stays a plain row range.
+JH_EXPORT int jh_iqnnet_learn_forward_m(jh_iqnnet* n, const float* d_x, int32_t B, const float* d_tau, float* d_logits, jh_stream stream) {
+  JH_ARG(n && d_x && d_tau && d_logits);
+  JH_ARG(B > 0 && B <= n->maxB);
+  IqJob jobs[3] = {{n->params, d_x, 0, B}, {n->params, d_x, B, B}, {n->target, d_x + (size_t)B * n->S, 2 * B, B}};
+  int rc = iq_forward(n, jobs, 3, d_tau, d_logits, jh_s(stream));
+  if (rc) return rc;
+  n->last_x = d_x;
+  n->last_B = B;
+  return JH_OK;
+}
+
+// Backward of logits[0] = online(state) of the last jh_iqnnet_learn_forward / _m: d_g = d(loss)/d(logits) [B][N][A]; fills the gradient
 // bucket (same layout as the parameters).  The online activations of the state rows are the first B (x N) rows of every buffer.
 JH_EXPORT int jh_iqnnet_backward(jh_iqnnet* n, const float* d_g, jh_stream stream) {
   JH_ARG(n && d_g);

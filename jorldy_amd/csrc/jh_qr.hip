@@ -1,8 +1,11 @@
-// The quantile family: what QR-DQN (core/agent/qrdqn.py) and IQN (core/agent/iqn.py) share below the network.  One loss and one
-// acting kernel, instantiated for the two layouts of a row block the networks write:
+// The quantile family: what QR-DQN (core/agent/qrdqn.py), IQN (core/agent/iqn.py) and M-IQN (core/agent/m_iqn.py) share below the
+// network.  One loss and one acting kernel, instantiated for the two layouts of a row block the networks write and, for the loss, the
+// two rules that turn the target network's quantiles into theta_target:
 //   jh_qr_loss       pairwise quantile-Huber loss, forward and backward to the online quantiles, online net selects / target net
 //                    evaluates; [B][A][N], tau [N] shared by the batch                (qrdqn.py:60-95)
 //   jh_iqn_loss      the same on [B][N][A] with tau [B][N], the draw of each sample   (iqn.py:89-121)
+//   jh_miqn_loss     jh_iqn_loss's pairwise phase under the Munchausen target: log-policy bonus of the online net's second draw at s,
+//                    soft bootstrap over the target net's policy at s'                (m_iqn.py:29-95)
 //   jh_quantile_act  epsilon-greedy acting on the mean of the N quantiles, [R][A][N]  (qrdqn.py:33-47, 112-115)
 //   jh_iqn_act       the same on [R][N][A]                                            (iqn.py:60-76, 142-146)
 // No floating-point atomics: every sum has a fixed order, so two runs (and a graph replay) give the same bits.
@@ -22,10 +25,18 @@ __device__ __forceinline__ size_t q_at(int b, int A, int N, int a, int i) {
   return L == Q_ACTION_MAJOR ? ((size_t)b * A + a) * N + i : (size_t)b * N * A + (size_t)i * A + a;
 }
 
+// The rule that fills the Bellman image T[j] of the target quantiles -- and with it what the second network output means.
+enum QTarget {
+  Q_TGT_GREEDY,     // next_logit = online(s'): its best mean selects the action the target net evaluates       (qrdqn.py:76-81, iqn.py:106-111)
+  Q_TGT_MUNCHAUSEN  // next_logit = online(s) under a second draw: its means are the policy of the log-policy
+                    // bonus; the target net's own means at s' are the policy of the soft bootstrap             (m_iqn.py:50-79)
+};
+
 struct QrArgs {
   int B, A, N;
   const float *logit, *next_logit, *target_logit, *action, *reward, *done, *tau;
   float gamma;
+  float alpha, tau_e, l_0;  // Munchausen: scale of the bonus, entropy temperature (the agent's self.tau), lower clip of the log-policy
   float *grad, *stats, *partial;  // partial [B][4] = {sum_j sum_i w * huber, max Q, max logit, min logit} of a sample
 };
 
@@ -47,10 +58,49 @@ __device__ __forceinline__ float qr_row_mean(const float* __restrict__ z, int b,
   return jh_wave_sum(s) / (float)N;
 }
 
-// One workgroup of 256 threads per sample (N <= 256: thread i owns prediction quantile i).
-// LDS: [N] Bellman image of the target quantiles, [A] selector means, [4][3] per-wave statistics, [16] reduction.
-// Every thread stays to the end: the work of threads i >= N is predicated, not skipped (block reduction at the end).
+// m_iqn.py:53-79 with agent/utils.py:29-39, for sample b: x = s_pol[A] (means of the online net's second draw at s), x' = s_nxt[A]
+// (means of the target net at s'), each with its row maximum subtracted before every exp:
+//   lp      = x[act] - (max x + tau_e log sum_k exp((x_k - max x) / tau_e)),  munchausen = alpha * clip(lp, l_0, 0)
+//   pi_k    = exp((x'_k - max x') / tau_e - log sum exp(...)),  logpi_k = x'_k - (max x' + tau_e log sum exp(...))
+//   T[j]    = (reward + munchausen) + ((1 - done) * gamma) * sum_k pi_k * (target[b][k][j] - logpi_k)
+// Every thread walks the same A values in the same order (as the first-maximum walk of the greedy rule does); pi and logpi meet in
+// LDS (s_pi, s_lpi [A]).  A = 1: lp = 0, pi = 1.  expf / logf are the accurate ones.
 template <QLayout L>
+__device__ __forceinline__ void qr_munchausen_target(const QrArgs& a, int b, int act, float r, float dn, const float* s_pol, const float* s_nxt, float* s_pi,
+                                                     float* s_lpi, float* s_T, int tid, bool own) {
+  const int A = a.A, N = a.N;
+  float m = s_pol[0], mn = s_nxt[0];
+  for (int k = 1; k < A; ++k) {
+    m = fmaxf(m, s_pol[k]);
+    mn = fmaxf(mn, s_nxt[k]);
+  }
+  float se = 0.f, sn = 0.f;
+  for (int k = 0; k < A; ++k) {
+    se += expf((s_pol[k] - m) / a.tau_e);
+    sn += expf((s_nxt[k] - mn) / a.tau_e);
+  }
+  const float lp = s_pol[act] - (m + a.tau_e * logf(se));
+  const float mun = a.alpha * fminf(fmaxf(lp, a.l_0), 0.f);
+  const float lsn = logf(sn);
+  const float tau_lse = mn + a.tau_e * lsn;
+  for (int k = tid; k < A; k += 256) {
+    const float x = s_nxt[k];
+    s_pi[k] = expf((x - mn) / a.tau_e - lsn);  // exp(log_softmax(y / tau)): the row maximum of y / tau is 0   utils.py:36-39
+    s_lpi[k] = x - tau_lse;
+  }
+  __syncthreads();
+  if (own) {
+    float soft = 0.f;
+    for (int k = 0; k < A; ++k) soft += s_pi[k] * (a.target_logit[q_at<L>(b, A, N, k, tid)] - s_lpi[k]);
+    s_T[tid] = (r + mun) + ((1.f - dn) * a.gamma) * soft;  // m_iqn.py:75-79, in torch's order of operations
+  }
+}
+
+// One workgroup of 256 threads per sample (N <= 256: thread i owns prediction quantile i).
+// LDS: [N] Bellman image of the target quantiles, [A] selector means, [4][3] per-wave statistics, [16] reduction; Munchausen: + [3][A]
+// (the target net's means at s', pi, logpi).
+// Every thread stays to the end: the work of threads i >= N is predicated, not skipped (block reduction at the end).
+template <QLayout L, QTarget T>
 __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -59,6 +109,7 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
   float* s_qsel = s_T + N;     // [A]
   float* s_stat = s_qsel + A;  // [4][3]
   float* s_red = s_stat + 12;  // [16]
+  float* s_nxt = s_red + 16;   // [A], then s_pi [A], s_lpi [A]   (Munchausen only)
   int act = (int)a.action[b];
   act = act < 0 ? 0 : (act >= A ? A - 1 : act);
   const float r = a.reward[b], dn = a.done[b];
@@ -69,16 +120,22 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
   // IQN: the FIRST forward's draw for this sample (iqn.py:90, 96)
   const float tau = a.tau[L == Q_ACTION_MAJOR ? (size_t)ti : (size_t)b * N + ti];
   const float inv_tau = 1.f - tau;  // qrdqn.py:31, iqn.py:120
-  // ---- phase 1: quantile means of online(s) (statistics) and online(s') (selector), actions strided over the waves
+  // ---- phase 1: quantile means of online(s) (statistics) and online(s') (selector), actions strided over the waves.  Munchausen: the
+  // second output is online(s) again; max / min logit are ITS extremes (m_iqn.py:50 reassigns `logit` before lines 94-95 read it),
+  // max_Q stays the first output's (m_iqn.py:31, 93); the target net's means at s' are the third set
   float maxq = -3.4e38f, maxl = -3.4e38f, minl = 3.4e38f;
   for (int aa = wid; aa < A; aa += 4) {
     float rmx, rmn, x0, x1;
     const float q = qr_row_mean<L>(a.logit, b, A, N, aa, lane, rmx, rmn);
     maxq = fmaxf(maxq, q);
-    maxl = fmaxf(maxl, rmx);
-    minl = fminf(minl, rmn);
     const float q2 = qr_row_mean<L>(a.next_logit, b, A, N, aa, lane, x0, x1);
+    maxl = fmaxf(maxl, T == Q_TGT_GREEDY ? rmx : x0);
+    minl = fminf(minl, T == Q_TGT_GREEDY ? rmn : x1);
     if (lane == 0) s_qsel[aa] = q2;
+    if constexpr (T == Q_TGT_MUNCHAUSEN) {
+      const float q3 = qr_row_mean<L>(a.target_logit, b, A, N, aa, lane, x0, x1);
+      if (lane == 0) s_nxt[aa] = q3;
+    }
     if constexpr (L == Q_ACTION_MAJOR) {
       if (aa != act) {  // the rows of the actions not taken: zero gradient (net.backward reads all of it)
         float* g = a.grad + q_at<L>(b, A, N, aa, 0);
@@ -94,15 +151,20 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
   }
   if (lane == 0) { s_stat[wid * 3 + 0] = maxq; s_stat[wid * 3 + 1] = maxl; s_stat[wid * 3 + 2] = minl; }
   __syncthreads();
-  // ---- a* = first maximum of the online net's means at s' (qrdqn.py:76, iqn.py:106); every thread walks the same A values
-  int best = 0;
-  float bq = -3.4e38f;
-  for (int aa = 0; aa < A; ++aa) {
-    const float q = s_qsel[aa];
-    if (q > bq) { bq = q; best = aa; }
+  if constexpr (T == Q_TGT_GREEDY) {
+    // ---- a* = first maximum of the online net's means at s' (qrdqn.py:76, iqn.py:106); every thread walks the same A values
+    int best = 0;
+    float bq = -3.4e38f;
+    for (int aa = 0; aa < A; ++aa) {
+      const float q = s_qsel[aa];
+      if (q > bq) { bq = q; best = aa; }
+    }
+    // ---- phase 2: theta_target = reward + (1 - done) * gamma * target(s')[a*]  (qrdqn.py:79-81, iqn.py:109-111, in torch's order of operations)
+    if (own) s_T[tid] = r + ((1.f - dn) * a.gamma) * a.target_logit[q_at<L>(b, A, N, best, tid)];
+  } else {
+    // ---- phase 2: theta_target = reward + Munchausen bonus + (1 - done) * gamma * soft value of target(s')   (m_iqn.py:53-79)
+    qr_munchausen_target<L>(a, b, act, r, dn, s_qsel, s_nxt, s_nxt + A, s_nxt + 2 * A, s_T, tid, own);
   }
-  // ---- phase 2: theta_target = reward + (1 - done) * gamma * target(s')[a*]  (qrdqn.py:79-81, iqn.py:109-111, in torch's order of operations)
-  if (own) s_T[tid] = r + ((1.f - dn) * a.gamma) * a.target_logit[q_at<L>(b, A, N, best, tid)];
   __syncthreads();
   // ---- phase 3: thread i walks the targets j; e = T[j] - P[i], smooth_l1 (beta 1), weight tau[i] / 1 - tau[i] by the sign of e
   float ls = 0.f, gs = 0.f;
@@ -189,13 +251,18 @@ __global__ void __launch_bounds__(256) jh_quantile_act_kernel(int R, int A, int 
   }
 }
 
+struct QMunchausen {
+  float alpha, tau_e, l_0;
+};
+
 // The launches keep the names the profile report and DESIGN.md's kernel table know them by, one set per entry point.
-template <QLayout L>
+template <QLayout L, QTarget T>
 int qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online, const float* d_target_logit,
             const float* d_action, const float* d_reward, const float* d_done, const float* d_tau, float gamma, float* d_grad_logit, float* d_stats,
-            jh_stream stream) {
+            jh_stream stream, QMunchausen mu = {0.f, 1.f, 0.f}) {
   JH_ARG(ctx && d_logit && d_next_logit_online && d_target_logit && d_action && d_reward && d_done && d_tau && d_grad_logit);
   JH_ARG(B >= 1 && A >= 1 && N >= 1 && N <= 256);
+  JH_ARG(mu.tau_e > 0.f && mu.l_0 <= 0.f);
   hipStream_t st = jh_s(stream);
   void* scratch = nullptr;
   int rc = jh_ctx_scratch(ctx, sizeof(float) * 4 * (size_t)B, &scratch);
@@ -204,12 +271,15 @@ int qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, 
   a.B = B; a.A = A; a.N = N;
   a.logit = d_logit; a.next_logit = d_next_logit_online; a.target_logit = d_target_logit; a.action = d_action;
   a.reward = d_reward; a.done = d_done; a.tau = d_tau; a.gamma = gamma; a.grad = d_grad_logit; a.stats = d_stats;
+  a.alpha = mu.alpha; a.tau_e = mu.tau_e; a.l_0 = mu.l_0;
   a.partial = (float*)scratch;
-  const size_t lds = sizeof(float) * ((size_t)N + (size_t)A + 12 + 16);
+  const size_t lds = sizeof(float) * ((size_t)N + (size_t)A * (T == Q_TGT_MUNCHAUSEN ? 4 : 1) + 12 + 16);
   JH_ARG(lds <= 64 * 1024);
-  JH_LAUNCH_NAMED(L == Q_ACTION_MAJOR ? "jh_qr_block_kernel" : "jh_iqn_block_kernel", jh_qr_block_kernel<L>, dim3(B), dim3(256), lds, st, a);
+  const bool m = T == Q_TGT_MUNCHAUSEN;
+  JH_LAUNCH_NAMED(m ? "jh_miqn_block_kernel" : L == Q_ACTION_MAJOR ? "jh_qr_block_kernel" : "jh_iqn_block_kernel", (jh_qr_block_kernel<L, T>), dim3(B), dim3(256), lds,
+                  st, a);
   JH_LAUNCH_CHECK();
-  JH_LAUNCH_NAMED(L == Q_ACTION_MAJOR ? "jh_qr_finish_kernel" : "jh_iqn_finish_kernel", jh_qr_finish_kernel, dim3(1), dim3(256), 0, st, a);
+  JH_LAUNCH_NAMED(m ? "jh_miqn_finish_kernel" : L == Q_ACTION_MAJOR ? "jh_qr_finish_kernel" : "jh_iqn_finish_kernel", jh_qr_finish_kernel, dim3(1), dim3(256), 0, st, a);
   JH_LAUNCH_CHECK();
   return JH_OK;
 }
@@ -235,12 +305,18 @@ int qr_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, 
 JH_EXPORT int jh_qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online,
                          const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done,
                          const float* d_tau, float gamma, float* d_grad_logit, float* d_stats, jh_stream stream) {
-  return qr_loss<Q_ACTION_MAJOR>(ctx, B, A, N, d_logit, d_next_logit_online, d_target_logit, d_action, d_reward, d_done, d_tau, gamma, d_grad_logit, d_stats, stream);
+  return qr_loss<Q_ACTION_MAJOR, Q_TGT_GREEDY>(ctx, B, A, N, d_logit, d_next_logit_online, d_target_logit, d_action, d_reward, d_done, d_tau, gamma, d_grad_logit, d_stats, stream);
 }
 JH_EXPORT int jh_iqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online,
                           const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done,
                           const float* d_tau, float gamma, float* d_grad_logit, float* d_stats, jh_stream stream) {
-  return qr_loss<Q_SAMPLE_MAJOR>(ctx, B, A, N, d_logit, d_next_logit_online, d_target_logit, d_action, d_reward, d_done, d_tau, gamma, d_grad_logit, d_stats, stream);
+  return qr_loss<Q_SAMPLE_MAJOR, Q_TGT_GREEDY>(ctx, B, A, N, d_logit, d_next_logit_online, d_target_logit, d_action, d_reward, d_done, d_tau, gamma, d_grad_logit, d_stats, stream);
+}
+JH_EXPORT int jh_miqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_logit_again, const float* d_target_logit,
+                           const float* d_action, const float* d_reward, const float* d_done, const float* d_tau, float gamma, float alpha, float tau_e,
+                           float l_0, float* d_grad_logit, float* d_stats, jh_stream stream) {
+  return qr_loss<Q_SAMPLE_MAJOR, Q_TGT_MUNCHAUSEN>(ctx, B, A, N, d_logit, d_logit_again, d_target_logit, d_action, d_reward, d_done, d_tau, gamma, d_grad_logit,
+                                                   d_stats, stream, QMunchausen{alpha, tau_e, l_0});
 }
 
 JH_EXPORT int jh_quantile_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,

@@ -881,6 +881,18 @@ def iqn_loss(logit, next_logit_online, target_logit, action, reward, done, tau, 
     return _quantile_loss(L.load().jh_iqn_loss, B, A, N, z, next_logit_online, target_logit, action, reward, done, t, gamma, stats)
 
 
+def miqn_loss(logit, logit_again, target_logit, action, reward, done, tau, gamma, alpha, tau_e, l_0, stats=None):
+    """jh_miqn_loss (m_iqn.py:29-95): logit / logit_again = online(state) under the first and a second draw, target_logit =
+    target(next_state), each [B, N, A]; action / reward / done [B] (or [B, 1]); tau float32 [B, N] = the FIRST draw; tau_e the entropy
+    temperature.  Returns (grad_logit [B, N, A], stats f32[8] as iqn_loss, max / min logit taken from logit_again)."""
+    z, t = _f32(logit), _f32(tau)
+    B, N, A = (int(v) for v in z.shape)
+    assert t.numel() == B * N
+    entry = lambda ctx, B, A, N, z, zn, zt, a, r, d, t, gamma, g, stats, stream: L.load().jh_miqn_loss(
+        ctx, B, A, N, z, zn, zt, a, r, d, t, gamma, float(alpha), float(tau_e), float(l_0), g, stats, stream)
+    return _quantile_loss(entry, B, A, N, z, logit_again, target_logit, action, reward, done, t, gamma, stats)
+
+
 def iqn_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_all=False):
     """jh_iqn_act: network outputs [R, N, A] (N samples per row, Q = their mean) -> (action int64 [R], q_taken float32 [R], q_all | None)
     on the device.  eps / u / rand_action as in value_act."""
@@ -1338,6 +1350,15 @@ class IQNNet:
         assert tau.is_contiguous() and tau.dtype == torch.float32 and tau.numel() == 3 * B * self.N
         assert out.is_contiguous() and out.numel() == 3 * B * self.N * self.A
         L.check(self.lib.jh_iqnnet_learn_forward(self.h, L.ptr(x_all), int(B), L.ptr(tau), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def learn_forward_m(self, x_all, B, tau, out):
+        """M-IQN's arrangement: x_all = [state; next_state] (2B rows), tau [3, B, N] -> out [3, B, N, A] = online(state) with draw 0 (the
+        one backward differentiates), online(state) with draw 1, target(next_state) with draw 2."""
+        assert x_all.is_contiguous() and x_all.dtype == torch.float32 and int(x_all.shape[0]) == 2 * B
+        assert tau.is_contiguous() and tau.dtype == torch.float32 and tau.numel() == 3 * B * self.N
+        assert out.is_contiguous() and out.numel() == 3 * B * self.N * self.A
+        L.check(self.lib.jh_iqnnet_learn_forward_m(self.h, L.ptr(x_all), int(B), L.ptr(tau), L.ptr(out), L.stream_ptr()))
         return out
 
     def backward(self, g, defer=False):
