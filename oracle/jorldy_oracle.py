@@ -459,7 +459,7 @@ def logits2Q(logits, z, shift_max=False):
 
 
 def c51_project_kl(logit, action, reward, done, target_logit, v_min, v_max, K, gamma,
-                   next_logit_online=None, weights=None, alpha=None, shift_max=False):
+                   next_logit_online=None, weights=None, alpha=None, shift_max=False, support=None):
     """C51 n-step categorical projection + cross-entropy ("KL") loss.
 
     rainbow.py:167-239 when next_logit_online/weights are given (double-Q action
@@ -468,10 +468,15 @@ def c51_project_kl(logit, action, reward, done, target_logit, v_min, v_max, K, g
     Quirks reproduced, not fixed: the PER weights enter only through their batch
     mean (shape broadcast, see below); the terminal branch is keyed on done[:,0]
     and averages the one-hot row sums (`mean` over source atoms); integral b
-    drops its mass in the non-terminal branch (l==u -> both weights 0)."""
+    drops its mass in the non-terminal branch (l==u -> both weights 0).
+    support: float32 [K] atoms used in place of np.linspace (floor / ceil of the projection depend on the
+    support's last bit, and np.linspace, torch.linspace and the kernel's form differ there)."""
     logit = np.asarray(logit, F32)
     B, A, _ = logit.shape
-    z = np.linspace(v_min, v_max, K, dtype=F32).reshape(1, K)  # torch.linspace fp32
+    if support is None:
+        z = np.linspace(v_min, v_max, K, dtype=F32).reshape(1, K)  # torch.linspace fp32
+    else:
+        z = np.asarray(support, F32).reshape(1, K)
     dz = F32((v_max - v_min) / (K - 1))
     p_logit, q_action = logits2Q(logit, z, shift_max)
     a = np.asarray(action).reshape(B).astype(np.int64)

@@ -321,7 +321,9 @@ def test_rbnet_independent_noise_matches_float64():
     _grads_vs_exact(nat, ref64, ref32)
 
 
-@pytest.mark.parametrize("head,S,A,K,H,B", [("mlp", 4, 3, 51, 32, 32), ("cnn", (4, 84, 84), 6, 51, 64, 8), ("mlp", 6, 5, 21, 16, 33)])
+@pytest.mark.parametrize("head,S,A,K,H,B", [("mlp", 4, 3, 51, 32, 32), ("cnn", (4, 84, 84), 6, 51, 64, 8), ("mlp", 6, 5, 21, 16, 33),
+                                              # the dueling block kernel at every NS of c51_project (K = 65, 129, 200) and its weight preload past B = 128
+                                              ("mlp", 4, 5, 65, 32, 130), ("mlp", 6, 9, 200, 16, 7), ("mlp", 4, 2, 129, 16, 64)])
 def test_rainbow_fused_step_is_bit_identical_to_the_separate_calls(head, S, A, K, H, B):
     """jh_rbnet_c51_step (dueling combine + C51 + gradient through the combine in one launch; statistics + PER leaf write-back in one;
     climb) followed by the deferred backward (d(sigma) and conv1's partial sums folded into the optimizer pass) against the calls it
