@@ -393,6 +393,61 @@ int jh_miqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_lo
 int jh_iqn_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
                const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream);
 
+/* ------------------------------------------------------------------ deterministic actor-critic (TD3, DDPG)
+ * The elementwise steps of td3.py:146-209 / ddpg.py:117-163 (float32, fixed summation order, capturable, no host sync):
+ *   jh_td3_next_action    a = clamp(tanh(z) + clamp(noise_std * eps, -noise_clip, noise_clip), -1, 1) on [B][A] (td3.py:159-162);
+ *                         d_eps NULL: a = tanh(z) (policy.py:20; ddpg.py:130, acting, the actor update)
+ *   jh_td3_critic_loss    d_q, d_q_next [n_critics][B]: y = r + (1 - d) * gamma * min_i q_next_i (td3.py:163-166, ddpg.py:131-132),
+ *                         loss_i = mean((y - q_i)^2), d_grad [n_critics][B] = 2 (q_i - y) / B, d_y [B] (optional);
+ *                         d_stats float32[4] = {loss_1, loss_2 (0 for one critic), max_b y (td3.py:178), arrival mark}.
+ *                         1 <= B <= 2^20, n_critics 1 or 2.
+ *   jh_td3_actor_seed     actor_loss = -mean(q) (td3.py:183, ddpg.py:144), d_grad_q [B] = -1 / B; d_stats float32[2] = {actor_loss, mark}
+ *   jh_td3_tanh_backward  d_grad_z = d_grad_a * (1 - a^2): the way back through a = tanh(z)
+ *   jh_td3_polyak         target <- tau * params + (1 - tau) * target (td3.py:203-209) bit for bit as torch evaluates it on float32 CPU
+ *                         tensors: tau and (1 - tau) -- formed in double -- rounded to float32, two products, one sum.  0 <= tau <= 1.  */
+int jh_td3_next_action(jh_ctx* ctx, int32_t B, int32_t A, const float* d_z, const float* d_eps, float noise_std, float noise_clip, float* d_out,
+                       jh_stream stream);
+int jh_td3_critic_loss(jh_ctx* ctx, int32_t B, int32_t n_critics, const float* d_q, const float* d_q_next, const float* d_reward,
+                       const float* d_done, float gamma, float* d_y, float* d_grad, float* d_stats, jh_stream stream);
+int jh_td3_actor_seed(jh_ctx* ctx, int32_t B, const float* d_q, float* d_grad_q, float* d_stats, jh_stream stream);
+int jh_td3_tanh_backward(jh_ctx* ctx, int32_t B, int32_t A, const float* d_grad_a, const float* d_a, float* d_grad_z, jh_stream stream);
+int jh_td3_polyak(jh_ctx* ctx, int64_t n, const float* d_params, float* d_target, double tau, jh_stream stream);
+/* The networks: a deterministic policy (network/policy.py:8-20: head.l -> relu(l) -> tanh(pi)) and n_critics = 1 (DDPG) or 2 (TD3)
+ * continuous Q networks (network/q_network.py:23-39: [head.l(s) | relu(e(a))] -> relu(l) -> q), each with a target copy.  MLP head,
+ * scalar S, H % 4 == 0, A >= 1.  Caller-owned flat fp32 buckets: five of actor_floats (online, target, gradients, exp_avg, exp_avg_sq)
+ * and five of n_critics * critic_floats, critic c at c * critic_floats (jh_acnet_param_counts_for).  The critics share one optimizer
+ * block and one Adam launch: td3.py:95-112 gives both the same settings.  jh_acnet_segment: segments 0-5 of the actor bucket
+ * (head.l.weight [H][S], head.l.bias, l.weight [H][H], l.bias, pi.weight [A][H], pi.bias) and 6-13 of one critic (head.l.weight [H][S],
+ * head.l.bias, e.weight [H][A], e.bias, l.weight [H][2H], l.bias, q.weight [1][H], q.bias), offsets relative to that critic.        */
+typedef struct jh_acnet jh_acnet;
+int jh_acnet_param_counts_for(int32_t S, int32_t H, int32_t A, int64_t* actor_floats, int64_t* critic_floats);
+int jh_acnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int32_t n_critics, int32_t max_batch, float* d_actor,
+                    float* d_actor_target, float* d_actor_grads, float* d_actor_m, float* d_actor_v, float* d_critics,
+                    float* d_critics_target, float* d_critics_grads, float* d_critics_m, float* d_critics_v, jh_acnet** out);
+void jh_acnet_destroy(jh_acnet* n);
+int32_t jh_acnet_segment_count(void);
+int jh_acnet_segment(const jh_acnet* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols);
+/* which: 0 the actor's Adam, 1 the critics'                                                                      */
+int jh_acnet_set_hyper(jh_acnet* n, int32_t which, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream);
+int jh_acnet_set_lr(jh_acnet* n, int32_t which, double lr, jh_stream stream);
+/* every target <- its online network; update_target_soft (td3.py:203-209, ddpg.py:159-163) as jh_td3_polyak on both buckets */
+int jh_acnet_sync_target(jh_acnet* n, jh_stream stream);
+int jh_acnet_soft_update(jh_acnet* n, double tau, jh_stream stream);
+/* actor(x) -> d_action [rows][A] (td3.py:139, ddpg.py:112), critic_c(x, action) -> d_q [n_critics][rows]; rows <= max_batch,
+ * which 0 online / 1 target                                                                                      */
+int jh_acnet_actor_forward(jh_acnet* n, int32_t which, const float* d_x, int32_t rows, float* d_action, jh_stream stream);
+int jh_acnet_critic_forward(jh_acnet* n, int32_t which, const float* d_x, const float* d_action, int32_t rows, float* d_q, jh_stream stream);
+/* The critic update (td3.py:157-176, ddpg.py:128-138): d_x = [state; next_state] (2B rows); d_noise [B][A] standard normals, or NULL
+ * for no target noise (DDPG).  Target pass and online pass share grouped launches; loss; backward; one Adam step of the critics.
+ * -> d_y [B], d_q [n_critics][B] (both optional), d_stats as jh_td3_critic_loss.  12 launches.                      */
+int jh_acnet_critic_update(jh_acnet* n, const float* d_x, const float* d_action, const float* d_reward, const float* d_done,
+                           const float* d_noise, int32_t B, float gamma, float noise_std, float noise_clip, float* d_y, float* d_q,
+                           float* d_stats, jh_stream stream);
+/* The actor update (td3.py:181-188, ddpg.py:143-148): a = actor(state), -mean(critic_1(state, a)), backward through critic 1's action
+ * input into the actor, the actor's Adam step.  Critic 1's parameters, gradient bucket and moments are not written.
+ * -> d_action_pred [B][A] (optional), d_stats as jh_td3_actor_seed.  16 launches.                                   */
+int jh_acnet_actor_update(jh_acnet* n, const float* d_x, int32_t B, float* d_action_pred, float* d_stats, jh_stream stream);
+
 /* ------------------------------------------------------------------ native policy-value MLP
  * The encoder of the PPO configs (core/network/head.py:6-18 MLP head + policy_value.py:8-57):
  * S -> H relu -> H relu -> {A logits | A mu, A log_std} + value, as hand-written kernels

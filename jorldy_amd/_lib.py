@@ -105,6 +105,24 @@ _PROTOS = {
     "jh_iqn_loss": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
     "jh_miqn_loss": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "jh_iqn_act": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_td3_next_action": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _f32, _f32, _vp, _vp]),
+    "jh_td3_critic_loss": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
+    "jh_td3_actor_seed": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "jh_td3_tanh_backward": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "jh_td3_polyak": (C.c_int, [_vp, _i64, _vp, _vp, _f64, _vp]),
+    "jh_acnet_param_counts_for": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "jh_acnet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pp]),
+    "jh_acnet_destroy": (None, [_vp]),
+    "jh_acnet_segment_count": (_i32, []),
+    "jh_acnet_segment": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
+    "jh_acnet_set_hyper": (C.c_int, [_vp, _i32, _f64, _f64, _f64, _f64, _i64, _vp]),
+    "jh_acnet_set_lr": (C.c_int, [_vp, _i32, _f64, _vp]),
+    "jh_acnet_sync_target": (C.c_int, [_vp, _vp]),
+    "jh_acnet_soft_update": (C.c_int, [_vp, _f64, _vp]),
+    "jh_acnet_actor_forward": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp]),
+    "jh_acnet_critic_forward": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "jh_acnet_critic_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "jh_acnet_actor_update": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "jh_pponet_param_count": (_i64, [_i32, _i32, _i32, _i32]),
     "jh_pponet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_uint64, _pp]),
     "jh_pponet_destroy": (None, [_vp]),

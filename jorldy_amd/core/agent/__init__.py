@@ -1,6 +1,7 @@
 """Agent factory with the reference's interface (core/agent/__init__.py:32-42): `Agent(name, **cfg)`.
 Keys match the reference's auto-registered snake_case class names."""
 from .base import BaseAgent
+from .ddpg import DDPG
 from .dqn import DQN, ApeX, Double, Multistep, PER
 from .iqn import IQN
 from .mdqn import MDQN
@@ -8,9 +9,10 @@ from .miqn import MIQN
 from .ppo import PPO
 from .qrdqn import QRDQN
 from .rainbow import C51, Rainbow
+from .td3 import TD3
 
 agent_dict = {"dqn": DQN, "double": Double, "multistep": Multistep, "per": PER, "ape_x": ApeX, "c51": C51, "rainbow": Rainbow, "ppo": PPO, "qrdqn": QRDQN, "m_dqn": MDQN, "iqn": IQN,
-              "m_iqn": MIQN}
+              "m_iqn": MIQN, "td3": TD3, "ddpg": DDPG}
 
 
 def Agent(name, *args, **kwargs):

@@ -10,6 +10,8 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   dueling                      core/network/dueling.py:8-35
   rainbow                      core/network/rainbow.py:8-94 (+ utils.py:55-107 noisy linear)
   iqn                          core/network/iqn.py:9-47
+  deterministic_policy         core/network/policy.py:8-20
+  continuous_q_network         core/network/q_network.py:23-39
 """
 import torch
 
@@ -153,6 +155,31 @@ class IQN(BaseNetwork):
         orthogonal_init(self.q, "linear")
 
 
+class DeterministicPolicy(BaseNetwork):
+    """The actor of TD3 / DDPG (policy.py:8-20): head -> relu(l) -> tanh(pi)."""
+
+    def __init__(self, D_in, D_out, D_hidden=512, head="mlp"):
+        super().__init__(D_in, D_hidden, head)
+        self.l = torch.nn.Linear(self.head.D_head_out, D_hidden)
+        self.pi = torch.nn.Linear(D_hidden, D_out)
+        orthogonal_init(self.l)
+        orthogonal_init(self.pi, "tanh")
+
+
+class ContinuousQ_Network(BaseNetwork):
+    """The critic of TD3 / DDPG (q_network.py:23-39): [head(state) | relu(e(action))] -> relu(l) -> q.  The reference's argument order:
+    head comes before D_hidden."""
+
+    def __init__(self, D_in1, D_in2, head="mlp", D_hidden=512):
+        super().__init__(D_in1, D_hidden, head)
+        self.e = torch.nn.Linear(D_in2, D_hidden)
+        self.l = torch.nn.Linear(D_hidden + self.head.D_head_out, D_hidden)
+        self.q = torch.nn.Linear(D_hidden, 1)
+        orthogonal_init(self.e)
+        orthogonal_init(self.l)
+        orthogonal_init(self.q, "linear")
+
+
 network_dict = {
     "discrete_q_network": DiscreteQ_Network,
     "discrete_policy_value": DiscretePolicyValue,
@@ -160,6 +187,8 @@ network_dict = {
     "dueling": Dueling,
     "rainbow": Rainbow,
     "iqn": IQN,
+    "deterministic_policy": DeterministicPolicy,
+    "continuous_q_network": ContinuousQ_Network,
 }
 
 

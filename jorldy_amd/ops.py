@@ -1373,6 +1373,184 @@ class IQNNet:
         L.check(self.lib.jh_iqnnet_optim_step(self.h, float(max_norm or 0.0), L.stream_ptr()))
 
 
+def td3_next_action(z, eps=None, noise_std=0.0, noise_clip=0.0, out=None):
+    """jh_td3_next_action: clamp(tanh(z) + clamp(noise_std * eps, -noise_clip, noise_clip), -1, 1) on [B, A] (td3.py:159-162); eps None: tanh(z)."""
+    z = _f32(z)
+    B, A = z.shape
+    eps = None if eps is None else _f32(eps)
+    assert eps is None or tuple(eps.shape) == (B, A)
+    out = torch.empty_like(z) if out is None else out
+    L.check(L.load().jh_td3_next_action(L.ctx(z.device.index), B, A, L.ptr(z), L.ptr(eps), float(noise_std), float(noise_clip), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def td3_critic_loss(q, q_next, reward, done, gamma, stats=None):
+    """jh_td3_critic_loss: q, q_next [n, B] (n = 1 or 2 critics) -> (y [B], d(loss_i)/d(q_i) [n, B], stats [4] = loss_1, loss_2, max_Q, mark)."""
+    q, q_next, reward, done = _f32(q), _f32(q_next), _f32(reward), _f32(done)
+    n, B = q.shape
+    assert tuple(q_next.shape) == (n, B) and reward.numel() == B and done.numel() == B
+    y = torch.empty(B, dtype=torch.float32, device=q.device)
+    grad = torch.empty(n, B, dtype=torch.float32, device=q.device)
+    stats = torch.zeros(4, dtype=torch.float32, device=q.device) if stats is None else stats
+    L.check(L.load().jh_td3_critic_loss(L.ctx(q.device.index), B, n, L.ptr(q), L.ptr(q_next), L.ptr(reward), L.ptr(done), float(gamma), L.ptr(y), L.ptr(grad),
+                                        L.ptr(stats), L.stream_ptr()))
+    return y, grad, stats
+
+
+def td3_actor_seed(q, stats=None):
+    """jh_td3_actor_seed: q [B] -> (d(actor_loss)/d(q) [B] = -1 / B, stats [2] = actor_loss = -mean(q), mark)."""
+    q = _f32(q).reshape(-1)
+    B = q.numel()
+    grad = torch.empty(B, dtype=torch.float32, device=q.device)
+    stats = torch.zeros(2, dtype=torch.float32, device=q.device) if stats is None else stats
+    L.check(L.load().jh_td3_actor_seed(L.ctx(q.device.index), B, L.ptr(q), L.ptr(grad), L.ptr(stats), L.stream_ptr()))
+    return grad, stats
+
+
+def td3_tanh_backward(grad_a, a):
+    """jh_td3_tanh_backward: d(z) = d(a) * (1 - a^2) on [B, A]."""
+    grad_a, a = _f32(grad_a), _f32(a)
+    B, A = a.shape
+    out = torch.empty_like(a)
+    L.check(L.load().jh_td3_tanh_backward(L.ctx(a.device.index), B, A, L.ptr(grad_a), L.ptr(a), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def td3_polyak(params, target, tau):
+    """jh_td3_polyak: target <- tau * params + (1 - tau) * target in place over flat float32 buckets (td3.py:203-209)."""
+    assert params.is_contiguous() and target.is_contiguous() and params.dtype == target.dtype == torch.float32 and params.numel() == target.numel()
+    L.check(L.load().jh_td3_polyak(L.ctx(params.device.index), int(params.numel()), L.ptr(params), L.ptr(target), float(tau), L.stream_ptr()))
+    return target
+
+
+class ACNet:
+    """jh_acnet_*: a deterministic policy (network/policy.py:8-20) and one (DDPG) or two (TD3) continuous Q networks
+    (network/q_network.py:23-39), each with a target copy, in flat buckets: `actor*` of n_actor floats, `critics*` of n_critics * n_critic
+    floats (critic c at c * n_critic).  The critic update, the actor update (backward through critic 1's action input), the soft update
+    and the target sync are tile-engine launches plus the elementwise kernels of jh_td3.hip.  Networks are named "actor", "critic1",
+    "critic2" ("critic" = "critic1"); export / import speak the reference's state_dict keys."""
+
+    _ASEG = ("head.l.weight", "head.l.bias", "l.weight", "l.bias", "pi.weight", "pi.bias")
+    _CSEG = ("head.l.weight", "head.l.bias", "e.weight", "e.bias", "l.weight", "l.bias", "q.weight", "q.bias")
+    KINDS = ("params", "target", "grads", "m", "v")
+    kind, cnn = "actor_critic", False
+
+    def __init__(self, state_size, action_size, hidden, n_critics, max_batch, device):
+        self.lib = L.load()
+        self.device = torch.device(device)
+        self.ctx = L.ctx(self.device.index)
+        self.S, self.A, self.H, self.nc, self.maxB = int(state_size), int(action_size), int(hidden), int(n_critics), int(max_batch)
+        na, ncr = C.c_int64(), C.c_int64()
+        L.check(self.lib.jh_acnet_param_counts_for(self.S, self.H, self.A, C.byref(na), C.byref(ncr)))
+        self.n_actor, self.n_critic = int(na.value), int(ncr.value)
+        mk = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.actor = {k: mk(self.n_actor) for k in self.KINDS}
+        self.critics = {k: mk(self.nc * self.n_critic) for k in self.KINDS}
+        self.h = C.c_void_p()
+        L.check(self.lib.jh_acnet_create(self.ctx, self.S, self.H, self.A, self.nc, self.maxB, *[L.ptr(self.actor[k]) for k in self.KINDS],
+                                         *[L.ptr(self.critics[k]) for k in self.KINDS], C.byref(self.h)))
+        names = self._ASEG + self._CSEG
+        assert int(self.lib.jh_acnet_segment_count()) == len(names)
+        self.aseg, self.cseg = {}, {}
+        for i, name in enumerate(names):
+            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
+            L.check(self.lib.jh_acnet_segment(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
+            (self.aseg if i < len(self._ASEG) else self.cseg)[name] = (off.value, rows.value, cols.value)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.jh_acnet_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def nets(self):
+        return ("actor",) + tuple(f"critic{c + 1}" for c in range(self.nc))
+
+    def flat(self, net, kind="params"):
+        """The flat float32 view of one network in one of the buckets KINDS."""
+        if net == "actor":
+            return self.actor[kind]
+        c = {"critic": 0, "critic1": 0, "critic2": 1}[net]
+        assert c < self.nc, f"{net}: this object has {self.nc} critic(s)"
+        return self.critics[kind][c * self.n_critic : (c + 1) * self.n_critic]
+
+    def _pairs(self, net, kind):
+        flat, seg = self.flat(net, kind), (self.aseg if net == "actor" else self.cseg)
+        out = []
+        for name, (off, rows, cols) in seg.items():
+            v = flat[off : off + rows * cols]
+            out.append((name, v.view(rows, cols) if name.endswith(".weight") else v))
+        return out
+
+    def export_state(self, net, kind="params"):
+        from collections import OrderedDict
+
+        return OrderedDict((k, v.clone()) for k, v in self._pairs(net, kind))
+
+    @torch.no_grad()
+    def import_state(self, sd, net, kind="params"):
+        pairs = dict(self._pairs(net, kind))
+        missing = [k for k in pairs if k not in sd]
+        if missing:
+            raise KeyError(f"state_dict is missing {missing}")
+        for k, v in pairs.items():
+            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
+            if tuple(src.shape) != tuple(v.shape):
+                raise ValueError(f"{k}: expected {tuple(v.shape)}, got {tuple(src.shape)}")
+            v.copy_(src)
+
+    def set_hyper(self, which, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
+        """which: "actor" | "critic" (one Adam for both critics)."""
+        L.check(self.lib.jh_acnet_set_hyper(self.h, 0 if which == "actor" else 1, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
+
+    def set_lr(self, which, lr):
+        L.check(self.lib.jh_acnet_set_lr(self.h, 0 if which == "actor" else 1, float(lr), L.stream_ptr()))
+
+    def sync_target(self):
+        L.check(self.lib.jh_acnet_sync_target(self.h, L.stream_ptr()))
+
+    def soft_update(self, tau):
+        L.check(self.lib.jh_acnet_soft_update(self.h, float(tau), L.stream_ptr()))
+
+    def actor_forward(self, x, which=0, out=None):
+        """actor(x) -> [rows, A]; rows <= max_batch; which 0 online / 1 target."""
+        assert x.is_contiguous() and x.device == self.device and x.dtype == torch.float32 and x.shape[1] == self.S
+        rows = int(x.shape[0])
+        out = torch.empty(rows, self.A, dtype=torch.float32, device=self.device) if out is None else out
+        assert out.is_contiguous() and out.numel() == rows * self.A
+        L.check(self.lib.jh_acnet_actor_forward(self.h, int(which), L.ptr(x), rows, L.ptr(out), L.stream_ptr()))
+        return out
+
+    def critic_forward(self, x, action, which=0):
+        """critic_c(x, action) for every critic -> [n_critics, rows]."""
+        assert x.is_contiguous() and x.dtype == torch.float32 and action.is_contiguous() and action.dtype == torch.float32
+        rows = int(x.shape[0])
+        assert tuple(x.shape) == (rows, self.S) and tuple(action.shape) == (rows, self.A)
+        out = torch.empty(self.nc, rows, dtype=torch.float32, device=self.device)
+        L.check(self.lib.jh_acnet_critic_forward(self.h, int(which), L.ptr(x), L.ptr(action), rows, L.ptr(out), L.stream_ptr()))
+        return out
+
+    def critic_update(self, x_all, action, reward, done, noise, gamma, noise_std, noise_clip, stats, y=None, q=None):
+        """x_all = [state; next_state] (2B rows); noise [B, A] standard normals or None.  stats [4] = loss_1, loss_2, max_Q, mark;
+        optional outputs y [B], q [n_critics, B]."""
+        B = int(action.shape[0])
+        for t in (x_all, action, reward, done):
+            assert t.is_contiguous() and t.dtype == torch.float32
+        assert tuple(x_all.shape) == (2 * B, self.S) and tuple(action.shape) == (B, self.A) and reward.numel() == B and done.numel() == B
+        assert noise is None or (noise.is_contiguous() and noise.dtype == torch.float32 and tuple(noise.shape) == (B, self.A))
+        assert (y is None or y.numel() == B) and (q is None or q.numel() == self.nc * B)
+        L.check(self.lib.jh_acnet_critic_update(self.h, L.ptr(x_all), L.ptr(action), L.ptr(reward), L.ptr(done), L.ptr(noise), B, float(gamma), float(noise_std),
+                                                float(noise_clip), L.ptr(y), L.ptr(q), L.ptr(stats), L.stream_ptr()))
+
+    def actor_update(self, x, stats, action_pred=None):
+        """x = state [B, S]; stats [2] = actor_loss, mark; optional output action_pred [B, A] = actor(state) before the step."""
+        B = int(x.shape[0])
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.shape[1] == self.S and (action_pred is None or action_pred.numel() == B * self.A)
+        L.check(self.lib.jh_acnet_actor_update(self.h, L.ptr(x), B, L.ptr(action_pred), L.ptr(stats), L.stream_ptr()))
+
+
 class StagingRing:
     """jh_ring_*: bounded lock-free multi-producer / single-consumer ring of transitions in pinned host memory
     (the async Ape-X transport).  `produce` may be called from any number of actor threads (the GIL is released
