@@ -448,6 +448,84 @@ int jh_acnet_critic_update(jh_acnet* n, const float* d_x, const float* d_action,
  * -> d_action_pred [B][A] (optional), d_stats as jh_td3_actor_seed.  16 launches.                                   */
 int jh_acnet_actor_update(jh_acnet* n, const float* d_x, int32_t B, float* d_action_pred, float* d_stats, jh_stream stream);
 
+/* ------------------------------------------------------------------ soft actor-critic, continuous actions (SAC)
+ * The elementwise steps of sac.py:161-269 on the Gaussian policy of policy.py:38-55 (float32, fixed summation order, capturable, no
+ * host sync).  The temperature lives in a caller-owned, 8-byte aligned device block of JH_SAC_ALPHA_FLOATS floats that the kernels read
+ * and advance themselves, so that a replayed graph sees the current alpha and counts its own Adam steps:
+ *   [0] log_alpha   [1] alpha in use: what the losses of the current learn() are formed with (sac.py:250 refreshes it only after the
+ *   actor step, before Adam moves log_alpha: the alpha of learn k is exp(log_alpha) after k - 1 steps)   [2] exp_avg   [3] exp_avg_sq
+ *   [4] Adam's step count   [5] alpha_lr   [6] Adam's eps   [7] dynamic (0: static log_alpha, the block is only read, but for [9])
+ *   [8] target_entropy = -action_size (sac.py:109)   [9] alpha / B of the actor loss just seeded (written by jh_sac_actor_seed, read
+ *   by jh_sac_sample_backward)   [10-11] beta1 and [12-13] beta2 as doubles   [14-15] unused
+ *   jh_sac_sample           mu = clamp(mu_raw, -5, 5), std = exp(tanh(ls_raw)) (policy.py:38-55), z = mu + std * eps, d_a = tanh(z) and
+ *                           d_logp [B] = sum_j [Normal(mu, std).log_prob(z)_j - log(1 - a_j^2 + 1e-7)], j ascending (sac.py:161-169).
+ *                           d_eps NULL: the evaluation action tanh(mu) (sac.py:149-150), d_ls_raw and d_logp unused.
+ *   jh_sac_critic_loss      d_q, d_q_next [2][B]: y = r + (1 - d) * gamma * (min_i q_next_i - alpha * logp_next) (sac.py:186-211), alpha
+ *                           from the block; loss_i = mean((y - q_i)^2), d_grad [2][B] = 2 (q_i - y) / B, d_y [B] (optional);
+ *                           d_stats float32[4] = {loss_1, loss_2, max_b y (sac.py:213), arrival mark}.  1 <= B <= 2^20.
+ *   jh_sac_actor_seed       d_q [2][B] = q_i(s, a), d_logp [B]: actor_loss = -mean(alpha * (-logp) + min(q_1, q_2)) (sac.py:241-242);
+ *                           d_grad_q [2][B] = -1 / B on the smaller critic, half each on a tie (torch.min's backward); block[9] = alpha / B;
+ *                           alpha_loss = log_alpha * mean(-logp - target_entropy) (sac.py:248); then, dynamic, alpha in use <-
+ *                           exp(log_alpha) and ONE Adam step of log_alpha (sac.py:250-255).  d_stats float32[6] = {actor_loss,
+ *                           alpha_loss, mean_Q = mean(min(q_1, q_2)), alpha (the refreshed one), entropy = mean(-logp), arrival mark}.
+ *   jh_sac_sample_backward  d_grad_a (+ d_grad_a2 when not NULL: the two critics' action gradients) and block[9] -> d(mu_raw), d(ls_raw):
+ *                           dz = da (1 - a^2) + c 2 a (1 - a^2) / (1 - a^2 + 1e-7); d(mu_raw) = dz where -5 <= mu_raw <= 5;
+ *                           d(ls_raw) = (dz std eps - c) (1 - tanh(ls_raw)^2).                                                    */
+#define JH_SAC_ALPHA_FLOATS 16
+int jh_sac_sample(jh_ctx* ctx, int32_t B, int32_t A, const float* d_mu_raw, const float* d_ls_raw, const float* d_eps, float* d_a,
+                  float* d_logp, jh_stream stream);
+int jh_sac_critic_loss(jh_ctx* ctx, int32_t B, const float* d_q, const float* d_q_next, const float* d_logp_next, const float* d_reward,
+                       const float* d_done, float gamma, const float* d_alpha, float* d_y, float* d_grad, float* d_stats, jh_stream stream);
+int jh_sac_actor_seed(jh_ctx* ctx, int32_t B, const float* d_q, const float* d_logp, float* d_alpha, float* d_grad_q, float* d_stats,
+                      jh_stream stream);
+int jh_sac_sample_backward(jh_ctx* ctx, int32_t B, int32_t A, const float* d_grad_a, const float* d_grad_a2, const float* d_mu_raw,
+                           const float* d_ls_raw, const float* d_eps, const float* d_a, const float* d_alpha, float* d_grad_mu_raw,
+                           float* d_grad_ls_raw, jh_stream stream);
+/* The networks (sac.py:75-95): a Gaussian policy, ONLINE ONLY (network/policy.py:38-55: head.l -> relu(l) -> mu, log_std; the module returns
+ * clamp(mu, -5, 5) and exp(tanh(log_std))), and two continuous Q networks (network/q_network.py:23-39) with their targets.  MLP head,
+ * scalar S, H % 4 == 0, A >= 1.  Caller-owned flat fp32 buckets: four of actor_floats (online, gradients, exp_avg, exp_avg_sq) and five of
+ * 2 * critic_floats (online, target, gradients, exp_avg, exp_avg_sq), critic c at c * critic_floats (jh_sacnet_param_counts_for, which
+ * needs no GPU).  jh_sacnet_segment: segments 0-7 of the actor bucket in the reference's state_dict order (head.l.weight [H][S],
+ * head.l.bias, l.weight [H][H], l.bias, mu.weight [A][H], mu.bias, log_std.weight [A][H], log_std.bias; inside the bucket mu.weight and
+ * log_std.weight are stored back to back, as are the two biases: one [2A][H] layer) and 8-15 of one critic as jh_acnet_segment's 6-13.
+ * The critics share one optimizer block and one Adam launch (sac.py:136-140 gives both the same settings); the temperature block of the
+ * jh_sac_* kernels lives inside the object.                                                                         */
+typedef struct jh_sacnet jh_sacnet;
+int jh_sacnet_param_counts_for(int32_t S, int32_t H, int32_t A, int64_t* actor_floats, int64_t* critic_floats);
+int jh_sacnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int32_t max_batch, float* d_actor, float* d_actor_grads, float* d_actor_m,
+                     float* d_actor_v, float* d_critics, float* d_critics_target, float* d_critics_grads, float* d_critics_m,
+                     float* d_critics_v, jh_sacnet** out);
+void jh_sacnet_destroy(jh_sacnet* n);
+int32_t jh_sacnet_segment_count(void);
+int jh_sacnet_segment(const jh_sacnet* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols);
+/* which: 0 the actor's Adam, 1 the critics'                                                                      */
+int jh_sacnet_set_hyper(jh_sacnet* n, int32_t which, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream);
+int jh_sacnet_set_lr(jh_sacnet* n, int32_t which, double lr, jh_stream stream);
+/* The temperature block as a whole (sac.py:97-109; target_entropy = -A is the object's own): log_alpha, the alpha in use, alpha_lr
+ * (never decayed: sac.py:292-300), Adam's betas, eps, step count and moments, dynamic (use_dynamic_alpha).  jh_sacnet_get_alpha copies
+ * the JH_SAC_ALPHA_FLOATS floats to host memory.  Both synchronise the stream: not for a capture.                  */
+int jh_sacnet_set_alpha(jh_sacnet* n, double log_alpha, double alpha, double lr, double beta1, double beta2, double eps, int64_t step,
+                        double m, double v, int32_t dynamic, jh_stream stream);
+int jh_sacnet_get_alpha(jh_sacnet* n, float* h_block, jh_stream stream);
+/* target critics <- online critics; update_target_soft (sac.py:271-275) as jh_td3_polyak on the critics' bucket     */
+int jh_sacnet_sync_target(jh_sacnet* n, jh_stream stream);
+int jh_sacnet_soft_update(jh_sacnet* n, double tau, jh_stream stream);
+/* actor(x) -> d_mu, d_std [rows][A] (sac.py:148); critic_c(x, action) -> d_q [2][rows], which 0 online / 1 target; rows <= max_batch */
+int jh_sacnet_actor_forward(jh_sacnet* n, const float* d_x, int32_t rows, float* d_mu, float* d_std, jh_stream stream);
+int jh_sacnet_critic_forward(jh_sacnet* n, int32_t which, const float* d_x, const float* d_action, int32_t rows, float* d_q, jh_stream stream);
+/* The critic update (sac.py:183-225): d_x = [state; next_state] (2B rows), d_eps [B][A] standard normals; a', logp' from the ONLINE actor
+ * on next_state, y with the alpha in use; loss; backward; one Adam step of the critics.
+ * -> d_y [B], d_q [2][B], d_a_next [B][A], d_logp_next [B] (all optional), d_stats as jh_sac_critic_loss.  12 launches. */
+int jh_sacnet_critic_update(jh_sacnet* n, const float* d_x, const float* d_action, const float* d_reward, const float* d_done,
+                            const float* d_eps, int32_t B, float gamma, float* d_y, float* d_q, float* d_a_next, float* d_logp_next,
+                            float* d_stats, jh_stream stream);
+/* The actor update and the temperature (sac.py:229-255): a, logp = sample(actor(state), d_eps), both critics AFTER their step, backward
+ * through both critics' action inputs and through logp, the actor's Adam step; the seed advances the temperature block.  The critics'
+ * parameters, gradient bucket and moments are not written.
+ * -> d_action [B][A], d_logp [B], d_q [2][B] (all optional), d_stats as jh_sac_actor_seed.  16 launches.           */
+int jh_sacnet_actor_update(jh_sacnet* n, const float* d_x, const float* d_eps, int32_t B, float* d_action, float* d_logp, float* d_q,
+                           float* d_stats, jh_stream stream);
+
 /* ------------------------------------------------------------------ native policy-value MLP
  * The encoder of the PPO configs (core/network/head.py:6-18 MLP head + policy_value.py:8-57):
  * S -> H relu -> H relu -> {A logits | A mu, A log_std} + value, as hand-written kernels

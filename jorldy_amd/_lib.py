@@ -123,6 +123,25 @@ _PROTOS = {
     "jh_acnet_critic_forward": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "jh_acnet_critic_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "jh_acnet_actor_update": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "jh_sac_sample": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_sac_critic_loss": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "jh_sac_actor_seed": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_sac_sample_backward": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_sacnet_param_counts_for": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "jh_sacnet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pp]),
+    "jh_sacnet_destroy": (None, [_vp]),
+    "jh_sacnet_segment_count": (_i32, []),
+    "jh_sacnet_segment": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
+    "jh_sacnet_set_hyper": (C.c_int, [_vp, _i32, _f64, _f64, _f64, _f64, _i64, _vp]),
+    "jh_sacnet_set_lr": (C.c_int, [_vp, _i32, _f64, _vp]),
+    "jh_sacnet_set_alpha": (C.c_int, [_vp, _f64, _f64, _f64, _f64, _f64, _f64, _i64, _f64, _f64, _i32, _vp]),
+    "jh_sacnet_get_alpha": (C.c_int, [_vp, _vp, _vp]),
+    "jh_sacnet_sync_target": (C.c_int, [_vp, _vp]),
+    "jh_sacnet_soft_update": (C.c_int, [_vp, _f64, _vp]),
+    "jh_sacnet_actor_forward": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "jh_sacnet_critic_forward": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "jh_sacnet_critic_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_sacnet_actor_update": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "jh_pponet_param_count": (_i64, [_i32, _i32, _i32, _i32]),
     "jh_pponet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_uint64, _pp]),
     "jh_pponet_destroy": (None, [_vp]),

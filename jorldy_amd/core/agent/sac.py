@@ -1,0 +1,241 @@
+import os
+
+import numpy as np
+import torch
+
+from ... import ops
+from ..buffer import ReplayBuffer
+from ..network import Network
+from ..optimizer import Optimizer
+from .base import BaseAgent
+from .td3 import ActorCriticView, DeterministicActorCritic
+
+SAC_ELIGIBLE = ("SAC runs on libjorldy_hip only: actor 'continuous_policy', critic 'continuous_q_network', head 'mlp' with a scalar state_size, "
+                "hidden_size % 4 == 0, action_size >= 1, optim_config {'actor': 'adam', 'critic': 'adam', 'alpha': 'adam', actor_lr, critic_lr, alpha_lr} "
+                "(config.sac x mujoco / pendulum / cartpole / hopper_mlagent and their shapes); the discrete SAC (discrete_policy / discrete_q_network) "
+                "and the cnn head are not on the native engine")
+
+
+class GaussianActorView(ActorCriticView):
+    """`agent.actor` as the reference's ContinuousPolicy is used: actor(x) -> (mu, std)."""
+
+    @torch.no_grad()
+    def __call__(self, x):
+        net = self._net
+        x = x.contiguous()
+        outs = [net.actor_forward(x[o : o + net.maxB]) for o in range(0, x.shape[0], net.maxB)]
+        return outs[0] if len(outs) == 1 else tuple(torch.cat(p, 0) for p in zip(*outs))
+
+
+class SAC(DeterministicActorCritic):
+    """core/agent/sac.py:14-352, continuous actions: a Gaussian actor (online only), two critics trained against
+    y = r + (1 - d) gamma (min_i Q_i'(s', a') - alpha logp(a')) with a' from the ONLINE actor, an actor step through both critics' action
+    inputs and through logp, and a temperature alpha = exp(log_alpha) that is either static or follows its own one-parameter Adam.  All of
+    learn() runs on libjorldy_hip (ops.SACNet, jh_sacnet_*) as one body -- critic update, actor update with the temperature's bookkeeping in
+    its seed kernel -- captured into one hipGraph after an eager warm-up; process() replays the variant that ends with the soft update of the
+    two target critics.  The two [B, A] normal draws of a learn() are torch.randn into static buffers before the replay, the target's first.
+    The temperature lives on the device: the alpha of learn k is exp(log_alpha) after k - 1 Adam steps (sac.py:250-255 refreshes it after
+    the actor step and steps log_alpha after that).  Unknown keywords are swallowed as in the reference (target_update_period is accepted
+    and unused for the continuous agent)."""
+
+    ELIGIBLE = SAC_ELIGIBLE
+    _RESUME_ATTRS = BaseAgent._RESUME_ATTRS + ("_adam_steps_actor", "_adam_steps_critic")
+    RESULT_KEYS = ("critic_loss1", "critic_loss2", "max_Q", None, "actor_loss", "alpha_loss", "mean_Q", "alpha", "entropy")
+
+    def __init__(self, state_size, action_size, hidden_size=512, actor="continuous_policy", critic="continuous_q_network", head="mlp",
+                 optim_config={"actor": "adam", "critic": "adam", "alpha": "adam", "actor_lr": 5e-4, "critic_lr": 1e-3, "alpha_lr": 3e-4}, use_dynamic_alpha=False,
+                 gamma=0.99, tau=5e-3, buffer_size=50000, batch_size=64, start_train_step=2000, static_log_alpha=-2.0, target_update_period=10000, run_step=1e6,
+                 lr_decay=True, device=None, use_graph=True, **kwargs):
+        got = (f"; got actor={actor!r}, critic={critic!r}, head={head!r}, state_size={state_size!r}, action_size={action_size!r}, hidden_size={hidden_size!r}, "
+               f"optim_config={optim_config!r}")
+        ok_opt = (isinstance(optim_config, dict) and set(optim_config) <= {"actor", "critic", "alpha", "actor_lr", "critic_lr", "alpha_lr"}
+                  and all(str(optim_config.get(k, "adam")).lower() == "adam" for k in ("actor", "critic", "alpha")))
+        ok = (actor == "continuous_policy" and critic == "continuous_q_network" and head == "mlp" and np.isscalar(state_size) and np.isscalar(action_size)
+              and int(action_size) >= 1 and isinstance(hidden_size, (int, np.integer)) and hidden_size % 4 == 0 and ok_opt)
+        if not ok:
+            raise ValueError(self.ELIGIBLE + got)
+        self.device = self._require_gpu(device)
+        self.use_graph = use_graph
+        self.grad_sync = None
+        self.state_size, self.action_size = int(state_size), int(action_size)
+        self._net = ops.SACNet(state_size, action_size, hidden_size, batch_size, self.device)
+        # the reference's construction order (sac.py:75-95): actor, critic 1, its target, critic 2, its target; every module draws its initial
+        # weights from torch's generator, the targets too, before they are overwritten by their online nets
+        self._net.import_state(Network(actor, state_size, action_size, D_hidden=hidden_size, head=head).state_dict(), "actor")
+        for net in ("critic1", "critic2"):
+            self._net.import_state(Network(critic, state_size, action_size, D_hidden=hidden_size, head=head).state_dict(), net)
+            Network(critic, state_size, action_size, D_hidden=hidden_size, head=head)
+        self._net.sync_target()
+        self.actor = GaussianActorView(self._net, "actor", 0)
+        self.network = self.actor  # BaseAgent.sync_in / sync_out carry the actor only (sac.py:345-352)
+        self.critic1, self.target_critic1 = ActorCriticView(self._net, "critic1", 0), ActorCriticView(self._net, "critic1", 1)
+        self.critic2, self.target_critic2 = ActorCriticView(self._net, "critic2", 0), ActorCriticView(self._net, "critic2", 1)
+        self._lr0 = {"actor": float(optim_config.get("actor_lr", 5e-4)), "critic": float(optim_config.get("critic_lr", 1e-3))}
+        self._lr_now = dict(self._lr0)
+        self._adam_steps_actor = self._adam_steps_critic = 0
+        for which in ("actor", "critic"):
+            self._net.set_hyper(which, self._lr0[which], 0.9, 0.999, 1e-8, 0)
+        self.use_dynamic_alpha = bool(use_dynamic_alpha)
+        self.alpha_lr = float(optim_config.get("alpha_lr", 3e-4))  # never decayed (sac.py:292-300)
+        self._net.set_alpha(0.0 if self.use_dynamic_alpha else static_log_alpha, lr=self.alpha_lr, dynamic=self.use_dynamic_alpha)
+        self.target_entropy = -self.action_size
+        self.gamma, self.tau = gamma, tau
+        self.buffer_size = buffer_size
+        self.memory = ReplayBuffer(buffer_size, device=self.device)
+        self.memory.defer_rows = 16  # per-step stores coalesce into one ring append before the next learn()
+        self.batch_size = batch_size
+        self.start_train_step = start_train_step
+        self.num_learn = 0
+        self.time_t = 0
+        self.target_update_stamp = 0
+        self.target_update_period = target_update_period
+        self.run_step = run_step
+        self.lr_decay = lr_decay
+        self._noise_inject = None  # test hook: the standard normals [2, B, A] of the next learn() -- the target's, the actor step's -- instead of torch.randn
+        self._stats, self._stats_np = self._mapped_stats(12)  # critic: loss_1, loss_2, max_Q, mark; actor: actor_loss, alpha_loss, mean_Q, alpha, entropy, mark
+        self._static, self._graphs, self._warm = None, {}, False
+
+    # ------------------------------------------------------------------------------------------ the temperature
+    @property
+    def log_alpha(self):
+        return self._net.get_alpha()["log_alpha"]
+
+    @property
+    def alpha(self):
+        """The alpha the next learn() forms its losses with."""
+        return self._net.get_alpha()["alpha"]
+
+    # ------------------------------------------------------------------------------------------ acting
+    @torch.no_grad()
+    def act(self, state, training=True):
+        """sac.py:143-159: tanh of a draw from Normal(mu, std) -- torch.normal on the device's generator -- or tanh(mu) in evaluation."""
+        self.actor.train(training)
+        mu, std = self.actor(self.as_tensor(state))
+        z = torch.normal(mu, std) if training else mu
+        return {"action": torch.tanh(z).cpu().numpy()}
+
+    # ------------------------------------------------------------------------------------------ learning
+    def _alloc_static(self):
+        st = super()._alloc_static()
+        B, A = self.batch_size, self.action_size
+        f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self.device)
+        st.update(noise=f(2, B, A), a_next=f(B, A), logp_next=f(B), logp=f(B), q_pi=f(2, B))
+        return st
+
+    def _draw(self, st):
+        """Host side of sampling (the reference's numpy draw), then the two normal draws of this learn() (sac.py:163 via 188 and 230), eagerly into
+        the static buffer the captured body reads: a replayed graph sees fresh draws."""
+        from ..buffer.base import h2d_small
+
+        st["idx"].copy_(h2d_small(self.memory.sample_indices(self.batch_size).astype(np.int64), self.device))
+        if self._noise_inject is not None:
+            st["noise"].copy_(torch.as_tensor(self._noise_inject).to(self.device, torch.float32).reshape(st["noise"].shape))
+        else:
+            torch.randn(st["noise"][0].shape, out=st["noise"][0])
+            torch.randn(st["noise"][1].shape, out=st["noise"][1])
+
+    def _learn_body(self, st, actor_step, soft):
+        B, net = self.batch_size, self._net
+        tr = self.memory.gather(st["idx"], as_float=True, out=st["tr"])
+        net.critic_update(st["x_all"], tr["action"], tr["reward"], tr["done"], st["noise"][0], self.gamma, self._stats, y=st["y"], q=st["q"], a_next=st["a_next"],
+                          logp_next=st["logp_next"])
+        net.actor_update(st["x_all"][:B], st["noise"][1], self._stats[4:10], action=st["a_pred"], logp=st["logp"], q=st["q_pi"])
+        if soft:
+            net.soft_update(self.tau)
+
+    def _learn(self, soft):
+        marks, view = (3, 9), self._stats_np
+        if view is not None:
+            for m in marks:
+                view[m] = -1.0
+        self._run_learn(True, soft, True)
+        if view is not None:
+            self._await_marks(view, marks, "SAC.learn()")
+            s = view.copy()
+        else:
+            s = self._read_stats(self._stats)[0].copy()
+        self.num_learn += 1
+        self.result = {k: float(s[i]) for i, k in enumerate(self.RESULT_KEYS) if k is not None}
+        return self.result
+
+    def learn(self):
+        """sac.py:171-269.  Moves no target."""
+        return self._learn(False)
+
+    def process(self, transitions, step):
+        """sac.py:281-310: learns when memory.size > batch_size (strict); the lr decay touches the actor's and the critics' optimizers only;
+        once learning has begun every call ends with the soft update of the two target critics -- inside the captured learn() when this call
+        learns (the update reads neither learning rate, so its place before the decay changes nothing)."""
+        result = {}
+        self._store(transitions)
+        self.target_update_stamp += step - self.time_t
+        self.time_t = step
+        if self.memory.size > self.batch_size and step >= self.start_train_step:
+            result = self._learn(True)
+            if self.lr_decay:
+                self.learning_rate_decay(step)
+        elif self.num_learn > 0:
+            self.update_target_soft()
+        return result
+
+    # ------------------------------------------------------------------------------------------ checkpoints
+    def _alpha_optimizer(self, blk):
+        p = torch.nn.Parameter(torch.tensor([blk["log_alpha"]], dtype=torch.float32, device=self.device))
+        opt = Optimizer("adam", [p], lr=self.alpha_lr, betas=(blk["beta1"], blk["beta2"]), eps=blk["eps"])
+        for grp in opt.param_groups:
+            grp["lr"] = blk["lr"]
+        if blk["step"] > 0:
+            t = lambda v: torch.tensor([v], dtype=torch.float32, device=self.device)
+            opt.state[p] = {"step": torch.tensor(float(blk["step"])), "exp_avg": t(blk["m"]), "exp_avg_sq": t(blk["v"])}
+        return p, opt
+
+    def save(self, path):
+        """The reference's keys (sac.py:312-326): TD3's six, plus log_alpha and alpha_optimizer when the temperature is dynamic."""
+        print(f"...Save model to {path}...")
+        out = {}
+        for key, net, what in self.CKPT_KEYS:
+            which = "actor" if net == "actor" else "critic"
+            if what == "net":
+                out[key] = self._net.export_state(net)
+            else:
+                out[key] = self._optimizer_state(net, self._adam_steps_actor if net == "actor" else self._adam_steps_critic, self._lr_now[which])
+        if self.use_dynamic_alpha:
+            p, opt = self._alpha_optimizer(self._net.get_alpha())
+            out["log_alpha"], out["alpha_optimizer"] = p.detach(), opt.state_dict()
+        torch.save(out, os.path.join(path, "ckpt"))
+
+    def load(self, path):
+        """The reference's ckpt, with three deliberate departures: critic 2 is restored from "critic2" (sac.py:335 loads it into critic 1 and
+        leaves critic 2 as constructed); both targets equal their loaded online critics afterwards (the reference copies critic 2 as
+        constructed); and the alpha in use becomes exp(loaded log_alpha) with the alpha optimizer's state restored (sac.py:341-343 rebinds
+        log_alpha, which orphans the optimizer's parameter, and leaves self.alpha as it was until the next learn())."""
+        print(f"...Load model from {path}...")
+        ckpt = torch.load(os.path.join(path, "ckpt"), map_location=self.device, weights_only=False)
+        self._load_ckpt(ckpt)
+        if self.use_dynamic_alpha and "log_alpha" in ckpt:
+            la = float(torch.as_tensor(ckpt["log_alpha"]).reshape(-1)[0])
+            p = torch.nn.Parameter(torch.tensor([la], dtype=torch.float32, device=self.device))
+            opt = Optimizer("adam", [p], lr=self.alpha_lr)
+            opt.load_state_dict(ckpt["alpha_optimizer"])
+            g0, st = opt.param_groups[0], opt.state.get(p) or {}
+            self._net.set_alpha(la, lr=float(g0["lr"]), beta1=g0["betas"][0], beta2=g0["betas"][1], eps=g0["eps"], step=int(float(st.get("step", 0))),
+                                m=float(st["exp_avg"]) if st else 0.0, v=float(st["exp_avg_sq"]) if st else 0.0, dynamic=True)
+
+    def save_full(self, path, version=None):
+        """BaseAgent's format version 2 only.  Beside the replay buffer, the counters and the generators it carries the two target critics and
+        the whole temperature block (log_alpha, the alpha in use, Adam's moments and step count): a resumed run continues bit for bit."""
+        if version not in (None, 2):
+            raise ValueError(f"SAC.save_full writes resume format version 2 only, got version={version!r}")
+        super(DeterministicActorCritic, self).save_full(path, version)
+        d = os.path.join(path, "resume")
+        os.makedirs(d, exist_ok=True)
+        torch.save({net: self._net.export_state(net, "target") for net in self._critic_names()}, os.path.join(d, "targets.pt"))
+        torch.save(self._net.get_alpha(), os.path.join(d, "alpha.pt"))
+
+    def load_full(self, path):
+        super().load_full(path)  # the targets: DeterministicActorCritic.load_full
+        f = os.path.join(path, "resume", "alpha.pt")
+        if os.path.exists(f):
+            b = torch.load(f, map_location="cpu", weights_only=False)
+            self._net.set_alpha(b["log_alpha"], alpha=b["alpha"], lr=b["lr"], beta1=b["beta1"], beta2=b["beta2"], eps=b["eps"], step=b["step"], m=b["m"], v=b["v"],
+                                dynamic=b["dynamic"])

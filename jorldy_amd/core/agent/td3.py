@@ -262,7 +262,9 @@ class DeterministicActorCritic(BaseAgent):
         leaves critic 2 as constructed), and EVERY target equals its loaded online network afterwards (ddpg.py:191-199 leaves target_actor
         stale).  The critics share one optimizer block: critic 1's step count, lr, betas and eps hold for both."""
         print(f"...Load model from {path}...")
-        ckpt = torch.load(os.path.join(path, "ckpt"), map_location=self.device, weights_only=False)
+        self._load_ckpt(torch.load(os.path.join(path, "ckpt"), map_location=self.device, weights_only=False))
+
+    def _load_ckpt(self, ckpt):
         for key, net, what in self.CKPT_KEYS:
             if what == "net":
                 self._net.import_state(ckpt[key], net)

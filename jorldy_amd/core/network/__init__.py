@@ -12,6 +12,7 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   iqn                          core/network/iqn.py:9-47
   deterministic_policy         core/network/policy.py:8-20
   continuous_q_network         core/network/q_network.py:23-39
+  continuous_policy            core/network/policy.py:38-55
 """
 import torch
 
@@ -166,6 +167,19 @@ class DeterministicPolicy(BaseNetwork):
         orthogonal_init(self.pi, "tanh")
 
 
+class ContinuousPolicy(BaseNetwork):
+    """The actor of SAC (policy.py:38-55): head -> relu(l) -> (clamp(mu, -5, 5), exp(tanh(log_std)))."""
+
+    def __init__(self, D_in, D_out, D_hidden=512, head="mlp"):
+        super().__init__(D_in, D_hidden, head)
+        self.l = torch.nn.Linear(self.head.D_head_out, D_hidden)
+        self.mu = torch.nn.Linear(D_hidden, D_out)
+        self.log_std = torch.nn.Linear(D_hidden, D_out)
+        orthogonal_init(self.l)
+        orthogonal_init(self.mu, "linear")
+        orthogonal_init(self.log_std, "tanh")
+
+
 class ContinuousQ_Network(BaseNetwork):
     """The critic of TD3 / DDPG (q_network.py:23-39): [head(state) | relu(e(action))] -> relu(l) -> q.  The reference's argument order:
     head comes before D_hidden."""
@@ -189,6 +203,7 @@ network_dict = {
     "iqn": IQN,
     "deterministic_policy": DeterministicPolicy,
     "continuous_q_network": ContinuousQ_Network,
+    "continuous_policy": ContinuousPolicy,
 }
 
 

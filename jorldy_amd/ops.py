@@ -1423,47 +1423,14 @@ def td3_polyak(params, target, tau):
     return target
 
 
-class ACNet:
-    """jh_acnet_*: a deterministic policy (network/policy.py:8-20) and one (DDPG) or two (TD3) continuous Q networks
-    (network/q_network.py:23-39), each with a target copy, in flat buckets: `actor*` of n_actor floats, `critics*` of n_critics * n_critic
-    floats (critic c at c * n_critic).  The critic update, the actor update (backward through critic 1's action input), the soft update
-    and the target sync are tile-engine launches plus the elementwise kernels of jh_td3.hip.  Networks are named "actor", "critic1",
-    "critic2" ("critic" = "critic1"); export / import speak the reference's state_dict keys."""
+class _ActorCriticBuckets:
+    """What ACNet and SACNet share: an actor and `nc` critics in flat float32 buckets (`self.actor[kind]` of n_actor floats,
+    `self.critics[kind]` of nc * n_critic floats, critic c at c * n_critic), the segment tables `aseg` / `cseg` name -> (offset, rows, cols), and
+    export / import under the reference's state_dict keys.  Networks are named "actor", "critic1", "critic2" ("critic" = "critic1")."""
 
-    _ASEG = ("head.l.weight", "head.l.bias", "l.weight", "l.bias", "pi.weight", "pi.bias")
     _CSEG = ("head.l.weight", "head.l.bias", "e.weight", "e.bias", "l.weight", "l.bias", "q.weight", "q.bias")
     KINDS = ("params", "target", "grads", "m", "v")
-    kind, cnn = "actor_critic", False
-
-    def __init__(self, state_size, action_size, hidden, n_critics, max_batch, device):
-        self.lib = L.load()
-        self.device = torch.device(device)
-        self.ctx = L.ctx(self.device.index)
-        self.S, self.A, self.H, self.nc, self.maxB = int(state_size), int(action_size), int(hidden), int(n_critics), int(max_batch)
-        na, ncr = C.c_int64(), C.c_int64()
-        L.check(self.lib.jh_acnet_param_counts_for(self.S, self.H, self.A, C.byref(na), C.byref(ncr)))
-        self.n_actor, self.n_critic = int(na.value), int(ncr.value)
-        mk = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.actor = {k: mk(self.n_actor) for k in self.KINDS}
-        self.critics = {k: mk(self.nc * self.n_critic) for k in self.KINDS}
-        self.h = C.c_void_p()
-        L.check(self.lib.jh_acnet_create(self.ctx, self.S, self.H, self.A, self.nc, self.maxB, *[L.ptr(self.actor[k]) for k in self.KINDS],
-                                         *[L.ptr(self.critics[k]) for k in self.KINDS], C.byref(self.h)))
-        names = self._ASEG + self._CSEG
-        assert int(self.lib.jh_acnet_segment_count()) == len(names)
-        self.aseg, self.cseg = {}, {}
-        for i, name in enumerate(names):
-            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
-            L.check(self.lib.jh_acnet_segment(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
-            (self.aseg if i < len(self._ASEG) else self.cseg)[name] = (off.value, rows.value, cols.value)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.jh_acnet_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+    cnn = False
 
     def nets(self):
         return ("actor",) + tuple(f"critic{c + 1}" for c in range(self.nc))
@@ -1500,6 +1467,47 @@ class ACNet:
             if tuple(src.shape) != tuple(v.shape):
                 raise ValueError(f"{k}: expected {tuple(v.shape)}, got {tuple(src.shape)}")
             v.copy_(src)
+
+
+class ACNet(_ActorCriticBuckets):
+    """jh_acnet_*: a deterministic policy (network/policy.py:8-20) and one (DDPG) or two (TD3) continuous Q networks
+    (network/q_network.py:23-39), each with a target copy, in flat buckets: `actor*` of n_actor floats, `critics*` of n_critics * n_critic
+    floats (critic c at c * n_critic).  The critic update, the actor update (backward through critic 1's action input), the soft update
+    and the target sync are tile-engine launches plus the elementwise kernels of jh_td3.hip.  Networks are named "actor", "critic1",
+    "critic2" ("critic" = "critic1"); export / import speak the reference's state_dict keys."""
+
+    _ASEG = ("head.l.weight", "head.l.bias", "l.weight", "l.bias", "pi.weight", "pi.bias")
+    kind = "actor_critic"
+
+    def __init__(self, state_size, action_size, hidden, n_critics, max_batch, device):
+        self.lib = L.load()
+        self.device = torch.device(device)
+        self.ctx = L.ctx(self.device.index)
+        self.S, self.A, self.H, self.nc, self.maxB = int(state_size), int(action_size), int(hidden), int(n_critics), int(max_batch)
+        na, ncr = C.c_int64(), C.c_int64()
+        L.check(self.lib.jh_acnet_param_counts_for(self.S, self.H, self.A, C.byref(na), C.byref(ncr)))
+        self.n_actor, self.n_critic = int(na.value), int(ncr.value)
+        mk = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.actor = {k: mk(self.n_actor) for k in self.KINDS}
+        self.critics = {k: mk(self.nc * self.n_critic) for k in self.KINDS}
+        self.h = C.c_void_p()
+        L.check(self.lib.jh_acnet_create(self.ctx, self.S, self.H, self.A, self.nc, self.maxB, *[L.ptr(self.actor[k]) for k in self.KINDS],
+                                         *[L.ptr(self.critics[k]) for k in self.KINDS], C.byref(self.h)))
+        names = self._ASEG + self._CSEG
+        assert int(self.lib.jh_acnet_segment_count()) == len(names)
+        self.aseg, self.cseg = {}, {}
+        for i, name in enumerate(names):
+            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
+            L.check(self.lib.jh_acnet_segment(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
+            (self.aseg if i < len(self._ASEG) else self.cseg)[name] = (off.value, rows.value, cols.value)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.jh_acnet_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
 
     def set_hyper(self, which, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
         """which: "actor" | "critic" (one Adam for both critics)."""
@@ -1549,6 +1557,200 @@ class ACNet:
         B = int(x.shape[0])
         assert x.is_contiguous() and x.dtype == torch.float32 and x.shape[1] == self.S and (action_pred is None or action_pred.numel() == B * self.A)
         L.check(self.lib.jh_acnet_actor_update(self.h, L.ptr(x), B, L.ptr(action_pred), L.ptr(stats), L.stream_ptr()))
+
+
+SAC_ALPHA_FLOATS = 16
+
+
+def sac_alpha_block(log_alpha, alpha=None, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8, step=0, m=0.0, v=0.0, dynamic=True, target_entropy=-1.0, device="cuda"):
+    """The temperature's device block of the jh_sac_* kernels (include/jorldy_hip.h): log_alpha, the alpha in use (None: exp(log_alpha) rounded
+    to float32), Adam's moments, step count and settings, the dynamic flag and target_entropy.  -> float32 [16] on `device`."""
+    import math
+
+    import numpy as np
+
+    h = np.zeros(SAC_ALPHA_FLOATS, np.float32)
+    la = np.float32(log_alpha)
+    h[:9] = [la, math.exp(float(la)) if alpha is None else alpha, m, v, step, lr, eps, 1.0 if dynamic else 0.0, target_entropy]
+    h[10:14] = np.asarray([beta1, beta2], np.float64).view(np.float32)
+    return torch.from_numpy(h).to(device)
+
+
+def sac_alpha_read(block):
+    """-> dict(log_alpha, alpha, m, v, step, lr, eps, dynamic, target_entropy, coef) of a temperature block, as Python numbers."""
+    h = block.detach().cpu().numpy()
+    names = ("log_alpha", "alpha", "m", "v", "step", "lr", "eps", "dynamic", "target_entropy", "coef")
+    out = {k: float(h[i]) for i, k in enumerate(names)}
+    out["step"], out["dynamic"] = int(out["step"]), bool(out["dynamic"])
+    return out
+
+
+def sac_sample(mu_raw, ls_raw=None, eps=None, a=None, logp=None):
+    """jh_sac_sample on [B, A] (sac.py:161-169, policy.py:38-55) -> (a [B, A], logp [B]); eps None: (tanh(clamp(mu_raw, -5, 5)), None)."""
+    mu_raw = _f32(mu_raw)
+    B, A = mu_raw.shape
+    ls_raw = None if ls_raw is None else _f32(ls_raw)
+    eps = None if eps is None else _f32(eps)
+    assert eps is None or (ls_raw is not None and tuple(eps.shape) == (B, A) and tuple(ls_raw.shape) == (B, A))
+    a = torch.empty_like(mu_raw) if a is None else a
+    if eps is not None and logp is None:
+        logp = torch.empty(B, dtype=torch.float32, device=mu_raw.device)
+    assert a.numel() == B * A and (eps is None or logp.numel() == B)
+    L.check(L.load().jh_sac_sample(L.ctx(mu_raw.device.index), B, A, L.ptr(mu_raw), L.ptr(ls_raw), L.ptr(eps), L.ptr(a), L.ptr(logp if eps is not None else None),
+                                   L.stream_ptr()))
+    return a, (logp if eps is not None else None)
+
+
+def sac_critic_loss(q, q_next, logp_next, reward, done, gamma, alpha_block, stats=None):
+    """jh_sac_critic_loss: q, q_next [2, B], logp_next [B] -> (y [B], d(loss_i)/d(q_i) [2, B], stats [4] = loss_1, loss_2, max_Q, mark)."""
+    q, q_next, logp_next, reward, done = _f32(q), _f32(q_next), _f32(logp_next), _f32(reward), _f32(done)
+    n, B = q.shape
+    assert n == 2 and tuple(q_next.shape) == (2, B) and logp_next.numel() == B and reward.numel() == B and done.numel() == B
+    assert alpha_block.dtype == torch.float32 and alpha_block.numel() == SAC_ALPHA_FLOATS and alpha_block.is_contiguous()
+    y = torch.empty(B, dtype=torch.float32, device=q.device)
+    grad = torch.empty(2, B, dtype=torch.float32, device=q.device)
+    stats = torch.zeros(4, dtype=torch.float32, device=q.device) if stats is None else stats
+    L.check(L.load().jh_sac_critic_loss(L.ctx(q.device.index), B, L.ptr(q), L.ptr(q_next), L.ptr(logp_next), L.ptr(reward), L.ptr(done), float(gamma),
+                                        L.ptr(alpha_block), L.ptr(y), L.ptr(grad), L.ptr(stats), L.stream_ptr()))
+    return y, grad, stats
+
+
+def sac_actor_seed(q, logp, alpha_block, stats=None):
+    """jh_sac_actor_seed: q [2, B], logp [B] -> (d(actor_loss)/d(q_i) [2, B], stats [6] = actor_loss, alpha_loss, mean_Q, alpha, entropy,
+    mark).  Advances `alpha_block` in place: the coefficient alpha / B, and, dynamic, the alpha in use and one Adam step of log_alpha."""
+    q, logp = _f32(q), _f32(logp).reshape(-1)
+    n, B = q.shape
+    assert n == 2 and logp.numel() == B
+    assert alpha_block.dtype == torch.float32 and alpha_block.numel() == SAC_ALPHA_FLOATS and alpha_block.is_contiguous()
+    grad = torch.empty(2, B, dtype=torch.float32, device=q.device)
+    stats = torch.zeros(6, dtype=torch.float32, device=q.device) if stats is None else stats
+    L.check(L.load().jh_sac_actor_seed(L.ctx(q.device.index), B, L.ptr(q), L.ptr(logp), L.ptr(alpha_block), L.ptr(grad), L.ptr(stats), L.stream_ptr()))
+    return grad, stats
+
+
+def sac_sample_backward(grad_a, mu_raw, ls_raw, eps, a, alpha_block, grad_a2=None):
+    """jh_sac_sample_backward on [B, A]: d(a) (+ grad_a2) and the block's coefficient alpha / B -> (d(mu_raw), d(ls_raw))."""
+    grad_a, mu_raw, ls_raw, eps, a = _f32(grad_a), _f32(mu_raw), _f32(ls_raw), _f32(eps), _f32(a)
+    grad_a2 = None if grad_a2 is None else _f32(grad_a2)
+    B, A = a.shape
+    for t in (grad_a, mu_raw, ls_raw, eps) + (() if grad_a2 is None else (grad_a2,)):
+        assert tuple(t.shape) == (B, A)
+    assert alpha_block.dtype == torch.float32 and alpha_block.numel() == SAC_ALPHA_FLOATS and alpha_block.is_contiguous()
+    dmu, dls = torch.empty_like(a), torch.empty_like(a)
+    L.check(L.load().jh_sac_sample_backward(L.ctx(a.device.index), B, A, L.ptr(grad_a), L.ptr(grad_a2), L.ptr(mu_raw), L.ptr(ls_raw), L.ptr(eps), L.ptr(a),
+                                            L.ptr(alpha_block), L.ptr(dmu), L.ptr(dls), L.stream_ptr()))
+    return dmu, dls
+
+
+class SACNet(_ActorCriticBuckets):
+    """jh_sacnet_*: a Gaussian policy (network/policy.py:38-55), online only, and two continuous Q networks (network/q_network.py:23-39) with
+    their targets, in the flat buckets of _ActorCriticBuckets (the actor has no "target" bucket), plus the temperature block of the jh_sac_* kernels.
+    Networks are named "actor", "critic1", "critic2"; export / import speak the reference's state_dict keys."""
+
+    _ASEG = ("head.l.weight", "head.l.bias", "l.weight", "l.bias", "mu.weight", "mu.bias", "log_std.weight", "log_std.bias")
+    AKINDS = ("params", "grads", "m", "v")
+    kind = "soft_actor_critic"
+
+    def __init__(self, state_size, action_size, hidden, max_batch, device):
+        self.lib = L.load()
+        self.device = torch.device(device)
+        self.ctx = L.ctx(self.device.index)
+        self.S, self.A, self.H, self.nc, self.maxB = int(state_size), int(action_size), int(hidden), 2, int(max_batch)
+        na, ncr = C.c_int64(), C.c_int64()
+        L.check(self.lib.jh_sacnet_param_counts_for(self.S, self.H, self.A, C.byref(na), C.byref(ncr)))
+        self.n_actor, self.n_critic = int(na.value), int(ncr.value)
+        mk = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.actor = {k: mk(self.n_actor) for k in self.AKINDS}
+        self.critics = {k: mk(self.nc * self.n_critic) for k in self.KINDS}
+        self.h = C.c_void_p()
+        L.check(self.lib.jh_sacnet_create(self.ctx, self.S, self.H, self.A, self.maxB, *[L.ptr(self.actor[k]) for k in self.AKINDS],
+                                          *[L.ptr(self.critics[k]) for k in self.KINDS], C.byref(self.h)))
+        names = self._ASEG + self._CSEG
+        assert int(self.lib.jh_sacnet_segment_count()) == len(names)
+        self.aseg, self.cseg = {}, {}
+        for i, name in enumerate(names):
+            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
+            L.check(self.lib.jh_sacnet_segment(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
+            (self.aseg if i < len(self._ASEG) else self.cseg)[name] = (off.value, rows.value, cols.value)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.jh_sacnet_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def set_hyper(self, which, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
+        """which: "actor" | "critic" (one Adam for both critics)."""
+        L.check(self.lib.jh_sacnet_set_hyper(self.h, 0 if which == "actor" else 1, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
+
+    def set_lr(self, which, lr):
+        L.check(self.lib.jh_sacnet_set_lr(self.h, 0 if which == "actor" else 1, float(lr), L.stream_ptr()))
+
+    def set_alpha(self, log_alpha, alpha=None, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8, step=0, m=0.0, v=0.0, dynamic=True):
+        """The whole temperature block; alpha None: exp(log_alpha as float32).  Synchronises."""
+        import math
+
+        import numpy as np
+
+        alpha = math.exp(float(np.float32(log_alpha))) if alpha is None else alpha
+        L.check(self.lib.jh_sacnet_set_alpha(self.h, float(log_alpha), float(alpha), float(lr), float(beta1), float(beta2), float(eps), int(step), float(m), float(v),
+                                             int(bool(dynamic)), L.stream_ptr()))
+
+    def get_alpha(self):
+        """-> dict(log_alpha, alpha, m, v, step, lr, eps, dynamic, target_entropy, coef, beta1, beta2).  Synchronises."""
+        import numpy as np
+
+        h = np.zeros(SAC_ALPHA_FLOATS, np.float32)
+        L.check(self.lib.jh_sacnet_get_alpha(self.h, L.ptr(h), L.stream_ptr()))
+        out = sac_alpha_read(torch.from_numpy(h))
+        out["beta1"], out["beta2"] = (float(b) for b in h[10:14].view(np.float64))
+        return out
+
+    def sync_target(self):
+        L.check(self.lib.jh_sacnet_sync_target(self.h, L.stream_ptr()))
+
+    def soft_update(self, tau):
+        L.check(self.lib.jh_sacnet_soft_update(self.h, float(tau), L.stream_ptr()))
+
+    def actor_forward(self, x, which=0):
+        """actor(x) -> (mu, std), each [rows, A]; rows <= max_batch.  There is no target actor."""
+        assert which == 0 and x.is_contiguous() and x.device == self.device and x.dtype == torch.float32 and x.shape[1] == self.S
+        rows = int(x.shape[0])
+        mu, std = (torch.empty(rows, self.A, dtype=torch.float32, device=self.device) for _ in range(2))
+        L.check(self.lib.jh_sacnet_actor_forward(self.h, L.ptr(x), rows, L.ptr(mu), L.ptr(std), L.stream_ptr()))
+        return mu, std
+
+    def critic_forward(self, x, action, which=0):
+        """critic_c(x, action) for both critics -> [2, rows]."""
+        assert x.is_contiguous() and x.dtype == torch.float32 and action.is_contiguous() and action.dtype == torch.float32
+        rows = int(x.shape[0])
+        assert tuple(x.shape) == (rows, self.S) and tuple(action.shape) == (rows, self.A)
+        out = torch.empty(self.nc, rows, dtype=torch.float32, device=self.device)
+        L.check(self.lib.jh_sacnet_critic_forward(self.h, int(which), L.ptr(x), L.ptr(action), rows, L.ptr(out), L.stream_ptr()))
+        return out
+
+    def critic_update(self, x_all, action, reward, done, eps, gamma, stats, y=None, q=None, a_next=None, logp_next=None):
+        """x_all = [state; next_state] (2B rows); eps [B, A] standard normals.  stats [4] = loss_1, loss_2, max_Q, mark; optional outputs
+        y [B], q [2, B], a_next [B, A], logp_next [B]."""
+        B = int(action.shape[0])
+        for t in (x_all, action, reward, done, eps):
+            assert t.is_contiguous() and t.dtype == torch.float32
+        assert tuple(x_all.shape) == (2 * B, self.S) and tuple(action.shape) == (B, self.A) and reward.numel() == B and done.numel() == B
+        assert tuple(eps.shape) == (B, self.A) and stats.numel() >= 4
+        assert (y is None or y.numel() == B) and (q is None or q.numel() == 2 * B) and (a_next is None or a_next.numel() == B * self.A)
+        assert logp_next is None or logp_next.numel() == B
+        L.check(self.lib.jh_sacnet_critic_update(self.h, L.ptr(x_all), L.ptr(action), L.ptr(reward), L.ptr(done), L.ptr(eps), B, float(gamma), L.ptr(y), L.ptr(q),
+                                                 L.ptr(a_next), L.ptr(logp_next), L.ptr(stats), L.stream_ptr()))
+
+    def actor_update(self, x, eps, stats, action=None, logp=None, q=None):
+        """x = state [B, S], eps [B, A]; stats [6] = actor_loss, alpha_loss, mean_Q, alpha, entropy, mark; optional outputs action [B, A],
+        logp [B], q [2, B] = q_i(state, action) with the critics as they stand."""
+        B = int(x.shape[0])
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.shape[1] == self.S and eps.is_contiguous() and tuple(eps.shape) == (B, self.A)
+        assert stats.numel() >= 6 and (action is None or action.numel() == B * self.A) and (logp is None or logp.numel() == B) and (q is None or q.numel() == 2 * B)
+        L.check(self.lib.jh_sacnet_actor_update(self.h, L.ptr(x), L.ptr(eps), B, L.ptr(action), L.ptr(logp), L.ptr(q), L.ptr(stats), L.stream_ptr()))
 
 
 class StagingRing:
