@@ -526,6 +526,41 @@ int jh_sacnet_critic_update(jh_sacnet* n, const float* d_x, const float* d_actio
 int jh_sacnet_actor_update(jh_sacnet* n, const float* d_x, const float* d_eps, int32_t B, float* d_action, float* d_logp, float* d_q,
                            float* d_stats, jh_stream stream);
 
+/* ------------------------------------------------------------------ V-MPO (vmpo.py:155-252)
+ * Everything of one minibatch update between the policy-value net's forward and its backward, in ONE launch of ONE workgroup:
+ * 1 <= B <= 1024 rows, 1 <= A <= 64; anything else is JH_ERR_ARG.  d_idx (int64 [B], or NULL for rows 0 .. B-1) selects the minibatch's
+ * rows of the rollout-sized d_action, d_adv, d_value_old and OLD raw heads (the pre-pass of vmpo.py:122-153); the new raw heads and
+ * d_value_pred are the minibatch's own [B][A] / [B].
+ *   top half   the LOWER median of adv[idx] (sorted element (B - 1) / 2, torch.median) by rank counting; a row belongs to the top half
+ *              exactly when adv > median (vmpo.py:174): ties at the median fall out, B == 1 or all-equal advantages leave it empty
+ *   psi        exp((adv - max_top) / eta) / sum_top(...); eta_loss = eta eps_eta + eta (max_top / eta + log mean_top exp((adv - max_top) / eta)):
+ *              the reference's formulas (vmpo.py:177-178, 194-196) wherever its float32 exp(adv / eta) is finite, and finite beyond
+ *   losses     ret = adv + value_old as one float32 add (vmpo.py:153: AFTER the standardisation), critic = mean (v - ret)^2;
+ *              actor = -sum_top psi logp; discrete: KL = sum_a pi_old (log pi_old - log pi), alpha_loss = mean[alpha_mu (eps_alpha_mu - KL) +
+ *              alpha_mu KL]; continuous (mu = clamp(mu_raw, -5, 5), std = exp(tanh(log_std_raw)), policy_value.py:51-57):
+ *              KLD_mu = 1/2 sum_a (mu - mu_old)^2 std_old^2 (vmpo.py:210-213 as written), KLD_sigma = 1/2 (sum_a std^2 / std_old^2 - A +
+ *              log(prod ss / prod ss_old)), ss = 1 / std^2, each with its own multiplier and threshold.  Per-row terms in double, every sum a
+ *              double with a fixed order: same bits every run.  Gradients with respect to the raw heads and d_value_pred.
+ *   d_block    the Lagrange multipliers, a caller-owned device block of JH_VMPO_BLOCK_FLOATS floats the kernel reads and advances:
+ *              [0-2] eta, alpha_mu, alpha_sigma   [3-5] exp_avg   [6-8] exp_avg_sq   [9-11] floors (min_eta, ..)   [12-14] thresholds
+ *              (eps_eta, ..)   [15-17] 1 once the multiplier has taken an Adam step   [18-20] the gradients of the last step   [21-23] unused.
+ *              After the sums one thread takes torch's single-tensor Adam step on each multiplier that has a gradient (a discrete policy
+ *              leaves alpha_sigma, its moments and its flag untouched) with d_hyper's lr, betas (the doubles), eps and t = step + 1 -- the
+ *              step the net's own Adam takes for this minibatch --, then x = max(x, floor) with NaN kept (reset_lgr_muls, vmpo.py:271-274).
+ *   d_hyper    an 8-byte aligned optimizer block of 16 floats as jh_pponet_hyper_ptr returns it; only read.
+ *   d_stats    optional float32[8] = {actor_loss, critic_loss, eta_loss, alpha_loss, eta', alpha_mu', alpha_sigma' (after the step and the
+ *              floor), arrival mark 0}, the mark written last behind a system-scope fence (device-mapped host memory may receive it).
+ *   d_mask     optional float32[B]: 1 where the row is in the top half.
+ * Empty top half: no actor gradient, eta_loss and the stepped eta are NaN, as in the reference.                         */
+#define JH_VMPO_BLOCK_FLOATS 24
+int jh_vmpo_loss_discrete(jh_ctx* ctx, int32_t B, int32_t A, const float* d_logits, const float* d_value_pred, const int64_t* d_idx,
+                          const float* d_action, const float* d_adv, const float* d_value_old, const float* d_logits_old, float* d_block,
+                          const float* d_hyper, float* d_grad_logits, float* d_grad_value, float* d_stats, float* d_mask, jh_stream stream);
+int jh_vmpo_loss_continuous(jh_ctx* ctx, int32_t B, int32_t A, const float* d_mu_raw, const float* d_log_std_raw, const float* d_value_pred,
+                            const int64_t* d_idx, const float* d_action, const float* d_adv, const float* d_value_old, const float* d_mu_raw_old,
+                            const float* d_log_std_raw_old, float* d_block, const float* d_hyper, float* d_grad_mu_raw,
+                            float* d_grad_log_std_raw, float* d_grad_value, float* d_stats, float* d_mask, jh_stream stream);
+
 /* ------------------------------------------------------------------ native policy-value MLP
  * The encoder of the PPO configs (core/network/head.py:6-18 MLP head + policy_value.py:8-57):
  * S -> H relu -> H relu -> {A logits | A mu, A log_std} + value, as hand-written kernels

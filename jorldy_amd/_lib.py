@@ -142,6 +142,8 @@ _PROTOS = {
     "jh_sacnet_critic_forward": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "jh_sacnet_critic_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_sacnet_actor_update": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "jh_vmpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_vmpo_loss_continuous": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_pponet_param_count": (_i64, [_i32, _i32, _i32, _i32]),
     "jh_pponet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_uint64, _pp]),
     "jh_pponet_destroy": (None, [_vp]),

@@ -11,9 +11,10 @@ from .qrdqn import QRDQN
 from .rainbow import C51, Rainbow
 from .sac import SAC
 from .td3 import TD3
+from .vmpo import VMPO
 
 agent_dict = {"dqn": DQN, "double": Double, "multistep": Multistep, "per": PER, "ape_x": ApeX, "c51": C51, "rainbow": Rainbow, "ppo": PPO, "qrdqn": QRDQN, "m_dqn": MDQN, "iqn": IQN,
-              "m_iqn": MIQN, "td3": TD3, "ddpg": DDPG, "sac": SAC}
+              "m_iqn": MIQN, "td3": TD3, "ddpg": DDPG, "sac": SAC, "vmpo": VMPO}
 
 
 def Agent(name, *args, **kwargs):

@@ -557,6 +557,82 @@ def policy_act_discrete(heads, A, seed, counter, training, out):
     return out
 
 
+# ============================================================================= V-MPO
+VMPO_BLOCK_FLOATS = 24
+_VMPO_NAMES = ("eta", "alpha_mu", "alpha_sigma")
+
+
+def vmpo_block(eta=1.0, alpha_mu=1.0, alpha_sigma=1.0, min_eta=1e-8, min_alpha_mu=1e-8, min_alpha_sigma=1e-8, eps_eta=0.02, eps_alpha_mu=0.1, eps_alpha_sigma=0.1,
+               m=(0.0, 0.0, 0.0), v=(0.0, 0.0, 0.0), has_state=(False, False, False), device="cuda"):
+    """The Lagrange multipliers' device block of the jh_vmpo_* kernels (include/jorldy_hip.h): values (already raised to their floors, as the
+    constructor's reset_lgr_muls does, vmpo.py:85), Adam's moments, floors, thresholds, the has-state flags.  -> float32 [24] on `device`."""
+    h = np.zeros(VMPO_BLOCK_FLOATS, np.float32)
+    h[9:12] = [min_eta, min_alpha_mu, min_alpha_sigma]
+    h[0:3] = np.maximum(np.asarray([eta, alpha_mu, alpha_sigma], np.float32), h[9:12])
+    h[3:6], h[6:9] = m, v
+    h[12:15] = [eps_eta, eps_alpha_mu, eps_alpha_sigma]
+    h[15:18] = [1.0 if f else 0.0 for f in has_state]
+    return torch.from_numpy(h).to(device)
+
+
+def vmpo_block_read(block):
+    """-> {"eta": {"value", "m", "v", "floor", "eps", "has_state", "grad"}, "alpha_mu": ..., "alpha_sigma": ...} as Python numbers."""
+    h = block.detach().cpu().numpy()
+    return {k: {"value": float(h[j]), "m": float(h[3 + j]), "v": float(h[6 + j]), "floor": float(h[9 + j]), "eps": float(h[12 + j]),
+                "has_state": bool(h[15 + j]), "grad": float(h[18 + j])} for j, k in enumerate(_VMPO_NAMES)}
+
+
+def vmpo_hyper(lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0, device="cuda"):
+    """A hand-made optimizer block in the layout of jh_pponet_hyper_ptr (16 floats: lr, betas, eps, step, ..., the betas as doubles at
+    [10:14]) for calling the V-MPO loss kernels without a network.  `step` = Adam steps taken BEFORE the coming one."""
+    h = np.zeros(16, np.float32)
+    h[:5] = [lr, beta1, beta2, eps, step]
+    h[7:9] = [1.0 - beta1, 1.0 - beta2]
+    h[10:14] = np.asarray([beta1, beta2], np.float64).view(np.float32)
+    return torch.from_numpy(h).to(device)
+
+
+def _vmpo_common(head, value_pred, idx, block, hyper, stats, mask):
+    B, A = head.shape
+    assert idx is None or (idx.dtype == torch.int64 and idx.numel() == B and idx.is_contiguous())
+    assert block.dtype == torch.float32 and block.numel() == VMPO_BLOCK_FLOATS and block.is_contiguous()
+    if torch.is_tensor(hyper):
+        assert hyper.dtype == torch.float32 and hyper.numel() >= 16 and hyper.is_contiguous() and hyper.device == head.device
+        hyper_ptr = C.c_void_p(hyper.data_ptr())
+    else:
+        hyper_ptr = C.c_void_p(int(hyper))
+    g_v = torch.empty(B, dtype=torch.float32, device=head.device)
+    if stats is None:
+        stats = torch.zeros(8, dtype=torch.float32, device=head.device)
+    assert mask is None or (mask.dtype == torch.float32 and mask.numel() >= B and mask.is_contiguous())
+    return B, A, hyper_ptr, g_v, stats
+
+
+def vmpo_loss_discrete(logits, value_pred, idx, action, adv, value_old, logits_old, block, hyper, stats=None, mask=None):
+    """jh_vmpo_loss_discrete: the minibatch's logits [B, A] and value_pred [B], idx int64 [B] into the rollout-sized action / adv / value_old /
+    logits_old.  `block` (vmpo_block) is advanced in place; hyper = a net's hyper_ptr() or a vmpo_hyper tensor.
+    -> (grad_logits [B, A], grad_value [B, 1], stats f32[8] = actor, critic, eta_loss, alpha_loss, eta', alpha_mu', alpha_sigma', mark)."""
+    z, v = _f32(logits), _f32(value_pred).reshape(-1)
+    B, A, hyper_ptr, g_v, stats = _vmpo_common(z, v, idx, block, hyper, stats, mask)
+    g_z = torch.empty_like(z)
+    L.check(L.load().jh_vmpo_loss_discrete(L.ctx(_dev(z)), B, A, L.ptr(z), L.ptr(v), L.ptr(idx), L.ptr(_f32(action).reshape(-1)), L.ptr(_f32(adv).reshape(-1)),
+                                           L.ptr(_f32(value_old).reshape(-1)), L.ptr(_f32(logits_old)), L.ptr(block), hyper_ptr, L.ptr(g_z), L.ptr(g_v), L.ptr(stats),
+                                           L.ptr(mask), L.stream_ptr()))
+    return g_z, g_v.view(-1, 1), stats
+
+
+def vmpo_loss_continuous(mu_raw, log_std_raw, value_pred, idx, action, adv, value_old, mu_raw_old, log_std_raw_old, block, hyper, stats=None, mask=None):
+    """jh_vmpo_loss_continuous, as vmpo_loss_discrete with the raw Gaussian heads -> (grad_mu_raw, grad_log_std_raw, grad_value [B, 1], stats)."""
+    mu, ls, v = _f32(mu_raw), _f32(log_std_raw), _f32(value_pred).reshape(-1)
+    B, A, hyper_ptr, g_v, stats = _vmpo_common(mu, v, idx, block, hyper, stats, mask)
+    assert tuple(ls.shape) == (B, A)
+    g_mu, g_ls = torch.empty_like(mu), torch.empty_like(ls)
+    L.check(L.load().jh_vmpo_loss_continuous(L.ctx(_dev(mu)), B, A, L.ptr(mu), L.ptr(ls), L.ptr(v), L.ptr(idx), L.ptr(_f32(action)), L.ptr(_f32(adv).reshape(-1)),
+                                             L.ptr(_f32(value_old).reshape(-1)), L.ptr(_f32(mu_raw_old)), L.ptr(_f32(log_std_raw_old)), L.ptr(block), hyper_ptr,
+                                             L.ptr(g_mu), L.ptr(g_ls), L.ptr(g_v), L.ptr(stats), L.ptr(mask), L.stream_ptr()))
+    return g_mu, g_ls, g_v.view(-1, 1), stats
+
+
 # ============================================================================= native policy-value MLP
 class PinnedBuffer:
     """Pinned host memory mapped into the device address space (jh_pinned_alloc): `.np` is the host
