@@ -1,7 +1,7 @@
 import numpy as np
 import torch
 
-from .td3 import _ELIGIBLE, ActorCriticView, DeterministicActorCritic
+from .td3 import _ELIGIBLE, DeterministicActorCritic
 
 DDPG_ELIGIBLE = _ELIGIBLE.format(name="DDPG", configs="config.ddpg x mujoco / pendulum / cartpole / hopper_mlagent")
 
@@ -36,8 +36,8 @@ class DDPG(DeterministicActorCritic):
                  optim_config={"actor": "adam", "critic": "adam", "actor_lr": 5e-4, "critic_lr": 1e-3}, gamma=0.99, buffer_size=50000, batch_size=128,
                  start_train_step=2000, tau=1e-3, run_step=1e6, lr_decay=True, mu=0, theta=1e-3, sigma=2e-3, device=None, use_graph=True, **kwargs):
         self._init_common(state_size, action_size, hidden_size, actor, critic, head, optim_config, gamma, buffer_size, batch_size, start_train_step, tau, run_step,
-                          lr_decay, device, use_graph, ("online:actor", "online:critic1", "target:actor", "target:critic1"))  # ddpg.py:74-87
-        self.critic, self.target_critic = ActorCriticView(self._net, "critic1", 0), ActorCriticView(self._net, "critic1", 1)
+                          lr_decay, device, use_graph, ("online:actor", "online:critic", "target:actor", "target:critic"))  # ddpg.py:74-87
+        self.actor_loss = 0.0
         self.OU = OUNoise(action_size, mu, theta, sigma)
 
     @torch.no_grad()

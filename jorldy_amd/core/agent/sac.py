@@ -4,8 +4,6 @@ import numpy as np
 import torch
 
 from ... import ops
-from ..buffer import ReplayBuffer
-from ..network import Network
 from ..optimizer import Optimizer
 from .base import BaseAgent
 from .td3 import ActorCriticView, DeterministicActorCritic
@@ -40,60 +38,25 @@ class SAC(DeterministicActorCritic):
 
     ELIGIBLE = SAC_ELIGIBLE
     _RESUME_ATTRS = BaseAgent._RESUME_ATTRS + ("_adam_steps_actor", "_adam_steps_critic")
+    # the stats after the critic's four: actor_loss, alpha_loss, mean_Q, alpha, entropy, mark
+    ACTOR, ACTOR_VIEW, OPTIMIZERS, ACTOR_LR, N_STATS, ACTOR_MARK = "continuous_policy", GaussianActorView, ("actor", "critic", "alpha"), 5e-4, 12, 9
     RESULT_KEYS = ("critic_loss1", "critic_loss2", "max_Q", None, "actor_loss", "alpha_loss", "mean_Q", "alpha", "entropy")
 
     def __init__(self, state_size, action_size, hidden_size=512, actor="continuous_policy", critic="continuous_q_network", head="mlp",
                  optim_config={"actor": "adam", "critic": "adam", "alpha": "adam", "actor_lr": 5e-4, "critic_lr": 1e-3, "alpha_lr": 3e-4}, use_dynamic_alpha=False,
                  gamma=0.99, tau=5e-3, buffer_size=50000, batch_size=64, start_train_step=2000, static_log_alpha=-2.0, target_update_period=10000, run_step=1e6,
                  lr_decay=True, device=None, use_graph=True, **kwargs):
-        got = (f"; got actor={actor!r}, critic={critic!r}, head={head!r}, state_size={state_size!r}, action_size={action_size!r}, hidden_size={hidden_size!r}, "
-               f"optim_config={optim_config!r}")
-        ok_opt = (isinstance(optim_config, dict) and set(optim_config) <= {"actor", "critic", "alpha", "actor_lr", "critic_lr", "alpha_lr"}
-                  and all(str(optim_config.get(k, "adam")).lower() == "adam" for k in ("actor", "critic", "alpha")))
-        ok = (actor == "continuous_policy" and critic == "continuous_q_network" and head == "mlp" and np.isscalar(state_size) and np.isscalar(action_size)
-              and int(action_size) >= 1 and isinstance(hidden_size, (int, np.integer)) and hidden_size % 4 == 0 and ok_opt)
-        if not ok:
-            raise ValueError(self.ELIGIBLE + got)
-        self.device = self._require_gpu(device)
-        self.use_graph = use_graph
-        self.grad_sync = None
-        self.state_size, self.action_size = int(state_size), int(action_size)
-        self._net = ops.SACNet(state_size, action_size, hidden_size, batch_size, self.device)
-        # the reference's construction order (sac.py:75-95): actor, critic 1, its target, critic 2, its target; every module draws its initial
-        # weights from torch's generator, the targets too, before they are overwritten by their online nets
-        self._net.import_state(Network(actor, state_size, action_size, D_hidden=hidden_size, head=head).state_dict(), "actor")
-        for net in ("critic1", "critic2"):
-            self._net.import_state(Network(critic, state_size, action_size, D_hidden=hidden_size, head=head).state_dict(), net)
-            Network(critic, state_size, action_size, D_hidden=hidden_size, head=head)
-        self._net.sync_target()
-        self.actor = GaussianActorView(self._net, "actor", 0)
-        self.network = self.actor  # BaseAgent.sync_in / sync_out carry the actor only (sac.py:345-352)
-        self.critic1, self.target_critic1 = ActorCriticView(self._net, "critic1", 0), ActorCriticView(self._net, "critic1", 1)
-        self.critic2, self.target_critic2 = ActorCriticView(self._net, "critic2", 0), ActorCriticView(self._net, "critic2", 1)
-        self._lr0 = {"actor": float(optim_config.get("actor_lr", 5e-4)), "critic": float(optim_config.get("critic_lr", 1e-3))}
-        self._lr_now = dict(self._lr0)
-        self._adam_steps_actor = self._adam_steps_critic = 0
-        for which in ("actor", "critic"):
-            self._net.set_hyper(which, self._lr0[which], 0.9, 0.999, 1e-8, 0)
+        self._init_common(state_size, action_size, hidden_size, actor, critic, head, optim_config, gamma, buffer_size, batch_size, start_train_step, tau, run_step,
+                          lr_decay, device, use_graph, ("online:actor", "online:critic1", "target:critic1", "online:critic2", "target:critic2"))  # sac.py:75-95
         self.use_dynamic_alpha = bool(use_dynamic_alpha)
         self.alpha_lr = float(optim_config.get("alpha_lr", 3e-4))  # never decayed (sac.py:292-300)
         self._net.set_alpha(0.0 if self.use_dynamic_alpha else static_log_alpha, lr=self.alpha_lr, dynamic=self.use_dynamic_alpha)
         self.target_entropy = -self.action_size
-        self.gamma, self.tau = gamma, tau
-        self.buffer_size = buffer_size
-        self.memory = ReplayBuffer(buffer_size, device=self.device)
-        self.memory.defer_rows = 16  # per-step stores coalesce into one ring append before the next learn()
-        self.batch_size = batch_size
-        self.start_train_step = start_train_step
-        self.num_learn = 0
-        self.time_t = 0
         self.target_update_stamp = 0
         self.target_update_period = target_update_period
-        self.run_step = run_step
-        self.lr_decay = lr_decay
-        self._noise_inject = None  # test hook: the standard normals [2, B, A] of the next learn() -- the target's, the actor step's -- instead of torch.randn
-        self._stats, self._stats_np = self._mapped_stats(12)  # critic: loss_1, loss_2, max_Q, mark; actor: actor_loss, alpha_loss, mean_Q, alpha, entropy, mark
-        self._static, self._graphs, self._warm = None, {}, False
+
+    def _make_net(self, state_size, action_size, hidden_size, batch_size):
+        return ops.SACNet(state_size, action_size, hidden_size, batch_size, self.device)
 
     # ------------------------------------------------------------------------------------------ the temperature
     @property
@@ -144,16 +107,7 @@ class SAC(DeterministicActorCritic):
             net.soft_update(self.tau)
 
     def _learn(self, soft):
-        marks, view = (3, 9), self._stats_np
-        if view is not None:
-            for m in marks:
-                view[m] = -1.0
-        self._run_learn(True, soft, True)
-        if view is not None:
-            self._await_marks(view, marks, "SAC.learn()")
-            s = view.copy()
-        else:
-            s = self._read_stats(self._stats)[0].copy()
+        s = self._learn_stats(True, soft)
         self.num_learn += 1
         self.result = {k: float(s[i]) for i, k in enumerate(self.RESULT_KEYS) if k is not None}
         return self.result
@@ -189,20 +143,13 @@ class SAC(DeterministicActorCritic):
             opt.state[p] = {"step": torch.tensor(float(blk["step"])), "exp_avg": t(blk["m"]), "exp_avg_sq": t(blk["v"])}
         return p, opt
 
-    def save(self, path):
+    def _ckpt(self):
         """The reference's keys (sac.py:312-326): TD3's six, plus log_alpha and alpha_optimizer when the temperature is dynamic."""
-        print(f"...Save model to {path}...")
-        out = {}
-        for key, net, what in self.CKPT_KEYS:
-            which = "actor" if net == "actor" else "critic"
-            if what == "net":
-                out[key] = self._net.export_state(net)
-            else:
-                out[key] = self._optimizer_state(net, self._adam_steps_actor if net == "actor" else self._adam_steps_critic, self._lr_now[which])
+        out = super()._ckpt()
         if self.use_dynamic_alpha:
             p, opt = self._alpha_optimizer(self._net.get_alpha())
             out["log_alpha"], out["alpha_optimizer"] = p.detach(), opt.state_dict()
-        torch.save(out, os.path.join(path, "ckpt"))
+        return out
 
     def load(self, path):
         """The reference's ckpt, with three deliberate departures: critic 2 is restored from "critic2" (sac.py:335 loads it into critic 1 and

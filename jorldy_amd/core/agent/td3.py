@@ -73,13 +73,20 @@ class DeterministicActorCritic(BaseAgent):
                  ("critic_optimizer1", "critic1", "opt"), ("critic_optimizer2", "critic2", "opt"))  # td3.py:232-239
     _RESUME_ATTRS = BaseAgent._RESUME_ATTRS + ("num_random_step", "actor_loss", "_adam_steps_actor", "_adam_steps_critic")
 
+    # what a member of the family sets: its policy module and the view `agent.actor` is, the optimizers optim_config may name, the actor's
+    # default lr, the floats of the mapped statistics and where in them the actor update leaves its arrival mark
+    ACTOR, ACTOR_VIEW, OPTIMIZERS, ACTOR_LR, N_STATS, ACTOR_MARK = "deterministic_policy", ActorCriticView, ("actor", "critic"), 1e-3, 8, 5
+
+    def _make_net(self, state_size, action_size, hidden_size, batch_size):
+        return ops.ACNet(state_size, action_size, hidden_size, self.N_CRITICS, batch_size, self.device)
+
     def _init_common(self, state_size, action_size, hidden_size, actor, critic, head, optim_config, gamma, buffer_size, batch_size, start_train_step, tau,
                      run_step, lr_decay, device, use_graph, build_order):
         got = (f"; got actor={actor!r}, critic={critic!r}, head={head!r}, state_size={state_size!r}, action_size={action_size!r}, hidden_size={hidden_size!r}, "
                f"optim_config={optim_config!r}")
-        ok_opt = (isinstance(optim_config, dict) and set(optim_config) <= {"actor", "critic", "actor_lr", "critic_lr"}
-                  and str(optim_config.get("actor", "adam")).lower() == "adam" and str(optim_config.get("critic", "adam")).lower() == "adam")
-        ok = (actor == "deterministic_policy" and critic == "continuous_q_network" and head == "mlp" and np.isscalar(state_size) and np.isscalar(action_size)
+        ok_opt = (isinstance(optim_config, dict) and set(optim_config) <= {o + s for o in self.OPTIMIZERS for s in ("", "_lr")}
+                  and all(str(optim_config.get(o, "adam")).lower() == "adam" for o in self.OPTIMIZERS))
+        ok = (actor == self.ACTOR and critic == "continuous_q_network" and head == "mlp" and np.isscalar(state_size) and np.isscalar(action_size)
               and int(action_size) >= 1 and isinstance(hidden_size, (int, np.integer)) and hidden_size % 4 == 0 and ok_opt)
         if not ok:
             raise ValueError(self.ELIGIBLE + got)
@@ -87,18 +94,20 @@ class DeterministicActorCritic(BaseAgent):
         self.use_graph = use_graph
         self.grad_sync = None
         self.state_size, self.action_size = int(state_size), int(action_size)
-        self._net = ops.ACNet(state_size, action_size, hidden_size, self.N_CRITICS, batch_size, self.device)
-        # the reference's construction order: every module, the targets included, draws its initial weights from torch's generator
+        self._net = self._make_net(state_size, action_size, hidden_size, batch_size)
+        # the reference's construction order: every module, the targets included, draws its initial weights from torch's generator (a target
+        # is then overwritten by its online net); each becomes `self.<net>` / `self.target_<net>`
         for name in build_order:
             kind, net = name.split(":")
-            mod = (Network(actor, state_size, action_size, D_hidden=hidden_size, head=head) if net == "actor"
-                   else Network(critic, state_size, action_size, D_hidden=hidden_size, head=head))
+            mod = Network(actor if net == "actor" else critic, state_size, action_size, D_hidden=hidden_size, head=head)
             if kind == "online":
                 self._net.import_state(mod.state_dict(), net)
+                setattr(self, net, (self.ACTOR_VIEW if net == "actor" else ActorCriticView)(self._net, net, 0))
+            else:
+                setattr(self, "target_" + net, ActorCriticView(self._net, net, 1))
         self._net.sync_target()  # target.load_state_dict(online.state_dict())
-        self.actor, self.target_actor = ActorCriticView(self._net, "actor", 0), ActorCriticView(self._net, "actor", 1)
-        self.network = self.actor  # BaseAgent.sync_in / sync_out carry the actor only (td3.py:255-265)
-        self._lr0 = {"actor": float(optim_config.get("actor_lr", 1e-3)), "critic": float(optim_config.get("critic_lr", 1e-3))}
+        self.network = self.actor  # BaseAgent.sync_in / sync_out carry the actor only (td3.py:255-265, sac.py:345-352)
+        self._lr0 = {"actor": float(optim_config.get("actor_lr", self.ACTOR_LR)), "critic": float(optim_config.get("critic_lr", 1e-3))}
         self._lr_now = dict(self._lr0)
         self._adam_steps_actor = self._adam_steps_critic = 0
         for which in ("actor", "critic"):
@@ -113,9 +122,8 @@ class DeterministicActorCritic(BaseAgent):
         self.time_t = 0
         self.run_step = run_step
         self.lr_decay = lr_decay
-        self.actor_loss = 0.0
-        self._noise_inject = None  # test hook: the standard normals [B, A] of the next learn()'s target noise instead of torch.randn
-        self._stats, self._stats_np = self._mapped_stats(8)  # critic: loss_1, loss_2, max_Q, mark; actor: actor_loss, mark
+        self._noise_inject = None  # test hook: the standard normals of the next learn() ([B, A]; SAC [2, B, A]) instead of torch.randn
+        self._stats, self._stats_np = self._mapped_stats(self.N_STATS)  # critic: loss_1, loss_2, max_Q, mark; then the actor update's, its mark last
         self._static, self._graphs, self._warm = None, {}, False
 
     # ------------------------------------------------------------------------------------------ acting
@@ -188,7 +196,7 @@ class DeterministicActorCritic(BaseAgent):
         self._adam_steps_actor += int(actor_step)
 
     def _learn_stats(self, actor_step, soft, capture=True):
-        marks = (3, 5) if actor_step else (3,)
+        marks = (3, self.ACTOR_MARK) if actor_step else (3,)
         view = self._stats_np
         if view is not None:
             for m in marks:
@@ -246,8 +254,7 @@ class DeterministicActorCritic(BaseAgent):
         g0 = opt.param_groups[0]
         return steps, float(g0["lr"]), g0["betas"], g0["eps"]
 
-    def save(self, path):
-        print(f"...Save model to {path}...")
+    def _ckpt(self):
         out = {}
         for key, net, what in self.CKPT_KEYS:
             which = "actor" if net == "actor" else "critic"
@@ -255,7 +262,11 @@ class DeterministicActorCritic(BaseAgent):
                 out[key] = self._net.export_state(net)
             else:
                 out[key] = self._optimizer_state(net, self._adam_steps_actor if net == "actor" else self._adam_steps_critic, self._lr_now[which])
-        torch.save(out, os.path.join(path, "ckpt"))
+        return out
+
+    def save(self, path):
+        print(f"...Save model to {path}...")
+        torch.save(self._ckpt(), os.path.join(path, "ckpt"))
 
     def load(self, path):
         """The reference's ckpt, with two deliberate departures: critic 2 is restored from "critic2" (td3.py:249 loads it into critic 1 and
@@ -314,8 +325,7 @@ class TD3(DeterministicActorCritic):
         self._init_common(state_size, action_size, hidden_size, actor, critic, head, optim_config, gamma, buffer_size, batch_size, start_train_step, tau, run_step,
                           lr_decay, device, use_graph,
                           ("online:actor", "target:actor", "online:critic1", "target:critic1", "online:critic2", "target:critic2"))  # td3.py:77-112
-        self.critic1, self.target_critic1 = ActorCriticView(self._net, "critic1", 0), ActorCriticView(self._net, "critic1", 1)
-        self.critic2, self.target_critic2 = ActorCriticView(self._net, "critic2", 0), ActorCriticView(self._net, "critic2", 1)
+        self.actor_loss = 0.0
         self.initial_random_step = initial_random_step
         self.num_random_step = 0
         self.update_delay = update_delay

@@ -2,7 +2,7 @@
 // between the dense layers.
 //   jh_sac_sample           mu = clamp(mu_raw, -5, 5), std = exp(tanh(ls_raw)), z = mu + std * eps, a = tanh(z) and
 //                           logp = sum_j [Normal(mu, std).log_prob(z)_j - log(1 - a_j^2 + 1e-7)]   (sac.py:161-169)
-//   jh_sac_critic_loss      jh_td3_critic_loss with the entropy term in the target: y = r + (1 - d) gamma (min_i q_i' - alpha logp')
+//   jh_sac_critic_loss      the shared critic loss (jh_acnet.hip) with the entropy term in the target: y = r + (1 - d) gamma (min_i q_i' - alpha logp')
 //   jh_sac_actor_seed       actor_loss = -mean(alpha (-logp) + min(q1, q2)), its gradient into q1 / q2, the coefficient alpha / B of logp's
 //                           way back, alpha_loss, and the temperature's bookkeeping: alpha <- exp(log_alpha), then Adam on log_alpha
 //   jh_sac_sample_backward  d(mu_raw), d(ls_raw) from d(a) and the coefficient of logp
@@ -52,44 +52,6 @@ __global__ void __launch_bounds__(256) jh_sac_sample_kernel(int B, int A, int ld
     s += (-0.5 * e * e - ls - kHalfLog2Pi) - log(om + 1e-7);
   }
   logp[b] = (float)s;
-}
-
-// ---------------------------------------------------------------------------------- critic loss
-// y = r + (1 - d) * gamma * (min(q1', q2') - alpha * logp'), loss_i = mean((y - q_i)^2), d(loss_i)/d(q_i) = 2 (q_i - y) / B, max_Q = max_b y
-// (sac.py:186-216).  One workgroup, as jh_td3_critic_loss_kernel.  stats = {loss_1, loss_2, max_Q, arrival mark}.
-struct SacCriticLossArgs {
-  int B, gstride;                              // grad of critic c starts at c * gstride
-  const float *q, *qn, *logp, *reward, *done;  // q, qn: [2][B]
-  const float* alpha;                          // the alpha block
-  float gamma;
-  float *y, *grad, *stats;                     // y [B] (optional), grad [2][B]
-};
-__global__ void __launch_bounds__(256) jh_sac_critic_loss_kernel(SacCriticLossArgs a) {
-  __shared__ float s_red[16];
-  float l0 = 0.f, l1 = 0.f, my = -3.4e38f;
-  const float inv = 2.f / (float)a.B;
-  const float alpha = a.alpha[SA_IN_USE];
-  for (int b = threadIdx.x; b < a.B; b += 256) {
-    const float mn = fminf(a.qn[b], a.qn[a.B + b]);
-    const float y = a.reward[b] + (1.f - a.done[b]) * a.gamma * (mn + alpha * -a.logp[b]);
-    if (a.y) a.y[b] = y;
-    my = fmaxf(my, y);
-    const float d0 = a.q[b] - y, d1 = a.q[a.B + b] - y;
-    l0 += d0 * d0;
-    l1 += d1 * d1;
-    a.grad[b] = d0 * inv;
-    a.grad[a.gstride + b] = d1 * inv;
-  }
-  const float s0 = jh_block_reduce(l0, s_red, JhAdd(), 0.f);
-  const float s1 = jh_block_reduce(l1, s_red, JhAdd(), 0.f);
-  const float m = jh_block_reduce(my, s_red, JhMax(), -3.4e38f);
-  if (threadIdx.x == 0 && a.stats) {
-    a.stats[0] = s0 / (float)a.B;
-    a.stats[1] = s1 / (float)a.B;
-    a.stats[2] = m;
-    __threadfence_system();  // payload before the arrival mark (mapped host memory, jh_host_wait_marks)
-    a.stats[3] = 0.f;
-  }
 }
 
 // ---------------------------------------------------------------------------------- actor seed + temperature
@@ -187,11 +149,6 @@ static int sac_sample(int B, int A, int ld, const float* mu_raw, const float* ls
   JH_LAUNCH_CHECK();
   return JH_OK;
 }
-static int sac_critic_loss(const SacCriticLossArgs& a, hipStream_t st) {
-  JH_LAUNCH(jh_sac_critic_loss_kernel, dim3(1), dim3(256), 0, st, a);
-  JH_LAUNCH_CHECK();
-  return JH_OK;
-}
 static int sac_actor_seed(int B, int qstride, int gstride, const float* q, const float* logp, float* dq, float* blk, float* stats, hipStream_t st) {
   JH_LAUNCH(jh_sac_actor_seed_kernel, dim3(1), dim3(256), 0, st, B, qstride, gstride, q, logp, dq, blk, stats);
   JH_LAUNCH_CHECK();
@@ -210,8 +167,6 @@ static int sac_mu_std(int64_t n, int A, int ld, const float* raw, float* mu, flo
   return JH_OK;
 }
 
-constexpr int kMaxLossRows = 1 << 20;
-
 }  // namespace
 
 static_assert(SA_FLOATS == JH_SAC_ALPHA_FLOATS, "the alpha block of include/jorldy_hip.h");
@@ -228,8 +183,8 @@ JH_EXPORT int jh_sac_critic_loss(jh_ctx* ctx, int32_t B, const float* d_q, const
                                  float gamma, const float* d_alpha, float* d_y, float* d_grad, float* d_stats, jh_stream stream) {
   JH_ARG(ctx && d_q && d_q_next && d_logp_next && d_reward && d_done && d_alpha && d_grad && d_stats);
   JH_ARG(B > 0 && B <= kMaxLossRows && ((uintptr_t)d_alpha & 7) == 0);
-  SacCriticLossArgs a{B, B, d_q, d_q_next, d_logp_next, d_reward, d_done, d_alpha, gamma, d_y, d_grad, d_stats};
-  return sac_critic_loss(a, jh_s(stream));
+  CriticLossArgs a{d_reward, d_done, gamma, d_y, d_stats, d_logp_next, d_alpha + SA_IN_USE, B, 2, B, d_q, d_q_next, d_grad};
+  return ac_critic_loss(a, jh_s(stream));
 }
 JH_EXPORT int jh_sac_actor_seed(jh_ctx* ctx, int32_t B, const float* d_q, const float* d_logp, float* d_alpha, float* d_grad_q, float* d_stats, jh_stream stream) {
   JH_ARG(ctx && d_q && d_logp && d_alpha && d_grad_q && d_stats);
@@ -245,41 +200,41 @@ JH_EXPORT int jh_sac_sample_backward(jh_ctx* ctx, int32_t B, int32_t A, const fl
 
 // ---------------------------------------------------------------------------------- the network object
 // A Gaussian policy (policy.py:38-55: head.l -> relu(l) -> (mu, log_std)), online only, and two continuous Q networks with their targets
-// (sac.py:75-95).  jh_sacnet embeds a jh_acnet (two critics, no target actor) and drives jh_acnet.h's builders with it.  mu and log_std are
-// ONE [2A][H] layer in the actor's bucket -- mu.weight, log_std.weight, then mu.bias, log_std.bias, back to back --, so a row of its output is
-// [mu_raw | ls_raw] and the way back into relu(l) is one contraction over 2A; jh_sacnet_segment reports the four tensors in the
-// reference's state_dict order.
+// (sac.py:75-95).  jh_sacnet embeds a jh_acnet (two critics, no target actor, a head of 2A columns) and drives jh_acnet.hip's pieces with it.
+// mu and log_std are ONE [2A][H] layer in the actor's bucket -- mu.weight, log_std.weight, then mu.bias, log_std.bias, back to back --, so a
+// row of its output is [mu_raw | ls_raw] and the way back into relu(l) is one contraction over 2A; jh_sacnet_segment reports the four
+// tensors in the reference's state_dict order.
 enum { SAC_A_WMU = 4, SAC_A_BMU, SAC_A_WLS, SAC_A_BLS, SAC_C_FIRST, SAC_SEG_COUNT = SAC_C_FIRST + 8 };
 
 struct jh_sacnet {
-  jh_acnet ac;                                // at == nullptr; AC_A_WPI / AC_A_BPI are the [2A][H] layer and its [2A] bias
-  float *d_raw = nullptr, *logp = nullptr;    // d[mu_raw | ls_raw] [maxB][2A] (the raw heads themselves: ac.a_z), logp [maxB]
-  float* da2 = nullptr;                       // critic 2's d(action) [maxB][A] (critic 1's: ac.da)
-  float* alpha = nullptr;                     // the temperature block
+  jh_acnet ac;              // at == nullptr; AC_A_WPI / AC_A_BPI are the [2A][H] layer and its [2A] bias; a_z = [mu_raw | ls_raw], dz its gradient
+  float* logp = nullptr;    // [maxB]
+  float* da2 = nullptr;     // critic 2's d(action) [maxB][A] (critic 1's: ac.da)
+  float* alpha = nullptr;   // the temperature block
 };
-
-static int sac_layout(jh_acnet* n, int32_t S, int32_t H, int32_t A, int32_t max_batch) {
-  int rc = ac_layout(n, S, H, A, 2, max_batch);
-  if (rc) return rc;
-  JH_ARG((int64_t)max_batch * 2 * A < ((int64_t)1 << 31));
-  n->seg_rows[AC_A_WPI] = 2 * A;
-  n->seg_cols[AC_A_BPI] = 2 * A;
-  n->seg_off[AC_A_BPI] = n->seg_off[AC_A_WPI] + (int64_t)2 * A * H;  // H % 4 == 0: aligned
-  n->nA = (n->seg_off[AC_A_BPI] + 2 * A + 3) & ~(int64_t)3;
-  return JH_OK;
-}
-static inline TGemm sac_a_heads(const jh_acnet* n, int rows) {
-  return mk_gemm(rows, 2 * n->A, n->H, op_dense(OP_KCONT, n->a_h, n->H), op_dense(OP_KCONT, n->ap + n->seg_off[AC_A_WPI], n->H), n->a_z, 2 * n->A, TEPI_BIAS,
-                 n->ap + n->seg_off[AC_A_BPI]);
-}
 
 JH_EXPORT int jh_sacnet_param_counts_for(int32_t S, int32_t H, int32_t A, int64_t* actor_floats, int64_t* critic_floats) {
   JH_ARG(actor_floats && critic_floats);
   jh_acnet tmp;
-  int rc = sac_layout(&tmp, S, H, A, 1);
+  int rc = ac_layout(&tmp, S, H, A, 2 * A, 2, 1);
   if (rc) return rc;
   *actor_floats = tmp.nA;
   *critic_floats = tmp.nC;
+  return JH_OK;
+}
+
+static int sac_init(jh_sacnet* s) {
+  jh_acnet* n = &s->ac;
+  int rc = ac_alloc(n, (void**)&s->logp, sizeof(float) * n->maxB, true);
+  if (!rc) rc = ac_alloc(n, (void**)&s->da2, sizeof(float) * n->maxB * n->A, true);
+  if (!rc) rc = ac_alloc(n, (void**)&s->alpha, sizeof(float) * SA_FLOATS, true);
+  if (rc) return rc;
+  float al[SA_FLOATS] = {0.f};
+  const double b1 = 0.9, b2 = 0.999;
+  al[SA_IN_USE] = 1.f; al[SA_LR] = 3e-4f; al[SA_EPS] = 1e-8f; al[SA_TARGET_ENTROPY] = -(float)n->A;
+  memcpy(al + SA_B1D, &b1, 8); memcpy(al + SA_B2D, &b2, 8);
+  JH_HIP(hipMemcpy(s->alpha, al, sizeof(al), hipMemcpyHostToDevice));
+  JH_HIP(hipDeviceSynchronize());
   return JH_OK;
 }
 
@@ -288,48 +243,13 @@ JH_EXPORT int jh_sacnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int
                                jh_sacnet** out) {
   JH_ARG(ctx && out && d_actor && d_actor_grads && d_actor_m && d_actor_v);
   JH_ARG(d_critics && d_critics_target && d_critics_grads && d_critics_m && d_critics_v);
-  JH_HIP(hipSetDevice(ctx->device));
+  float* const actor[5] = {d_actor, nullptr, d_actor_grads, d_actor_m, d_actor_v};
+  float* const critics[5] = {d_critics, d_critics_target, d_critics_grads, d_critics_m, d_critics_v};
   jh_sacnet* s = new jh_sacnet();
-  jh_acnet* n = &s->ac;
-  n->ctx = ctx;
-  int rc = sac_layout(n, S, H, A, max_batch);
+  int rc = ac_init(&s->ac, ctx, S, H, A, 2 * A, 2, max_batch, actor, critics);
+  if (!rc) rc = sac_init(s);
   if (rc) {
-    delete s;
-    return rc;
-  }
-  n->ap = d_actor; n->ag = d_actor_grads; n->am = d_actor_m; n->av = d_actor_v;
-  n->cp = d_critics; n->ct = d_critics_target; n->cg = d_critics_grads; n->cm = d_critics_m; n->cv = d_critics_v;
-  const size_t B = (size_t)max_batch, NB = 2 * B;
-  auto A4 = [&](float** p, size_t floats, bool zero = true) { if (!rc) rc = ac_alloc(n, (void**)p, floats * sizeof(float), zero); };
-  A4(&n->hyper_a, JH_HY_FLOATS); A4(&n->hyper_c, JH_HY_FLOATS);
-  A4(&n->norm_partial, 256);
-  if (!rc) rc = ac_alloc(n, (void**)&n->ticket_a, 2048, true);  // jh_rb_optim_kernel: eight counters 128 bytes apart + the one on top of them
-  if (!rc) rc = ac_alloc(n, (void**)&n->ticket_c, 2048, true);
-  A4(&n->a_feat, B * H); A4(&n->a_h, B * H); A4(&n->a_z, B * 2 * A); A4(&n->a_out, B * A);
-  for (int k = 0; k < 2; ++k) {
-    A4(&n->c_cat[k], NB * 2 * H); A4(&n->c_h[k], NB * H); A4(&n->c_q[k], NB);
-  }
-  A4(&n->dq, NB); A4(&n->dh, NB * H); A4(&n->dcat, NB * 2 * H); A4(&n->da, B * A); A4(&n->dah, B * H); A4(&n->dafeat, B * H);
-  A4(&s->d_raw, B * 2 * A); A4(&s->logp, B); A4(&s->da2, B * A); A4(&s->alpha, SA_FLOATS);
-  n->ws_floats = (size_t)8 << 20;  // 32 MB of split-K partials
-  A4(&n->ws, n->ws_floats, false);
-  n->cnt_slots = 8192;
-  if (!rc) rc = ac_alloc(n, (void**)&n->cnt, sizeof(unsigned) * (size_t)n->cnt_slots * kTgemmCntStride, true);
-  float hy[JH_HY_FLOATS], al[SA_FLOATS] = {0.f};
-  jh_hyper_fill(hy, 1e-3, 0.9, 0.999, 1e-8, 0.0);
-  const double b1 = 0.9, b2 = 0.999;
-  al[SA_IN_USE] = 1.f; al[SA_LR] = 3e-4f; al[SA_EPS] = 1e-8f; al[SA_TARGET_ENTROPY] = -(float)A;
-  memcpy(al + SA_B1D, &b1, 8); memcpy(al + SA_B2D, &b2, 8);
-  auto init = [&]() -> int {
-    JH_HIP(hipMemcpy(n->hyper_a, hy, sizeof(hy), hipMemcpyHostToDevice));
-    JH_HIP(hipMemcpy(n->hyper_c, hy, sizeof(hy), hipMemcpyHostToDevice));
-    JH_HIP(hipMemcpy(s->alpha, al, sizeof(al), hipMemcpyHostToDevice));
-    JH_HIP(hipDeviceSynchronize());
-    return JH_OK;
-  };
-  if (!rc) rc = init();
-  if (rc) {
-    for (void* p : n->owned) (void)hipFree(p);
+    ac_release(&s->ac);
     delete s;
     return rc;
   }
@@ -339,9 +259,7 @@ JH_EXPORT int jh_sacnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int
 
 JH_EXPORT void jh_sacnet_destroy(jh_sacnet* s) {
   if (!s) return;
-  (void)hipSetDevice(s->ac.ctx->device);
-  (void)hipDeviceSynchronize();
-  for (void* p : s->ac.owned) (void)hipFree(p);
+  ac_release(&s->ac);
   delete s;
 }
 
@@ -363,7 +281,8 @@ JH_EXPORT int jh_sacnet_segment(const jh_sacnet* s, int32_t i, int64_t* offset, 
   return JH_OK;
 }
 
-// which: 0 the actor's Adam, 1 the critics' (one block and one launch for both: sac.py:136-140 gives them the same settings)
+// The entries the embedded jh_acnet answers (jh_acnet.hip).  which: 0 the actor's Adam, 1 the critics'; there is no target actor, so the
+// target sync and update_target_soft (sac.py:271-275) move the two target critics alone.
 JH_EXPORT int jh_sacnet_set_hyper(jh_sacnet* s, int32_t which, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream) {
   JH_ARG(s != nullptr);
   return jh_acnet_set_hyper(&s->ac, which, lr, beta1, beta2, eps, step, stream);
@@ -371,6 +290,19 @@ JH_EXPORT int jh_sacnet_set_hyper(jh_sacnet* s, int32_t which, double lr, double
 JH_EXPORT int jh_sacnet_set_lr(jh_sacnet* s, int32_t which, double lr, jh_stream stream) {
   JH_ARG(s != nullptr);
   return jh_acnet_set_lr(&s->ac, which, lr, stream);
+}
+JH_EXPORT int jh_sacnet_sync_target(jh_sacnet* s, jh_stream stream) {
+  JH_ARG(s != nullptr);
+  return jh_acnet_sync_target(&s->ac, stream);
+}
+JH_EXPORT int jh_sacnet_soft_update(jh_sacnet* s, double tau, jh_stream stream) {
+  JH_ARG(s != nullptr);
+  return jh_acnet_soft_update(&s->ac, tau, stream);
+}
+// critic_c(x, action) for both critics -> d_q [2][rows]; which 0 online / 1 target
+JH_EXPORT int jh_sacnet_critic_forward(jh_sacnet* s, int32_t which, const float* d_x, const float* d_action, int32_t rows, float* d_q, jh_stream stream) {
+  JH_ARG(s != nullptr);
+  return jh_acnet_critic_forward(&s->ac, which, d_x, d_action, rows, d_q, stream);
 }
 // The whole temperature block.  Synchronous (checkpoints and construction): not for a captured stream.
 JH_EXPORT int jh_sacnet_set_alpha(jh_sacnet* s, double log_alpha, double alpha, double lr, double beta1, double beta2, double eps, int64_t step, double m, double v,
@@ -391,144 +323,60 @@ JH_EXPORT int jh_sacnet_get_alpha(jh_sacnet* s, float* h_block, jh_stream stream
   JH_HIP(hipMemcpy(h_block, s->alpha, sizeof(float) * SA_FLOATS, hipMemcpyDeviceToHost));
   return JH_OK;
 }
-JH_EXPORT int jh_sacnet_sync_target(jh_sacnet* s, jh_stream stream) {
-  JH_ARG(s != nullptr);
-  JH_HIP(hipMemcpyAsync(s->ac.ct, s->ac.cp, sizeof(float) * (size_t)s->ac.nC * 2, hipMemcpyDeviceToDevice, jh_s(stream)));
-  return JH_OK;
-}
-// update_target_soft (sac.py:271-275): the two target critics; there is no target actor
-JH_EXPORT int jh_sacnet_soft_update(jh_sacnet* s, double tau, jh_stream stream) {
-  JH_ARG(s != nullptr);
-  return jh_td3_polyak(s->ac.ctx, s->ac.nC * 2, s->ac.cp, s->ac.ct, tau, stream);
-}
 
 // actor(x) -> d_mu, d_std [rows][A]   (policy.py:38-55; sac.py:148)
 JH_EXPORT int jh_sacnet_actor_forward(jh_sacnet* s, const float* d_x, int32_t rows, float* d_mu, float* d_std, jh_stream stream) {
   JH_ARG(s && d_x && d_mu && d_std);
   jh_acnet* n = &s->ac;
   JH_ARG(rows > 0 && rows <= n->maxB);
-  hipStream_t st = jh_s(stream);
-  TGemm g[1];
-  int rc;
-  g[0] = ac_head(n, n->ap, AC_A_W1, AC_A_B1, d_x, rows, n->a_feat, n->H);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
-  g[0] = ac_a_l(n, n->ap, rows);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
-  g[0] = sac_a_heads(n, rows);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
-  return sac_mu_std((int64_t)rows * n->A, n->A, 2 * n->A, n->a_z, d_mu, d_std, st);
-}
-// critic_c(x, action) for both critics -> d_q [2][rows]; which 0 online / 1 target
-JH_EXPORT int jh_sacnet_critic_forward(jh_sacnet* s, int32_t which, const float* d_x, const float* d_action, int32_t rows, float* d_q, jh_stream stream) {
-  JH_ARG(s != nullptr);
-  return jh_acnet_critic_forward(&s->ac, which, d_x, d_action, rows, d_q, stream);
+  int rc = ac_actor_forward(n, n->ap, d_x, rows, jh_s(stream));
+  return rc ? rc : sac_mu_std((int64_t)rows * n->A, n->A, 2 * n->A, n->a_z, d_mu, d_std, jh_s(stream));
 }
 
 // The critic update of learn() (sac.py:183-225).  d_x = [state; next_state] (2B rows), d_eps [B][A] standard normals: a', logp' come from the
 // ONLINE actor on next_state, which rides in the three grouped levels where TD3's target actor rides.
 // -> d_y [B], d_q [2][B], d_a_next [B][A], d_logp_next [B] (all optional), d_stats {loss_1, loss_2, max_Q, mark}; the critics have taken
 // their Adam step on return.
-// Launches: 6 grouped GEMMs of the two forward passes + sample + loss + 3 grouped GEMMs of the backward + Adam = 12.
+// Launches: 3 grouped GEMMs (ac_critic_front, the online actor riding along) + sample + 3 grouped GEMMs, loss, 3 grouped GEMMs of the backward
+// and Adam (ac_critic_back) = 12.
 JH_EXPORT int jh_sacnet_critic_update(jh_sacnet* s, const float* d_x, const float* d_action, const float* d_reward, const float* d_done, const float* d_eps,
                                       int32_t B, float gamma, float* d_y, float* d_q, float* d_a_next, float* d_logp_next, float* d_stats, jh_stream stream) {
   JH_ARG(s && d_x && d_action && d_reward && d_done && d_eps && d_stats);
   jh_acnet* n = &s->ac;
   JH_ARG(B > 0 && B <= n->maxB);
   hipStream_t st = jh_s(stream);
-  const int S = n->S, A = n->A;
-  const float* xs = d_x;
-  const float* xn = d_x + (size_t)B * S;
-  float* q_on = d_q ? d_q : n->c_q[0];  // [2][B], packed
+  const int A = n->A;
   float* a_next = d_a_next ? d_a_next : n->a_out;
   float* lp_next = d_logp_next ? d_logp_next : s->logp;
-  TGemm g[kMaxGroup];
-  int k, rc;
-  // 1: head.l of the online actor and the target critics on s', of the online critics on s
-  k = 0;
-  g[k++] = ac_head(n, n->ap, AC_A_W1, AC_A_B1, xn, B, n->a_feat, n->H);
-  for (int c = 0; c < 2; ++c) g[k++] = ac_c_head(n, n->ct + c * n->nC, 1, c, xn, B);
-  for (int c = 0; c < 2; ++c) g[k++] = ac_c_head(n, n->cp + c * n->nC, 0, c, xs, B);
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
-  // 2: the actor's l, the online critics' e(a)
-  k = 0;
-  g[k++] = ac_a_l(n, n->ap, B);
-  for (int c = 0; c < 2; ++c) g[k++] = ac_c_embed(n, n->cp + c * n->nC, 0, c, d_action, B);
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
-  // 3: the actor's [mu | log_std], the online critics' l
-  k = 0;
-  g[k++] = sac_a_heads(n, B);
-  for (int c = 0; c < 2; ++c) g[k++] = ac_c_l(n, n->cp + c * n->nC, 0, c, B);
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
+  int rc;
+  if ((rc = ac_critic_front(n, n->ap, d_x, d_action, B, st))) return rc;
   if ((rc = sac_sample(B, A, 2 * A, n->a_z, n->a_z + A, d_eps, a_next, lp_next, st))) return rc;
-  // 4: the target critics' e(a'), the online critics' q
-  k = 0;
-  for (int c = 0; c < 2; ++c) g[k++] = ac_c_embed(n, n->ct + c * n->nC, 1, c, a_next, B);
-  for (int c = 0; c < 2; ++c) g[k++] = ac_c_q(n, n->cp + c * n->nC, 0, c, B, q_on + (size_t)c * B);
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
-  // 5, 6: the target critics' l and q
-  for (int c = 0; c < 2; ++c) g[c] = ac_c_l(n, n->ct + c * n->nC, 1, c, B);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
-  for (int c = 0; c < 2; ++c) g[c] = ac_c_q(n, n->ct + c * n->nC, 1, c, B, n->c_q[1] + (size_t)c * B);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
-  // loss: q and q' are packed [2][B]; the gradient of critic c goes where the backward reads it, at c * maxB
-  SacCriticLossArgs a{B, n->maxB, q_on, n->c_q[1], lp_next, d_reward, d_done, s->alpha, gamma, d_y, n->dq, d_stats};
-  if ((rc = sac_critic_loss(a, st))) return rc;
-  if ((rc = ac_critic_backward(n, B, xs, d_action, true, 0, 2, st))) return rc;
-  return jh_flat_adam_step(n->nC * 2, n->cp, n->cg, n->cm, n->cv, n->hyper_c, n->ticket_c, n->norm_partial, 0.f, st);
+  CriticLossArgs loss{d_reward, d_done, gamma, d_y, d_stats, lp_next, s->alpha + SA_IN_USE};
+  return ac_critic_back(n, d_x, d_action, B, a_next, d_q ? d_q : n->c_q[0], loss, st);
 }
 
 // The actor update of learn() (sac.py:229-255): a, logp = sample(actor(state), eps), q_i = critic_i(state, a) with the critics AFTER their step,
 // actor_loss = -mean(alpha * (-logp) + min(q_1, q_2)); backward through BOTH critics' action inputs and through logp into the actor; the
 // actor's Adam step; the temperature's bookkeeping rides in the seed.  The critics' parameters, gradient bucket and moments are not written.
 // -> d_action [B][A], d_logp [B], d_q [2][B] (all optional), d_stats as jh_sac_actor_seed.
-// Launches: 3 GEMM levels of the actor (the critics' heads in the first) + sample + 3 of the critics + seed (+ temperature) + 2 back through
-// the critics + d(action) + sample backward + 3 of the actor's backward + Adam = 16.
+// Launches: 3 GEMMs (ac_actor_trunk, both critics' heads in the first) + sample + 3 GEMMs (ac_actor_q) + seed (+ temperature) + 3 GEMMs back
+// through the critics (ac_actor_dact) + sample backward + 3 GEMMs of the actor's backward and Adam (ac_actor_backward) = 16.
 JH_EXPORT int jh_sacnet_actor_update(jh_sacnet* s, const float* d_x, const float* d_eps, int32_t B, float* d_action, float* d_logp, float* d_q, float* d_stats,
                                      jh_stream stream) {
   JH_ARG(s && d_x && d_eps && d_stats);
   jh_acnet* n = &s->ac;
   JH_ARG(B > 0 && B <= n->maxB);
   hipStream_t st = jh_s(stream);
-  const int H = n->H, S = n->S, A = n->A;
-  const float* P = n->ap;
-  float* G = n->ag;
+  const int A = n->A;
   float* a_out = d_action ? d_action : n->a_out;
   float* logp = d_logp ? d_logp : s->logp;
   float* q = d_q ? d_q : n->c_q[0];  // [2][B], packed
-  TGemm g[kMaxGroup];
-  int k, rc;
-  k = 0;
-  g[k++] = ac_head(n, P, AC_A_W1, AC_A_B1, d_x, B, n->a_feat, H);
-  for (int c = 0; c < 2; ++c) g[k++] = ac_c_head(n, n->cp + c * n->nC, 0, c, d_x, B);
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
-  g[0] = ac_a_l(n, P, B);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
-  g[0] = sac_a_heads(n, B);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
+  int rc;
+  if ((rc = ac_actor_trunk(n, d_x, B, 2, st))) return rc;
   if ((rc = sac_sample(B, A, 2 * A, n->a_z, n->a_z + A, d_eps, a_out, logp, st))) return rc;
-  for (int c = 0; c < 2; ++c) g[c] = ac_c_embed(n, n->cp + c * n->nC, 0, c, a_out, B);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
-  for (int c = 0; c < 2; ++c) g[c] = ac_c_l(n, n->cp + c * n->nC, 0, c, B);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
-  for (int c = 0; c < 2; ++c) g[c] = ac_c_q(n, n->cp + c * n->nC, 0, c, B, q + (size_t)c * B);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
+  if ((rc = ac_actor_q(n, a_out, B, 2, q, st))) return rc;
   if ((rc = sac_actor_seed(B, B, n->maxB, q, logp, n->dq, s->alpha, d_stats, st))) return rc;
-  // back through both critics to their action inputs: d(cat) -> da_c = d(cat_c)[:, H:] We_c
-  if ((rc = ac_critic_backward(n, B, d_x, a_out, false, 0, 2, st))) return rc;
-  for (int c = 0; c < 2; ++c)
-    g[c] = mk_gemm(B, A, H, op_dense(OP_KCONT, n->dcat + (size_t)c * n->maxB * 2 * H + H, 2 * H), op_dense(OP_XCONT, n->cp + c * n->nC + n->seg_off[AC_C_WE], A),
-                   c == 0 ? n->da : s->da2, A, TEPI_NONE);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
-  if ((rc = sac_sample_bwd((int64_t)B * A, A, 2 * A, n->da, s->da2, n->a_z, n->a_z + A, d_eps, a_out, s->alpha, s->d_raw, s->d_raw + A, st))) return rc;
-  // the actor's backward: the [2A][H] layer, l, head.l
-  g[0] = mk_gemm(2 * A, H, B, op_dense(OP_XCONT, s->d_raw, 2 * A), op_dense(OP_XCONT, n->a_h, H), G + n->seg_off[AC_A_WPI], H, TEPI_NONE, nullptr, nullptr, 0,
-                 G + n->seg_off[AC_A_BPI]);
-  g[1] = mk_gemm(B, H, 2 * A, op_dense(OP_KCONT, s->d_raw, 2 * A), op_dense(OP_XCONT, P + n->seg_off[AC_A_WPI], H), n->dah, H, TEPI_MASK, nullptr, n->a_h, H);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
-  g[0] = mk_gemm(H, H, B, op_dense(OP_XCONT, n->dah, H), op_dense(OP_XCONT, n->a_feat, H), G + n->seg_off[AC_A_WL], H, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[AC_A_BL]);
-  g[1] = mk_gemm(B, H, H, op_dense(OP_KCONT, n->dah, H), op_dense(OP_XCONT, P + n->seg_off[AC_A_WL], H), n->dafeat, H, TEPI_MASK, nullptr, n->a_feat, H);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
-  g[0] = mk_gemm(H, S, B, op_dense(OP_XCONT, n->dafeat, H), op_dense(OP_XCONT, d_x, S), G + n->seg_off[AC_A_W1], S, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[AC_A_B1]);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
-  return jh_flat_adam_step(n->nA, n->ap, n->ag, n->am, n->av, n->hyper_a, n->ticket_a, n->norm_partial, 0.f, st);
+  if ((rc = ac_actor_dact(n, B, 2, s->da2, st))) return rc;
+  if ((rc = sac_sample_bwd((int64_t)B * A, A, 2 * A, n->da, s->da2, n->a_z, n->a_z + A, d_eps, a_out, s->alpha, n->dz, n->dz + A, st))) return rc;
+  return ac_actor_backward(n, d_x, B, st);
 }

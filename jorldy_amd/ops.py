@@ -1501,12 +1501,78 @@ def td3_polyak(params, target, tau):
 
 class _ActorCriticBuckets:
     """What ACNet and SACNet share: an actor and `nc` critics in flat float32 buckets (`self.actor[kind]` of n_actor floats,
-    `self.critics[kind]` of nc * n_critic floats, critic c at c * n_critic), the segment tables `aseg` / `cseg` name -> (offset, rows, cols), and
-    export / import under the reference's state_dict keys.  Networks are named "actor", "critic1", "critic2" ("critic" = "critic1")."""
+    `self.critics[kind]` of nc * n_critic floats, critic c at c * n_critic), the segment tables `aseg` / `cseg` name -> (offset, rows, cols),
+    export / import under the reference's state_dict keys, and every native entry the two objects have in common, called as `_SYM + name`.
+    Networks are named "actor", "critic1", "critic2" ("critic" = "critic1").  A subclass names its entries' prefix `_SYM`, the actor's
+    segments `_ASEG` and buckets `AKINDS`, and the sizes its create entry takes."""
 
     _CSEG = ("head.l.weight", "head.l.bias", "e.weight", "e.bias", "l.weight", "l.bias", "q.weight", "q.bias")
-    KINDS = ("params", "target", "grads", "m", "v")
+    KINDS = AKINDS = ("params", "target", "grads", "m", "v")
     cnn = False
+
+    def __init__(self, state_size, action_size, hidden, n_critics, max_batch, device):
+        self.lib = L.load()
+        self.device = torch.device(device)
+        self.ctx = L.ctx(self.device.index)
+        self.S, self.A, self.H, self.nc, self.maxB = int(state_size), int(action_size), int(hidden), int(n_critics), int(max_batch)
+        na, ncr = C.c_int64(), C.c_int64()
+        L.check(self._fn("param_counts_for")(self.S, self.H, self.A, C.byref(na), C.byref(ncr)))
+        self.n_actor, self.n_critic = int(na.value), int(ncr.value)
+        mk = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.actor = {k: mk(self.n_actor) for k in self.AKINDS}
+        self.critics = {k: mk(self.nc * self.n_critic) for k in self.KINDS}
+        self.h = C.c_void_p()
+        L.check(self._fn("create")(self.ctx, *self._create_sizes(), *[L.ptr(self.actor[k]) for k in self.AKINDS], *[L.ptr(self.critics[k]) for k in self.KINDS],
+                                   C.byref(self.h)))
+        names = self._ASEG + self._CSEG
+        assert int(self._fn("segment_count")()) == len(names)
+        self.aseg, self.cseg = {}, {}
+        for i, name in enumerate(names):
+            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
+            L.check(self._fn("segment")(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
+            (self.aseg if i < len(self._ASEG) else self.cseg)[name] = (off.value, rows.value, cols.value)
+
+    def _fn(self, name):
+        return getattr(self.lib, self._SYM + name)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self._fn("destroy")(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def set_hyper(self, which, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
+        """which: "actor" | "critic" (one Adam for both critics)."""
+        L.check(self._fn("set_hyper")(self.h, 0 if which == "actor" else 1, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
+
+    def set_lr(self, which, lr):
+        L.check(self._fn("set_lr")(self.h, 0 if which == "actor" else 1, float(lr), L.stream_ptr()))
+
+    def sync_target(self):
+        L.check(self._fn("sync_target")(self.h, L.stream_ptr()))
+
+    def soft_update(self, tau):
+        L.check(self._fn("soft_update")(self.h, float(tau), L.stream_ptr()))
+
+    def critic_forward(self, x, action, which=0):
+        """critic_c(x, action) for every critic -> [n_critics, rows]."""
+        assert x.is_contiguous() and x.dtype == torch.float32 and action.is_contiguous() and action.dtype == torch.float32
+        rows = int(x.shape[0])
+        assert tuple(x.shape) == (rows, self.S) and tuple(action.shape) == (rows, self.A)
+        out = torch.empty(self.nc, rows, dtype=torch.float32, device=self.device)
+        L.check(self._fn("critic_forward")(self.h, int(which), L.ptr(x), L.ptr(action), rows, L.ptr(out), L.stream_ptr()))
+        return out
+
+    def _check_batch(self, x_all, action, reward, done, y, q):
+        """The critic update's inputs x_all = [state; next_state] (2B rows), action [B, A], reward, done [B] and optional outputs -> B."""
+        B = int(action.shape[0])
+        for t in (x_all, action, reward, done):
+            assert t.is_contiguous() and t.dtype == torch.float32
+        assert tuple(x_all.shape) == (2 * B, self.S) and tuple(action.shape) == (B, self.A) and reward.numel() == B and done.numel() == B
+        assert (y is None or y.numel() == B) and (q is None or q.numel() == self.nc * B)
+        return B
 
     def nets(self):
         return ("actor",) + tuple(f"critic{c + 1}" for c in range(self.nc))
@@ -1549,54 +1615,15 @@ class ACNet(_ActorCriticBuckets):
     """jh_acnet_*: a deterministic policy (network/policy.py:8-20) and one (DDPG) or two (TD3) continuous Q networks
     (network/q_network.py:23-39), each with a target copy, in flat buckets: `actor*` of n_actor floats, `critics*` of n_critics * n_critic
     floats (critic c at c * n_critic).  The critic update, the actor update (backward through critic 1's action input), the soft update
-    and the target sync are tile-engine launches plus the elementwise kernels of jh_td3.hip.  Networks are named "actor", "critic1",
+    and the target sync are tile-engine launches plus the elementwise kernels of jh_td3.hip and jh_acnet.hip.  Networks are named "actor", "critic1",
     "critic2" ("critic" = "critic1"); export / import speak the reference's state_dict keys."""
 
     _ASEG = ("head.l.weight", "head.l.bias", "l.weight", "l.bias", "pi.weight", "pi.bias")
+    _SYM = "jh_acnet_"
     kind = "actor_critic"
 
-    def __init__(self, state_size, action_size, hidden, n_critics, max_batch, device):
-        self.lib = L.load()
-        self.device = torch.device(device)
-        self.ctx = L.ctx(self.device.index)
-        self.S, self.A, self.H, self.nc, self.maxB = int(state_size), int(action_size), int(hidden), int(n_critics), int(max_batch)
-        na, ncr = C.c_int64(), C.c_int64()
-        L.check(self.lib.jh_acnet_param_counts_for(self.S, self.H, self.A, C.byref(na), C.byref(ncr)))
-        self.n_actor, self.n_critic = int(na.value), int(ncr.value)
-        mk = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.actor = {k: mk(self.n_actor) for k in self.KINDS}
-        self.critics = {k: mk(self.nc * self.n_critic) for k in self.KINDS}
-        self.h = C.c_void_p()
-        L.check(self.lib.jh_acnet_create(self.ctx, self.S, self.H, self.A, self.nc, self.maxB, *[L.ptr(self.actor[k]) for k in self.KINDS],
-                                         *[L.ptr(self.critics[k]) for k in self.KINDS], C.byref(self.h)))
-        names = self._ASEG + self._CSEG
-        assert int(self.lib.jh_acnet_segment_count()) == len(names)
-        self.aseg, self.cseg = {}, {}
-        for i, name in enumerate(names):
-            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
-            L.check(self.lib.jh_acnet_segment(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
-            (self.aseg if i < len(self._ASEG) else self.cseg)[name] = (off.value, rows.value, cols.value)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.jh_acnet_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def set_hyper(self, which, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
-        """which: "actor" | "critic" (one Adam for both critics)."""
-        L.check(self.lib.jh_acnet_set_hyper(self.h, 0 if which == "actor" else 1, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
-
-    def set_lr(self, which, lr):
-        L.check(self.lib.jh_acnet_set_lr(self.h, 0 if which == "actor" else 1, float(lr), L.stream_ptr()))
-
-    def sync_target(self):
-        L.check(self.lib.jh_acnet_sync_target(self.h, L.stream_ptr()))
-
-    def soft_update(self, tau):
-        L.check(self.lib.jh_acnet_soft_update(self.h, float(tau), L.stream_ptr()))
+    def _create_sizes(self):
+        return self.S, self.H, self.A, self.nc, self.maxB
 
     def actor_forward(self, x, which=0, out=None):
         """actor(x) -> [rows, A]; rows <= max_batch; which 0 online / 1 target."""
@@ -1607,24 +1634,11 @@ class ACNet(_ActorCriticBuckets):
         L.check(self.lib.jh_acnet_actor_forward(self.h, int(which), L.ptr(x), rows, L.ptr(out), L.stream_ptr()))
         return out
 
-    def critic_forward(self, x, action, which=0):
-        """critic_c(x, action) for every critic -> [n_critics, rows]."""
-        assert x.is_contiguous() and x.dtype == torch.float32 and action.is_contiguous() and action.dtype == torch.float32
-        rows = int(x.shape[0])
-        assert tuple(x.shape) == (rows, self.S) and tuple(action.shape) == (rows, self.A)
-        out = torch.empty(self.nc, rows, dtype=torch.float32, device=self.device)
-        L.check(self.lib.jh_acnet_critic_forward(self.h, int(which), L.ptr(x), L.ptr(action), rows, L.ptr(out), L.stream_ptr()))
-        return out
-
     def critic_update(self, x_all, action, reward, done, noise, gamma, noise_std, noise_clip, stats, y=None, q=None):
         """x_all = [state; next_state] (2B rows); noise [B, A] standard normals or None.  stats [4] = loss_1, loss_2, max_Q, mark;
         optional outputs y [B], q [n_critics, B]."""
-        B = int(action.shape[0])
-        for t in (x_all, action, reward, done):
-            assert t.is_contiguous() and t.dtype == torch.float32
-        assert tuple(x_all.shape) == (2 * B, self.S) and tuple(action.shape) == (B, self.A) and reward.numel() == B and done.numel() == B
+        B = self._check_batch(x_all, action, reward, done, y, q)
         assert noise is None or (noise.is_contiguous() and noise.dtype == torch.float32 and tuple(noise.shape) == (B, self.A))
-        assert (y is None or y.numel() == B) and (q is None or q.numel() == self.nc * B)
         L.check(self.lib.jh_acnet_critic_update(self.h, L.ptr(x_all), L.ptr(action), L.ptr(reward), L.ptr(done), L.ptr(noise), B, float(gamma), float(noise_std),
                                                 float(noise_clip), L.ptr(y), L.ptr(q), L.ptr(stats), L.stream_ptr()))
 
@@ -1725,44 +1739,14 @@ class SACNet(_ActorCriticBuckets):
 
     _ASEG = ("head.l.weight", "head.l.bias", "l.weight", "l.bias", "mu.weight", "mu.bias", "log_std.weight", "log_std.bias")
     AKINDS = ("params", "grads", "m", "v")
+    _SYM = "jh_sacnet_"
     kind = "soft_actor_critic"
 
     def __init__(self, state_size, action_size, hidden, max_batch, device):
-        self.lib = L.load()
-        self.device = torch.device(device)
-        self.ctx = L.ctx(self.device.index)
-        self.S, self.A, self.H, self.nc, self.maxB = int(state_size), int(action_size), int(hidden), 2, int(max_batch)
-        na, ncr = C.c_int64(), C.c_int64()
-        L.check(self.lib.jh_sacnet_param_counts_for(self.S, self.H, self.A, C.byref(na), C.byref(ncr)))
-        self.n_actor, self.n_critic = int(na.value), int(ncr.value)
-        mk = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.actor = {k: mk(self.n_actor) for k in self.AKINDS}
-        self.critics = {k: mk(self.nc * self.n_critic) for k in self.KINDS}
-        self.h = C.c_void_p()
-        L.check(self.lib.jh_sacnet_create(self.ctx, self.S, self.H, self.A, self.maxB, *[L.ptr(self.actor[k]) for k in self.AKINDS],
-                                          *[L.ptr(self.critics[k]) for k in self.KINDS], C.byref(self.h)))
-        names = self._ASEG + self._CSEG
-        assert int(self.lib.jh_sacnet_segment_count()) == len(names)
-        self.aseg, self.cseg = {}, {}
-        for i, name in enumerate(names):
-            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
-            L.check(self.lib.jh_sacnet_segment(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
-            (self.aseg if i < len(self._ASEG) else self.cseg)[name] = (off.value, rows.value, cols.value)
+        super().__init__(state_size, action_size, hidden, 2, max_batch, device)
 
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.jh_sacnet_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def set_hyper(self, which, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
-        """which: "actor" | "critic" (one Adam for both critics)."""
-        L.check(self.lib.jh_sacnet_set_hyper(self.h, 0 if which == "actor" else 1, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
-
-    def set_lr(self, which, lr):
-        L.check(self.lib.jh_sacnet_set_lr(self.h, 0 if which == "actor" else 1, float(lr), L.stream_ptr()))
+    def _create_sizes(self):
+        return self.S, self.H, self.A, self.maxB
 
     def set_alpha(self, log_alpha, alpha=None, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8, step=0, m=0.0, v=0.0, dynamic=True):
         """The whole temperature block; alpha None: exp(log_alpha as float32).  Synchronises."""
@@ -1784,12 +1768,6 @@ class SACNet(_ActorCriticBuckets):
         out["beta1"], out["beta2"] = (float(b) for b in h[10:14].view(np.float64))
         return out
 
-    def sync_target(self):
-        L.check(self.lib.jh_sacnet_sync_target(self.h, L.stream_ptr()))
-
-    def soft_update(self, tau):
-        L.check(self.lib.jh_sacnet_soft_update(self.h, float(tau), L.stream_ptr()))
-
     def actor_forward(self, x, which=0):
         """actor(x) -> (mu, std), each [rows, A]; rows <= max_batch.  There is no target actor."""
         assert which == 0 and x.is_contiguous() and x.device == self.device and x.dtype == torch.float32 and x.shape[1] == self.S
@@ -1798,25 +1776,12 @@ class SACNet(_ActorCriticBuckets):
         L.check(self.lib.jh_sacnet_actor_forward(self.h, L.ptr(x), rows, L.ptr(mu), L.ptr(std), L.stream_ptr()))
         return mu, std
 
-    def critic_forward(self, x, action, which=0):
-        """critic_c(x, action) for both critics -> [2, rows]."""
-        assert x.is_contiguous() and x.dtype == torch.float32 and action.is_contiguous() and action.dtype == torch.float32
-        rows = int(x.shape[0])
-        assert tuple(x.shape) == (rows, self.S) and tuple(action.shape) == (rows, self.A)
-        out = torch.empty(self.nc, rows, dtype=torch.float32, device=self.device)
-        L.check(self.lib.jh_sacnet_critic_forward(self.h, int(which), L.ptr(x), L.ptr(action), rows, L.ptr(out), L.stream_ptr()))
-        return out
-
     def critic_update(self, x_all, action, reward, done, eps, gamma, stats, y=None, q=None, a_next=None, logp_next=None):
         """x_all = [state; next_state] (2B rows); eps [B, A] standard normals.  stats [4] = loss_1, loss_2, max_Q, mark; optional outputs
         y [B], q [2, B], a_next [B, A], logp_next [B]."""
-        B = int(action.shape[0])
-        for t in (x_all, action, reward, done, eps):
-            assert t.is_contiguous() and t.dtype == torch.float32
-        assert tuple(x_all.shape) == (2 * B, self.S) and tuple(action.shape) == (B, self.A) and reward.numel() == B and done.numel() == B
-        assert tuple(eps.shape) == (B, self.A) and stats.numel() >= 4
-        assert (y is None or y.numel() == B) and (q is None or q.numel() == 2 * B) and (a_next is None or a_next.numel() == B * self.A)
-        assert logp_next is None or logp_next.numel() == B
+        B = self._check_batch(x_all, action, reward, done, y, q)
+        assert eps.is_contiguous() and eps.dtype == torch.float32 and tuple(eps.shape) == (B, self.A) and stats.numel() >= 4
+        assert (a_next is None or a_next.numel() == B * self.A) and (logp_next is None or logp_next.numel() == B)
         L.check(self.lib.jh_sacnet_critic_update(self.h, L.ptr(x_all), L.ptr(action), L.ptr(reward), L.ptr(done), L.ptr(eps), B, float(gamma), L.ptr(y), L.ptr(q),
                                                  L.ptr(a_next), L.ptr(logp_next), L.ptr(stats), L.stream_ptr()))
 
