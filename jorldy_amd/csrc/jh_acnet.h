@@ -3,44 +3,34 @@
 // Polyak average, the object's core, the critics' forward, and the pieces the two critic updates and the two actor updates are made of.
 // jh_sacnet embeds a jh_acnet and drives these with it.
 #pragma once
-#include "jh_fused.h"
-#include "jh_tgemm.h"
+#include "jh_netcore.h"
 
 enum { AC_A_W1, AC_A_B1, AC_A_WL, AC_A_BL, AC_A_WPI, AC_A_BPI, AC_C_W1, AC_C_B1, AC_C_WE, AC_C_BE, AC_C_WL, AC_C_BL, AC_C_WQ, AC_C_BQ, AC_SEG_COUNT };
 
 struct jh_acnet {
-  jh_ctx* ctx = nullptr;
+  NetCore core;
+  FlatOptim opt_a, opt_c;  // the actor's Adam, the critics' (one block and one launch for all critics)
   int S = 0, H = 0, A = 0, nc = 0, maxB = 0;
   int64_t seg_off[AC_SEG_COUNT] = {0};  // actor segments: offsets in the actor bucket; critic segments: offsets inside ONE critic
   int seg_rows[AC_SEG_COUNT] = {0}, seg_cols[AC_SEG_COUNT] = {0};
   int64_t nA = 0, nC = 0;  // floats of the actor bucket / of one critic (the critic buckets hold nc of them back to back)
   float *ap = nullptr, *at = nullptr, *ag = nullptr, *am = nullptr, *av = nullptr;  // at == nullptr: no target actor
   float *cp = nullptr, *ct = nullptr, *cg = nullptr, *cm = nullptr, *cv = nullptr;
-  float *hyper_a = nullptr, *hyper_c = nullptr, *norm_partial = nullptr;
-  unsigned *ticket_a = nullptr, *ticket_c = nullptr;
   // actor activations [maxB] rows: feat, h, z (the head's output, `head` columns), a
   float *a_feat = nullptr, *a_h = nullptr, *a_z = nullptr, *a_out = nullptr;
   // critic activations, set 0 = online, 1 = target: cat [nc][maxB][2H] = [head(s) | relu(e(a))], h [nc][maxB][H], q [nc][maxB]
   float *c_cat[2] = {nullptr, nullptr}, *c_h[2] = {nullptr, nullptr}, *c_q[2] = {nullptr, nullptr};
   // backward: dq [nc][maxB], dh [nc][maxB][H], dcat [nc][maxB][2H], da [maxB][A], dz [maxB][head], d(actor h) / d(actor feat) [maxB][H]
   float *dq = nullptr, *dh = nullptr, *dcat = nullptr, *da = nullptr, *dz = nullptr, *dah = nullptr, *dafeat = nullptr;
-  float* ws = nullptr;
-  size_t ws_floats = 0;
-  unsigned* cnt = nullptr;
-  int cnt_slots = 0;
-  std::vector<void*> owned;
 };
 
 constexpr int kMaxLossRows = 1 << 20;
 
 // ---- the object's core (jh_acnet.hip).  head: the columns of the actor's last layer, A (pi) or 2A ([mu | log_std]).
 int ac_layout(jh_acnet* n, int32_t S, int32_t H, int32_t A, int32_t head, int32_t nc, int32_t max_batch);
-int ac_alloc(jh_acnet* n, void** out, size_t bytes, bool zero);
 // layout, the caller's buckets {params, target, grads, m, v}, every buffer above, workspace, counters, both hyper blocks.  On failure the
-// caller releases: ac_release frees what the object owns (after the device has drained), the object itself stays the caller's.
+// caller releases: core_release(&n->core) frees what the object owns (after the device has drained), the object itself stays the caller's.
 int ac_init(jh_acnet* n, jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int32_t head, int32_t nc, int32_t max_batch, float* const actor[5], float* const critics[5]);
-void ac_release(jh_acnet* n);
-int ac_tgemm(jh_acnet* n, TGemm* probs, int ng, hipStream_t st);
 
 // ---- layer builders of the actor's trunk.  P: the actor's parameter bucket (online or target)
 static inline TGemm ac_head(const jh_acnet* n, const float* P, int w, int b, const float* x, int rows, float* out, int ldc) {

@@ -98,7 +98,7 @@ int ac_critic_backward(jh_acnet* n, int B, const float* d_x, const float* d_acti
       g[k++] = mk_gemm(1, H, B, op_dense(OP_XCONT, dq, 1), op_dense(OP_XCONT, ac_ch(n, 0, c), H), G + n->seg_off[AC_C_WQ], H, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[AC_C_BQ]);
     g[k++] = mk_gemm(B, H, 1, op_dense(OP_KCONT, dq, 1), op_dense(OP_XCONT, P + n->seg_off[AC_C_WQ], H), dh, H, TEPI_MASK, nullptr, ac_ch(n, 0, c), H);
   }
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, k, st))) return rc;
   k = 0;
   for (int c = c0; c < c1; ++c) {
     const float* P = n->cp + c * n->nC;
@@ -113,7 +113,7 @@ int ac_critic_backward(jh_acnet* n, int B, const float* d_x, const float* d_acti
     g[k++] = mk_gemm(B, 2 * H - o, H, op_dense(OP_KCONT, dh, H), op_dense(OP_XCONT, P + n->seg_off[AC_C_WL] + o, 2 * H), dcat + o, 2 * H, TEPI_MASK, nullptr,
                      ac_cat(n, 0, c) + o, 2 * H);
   }
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, k, st))) return rc;
   if (!weights) return JH_OK;
   k = 0;
   for (int c = c0; c < c1; ++c) {
@@ -123,7 +123,7 @@ int ac_critic_backward(jh_acnet* n, int B, const float* d_x, const float* d_acti
     g[k++] = mk_gemm(H, A, B, op_dense(OP_XCONT, dcat + H, 2 * H), op_dense(OP_XCONT, d_action, A), G + n->seg_off[AC_C_WE], A, TEPI_NONE, nullptr, nullptr, 0,
                      G + n->seg_off[AC_C_BE]);
   }
-  return ac_tgemm(n, g, k, st);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, k, st);
 }
 
 }  // namespace
@@ -148,85 +148,40 @@ int ac_layout(jh_acnet* n, int32_t S, int32_t H, int32_t A, int32_t head, int32_
   seg(AC_A_W1, H, S); seg(AC_A_B1, 1, H); seg(AC_A_WL, H, H); seg(AC_A_BL, 1, H); seg(AC_A_WPI, head, H); seg(AC_A_BPI, 1, head);
   seg(AC_C_W1, H, S); seg(AC_C_B1, 1, H); seg(AC_C_WE, H, A); seg(AC_C_BE, 1, H); seg(AC_C_WL, H, 2 * H); seg(AC_C_BL, 1, H);
   seg(AC_C_WQ, 1, H); seg(AC_C_BQ, 1, 1);
-  int64_t off = 0;
-  for (int i = AC_A_W1; i <= AC_A_BPI; ++i) {
-    n->seg_off[i] = off;
-    off = (off + (int64_t)n->seg_rows[i] * n->seg_cols[i] + 3) & ~(int64_t)3;
-  }
-  n->nA = off;
-  off = 0;
-  for (int i = AC_C_W1; i <= AC_C_BQ; ++i) {
-    n->seg_off[i] = off;
-    off = (off + (int64_t)n->seg_rows[i] * n->seg_cols[i] + 3) & ~(int64_t)3;
-  }
-  n->nC = off;
-  return JH_OK;
-}
-
-int ac_alloc(jh_acnet* n, void** out, size_t bytes, bool zero) {
-  if (bytes == 0) bytes = 16;
-  hipError_t e = hipMalloc(out, bytes);
-  if (e != hipSuccess) return jh_fail(JH_ERR_NOMEM, "jh_acnet: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  n->owned.push_back(*out);
-  if (zero) JH_HIP(hipMemset(*out, 0, bytes));
+  n->nA = seg_pack(n->seg_rows, n->seg_cols, AC_A_W1, AC_C_W1, n->seg_off);
+  n->nC = seg_pack(n->seg_rows, n->seg_cols, AC_C_W1, AC_SEG_COUNT, n->seg_off);
   return JH_OK;
 }
 
 int ac_init(jh_acnet* n, jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int32_t head, int32_t nc, int32_t max_batch, float* const actor[5], float* const critics[5]) {
   JH_HIP(hipSetDevice(ctx->device));
-  n->ctx = ctx;
+  n->core.ctx = ctx;
   int rc = ac_layout(n, S, H, A, head, nc, max_batch);
   if (rc) return rc;
   n->ap = actor[0]; n->at = actor[1]; n->ag = actor[2]; n->am = actor[3]; n->av = actor[4];
   n->cp = critics[0]; n->ct = critics[1]; n->cg = critics[2]; n->cm = critics[3]; n->cv = critics[4];
   const size_t B = (size_t)max_batch, NB = (size_t)nc * B;
-  auto A4 = [&](float** p, size_t floats, bool zero = true) { if (!rc) rc = ac_alloc(n, (void**)p, floats * sizeof(float), zero); };
-  A4(&n->hyper_a, JH_HY_FLOATS); A4(&n->hyper_c, JH_HY_FLOATS);
-  A4(&n->norm_partial, 256);
-  if (!rc) rc = ac_alloc(n, (void**)&n->ticket_a, 2048, true);  // jh_rb_optim_kernel: eight counters 128 bytes apart + the one on top of them
-  if (!rc) rc = ac_alloc(n, (void**)&n->ticket_c, 2048, true);
+  auto A4 = [&](float** p, size_t floats) { if (!rc) rc = core_alloc(&n->core, "jh_acnet", (void**)p, floats * sizeof(float), true); };
+  rc = optim_init(&n->core, "jh_acnet", &n->opt_a);
+  if (!rc) rc = optim_init(&n->core, "jh_acnet", &n->opt_c);
   A4(&n->a_feat, B * H); A4(&n->a_h, B * H); A4(&n->a_z, B * head); A4(&n->a_out, B * A);
   for (int s = 0; s < 2; ++s) {
     A4(&n->c_cat[s], NB * 2 * H); A4(&n->c_h[s], NB * H); A4(&n->c_q[s], NB);
   }
   A4(&n->dq, NB); A4(&n->dh, NB * H); A4(&n->dcat, NB * 2 * H); A4(&n->da, B * A); A4(&n->dz, B * head); A4(&n->dah, B * H); A4(&n->dafeat, B * H);
-  n->ws_floats = (size_t)8 << 20;  // 32 MB of split-K partials
-  A4(&n->ws, n->ws_floats, false);
-  n->cnt_slots = 8192;
-  if (!rc) rc = ac_alloc(n, (void**)&n->cnt, sizeof(unsigned) * (size_t)n->cnt_slots * kTgemmCntStride, true);
-  if (rc) return rc;
-  float hy[JH_HY_FLOATS];
-  jh_hyper_fill(hy, 1e-3, 0.9, 0.999, 1e-8, 0.0);
-  JH_HIP(hipMemcpy(n->hyper_a, hy, sizeof(hy), hipMemcpyHostToDevice));
-  JH_HIP(hipMemcpy(n->hyper_c, hy, sizeof(hy), hipMemcpyHostToDevice));
-  JH_HIP(hipDeviceSynchronize());
-  return JH_OK;
-}
-
-void ac_release(jh_acnet* n) {
-  if (n->ctx) {
-    (void)hipSetDevice(n->ctx->device);
-    (void)hipDeviceSynchronize();
-  }
-  for (void* p : n->owned) (void)hipFree(p);
-  n->owned.clear();
-}
-
-int ac_tgemm(jh_acnet* n, TGemm* probs, int ng, hipStream_t st) {
-  TGemmWorkspace w;
-  w.ws = n->ws; w.ws_floats = n->ws_floats; w.cnt = n->cnt; w.cnt_slots = n->cnt_slots;
-  return jh_tgemm_launch(w, "jh_tgemm_dense", probs, ng, st);
+  if (!rc) rc = core_workspace(&n->core, "jh_acnet", (size_t)8 << 20, 8192);  // 32 MB of split-K partials
+  return rc ? rc : core_drain();
 }
 
 // ---------------------------------------------------------------------------------- the entries both objects answer with the core
 // which: 0 the actor's optimizer, 1 the critics' (one block and one launch for all critics: td3.py:95-112 and sac.py:136-140 give them the same settings)
 JH_EXPORT int jh_acnet_set_hyper(jh_acnet* n, int32_t which, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream) {
   JH_ARG(n && (which == 0 || which == 1));
-  return jh_hyper_upload(n->ctx, which == 0 ? n->hyper_a : n->hyper_c, lr, beta1, beta2, eps, step, 0, jh_s(stream));
+  return jh_hyper_upload(n->core.ctx, which == 0 ? n->opt_a.hyper : n->opt_c.hyper, lr, beta1, beta2, eps, step, 0, jh_s(stream));
 }
 JH_EXPORT int jh_acnet_set_lr(jh_acnet* n, int32_t which, double lr, jh_stream stream) {
   JH_ARG(n && (which == 0 || which == 1));
-  return jh_hyper_upload_lr(n->ctx, which == 0 ? n->hyper_a : n->hyper_c, lr, jh_s(stream));
+  return jh_hyper_upload_lr(n->core.ctx, which == 0 ? n->opt_a.hyper : n->opt_c.hyper, lr, jh_s(stream));
 }
 JH_EXPORT int jh_acnet_sync_target(jh_acnet* n, jh_stream stream) {
   JH_ARG(n != nullptr);
@@ -245,11 +200,11 @@ int ac_actor_forward(jh_acnet* n, const float* P, const float* d_x, int rows, hi
   TGemm g[1];
   int rc;
   g[0] = ac_head(n, P, AC_A_W1, AC_A_B1, d_x, rows, n->a_feat, n->H);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 1, st))) return rc;
   g[0] = ac_a_l(n, P, rows);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 1, st))) return rc;
   g[0] = ac_a_pi(n, P, rows);
-  return ac_tgemm(n, g, 1, st);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, 1, st);
 }
 
 // critic_c(x, a) for every critic -> d_q [n_critics][rows]; which 0 online / 1 target
@@ -265,11 +220,11 @@ JH_EXPORT int jh_acnet_critic_forward(jh_acnet* n, int32_t which, const float* d
     g[2 * c] = ac_c_head(n, base + c * n->nC, which, c, d_x, rows);
     g[2 * c + 1] = ac_c_embed(n, base + c * n->nC, which, c, d_action, rows);
   }
-  if ((rc = ac_tgemm(n, g, 2 * nc, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 2 * nc, st))) return rc;
   for (int c = 0; c < nc; ++c) g[c] = ac_c_l(n, base + c * n->nC, which, c, rows);
-  if ((rc = ac_tgemm(n, g, nc, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, nc, st))) return rc;
   for (int c = 0; c < nc; ++c) g[c] = ac_c_q(n, base + c * n->nC, which, c, rows, d_q + (size_t)c * rows);
-  return ac_tgemm(n, g, nc, st);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, nc, st);
 }
 
 // ---------------------------------------------------------------------------------- the critic update
@@ -285,17 +240,17 @@ int ac_critic_front(jh_acnet* n, const float* actor, const float* d_x, const flo
   g[k++] = ac_head(n, actor, AC_A_W1, AC_A_B1, xn, B, n->a_feat, n->H);
   for (int c = 0; c < nc; ++c) g[k++] = ac_c_head(n, n->ct + c * n->nC, 1, c, xn, B);
   for (int c = 0; c < nc; ++c) g[k++] = ac_c_head(n, n->cp + c * n->nC, 0, c, xs, B);
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, k, st))) return rc;
   // 2: the policy's l, the online critics' e(a)
   k = 0;
   g[k++] = ac_a_l(n, actor, B);
   for (int c = 0; c < nc; ++c) g[k++] = ac_c_embed(n, n->cp + c * n->nC, 0, c, d_action, B);
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, k, st))) return rc;
   // 3: the policy's last layer, the online critics' l
   k = 0;
   g[k++] = ac_a_pi(n, actor, B);
   for (int c = 0; c < nc; ++c) g[k++] = ac_c_l(n, n->cp + c * n->nC, 0, c, B);
-  return ac_tgemm(n, g, k, st);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, k, st);
 }
 
 int ac_critic_back(jh_acnet* n, const float* d_x, const float* d_action, int B, const float* a_next, float* q_on, CriticLossArgs loss, hipStream_t st) {
@@ -306,17 +261,17 @@ int ac_critic_back(jh_acnet* n, const float* d_x, const float* d_action, int B, 
   k = 0;
   for (int c = 0; c < nc; ++c) g[k++] = ac_c_embed(n, n->ct + c * n->nC, 1, c, a_next, B);
   for (int c = 0; c < nc; ++c) g[k++] = ac_c_q(n, n->cp + c * n->nC, 0, c, B, q_on + (size_t)c * B);
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, k, st))) return rc;
   // 5, 6: the target critics' l and q
   for (int c = 0; c < nc; ++c) g[c] = ac_c_l(n, n->ct + c * n->nC, 1, c, B);
-  if ((rc = ac_tgemm(n, g, nc, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, nc, st))) return rc;
   for (int c = 0; c < nc; ++c) g[c] = ac_c_q(n, n->ct + c * n->nC, 1, c, B, n->c_q[1] + (size_t)c * B);
-  if ((rc = ac_tgemm(n, g, nc, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, nc, st))) return rc;
   // loss: q and q' are packed [nc][B]; the gradient of critic c goes where the backward reads it, at c * maxB
   loss.B = B; loss.n = nc; loss.gstride = n->maxB; loss.q = q_on; loss.qn = n->c_q[1]; loss.grad = n->dq;
   if ((rc = ac_critic_loss(loss, st))) return rc;
   if ((rc = ac_critic_backward(n, B, d_x, d_action, true, 0, nc, st))) return rc;
-  return jh_flat_adam_step(n->nC * nc, n->cp, n->cg, n->cm, n->cv, n->hyper_c, n->ticket_c, n->norm_partial, 0.f, st);
+  return jh_flat_adam_step(n->nC * nc, n->cp, n->cg, n->cm, n->cv, n->opt_c.hyper, n->opt_c.ticket, n->core.norm_partial, 0.f, st);
 }
 
 // ---------------------------------------------------------------------------------- the actor update
@@ -326,22 +281,22 @@ int ac_actor_trunk(jh_acnet* n, const float* d_x, int B, int ncq, hipStream_t st
   int k = 0, rc;
   g[k++] = ac_head(n, n->ap, AC_A_W1, AC_A_B1, d_x, B, n->a_feat, n->H);
   for (int c = 0; c < ncq; ++c) g[k++] = ac_c_head(n, n->cp + c * n->nC, 0, c, d_x, B);
-  if ((rc = ac_tgemm(n, g, k, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, k, st))) return rc;
   g[0] = ac_a_l(n, n->ap, B);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 1, st))) return rc;
   g[0] = ac_a_pi(n, n->ap, B);
-  return ac_tgemm(n, g, 1, st);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, 1, st);
 }
 
 int ac_actor_q(jh_acnet* n, const float* action, int B, int ncq, float* q, hipStream_t st) {
   TGemm g[2];
   int rc;
   for (int c = 0; c < ncq; ++c) g[c] = ac_c_embed(n, n->cp + c * n->nC, 0, c, action, B);
-  if ((rc = ac_tgemm(n, g, ncq, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, ncq, st))) return rc;
   for (int c = 0; c < ncq; ++c) g[c] = ac_c_l(n, n->cp + c * n->nC, 0, c, B);
-  if ((rc = ac_tgemm(n, g, ncq, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, ncq, st))) return rc;
   for (int c = 0; c < ncq; ++c) g[c] = ac_c_q(n, n->cp + c * n->nC, 0, c, B, q + (size_t)c * B);
-  return ac_tgemm(n, g, ncq, st);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, ncq, st);
 }
 
 // back through the critics to their action inputs: d(cat) -> da_c = d(cat_c)[:, H:] We_c
@@ -353,7 +308,7 @@ int ac_actor_dact(jh_acnet* n, int B, int ncq, float* da2, hipStream_t st) {
   for (int c = 0; c < ncq; ++c)
     g[c] = mk_gemm(B, A, H, op_dense(OP_KCONT, n->dcat + (size_t)c * n->maxB * 2 * H + H, 2 * H), op_dense(OP_XCONT, n->cp + c * n->nC + n->seg_off[AC_C_WE], A),
                    c == 0 ? n->da : da2, A, TEPI_NONE);
-  return ac_tgemm(n, g, ncq, st);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, ncq, st);
 }
 
 // the actor's backward from dz [B][head]: the last layer, l, head.l; then its Adam
@@ -365,11 +320,11 @@ int ac_actor_backward(jh_acnet* n, const float* d_x, int B, hipStream_t st) {
   int rc;
   g[0] = mk_gemm(W, H, B, op_dense(OP_XCONT, n->dz, W), op_dense(OP_XCONT, n->a_h, H), G + n->seg_off[AC_A_WPI], H, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[AC_A_BPI]);
   g[1] = mk_gemm(B, H, W, op_dense(OP_KCONT, n->dz, W), op_dense(OP_XCONT, P + n->seg_off[AC_A_WPI], H), n->dah, H, TEPI_MASK, nullptr, n->a_h, H);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 2, st))) return rc;
   g[0] = mk_gemm(H, H, B, op_dense(OP_XCONT, n->dah, H), op_dense(OP_XCONT, n->a_feat, H), G + n->seg_off[AC_A_WL], H, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[AC_A_BL]);
   g[1] = mk_gemm(B, H, H, op_dense(OP_KCONT, n->dah, H), op_dense(OP_XCONT, P + n->seg_off[AC_A_WL], H), n->dafeat, H, TEPI_MASK, nullptr, n->a_feat, H);
-  if ((rc = ac_tgemm(n, g, 2, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 2, st))) return rc;
   g[0] = mk_gemm(H, S, B, op_dense(OP_XCONT, n->dafeat, H), op_dense(OP_XCONT, d_x, S), G + n->seg_off[AC_A_W1], S, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[AC_A_B1]);
-  if ((rc = ac_tgemm(n, g, 1, st))) return rc;
-  return jh_flat_adam_step(n->nA, n->ap, n->ag, n->am, n->av, n->hyper_a, n->ticket_a, n->norm_partial, 0.f, st);
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 1, st))) return rc;
+  return jh_flat_adam_step(n->nA, n->ap, n->ag, n->am, n->av, n->opt_a.hyper, n->opt_a.ticket, n->core.norm_partial, 0.f, st);
 }

@@ -159,8 +159,10 @@ struct jh_control;
 void jh_control_obs_rows(const jh_control* e, int r0, int r1, float* h_obs);
 void jh_control_step_rows(jh_control* e, int r0, int r1, const float* h_action, float* h_next_obs, float* h_reward, uint8_t* h_done);
 
+struct NetCore;
 struct jh_pponet {
   jh_ctx* ctx = nullptr;
+  NetCore* core = nullptr;  // every allocation below and the tile engine's workspace (jh_netcore.h)
   int S = 0, H = 0, A = 0, cont = 0, max_rows = 0;
   int n_out = 0;  // head outputs: A + 1 (discrete) | 2 A + 1 (continuous)
   int gld = 8;    // row width of g_all: 8, or n_out rounded up to 4 beyond 8 outputs (separate-call / tiled paths only)
@@ -190,10 +192,6 @@ struct jh_pponet {
   float* upd_ws = nullptr;    // jh_pponet_ppo_update_rows: raw heads, their gradients, the second critic branch, loss partials, {w1, w2}, ticket
   size_t upd_floats = 0;
   float* xg = nullptr;        // [max_rows][S] gathered observation rows (B operand of dW1 on the tiled engine)
-  float* tg_ws = nullptr;
-  size_t tg_ws_floats = 0;
-  unsigned* tg_cnt = nullptr;
-  int tg_cnt_slots = 0;
 };
 
 // ---------------------------------------------------------------- host-side action sampling (PPO.act, ppo.py:55-69)

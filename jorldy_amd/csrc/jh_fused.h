@@ -182,12 +182,13 @@ int jh_c51_run(jh_ctx* ctx, C51Args a, const C51Duel* duel, const PerDeltaArgs* 
 
 // ---------------------------------------------------------------------------------------------- Adam on flat buckets
 // jh_rbnet.hip's optimizer kernels ([global-norm clip,] torch.optim.Adam step, step counter advanced inside) for any owner of flat fp32
-// parameter / gradient / moment buckets (jh_iqn.hip).  hyper: JH_HY_FLOATS floats; ticket: 2048 zeroed bytes; norm_partial: 256 floats.
+// parameter / gradient / moment buckets (jh_iqn.hip, jh_acnet.hip).  hyper and ticket: a FlatOptim, norm_partial: its core's (jh_netcore.h).
 int jh_flat_adam_step(int64_t n_params, float* p, float* g, float* m, float* v, float* hyper, unsigned* ticket, float* norm_partial, float max_norm,
                       hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------- optimizer hyper block
-// For any owner of a JH_HY_FLOATS device block (jh_rbnet.hip, jh_iqn.hip): the values ride in a pinned slab, one device-side copy on the stream.
+// Defined in jh_netcore.hip for the owners of a FlatOptim's hyper block (jh_rbnet.hip, jh_iqn.hip, jh_acnet.hip): the values ride in a pinned slab,
+// one device-side copy on the stream.
 // jh_hyper_upload writes the whole block (the step counter too; `centered`: the JH_HY_BC1 word, RMSprop's flag), jh_hyper_upload_lr only lr.
 int jh_hyper_upload(jh_ctx* ctx, float* d_hyper, double lr, double beta1, double beta2, double eps, int64_t step, int centered, hipStream_t st);
 int jh_hyper_upload_lr(jh_ctx* ctx, float* d_hyper, double lr, hipStream_t st);

@@ -6,8 +6,7 @@
 // elementwise steps between them: cosine features, the Hadamard product and its backward.  The loss and acting entries jh_iqn_loss /
 // jh_iqn_act are the sample-major instantiations of the quantile family's kernels in jh_qr.hip.
 // No floating-point atomics: every sum has a fixed order, so two runs (and a graph replay) give the same bits.
-#include "jh_fused.h"
-#include "jh_tgemm.h"
+#include "jh_netcore.h"
 
 namespace {
 
@@ -95,25 +94,18 @@ static int iqn_hadamard_bwd(int B, int N, int H, const float* dem, const float* 
 enum { IQ_W1, IQ_B1, IQ_WSE, IQ_BSE, IQ_WSA, IQ_BSA, IQ_WL1, IQ_BL1, IQ_WL2, IQ_BL2, IQ_WQ, IQ_BQ, IQ_SEG_COUNT };
 
 struct jh_iqnnet {
-  jh_ctx* ctx = nullptr;
+  NetCore core;
+  FlatOptim opt;
   int S = 0, H = 0, E = 0, N = 0, A = 0, maxB = 0;
   int64_t seg_off[IQ_SEG_COUNT] = {0};
   int seg_rows[IQ_SEG_COUNT] = {0}, seg_cols[IQ_SEG_COUNT] = {0};
   int64_t n_params = 0;
   float *params = nullptr, *target = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr;
-  float* hyper = nullptr;
-  float* norm_partial = nullptr;
-  unsigned* ticket = nullptr;
   // activations of up to three forwards, rows [online: 2 maxB | target: maxB] (x N for the per-sample ones)
   float *feat = nullptr, *psi = nullptr, *cosf_ = nullptr, *phi = nullptr, *emb = nullptr, *h1 = nullptr, *h2 = nullptr;
   float *dA = nullptr, *dB = nullptr, *dpsi = nullptr, *dfeat = nullptr;  // backward: [maxB * N][H] x 2, [maxB][H] x 2
-  float* ws = nullptr;
-  size_t ws_floats = 0;
-  unsigned* cnt = nullptr;
-  int cnt_slots = 0;
   const float* last_x = nullptr;  // state rows of the last learn_forward (the head's weight gradient reads them again)
   int last_B = 0;
-  std::vector<void*> owned;
 };
 
 static int iq_layout(jh_iqnnet* n, int32_t S, int32_t H, int32_t E, int32_t N, int32_t A, int32_t max_batch) {
@@ -128,28 +120,8 @@ static int iq_layout(jh_iqnnet* n, int32_t S, int32_t H, int32_t E, int32_t N, i
   seg(IQ_WL1, H, H); seg(IQ_BL1, 1, H);
   seg(IQ_WL2, H, H); seg(IQ_BL2, 1, H);
   seg(IQ_WQ, A, H); seg(IQ_BQ, 1, A);
-  int64_t off = 0;
-  for (int i = 0; i < IQ_SEG_COUNT; ++i) {
-    n->seg_off[i] = off;
-    off = (off + (int64_t)n->seg_rows[i] * n->seg_cols[i] + 3) & ~(int64_t)3;
-  }
-  n->n_params = off;
+  n->n_params = seg_pack(n->seg_rows, n->seg_cols, 0, IQ_SEG_COUNT, n->seg_off);
   return JH_OK;
-}
-
-static int iq_alloc(jh_iqnnet* n, void** out, size_t bytes, bool zero) {
-  if (bytes == 0) bytes = 16;
-  hipError_t e = hipMalloc(out, bytes);
-  if (e != hipSuccess) return jh_fail(JH_ERR_NOMEM, "jh_iqnnet: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  n->owned.push_back(*out);
-  if (zero) JH_HIP(hipMemset(*out, 0, bytes));
-  return JH_OK;
-}
-
-static int iq_tgemm(jh_iqnnet* n, TGemm* probs, int ng, hipStream_t st) {
-  TGemmWorkspace w;
-  w.ws = n->ws; w.ws_floats = n->ws_floats; w.cnt = n->cnt; w.cnt_slots = n->cnt_slots;
-  return jh_tgemm_launch(w, "jh_tgemm_dense", probs, ng, st);
 }
 
 JH_EXPORT int64_t jh_iqnnet_param_count_for(int32_t S, int32_t H, int32_t E, int32_t N, int32_t A) {
@@ -163,7 +135,7 @@ JH_EXPORT int jh_iqnnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t E, int
   JH_ARG(ctx && out && d_params && d_target && d_grads && d_m && d_v);
   JH_HIP(hipSetDevice(ctx->device));
   jh_iqnnet* n = new jh_iqnnet();
-  n->ctx = ctx;
+  n->core.ctx = ctx;
   int rc = iq_layout(n, S, H, E, N, A, max_batch);
   if (rc) {
     delete n;
@@ -171,52 +143,40 @@ JH_EXPORT int jh_iqnnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t E, int
   }
   n->params = d_params; n->target = d_target; n->grads = d_grads; n->m = d_m; n->v = d_v;
   const size_t R3 = 3 * (size_t)max_batch, RN = R3 * N, BN = (size_t)max_batch * N;
-  auto A4 = [&](float** p, size_t floats, bool zero = true) { if (!rc) rc = iq_alloc(n, (void**)p, floats * sizeof(float), zero); };
-  A4(&n->hyper, JH_HY_FLOATS);
-  A4(&n->norm_partial, 256);
-  if (!rc) rc = iq_alloc(n, (void**)&n->ticket, 2048, true);  // jh_rb_optim_kernel: eight counters 128 bytes apart + the one on top of them
+  auto A4 = [&](float** p, size_t floats) { if (!rc) rc = core_alloc(&n->core, "jh_iqnnet", (void**)p, floats * sizeof(float), true); };
+  rc = optim_init(&n->core, "jh_iqnnet", &n->opt);
   A4(&n->feat, R3 * H); A4(&n->psi, R3 * H);
   A4(&n->cosf_, RN * E); A4(&n->phi, RN * H); A4(&n->emb, RN * H); A4(&n->h1, RN * H); A4(&n->h2, RN * H);
   A4(&n->dA, BN * H); A4(&n->dB, BN * H); A4(&n->dpsi, (size_t)max_batch * H); A4(&n->dfeat, (size_t)max_batch * H);
-  n->ws_floats = (size_t)8 << 20;  // 32 MB of split-K partials
-  A4(&n->ws, n->ws_floats, false);
-  n->cnt_slots = 8192;
-  if (!rc) rc = iq_alloc(n, (void**)&n->cnt, sizeof(unsigned) * (size_t)n->cnt_slots * kTgemmCntStride, true);
+  if (!rc) rc = core_workspace(&n->core, "jh_iqnnet", (size_t)8 << 20, 8192);  // 32 MB of split-K partials
+  if (!rc) rc = core_drain();
   if (rc) {
-    for (void* p : n->owned) (void)hipFree(p);
+    core_release(&n->core);
     delete n;
     return rc;
   }
-  float hy[JH_HY_FLOATS];
-  jh_hyper_fill(hy, 1e-3, 0.9, 0.999, 1e-8, 0.0);
-  JH_HIP(hipMemcpy(n->hyper, hy, sizeof(hy), hipMemcpyHostToDevice));
-  JH_HIP(hipDeviceSynchronize());
   *out = n;
   return JH_OK;
 }
 
 JH_EXPORT void jh_iqnnet_destroy(jh_iqnnet* n) {
   if (!n) return;
-  (void)hipSetDevice(n->ctx->device);
-  (void)hipDeviceSynchronize();
-  for (void* p : n->owned) (void)hipFree(p);
+  core_release(&n->core);
   delete n;
 }
 
 JH_EXPORT int32_t jh_iqnnet_segment_count(void) { return IQ_SEG_COUNT; }
 JH_EXPORT int jh_iqnnet_segment(const jh_iqnnet* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols) {
-  JH_ARG(n && i >= 0 && i < IQ_SEG_COUNT && offset && rows && cols);
-  *offset = n->seg_off[i]; *rows = n->seg_rows[i]; *cols = n->seg_cols[i];
-  return JH_OK;
+  return seg_query(n, IQ_SEG_COUNT, i, offset, rows, cols);
 }
 
 JH_EXPORT int jh_iqnnet_set_hyper(jh_iqnnet* n, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream) {
   JH_ARG(n != nullptr);
-  return jh_hyper_upload(n->ctx, n->hyper, lr, beta1, beta2, eps, step, 0, jh_s(stream));
+  return jh_hyper_upload(n->core.ctx, n->opt.hyper, lr, beta1, beta2, eps, step, 0, jh_s(stream));
 }
 JH_EXPORT int jh_iqnnet_set_lr(jh_iqnnet* n, double lr, jh_stream stream) {
   JH_ARG(n != nullptr);
-  return jh_hyper_upload_lr(n->ctx, n->hyper, lr, jh_s(stream));
+  return jh_hyper_upload_lr(n->core.ctx, n->opt.hyper, lr, jh_s(stream));
 }
 JH_EXPORT int jh_iqnnet_sync_target(jh_iqnnet* n, jh_stream stream) {
   JH_ARG(n != nullptr);
@@ -243,13 +203,13 @@ static int iq_forward(jh_iqnnet* n, const IqJob* jobs, int nj, const float* d_ta
     g[j] = mk_gemm(J.rows, H, S, op_dense(OP_KCONT, J.x, S), op_dense(OP_KCONT, J.P + n->seg_off[IQ_W1], S), n->feat + (size_t)J.row0 * H, H,
                    TEPI_BIAS_RELU, J.P + n->seg_off[IQ_B1]);
   }
-  if ((rc = iq_tgemm(n, g, nj, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, nj, st))) return rc;
   for (int j = 0; j < nj; ++j) {
     const IqJob& J = jobs[j];
     g[j] = mk_gemm(J.rows, H, H, op_dense(OP_KCONT, n->feat + (size_t)J.row0 * H, H), op_dense(OP_KCONT, J.P + n->seg_off[IQ_WSE], H), n->psi + (size_t)J.row0 * H, H,
                    TEPI_BIAS_RELU, J.P + n->seg_off[IQ_BSE]);
   }
-  if ((rc = iq_tgemm(n, g, nj, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, nj, st))) return rc;
   // cosine features of every (row, sample), then sample_embed
   if ((rc = iqn_cos((int64_t)total * N, E, d_tau, n->cosf_, st))) return rc;
   for (int j = 0; j < nj; ++j) {
@@ -258,7 +218,7 @@ static int iq_forward(jh_iqnnet* n, const IqJob* jobs, int nj, const float* d_ta
     g[j] = mk_gemm(J.rows * N, H, E, op_dense(OP_KCONT, n->cosf_ + r0 * E, E), op_dense(OP_KCONT, J.P + n->seg_off[IQ_WSA], E), n->phi + r0 * H, H, TEPI_BIAS_RELU,
                    J.P + n->seg_off[IQ_BSA]);
   }
-  if ((rc = iq_tgemm(n, g, nj, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, nj, st))) return rc;
   if ((rc = iqn_hadamard((int64_t)total * N, N, H, n->psi, n->phi, n->emb, st))) return rc;
   const float* in[2] = {n->emb, n->h1};
   float* outp[2] = {n->h1, n->h2};
@@ -270,7 +230,7 @@ static int iq_forward(jh_iqnnet* n, const IqJob* jobs, int nj, const float* d_ta
       g[j] = mk_gemm(J.rows * N, H, H, op_dense(OP_KCONT, in[l] + r0 * H, H), op_dense(OP_KCONT, J.P + n->seg_off[wseg[l]], H), outp[l] + r0 * H, H, TEPI_BIAS_RELU,
                      J.P + n->seg_off[bseg[l]]);
     }
-    if ((rc = iq_tgemm(n, g, nj, st))) return rc;
+    if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, nj, st))) return rc;
   }
   for (int j = 0; j < nj; ++j) {
     const IqJob& J = jobs[j];
@@ -278,7 +238,7 @@ static int iq_forward(jh_iqnnet* n, const IqJob* jobs, int nj, const float* d_ta
     g[j] = mk_gemm(J.rows * N, A, H, op_dense(OP_KCONT, n->h2 + r0 * H, H), op_dense(OP_KCONT, J.P + n->seg_off[IQ_WQ], H), d_logits + r0 * A, A, TEPI_BIAS,
                    J.P + n->seg_off[IQ_BQ]);
   }
-  return iq_tgemm(n, g, nj, st);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, nj, st);
 }
 
 JH_EXPORT int jh_iqnnet_forward(jh_iqnnet* n, int32_t which, const float* d_x, int32_t rows, const float* d_tau, float* d_logits, jh_stream stream) {
@@ -332,27 +292,27 @@ JH_EXPORT int jh_iqnnet_backward(jh_iqnnet* n, const float* d_g, jh_stream strea
   // q: weight gradient (+ bias gradient as row sums) and data gradient (+ relu' of l2)
   g[0] = mk_gemm(A, H, BN, op_dense(OP_XCONT, d_g, A), op_dense(OP_XCONT, n->h2, H), G + n->seg_off[IQ_WQ], H, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[IQ_BQ]);
   g[1] = mk_gemm(BN, H, A, op_dense(OP_KCONT, d_g, A), op_dense(OP_XCONT, P + n->seg_off[IQ_WQ], H), dh2, H, TEPI_MASK, nullptr, n->h2, H);
-  if ((rc = iq_tgemm(n, g, 2, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 2, st))) return rc;
   g[0] = mk_gemm(H, H, BN, op_dense(OP_XCONT, dh2, H), op_dense(OP_XCONT, n->h1, H), G + n->seg_off[IQ_WL2], H, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[IQ_BL2]);
   g[1] = mk_gemm(BN, H, H, op_dense(OP_KCONT, dh2, H), op_dense(OP_XCONT, P + n->seg_off[IQ_WL2], H), dh1, H, TEPI_MASK, nullptr, n->h1, H);
-  if ((rc = iq_tgemm(n, g, 2, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 2, st))) return rc;
   // l1 reads the product itself: no relu between them
   g[0] = mk_gemm(H, H, BN, op_dense(OP_XCONT, dh1, H), op_dense(OP_XCONT, n->emb, H), G + n->seg_off[IQ_WL1], H, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[IQ_BL1]);
   g[1] = mk_gemm(BN, H, H, op_dense(OP_KCONT, dh1, H), op_dense(OP_XCONT, P + n->seg_off[IQ_WL1], H), dem, H, TEPI_NONE);
-  if ((rc = iq_tgemm(n, g, 2, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 2, st))) return rc;
   if ((rc = iqn_hadamard_bwd(B, N, H, dem, n->psi, n->phi, dphi, n->dpsi, st))) return rc;
   // sample_embed (its input, the cosine features, has no gradient) and state_embed
   g[0] = mk_gemm(H, E, BN, op_dense(OP_XCONT, dphi, H), op_dense(OP_XCONT, n->cosf_, E), G + n->seg_off[IQ_WSA], E, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[IQ_BSA]);
   g[1] = mk_gemm(H, H, B, op_dense(OP_XCONT, n->dpsi, H), op_dense(OP_XCONT, n->feat, H), G + n->seg_off[IQ_WSE], H, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[IQ_BSE]);
   g[2] = mk_gemm(B, H, H, op_dense(OP_KCONT, n->dpsi, H), op_dense(OP_XCONT, P + n->seg_off[IQ_WSE], H), n->dfeat, H, TEPI_MASK, nullptr, n->feat, H);
-  if ((rc = iq_tgemm(n, g, 3, st))) return rc;
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 3, st))) return rc;
   g[0] = mk_gemm(H, S, B, op_dense(OP_XCONT, n->dfeat, H), op_dense(OP_XCONT, n->last_x, S), G + n->seg_off[IQ_W1], S, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[IQ_B1]);
-  return iq_tgemm(n, g, 1, st);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, 1, st);
 }
 
 JH_EXPORT int jh_iqnnet_optim_step(jh_iqnnet* n, float max_norm, jh_stream stream) {
   JH_ARG(n != nullptr);
-  return jh_flat_adam_step(n->n_params, n->params, n->grads, n->m, n->v, n->hyper, n->ticket, n->norm_partial, max_norm, jh_s(stream));
+  return jh_flat_adam_step(n->n_params, n->params, n->grads, n->m, n->v, n->opt.hyper, n->opt.ticket, n->core.norm_partial, max_norm, jh_s(stream));
 }
 
 // ---------------------------------------------------------------------------------- standalone entries

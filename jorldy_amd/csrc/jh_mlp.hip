@@ -18,7 +18,7 @@
 //   * bias gradients (column sums of the upstream gradient) fall out of the A fragments as row
 //     sums, so they cost no extra pass.
 #include "jh_ppo_mb.h"
-#include "jh_tgemm.h"
+#include "jh_netcore.h"
 #include "jh_ppo_finish.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -680,76 +680,54 @@ JH_EXPORT int jh_pponet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int
   JH_ARG((continuous ? 2 * A + 1 : A + 1) <= kMaxHeadOutputs);
   JH_HIP(hipSetDevice(ctx->device));
   jh_pponet* n = new jh_pponet();
-  n->ctx = ctx; n->S = S; n->H = H; n->A = A; n->cont = continuous ? 1 : 0; n->max_rows = max_rows;
+  n->core = new NetCore();
+  n->ctx = n->core->ctx = ctx; n->S = S; n->H = H; n->A = A; n->cont = continuous ? 1 : 0; n->max_rows = max_rows;
   n->n_params = pponet_layout(n);
   n->params = d_params; n->grads = d_grads; n->m = d_m; n->v = d_v;
-  const size_t act = sizeof(float) * (size_t)max_rows * (size_t)H;
-  JH_HIP(hipMalloc((void**)&n->h1, act));
-  JH_HIP(hipMalloc((void**)&n->h2, act));
-  JH_HIP(hipMalloc((void**)&n->dh1, act));
-  JH_HIP(hipMalloc((void**)&n->dh2, act));
   n->n_out = continuous ? 2 * A + 1 : A + 1;
   n->gld = n->n_out <= 8 ? 8 : (n->n_out + 3) / 4 * 4;
-  JH_HIP(hipMalloc((void**)&n->g_all, sizeof(float) * (size_t)n->gld * (size_t)max_rows));
   n->max_act_rows = max_rows < 1024 ? max_rows : 1024;
-  {
-    const size_t tiles = (size_t)((n->max_act_rows + 15) / 16) * (size_t)(H / 16);
-    JH_HIP(hipHostMalloc((void**)&n->obs_pin_h, sizeof(float) * (size_t)n->max_act_rows * (size_t)S, hipHostMallocMapped));
-    JH_HIP(hipHostGetDevicePointer((void**)&n->obs_pin_d, n->obs_pin_h, 0));
-    JH_HIP(hipHostMalloc((void**)&n->part_pin_h, sizeof(float) * 8 * (size_t)n->max_act_rows * (size_t)(H / 16), hipHostMallocMapped));
-    JH_HIP(hipHostGetDevicePointer((void**)&n->part_pin_d, n->part_pin_h, 0));
-    JH_HIP(hipHostMalloc((void**)&n->flag_pin_h, sizeof(unsigned) * tiles, hipHostMallocMapped));
-    JH_HIP(hipHostGetDevicePointer((void**)&n->flag_pin_d, n->flag_pin_h, 0));
-    memset(n->flag_pin_h, 0, sizeof(unsigned) * tiles);
-    n->act_seed = seed;
-    if (n->n_out > 8) {
-      JH_HIP(hipHostMalloc((void**)&n->act_out_h, sizeof(float) * (size_t)n->max_act_rows * (size_t)n->n_out, hipHostMallocMapped));
-      JH_HIP(hipHostGetDevicePointer((void**)&n->act_out_d, n->act_out_h, 0));
-    }
-  }
-  n->tg_ws_floats = (size_t)4 << 20;
-  n->tg_cnt_slots = 4096;
-  JH_HIP(hipMalloc((void**)&n->xg, sizeof(float) * (size_t)max_rows * (size_t)S));
-  JH_HIP(hipMalloc((void**)&n->tg_ws, sizeof(float) * n->tg_ws_floats));
-  JH_HIP(hipMalloc((void**)&n->tg_cnt, sizeof(unsigned) * (size_t)n->tg_cnt_slots * kTgemmCntStride));
-  JH_HIP(hipMemset(n->tg_cnt, 0, sizeof(unsigned) * (size_t)n->tg_cnt_slots * kTgemmCntStride));
-  {
-    const size_t part_bytes = sizeof(float) * 8 * (size_t)max_rows * (size_t)(H / 16);
-    JH_HIP(hipMalloc((void**)&n->fwd_part, part_bytes));
-    JH_HIP(hipMemset(n->fwd_part, 0, part_bytes));  // head slots >= n_out are never written: they must read as 0
-    JH_HIP(hipMemset(n->g_all, 0, sizeof(float) * (size_t)n->gld * (size_t)max_rows));
-    JH_HIP(hipMalloc((void**)&n->dv2, sizeof(float) * ((size_t)(max_rows < 1024 ? max_rows : 1024) + 8)));
-    n->stats_tmp = n->dv2 + (max_rows < 1024 ? max_rows : 1024);
-    const size_t slabs = (size_t)(((max_rows < 1024 ? max_rows : 1024) + 15) / 16);
-    JH_HIP(hipMalloc((void**)&n->part_w1, sizeof(float) * slabs * ((size_t)H * S + H + 8 * (size_t)H)));
-    JH_HIP(hipMalloc((void**)&n->ssq_part, sizeof(float) * ((size_t)(H / 32) * (H / 32) + H / 32 + 1)));
-  }
-  {  // jh_pponet_ppo_update_rows: raw heads + their gradients as separate arrays ([max_rows][A] x 2 x 2, [max_rows] x 3), the loss's partials, {w1, w2}, a ticket
-    const size_t rows = (size_t)max_rows, per = 4 * (size_t)A + 3;
-    n->upd_floats = rows * per + 8 * ((rows + 255) / 256) + 16;
-    JH_HIP(hipMalloc((void**)&n->upd_ws, sizeof(float) * n->upd_floats));
-    JH_HIP(hipMemset(n->upd_ws, 0, sizeof(float) * n->upd_floats));
-  }
-  JH_HIP(hipMalloc((void**)&n->norm_partial, sizeof(float) * kNormSlots));
-  JH_HIP(hipMalloc((void**)&n->hyper, sizeof(float) * JH_HY_FLOATS));
+  n->act_seed = seed;
+  // every allocation is the core's the moment it exists: a failure at any line releases what came before it, and the object
+  int rc = JH_OK;
+  auto D = [&](float** p, size_t floats, bool zero = false) { if (!rc) rc = core_alloc(n->core, "jh_pponet", (void**)p, sizeof(float) * floats, zero); };
+  auto M = [&](auto** host, auto** dev, size_t bytes) { if (!rc) rc = core_alloc_mapped(n->core, "jh_pponet", (void**)host, (void**)dev, bytes); };
+  const size_t rows = (size_t)max_rows, arows = (size_t)n->max_act_rows, act = rows * (size_t)H;
+  D(&n->h1, act); D(&n->h2, act); D(&n->dh1, act); D(&n->dh2, act);
+  D(&n->g_all, (size_t)n->gld * rows, true);
+  const size_t tiles = (size_t)((n->max_act_rows + 15) / 16) * (size_t)(H / 16);
+  M(&n->obs_pin_h, &n->obs_pin_d, sizeof(float) * arows * (size_t)S);
+  M(&n->part_pin_h, &n->part_pin_d, sizeof(float) * 8 * arows * (size_t)(H / 16));
+  M(&n->flag_pin_h, &n->flag_pin_d, sizeof(unsigned) * tiles);
+  if (!rc) memset(n->flag_pin_h, 0, sizeof(unsigned) * tiles);
+  if (n->n_out > 8) M(&n->act_out_h, &n->act_out_d, sizeof(float) * arows * (size_t)n->n_out);
+  D(&n->xg, rows * (size_t)S);
+  if (!rc) rc = core_workspace(n->core, "jh_pponet", (size_t)4 << 20, 4096);
+  D(&n->fwd_part, 8 * rows * (size_t)(H / 16), true);  // head slots >= n_out are never written: they must read as 0
+  D(&n->dv2, arows + 8);
+  if (!rc) n->stats_tmp = n->dv2 + arows;
+  D(&n->part_w1, (size_t)((n->max_act_rows + 15) / 16) * ((size_t)H * S + H + 8 * (size_t)H));
+  D(&n->ssq_part, (size_t)(H / 32) * (H / 32) + H / 32 + 1);
+  // jh_pponet_ppo_update_rows: raw heads + their gradients as separate arrays ([max_rows][A] x 2 x 2, [max_rows] x 3), the loss's partials, {w1, w2}, a ticket
+  n->upd_floats = rows * (4 * (size_t)A + 3) + 8 * ((rows + 255) / 256) + 16;
+  D(&n->upd_ws, n->upd_floats, true);
+  D(&n->norm_partial, kNormSlots);
+  D(&n->hyper, JH_HY_FLOATS);
   float hy[JH_HY_FLOATS];
   jh_hyper_fill(hy, 1e-3, 0.9, 0.999, 1e-8, 0.0);
-  JH_HIP(hipMemcpy(n->hyper, hy, sizeof(hy), hipMemcpyHostToDevice));
+  if (!rc && hipMemcpy(n->hyper, hy, sizeof(hy), hipMemcpyHostToDevice) != hipSuccess) rc = jh_fail(JH_ERR_HIP, "jh_pponet: the hyper block's upload failed");
+  if (rc) {
+    jh_pponet_destroy(n);
+    return rc;
+  }
   *out = n;
   return JH_OK;
 }
 
 JH_EXPORT void jh_pponet_destroy(jh_pponet* n) {
   if (!n) return;
-  (void)hipSetDevice(n->ctx->device);
-  (void)hipDeviceSynchronize();
-  (void)hipFree(n->h1); (void)hipFree(n->h2); (void)hipFree(n->dh1); (void)hipFree(n->dh2);
-  (void)hipFree(n->g_all);
-  (void)hipHostFree(n->obs_pin_h); (void)hipHostFree(n->part_pin_h); (void)hipHostFree(n->flag_pin_h);
-  if (n->act_out_h) (void)hipHostFree(n->act_out_h);
-  (void)hipFree(n->norm_partial); (void)hipFree(n->hyper); (void)hipFree(n->dv2);
-  (void)hipFree(n->fwd_part); (void)hipFree(n->part_w1); (void)hipFree(n->ssq_part);
-  (void)hipFree(n->tg_ws); (void)hipFree(n->tg_cnt); (void)hipFree(n->xg); (void)hipFree(n->upd_ws);
+  core_release(n->core);
+  delete n->core;
   delete n;
 }
 
@@ -1172,9 +1150,7 @@ JH_EXPORT int jh_pponet_forward(jh_pponet* n, int32_t B, const float* d_x, const
   if (rc) return rc;
   if (pponet_use_tiled(B)) {
     TGemm tg = mk_gemm(B, H, H, op_dense(OP_KCONT, n->h1, H), op_dense(OP_KCONT, n->params + n->o_w2, H), n->h2, H, TEPI_BIAS_RELU, n->params + n->o_b2);
-    TGemmWorkspace tw;
-    tw.ws = n->tg_ws; tw.ws_floats = n->tg_ws_floats; tw.cnt = n->tg_cnt; tw.cnt_slots = n->tg_cnt_slots;
-    rc = jh_tgemm_launch(tw, "jh_tgemm_ppo_fwd_h2", &tg, 1, st);
+    rc = core_tgemm(n->core, "jh_tgemm_ppo_fwd_h2", &tg, 1, st);
   } else {
     GemmArgs g{};
     g.M = B; g.N = H; g.K = H; g.A = n->h1; g.lda = H; g.B = n->params + n->o_w2; g.ldb = H; g.C = n->h2; g.ldc = H;
@@ -1246,15 +1222,13 @@ static int pponet_backward(jh_pponet* n, int32_t B, const float* d_x, const int6
       }
       g[ng++] = mk_gemm(1, H, B, op_dense(OP_XCONT, n->g_all + col, gld), op_dense(OP_XCONT, n->h2, H), n->grads + n->o_wv, H, TEPI_NONE, nullptr, nullptr, 0, n->grads + n->o_bv);
     }
-    TGemmWorkspace tw;
-    tw.ws = n->tg_ws; tw.ws_floats = n->tg_ws_floats; tw.cnt = n->tg_cnt; tw.cnt_slots = n->tg_cnt_slots;
-    rc = jh_tgemm_launch(tw, "jh_tgemm_ppo_bwd", g, ng, st);
+    rc = core_tgemm(n->core, "jh_tgemm_ppo_bwd", g, ng, st);
     if (rc) return rc;
     if (reduce) return pponet_dw1_reduce(n, B, d_x, d_idx, reduce_heads, st, with_norm);
     JH_LAUNCH(jh_rowgather_f32_kernel, dim3((unsigned)(((int64_t)B * S + 255) / 256)), dim3(256), 0, st, B, S, d_x, d_idx, n->xg);
     JH_LAUNCH_CHECK();
     g[0] = mk_gemm(H, S, B, op_dense(OP_XCONT, n->dh1, H), op_dense(OP_XCONT, n->xg, S), n->grads + n->o_w1, S, TEPI_NONE, nullptr, nullptr, 0, n->grads + n->o_b1);
-    return jh_tgemm_launch(tw, "jh_tgemm_ppo_bwd_dW1", g, 1, st);
+    return core_tgemm(n->core, "jh_tgemm_ppo_bwd_dW1", g, 1, st);
   }
   for (int o0 = 0; o0 < n_out; o0 += 8) {  // dWh[o][k] = sum_b g[b][o] h2[b][k] ; dbh[o] = sum_b g[b][o]   (A = g_all^T stored [K=B][gld]; 8 output rows per launch)
     GemmArgs g{};

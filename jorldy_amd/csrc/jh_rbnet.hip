@@ -17,8 +17,7 @@
 //   conv weights [out][(ky, kx, c)]  (layer 1: [out][(c, ky, kx)] = the reference layout, input is NCHW)
 //   linear / noisy weights [out][in] (the reference keeps noisy weights as [in][out])
 //   a1 | v1 noisy layers stacked into one [2H][H] matrix (one GEMM feeds both streams)
-#include "jh_tgemm.h"
-#include "jh_fused.h"
+#include "jh_netcore.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -608,13 +607,13 @@ enum {
 
 constexpr int kC1Parts = 256;  // conv1 weight gradient: at most this many K slices (workgroups)
 struct jh_rbnet {
-  jh_ctx* ctx = nullptr;
+  NetCore core;
+  FlatOptim opt;
   int cnn = 0, Cin = 0, Hin = 0, Win = 0, hidden = 0, A = 0, K = 0, NA = 0, maxB = 0, F = 0;
   // kind 0 rainbow: head -> l -> noisy a1|v1 -> noisy a2, v2 -> dueling over K atoms   (network/rainbow.py:8-94)
   //      1 dueling: head -> l1_a|l1_v -> l2_a, l2_v -> dueling combine (K = 1)         (network/dueling.py:8-35)
   //      2 q:       head -> l -> q                                                      (network/q_network.py:8-20)
   int kind = 0, noisy = 1, dueling = 1, has_l = 1, has_av1 = 1, in1 = 0, noise_independent = 0;
-  float* norm_partial = nullptr;
   int NA4 = 0, K4 = 0;
   ConvGeom c1{}, c2{}, c3{};
   int P1 = 0, P2 = 0, P3 = 0;  // output pixels per sample
@@ -622,18 +621,12 @@ struct jh_rbnet {
   int seg_rows[SEG_COUNT] = {0}, seg_cols[SEG_COUNT] = {0};
   int64_t n_params = 0;
   float *params = nullptr, *target = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr;
-  float* hyper = nullptr;
-  unsigned* ticket = nullptr;
   NoisyDims nd{};
   int64_t n_noisy = 0;
   float* weff = nullptr;                                // [3][set_stride]
   float *act1[2] = {nullptr, nullptr}, *act2[2] = {nullptr, nullptr}, *feat[2] = {nullptr, nullptr}, *h[2] = {nullptr, nullptr};
   float *hav = nullptr, *xa = nullptr, *xv = nullptr;  // [3][maxB][...]
   float *dxa = nullptr, *dxv = nullptr, *dhav = nullptr, *dh = nullptr, *dfeat = nullptr, *dcol = nullptr, *dact2 = nullptr, *dact1 = nullptr;
-  float* ws = nullptr;
-  size_t ws_floats = 0;
-  unsigned* cnt = nullptr;
-  int cnt_slots = 0;
   float* c1_part = nullptr;    // conv1 weight-gradient partials [kC1Parts][32 * 64 Cin + 32]
   const void* last_x = nullptr;  // input of the last learn_forward (backward of layer 1 reads it again)
   int last_x_u8 = 0, last_B = 0;
@@ -643,25 +636,7 @@ struct jh_rbnet {
   int dx_ready = 0;     // dxa / dxv already hold the gradient pulled through the dueling combine (jh_rbnet_c51_step)
   int pend_parts = 0;   // conv1 weight-gradient partials not yet summed into the bucket (jh_rbnet_backward_deferred): their count
   int tgt_rows = 0;     // rows the target slot's activation buffers (act1 / act2 / feat / h [1]) hold: maxB, or what jh_rbnet_reserve_target_rows asked for
-  std::vector<void*> owned;
 };
-
-static int rb_alloc(jh_rbnet* n, void** out, size_t bytes, bool zero) {
-  if (bytes == 0) bytes = 16;
-  hipError_t e = hipMalloc(out, bytes);
-  if (e != hipSuccess) return jh_fail(JH_ERR_NOMEM, "jh_rbnet: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  n->owned.push_back(*out);
-  if (zero) JH_HIP(hipMemset(*out, 0, bytes));
-  return JH_OK;
-}
-
-static int launch_tgemm(jh_rbnet* net, const char* name, TGemm* probs, int n, hipStream_t st) {
-  TGemmWorkspace w;
-  w.ws = net->ws; w.ws_floats = net->ws_floats; w.cnt = net->cnt; w.cnt_slots = net->cnt_slots;
-  return jh_tgemm_launch(w, name, probs, n, st);
-}
-
-static inline int64_t up4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 
 static int rb_layout(jh_rbnet* n, int32_t kind, int32_t head_cnn, int32_t c_or_s, int32_t h_in, int32_t w_in, int32_t hidden, int32_t A, int32_t K,
                      int32_t max_batch) {
@@ -707,12 +682,7 @@ static int rb_layout(jh_rbnet* n, int32_t kind, int32_t head_cnn, int32_t c_or_s
     seg(SEG_MU_V2, K, H); seg(SEG_MUB_V2, 1, K);
     if (n->noisy) { seg(SEG_SIG_V2, K, H); seg(SEG_SIGB_V2, 1, K); }
   }
-  int64_t off = 0;
-  for (int i = 0; i < SEG_COUNT; ++i) {
-    n->seg_off[i] = off;
-    off = up4(off + (int64_t)n->seg_rows[i] * n->seg_cols[i]);
-  }
-  n->n_params = off;
+  n->n_params = seg_pack(n->seg_rows, n->seg_cols, 0, SEG_COUNT, n->seg_off);
   NoisyDims& d = n->nd;
   d.H = H; d.NA = n->NA; d.K = K;
   d.o_av1 = 0;
@@ -742,7 +712,7 @@ JH_EXPORT int jh_rbnet_create(jh_ctx* ctx, int32_t kind, int32_t head_cnn, int32
   JH_ARG(ctx && out && d_params && d_target && d_grads && d_m && d_v);
   JH_HIP(hipSetDevice(ctx->device));
   jh_rbnet* n = new jh_rbnet();
-  n->ctx = ctx;
+  n->core.ctx = ctx;
   int rc = rb_layout(n, kind, head_cnn, c_or_s, h_in, w_in, hidden, A, K, max_batch);
   if (rc) {
     delete n;
@@ -753,10 +723,8 @@ JH_EXPORT int jh_rbnet_create(jh_ctx* ctx, int32_t kind, int32_t head_cnn, int32
   const NoisyDims& d = n->nd;
   const int H = hidden;
   const size_t B = (size_t)max_batch;
-  auto A4 = [&](float** p, size_t floats, bool zero = true) { if (!rc) rc = rb_alloc(n, (void**)p, floats * sizeof(float), zero); };
-  A4(&n->hyper, JH_HY_FLOATS);
-  A4(&n->norm_partial, 256);
-  if (!rc) rc = rb_alloc(n, (void**)&n->ticket, 2048, true);  // jh_rb_optim_kernel: eight counters 128 bytes apart + the one on top of them
+  auto A4 = [&](float** p, size_t floats, bool zero = true) { if (!rc) rc = core_alloc(&n->core, "jh_rbnet", (void**)p, floats * sizeof(float), zero); };
+  rc = optim_init(&n->core, "jh_rbnet", &n->opt);
   A4(&n->weff, 3 * (size_t)d.set_stride);
   for (int s = 0; s < 2; ++s) {
     const size_t rows = s == 0 ? 2 * B : B;
@@ -798,72 +766,43 @@ JH_EXPORT int jh_rbnet_create(jh_ctx* ctx, int32_t kind, int32_t head_cnn, int32
         }
       }
       int* d_tab = nullptr;
-      if (!rc) rc = rb_alloc(n, (void**)&d_tab, tab.size() * sizeof(int), false);
+      if (!rc) rc = core_alloc(&n->core, "jh_rbnet", (void**)&d_tab, tab.size() * sizeof(int), false);
       if (!rc && hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc = jh_fail(JH_ERR_HIP, "im2col table upload failed");
       c.pix_tab = d_tab;
       c.tap_tab = d_tab + n_pix;
     }
   }
-  n->ws_floats = (size_t)8 << 20;  // 32 MB of split-K partials
-  A4(&n->ws, n->ws_floats, false);
-  n->cnt_slots = 8192;
-  if (!rc) rc = rb_alloc(n, (void**)&n->cnt, sizeof(unsigned) * (size_t)n->cnt_slots * kTgemmCntStride, true);
+  if (!rc) rc = core_workspace(&n->core, "jh_rbnet", (size_t)8 << 20, 8192);  // 32 MB of split-K partials
+  if (!rc) rc = core_drain();
   if (rc) {
-    for (void* p : n->owned) (void)hipFree(p);
+    core_release(&n->core);
     delete n;
     return rc;
   }
-  float hy[JH_HY_FLOATS];
-  jh_hyper_fill(hy, 1e-3, 0.9, 0.999, 1e-8, 0.0);
-  JH_HIP(hipMemcpy(n->hyper, hy, sizeof(hy), hipMemcpyHostToDevice));
-  JH_HIP(hipDeviceSynchronize());
   *out = n;
   return JH_OK;
 }
 
 JH_EXPORT void jh_rbnet_destroy(jh_rbnet* n) {
   if (!n) return;
-  (void)hipSetDevice(n->ctx->device);
-  (void)hipDeviceSynchronize();
-  for (void* p : n->owned) (void)hipFree(p);
+  core_release(&n->core);
   delete n;
 }
 
 JH_EXPORT int64_t jh_rbnet_param_count(const jh_rbnet* n) { return n ? n->n_params : -1; }
 JH_EXPORT int32_t jh_rbnet_segment_count(void) { return SEG_COUNT; }
 JH_EXPORT int jh_rbnet_segment(const jh_rbnet* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols) {
-  JH_ARG(n && i >= 0 && i < SEG_COUNT && offset && rows && cols);
-  *offset = n->seg_off[i]; *rows = n->seg_rows[i]; *cols = n->seg_cols[i];
-  return JH_OK;
+  return seg_query(n, SEG_COUNT, i, offset, rows, cols);
 }
 JH_EXPORT int64_t jh_rbnet_noise_len(const jh_rbnet* n) { return n ? n->nd.noise_len : -1; }
 
-int jh_hyper_upload(jh_ctx* ctx, float* d_hyper, double lr, double beta1, double beta2, double eps, int64_t step, int centered, hipStream_t st) {
-  jh_pinned_slab* slab = nullptr;
-  int rc = jh_ctx_slab(ctx, 64, &slab);
-  if (rc) return rc;
-  float* h = (float*)slab->host;
-  jh_hyper_fill(h, lr, beta1, beta2, eps, (double)step);
-  h[JH_HY_BC1] = centered ? 1.f : 0.f;
-  JH_HIP(hipMemcpyAsync(d_hyper, slab->dev, JH_HY_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, st));
-  return jh_ctx_slab_release(ctx, slab, st);
-}
-int jh_hyper_upload_lr(jh_ctx* ctx, float* d_hyper, double lr, hipStream_t st) {
-  jh_pinned_slab* slab = nullptr;
-  int rc = jh_ctx_slab(ctx, 16, &slab);
-  if (rc) return rc;
-  *(float*)slab->host = (float)lr;
-  JH_HIP(hipMemcpyAsync(d_hyper, slab->dev, sizeof(float), hipMemcpyDeviceToDevice, st));
-  return jh_ctx_slab_release(ctx, slab, st);
-}
-
 JH_EXPORT int jh_rbnet_set_hyper(jh_rbnet* n, double lr, double beta1, double beta2, double eps, int64_t step, int32_t centered, jh_stream stream) {
   JH_ARG(n != nullptr);
-  return jh_hyper_upload(n->ctx, n->hyper, lr, beta1, beta2, eps, step, centered, jh_s(stream));
+  return jh_hyper_upload(n->core.ctx, n->opt.hyper, lr, beta1, beta2, eps, step, centered, jh_s(stream));
 }
 JH_EXPORT int jh_rbnet_set_lr(jh_rbnet* n, double lr, jh_stream stream) {
   JH_ARG(n != nullptr);
-  return jh_hyper_upload_lr(n->ctx, n->hyper, lr, jh_s(stream));
+  return jh_hyper_upload_lr(n->core.ctx, n->opt.hyper, lr, jh_s(stream));
 }
 JH_EXPORT int jh_rbnet_sync_target(jh_rbnet* n, jh_stream stream) {
   JH_ARG(n != nullptr);
@@ -911,7 +850,7 @@ static int rb_trunk(jh_rbnet* n, const TrunkJob* jobs, int nj, int x_u8, hipStre
       JH_LAUNCH_IDEM("jh_rb_conv1_fwd_kernel", 2.0 * 32 * 256 * (double)imgs * n->P1, jh_rb_conv1_fwd_kernel<4>, dim3(wgs), dim3(256), 0, st, a);
       JH_LAUNCH_CHECK();
     } else {
-      rc = launch_tgemm(n, "jh_tgemm_conv1_fwd", g, nj, st);
+      rc = core_tgemm(&n->core, "jh_tgemm_conv1_fwd", g, nj, st);
     }
     if (rc) return rc;
     for (int j = 0; j < nj; ++j) {
@@ -919,14 +858,14 @@ static int rb_trunk(jh_rbnet* n, const TrunkJob* jobs, int nj, int x_u8, hipStre
       g[j] = mk_gemm(J.rows * n->P2, 64, 512, op_conv(OP_NHWC_K, n->act1[J.slot], 0, n->c2), op_dense(OP_KCONT, J.P + n->seg_off[SEG_W2], 512),
                      n->act2[J.slot], 64, TEPI_BIAS_RELU, J.P + n->seg_off[SEG_B2]);
     }
-    rc = launch_tgemm(n, "jh_tgemm_conv2_fwd", g, nj, st);
+    rc = core_tgemm(&n->core, "jh_tgemm_conv2_fwd", g, nj, st);
     if (rc) return rc;
     for (int j = 0; j < nj; ++j) {
       const TrunkJob& J = jobs[j];
       g[j] = mk_gemm(J.rows * n->P3, 64, 576, op_conv(OP_NHWC_K, n->act2[J.slot], 0, n->c3), op_dense(OP_KCONT, J.P + n->seg_off[SEG_W3], 576),
                      n->feat[J.slot], 64, TEPI_BIAS_RELU, J.P + n->seg_off[SEG_B3]);
     }
-    rc = launch_tgemm(n, "jh_tgemm_conv3_fwd", g, nj, st);
+    rc = core_tgemm(&n->core, "jh_tgemm_conv3_fwd", g, nj, st);
     if (rc) return rc;
   } else {
     if (x_u8) return jh_fail(JH_ERR_ARG, "mlp head takes fp32 observations");
@@ -935,7 +874,7 @@ static int rb_trunk(jh_rbnet* n, const TrunkJob* jobs, int nj, int x_u8, hipStre
       g[j] = mk_gemm(J.rows, H, n->Cin, op_dense(OP_KCONT, (const float*)J.x, n->Cin), op_dense(OP_KCONT, J.P + n->seg_off[SEG_W1], n->Cin),
                      n->feat[J.slot], H, TEPI_BIAS_RELU, J.P + n->seg_off[SEG_B1]);
     }
-    int rc = launch_tgemm(n, "jh_tgemm_head_fwd", g, nj, st);
+    int rc = core_tgemm(&n->core, "jh_tgemm_head_fwd", g, nj, st);
     if (rc) return rc;
   }
   if (!n->has_l) return JH_OK;  // dueling.py: the streams read the head's features directly
@@ -944,7 +883,7 @@ static int rb_trunk(jh_rbnet* n, const TrunkJob* jobs, int nj, int x_u8, hipStre
     g[j] = mk_gemm(J.rows, H, n->F, op_dense(OP_KCONT, n->feat[J.slot], n->F), op_dense(OP_KCONT, J.P + n->seg_off[SEG_WL], n->F), n->h[J.slot], H,
                    TEPI_BIAS_RELU, J.P + n->seg_off[SEG_BL]);
   }
-  return launch_tgemm(n, "jh_tgemm_fc_fwd", g, nj, st);
+  return core_tgemm(&n->core, "jh_tgemm_fc_fwd", g, nj, st);
 }
 
 // weights of the stream layers as the GEMMs see them: the materialised noisy set, or the parameters themselves
@@ -994,7 +933,7 @@ static int rb_heads(jh_rbnet* n, const HeadJob* jobs, int nj, int B, hipStream_t
       const StreamW w = stream_w(n, jobs[j].P, j);
       g[j] = mk_gemm(B, 2 * H, in1, op_dense(OP_KCONT, jobs[j].h, in1), op_dense(OP_KCONT, w.av1, in1), n->hav + j * B_ * 2 * H, 2 * H, TEPI_BIAS_RELU, w.bav1);
     }
-    rc = launch_tgemm(n, "jh_tgemm_stream1_fwd", g, nj, st);
+    rc = core_tgemm(&n->core, "jh_tgemm_stream1_fwd", g, nj, st);
     if (rc) return rc;
   }
   int ng = 0;
@@ -1007,7 +946,7 @@ static int rb_heads(jh_rbnet* n, const HeadJob* jobs, int nj, int B, hipStream_t
     if (n->dueling)
       g[ng++] = mk_gemm(B, K, H, op_dense(OP_KCONT, in_a + H, ld_in), op_dense(OP_KCONT, w.v2, H), n->xv + j * B_ * n->K4, n->K4, TEPI_BIAS, w.bv2);
   }
-  rc = launch_tgemm(n, "jh_tgemm_stream2_fwd", g, ng, st);
+  rc = core_tgemm(&n->core, "jh_tgemm_stream2_fwd", g, ng, st);
   if (rc) return rc;
   if (!n->dueling || raw) return JH_OK;
   DuelSets ds{};
@@ -1146,7 +1085,7 @@ JH_EXPORT int jh_rbnet_c51_step(jh_rbnet* n, jh_per* per, int32_t B, int32_t n_s
     rc = jh_per_delta_args(per, B, d_tree_idx, d_prio, JH_F32, &pa);
     if (rc) return rc;
   }
-  rc = jh_c51_run(n->ctx, a, &d, per ? &pa : nullptr, st);
+  rc = jh_c51_run(n->core.ctx, a, &d, per ? &pa : nullptr, st);
   if (rc) return rc;
   n->raw_heads = 0;
   n->dx_ready = 1;
@@ -1168,7 +1107,7 @@ JH_EXPORT int jh_rbnet_reserve_target_rows(jh_rbnet* n, int32_t rows) {
   JH_ARG(n != nullptr);
   JH_ARG(rows > 0 && rows <= 2 * n->maxB);
   if (rows <= n->tgt_rows) return JH_OK;
-  JH_HIP(hipSetDevice(n->ctx->device));
+  JH_HIP(hipSetDevice(n->core.ctx->device));
   JH_HIP(hipDeviceSynchronize());  // nothing in flight reads the buffers that go
   const size_t R = (size_t)rows;
   float* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -1176,14 +1115,14 @@ JH_EXPORT int jh_rbnet_reserve_target_rows(jh_rbnet* n, int32_t rows) {
   const size_t floats[4] = {n->cnn ? R * n->P1 * 32 : 0, n->cnn ? R * n->P2 * 64 : 0, R * n->F, R * n->hidden};
   int rc = JH_OK;
   for (int i = 0; i < 4 && !rc; ++i)
-    if (floats[i]) rc = rb_alloc(n, (void**)&fresh[i], floats[i] * sizeof(float), true);
+    if (floats[i]) rc = core_alloc(&n->core, "jh_rbnet", (void**)&fresh[i], floats[i] * sizeof(float), true);
   if (rc) return rc;  // what was allocated stays owned by the net and goes with it; the old buffers are still in place
   for (int i = 0; i < 4; ++i) {
     if (!floats[i]) continue;
-    for (size_t k = 0; k < n->owned.size(); ++k)
-      if (n->owned[k] == (void*)*old[i]) {
-        (void)hipFree(n->owned[k]);
-        n->owned.erase(n->owned.begin() + (long)k);
+    for (size_t k = 0; k < n->core.owned.size(); ++k)
+      if (n->core.owned[k] == (void*)*old[i]) {
+        (void)hipFree(n->core.owned[k]);
+        n->core.owned.erase(n->core.owned.begin() + (long)k);
         break;
       }
     *old[i] = fresh[i];
@@ -1295,7 +1234,7 @@ static int rb_backward(jh_rbnet* n, const float* d_g, bool defer, jh_stream stre
     with_sigma(g[ng - 1], SEG_SIG_V2, SEG_SIGB_V2, e0 + 6 * H + NA, e0 + 5 * H + NA, K, nullptr, nullptr);
     g[ng++] = mk_gemm(B, H, K, op_dense(OP_KCONT, n->dxv, n->K4), op_dense(OP_XCONT, w0.v2, H), d_in + H, ld_in, TEPI_MASK, nullptr, in_a + H, ld_in);
   }
-  rc = launch_tgemm(n, "jh_tgemm_stream2_bwd", g, ng, st);
+  rc = core_tgemm(&n->core, "jh_tgemm_stream2_bwd", g, ng, st);
   if (rc) return rc;
   if (n->has_av1) {  // first stream layer (a1 | v1 stacked)
     g[0] = mk_gemm(2 * H, in1, B, op_dense(OP_XCONT, n->dhav, 2 * H), op_dense(OP_XCONT, sin0, in1), G + n->seg_off[SEG_MU_AV1], in1, TEPI_NONE, nullptr, nullptr, 0,
@@ -1303,7 +1242,7 @@ static int rb_backward(jh_rbnet* n, const float* d_g, bool defer, jh_stream stre
     // rows m < H are a1 (e_out at H + m, e_in at k), rows m >= H are v1 (e_out at 3H + (m - H) = 2H + m, e_in at 2H + k)
     with_sigma(g[0], SEG_SIG_AV1, SEG_SIGB_AV1, e0 + H, e0, H, e0 + 2 * H, e0 + 2 * H);
     g[1] = mk_gemm(B, in1, 2 * H, op_dense(OP_KCONT, n->dhav, 2 * H), op_dense(OP_XCONT, w0.av1, in1), dsin, in1, TEPI_MASK, nullptr, sin0, in1);
-    rc = launch_tgemm(n, "jh_tgemm_stream1_bwd", g, 2, st);
+    rc = core_tgemm(&n->core, "jh_tgemm_stream1_bwd", g, 2, st);
     if (rc) return rc;
   }
   if (n->noisy && !sig_epi) {  // independent noise (utils.py:73-76): eps is a matrix of its own, the elementwise kernel forms d(sig)
@@ -1314,19 +1253,19 @@ static int rb_backward(jh_rbnet* n, const float* d_g, bool defer, jh_stream stre
     g[0] = mk_gemm(H, F, B, op_dense(OP_XCONT, n->dh, H), op_dense(OP_XCONT, n->feat[0], F), G + n->seg_off[SEG_WL], F, TEPI_NONE, nullptr, nullptr, 0,
                    G + n->seg_off[SEG_BL]);
     g[1] = mk_gemm(B, F, H, op_dense(OP_KCONT, n->dh, H), op_dense(OP_XCONT, n->params + n->seg_off[SEG_WL], F), n->dfeat, F, TEPI_MASK, nullptr, n->feat[0], F);
-    rc = launch_tgemm(n, "jh_tgemm_fc_bwd", g, 2, st);
+    rc = core_tgemm(&n->core, "jh_tgemm_fc_bwd", g, 2, st);
     if (rc) return rc;
   }
   if (!n->cnn) {
     g[0] = mk_gemm(H, n->Cin, B, op_dense(OP_XCONT, n->dfeat, H), op_dense(OP_XCONT, (const float*)n->last_x, n->Cin), G + n->seg_off[SEG_W1], n->Cin, TEPI_NONE,
                    nullptr, nullptr, 0, G + n->seg_off[SEG_B1]);
-    return launch_tgemm(n, "jh_tgemm_head_bwd", g, 1, st);
+    return core_tgemm(&n->core, "jh_tgemm_head_bwd", g, 1, st);
   }
   // conv3: d(feat) is d(act3) in NHWC [B*P3][64]
   g[0] = mk_gemm(64, 576, B * n->P3, op_dense(OP_XCONT, n->dfeat, 64), op_conv(OP_NHWC_X, n->act2[0], 0, n->c3), G + n->seg_off[SEG_W3], 576, TEPI_NONE, nullptr,
                  nullptr, 0, G + n->seg_off[SEG_B3]);
   g[1] = mk_gemm(B * n->P3, 576, 64, op_dense(OP_KCONT, n->dfeat, 64), op_dense(OP_XCONT, n->params + n->seg_off[SEG_W3], 576), n->dcol, 576, TEPI_NONE);
-  rc = launch_tgemm(n, "jh_tgemm_conv3_bwd", g, 2, st);
+  rc = core_tgemm(&n->core, "jh_tgemm_conv3_bwd", g, 2, st);
   if (rc) return rc;
   {
     const int n_pix = B * n->P2;
@@ -1337,7 +1276,7 @@ static int rb_backward(jh_rbnet* n, const float* d_g, bool defer, jh_stream stre
   g[0] = mk_gemm(64, 512, B * n->P2, op_dense(OP_XCONT, n->dact2, 64), op_conv(OP_NHWC_X, n->act1[0], 0, n->c2), G + n->seg_off[SEG_W2], 512, TEPI_NONE, nullptr,
                  nullptr, 0, G + n->seg_off[SEG_B2]);
   g[1] = mk_gemm(B * n->P2, 512, 64, op_dense(OP_KCONT, n->dact2, 64), op_dense(OP_XCONT, n->params + n->seg_off[SEG_W2], 512), n->dcol, 512, TEPI_NONE);
-  rc = launch_tgemm(n, "jh_tgemm_conv2_bwd", g, 2, st);
+  rc = core_tgemm(&n->core, "jh_tgemm_conv2_bwd", g, 2, st);
   if (rc) return rc;
   {
     const int n_pix = B * n->P1;
@@ -1367,7 +1306,7 @@ static int rb_backward(jh_rbnet* n, const float* d_g, bool defer, jh_stream stre
   }
   g[0] = mk_gemm(32, n->Cin * 64, B * n->P1, op_dense(OP_XCONT, n->dact1, 32), op_conv(OP_NCHW_X, n->last_x, n->last_x_u8, n->c1), G + n->seg_off[SEG_W1],
                  n->Cin * 64, TEPI_NONE, nullptr, nullptr, 0, G + n->seg_off[SEG_B1]);
-  return launch_tgemm(n, "jh_tgemm_conv1_bwd", g, 1, st);
+  return core_tgemm(&n->core, "jh_tgemm_conv1_bwd", g, 1, st);
 }
 JH_EXPORT int jh_rbnet_backward(jh_rbnet* n, const float* d_g, jh_stream stream) { return rb_backward(n, d_g, false, stream); }
 // The same, but one tail stays undone -- the sum of conv1's weight-gradient partials -- for jh_rbnet_optim_step to do inside the optimizer's
@@ -1392,14 +1331,14 @@ JH_EXPORT int jh_rbnet_optim_step(jh_rbnet* n, int32_t optimizer, float max_norm
   int rc = rb_flush_grads(n, st);  // whatever is still pending runs as the launch it was
   if (rc) return rc;
   if (max_norm > 0.f) {
-    JH_LAUNCH(jh_rb_gradnorm_kernel, dim3(256), dim3(256), 0, st, n->n_params, n->grads, n->norm_partial);
+    JH_LAUNCH(jh_rb_gradnorm_kernel, dim3(256), dim3(256), 0, st, n->n_params, n->grads, n->core.norm_partial);
     JH_LAUNCH_CHECK();
   }
   static const unsigned kOptGrid = getenv("JH_RB_OPTIM_GRID") ? (unsigned)atoi(getenv("JH_RB_OPTIM_GRID")) : 512u;
   if (optimizer == 0) {
-    JH_LAUNCH(jh_rb_optim_kernel<0>, dim3(kOptGrid + f.extra_wgs), dim3(256), 0, st, n->n_params, n->params, n->grads, n->m, n->v, n->hyper, n->ticket, n->norm_partial, 256, max_norm, f);
+    JH_LAUNCH(jh_rb_optim_kernel<0>, dim3(kOptGrid + f.extra_wgs), dim3(256), 0, st, n->n_params, n->params, n->grads, n->m, n->v, n->opt.hyper, n->opt.ticket, n->core.norm_partial, 256, max_norm, f);
   } else {
-    JH_LAUNCH(jh_rb_optim_kernel<1>, dim3(kOptGrid + f.extra_wgs), dim3(256), 0, st, n->n_params, n->params, n->grads, n->m, n->v, n->hyper, n->ticket, n->norm_partial, 256, max_norm, f);
+    JH_LAUNCH(jh_rb_optim_kernel<1>, dim3(kOptGrid + f.extra_wgs), dim3(256), 0, st, n->n_params, n->params, n->grads, n->m, n->v, n->opt.hyper, n->opt.ticket, n->core.norm_partial, 256, max_norm, f);
   }
   JH_LAUNCH_CHECK();
   return JH_OK;

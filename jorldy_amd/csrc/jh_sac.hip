@@ -225,9 +225,9 @@ JH_EXPORT int jh_sacnet_param_counts_for(int32_t S, int32_t H, int32_t A, int64_
 
 static int sac_init(jh_sacnet* s) {
   jh_acnet* n = &s->ac;
-  int rc = ac_alloc(n, (void**)&s->logp, sizeof(float) * n->maxB, true);
-  if (!rc) rc = ac_alloc(n, (void**)&s->da2, sizeof(float) * n->maxB * n->A, true);
-  if (!rc) rc = ac_alloc(n, (void**)&s->alpha, sizeof(float) * SA_FLOATS, true);
+  int rc = core_alloc(&n->core, "jh_acnet", (void**)&s->logp, sizeof(float) * n->maxB, true);
+  if (!rc) rc = core_alloc(&n->core, "jh_acnet", (void**)&s->da2, sizeof(float) * n->maxB * n->A, true);
+  if (!rc) rc = core_alloc(&n->core, "jh_acnet", (void**)&s->alpha, sizeof(float) * SA_FLOATS, true);
   if (rc) return rc;
   float al[SA_FLOATS] = {0.f};
   const double b1 = 0.9, b2 = 0.999;
@@ -249,7 +249,7 @@ JH_EXPORT int jh_sacnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int
   int rc = ac_init(&s->ac, ctx, S, H, A, 2 * A, 2, max_batch, actor, critics);
   if (!rc) rc = sac_init(s);
   if (rc) {
-    ac_release(&s->ac);
+    core_release(&s->ac.core);
     delete s;
     return rc;
   }
@@ -259,7 +259,7 @@ JH_EXPORT int jh_sacnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int
 
 JH_EXPORT void jh_sacnet_destroy(jh_sacnet* s) {
   if (!s) return;
-  ac_release(&s->ac);
+  core_release(&s->ac.core);
   delete s;
 }
 
@@ -270,9 +270,7 @@ JH_EXPORT int jh_sacnet_segment(const jh_sacnet* s, int32_t i, int64_t* offset, 
   const jh_acnet* n = &s->ac;
   const int A = n->A, H = n->H;
   if (i < SAC_A_WMU || i >= SAC_C_FIRST) {
-    const int k = i < SAC_A_WMU ? i : AC_C_W1 + (i - SAC_C_FIRST);
-    *offset = n->seg_off[k]; *rows = n->seg_rows[k]; *cols = n->seg_cols[k];
-    return JH_OK;
+    return seg_query(n, AC_SEG_COUNT, i < SAC_A_WMU ? i : AC_C_W1 + (i - SAC_C_FIRST), offset, rows, cols);
   }
   const bool weight = i == SAC_A_WMU || i == SAC_A_WLS, second = i >= SAC_A_WLS;
   *offset = weight ? n->seg_off[AC_A_WPI] + (second ? (int64_t)A * H : 0) : n->seg_off[AC_A_BPI] + (second ? A : 0);

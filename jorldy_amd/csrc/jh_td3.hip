@@ -121,7 +121,7 @@ JH_EXPORT int jh_acnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int3
   jh_acnet* n = new jh_acnet();
   int rc = ac_init(n, ctx, S, H, A, A, n_critics, max_batch, actor, critics);
   if (rc) {
-    ac_release(n);
+    core_release(&n->core);
     delete n;
     return rc;
   }
@@ -131,15 +131,13 @@ JH_EXPORT int jh_acnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int3
 
 JH_EXPORT void jh_acnet_destroy(jh_acnet* n) {
   if (!n) return;
-  ac_release(n);
+  core_release(&n->core);
   delete n;
 }
 
 JH_EXPORT int32_t jh_acnet_segment_count(void) { return AC_SEG_COUNT; }
 JH_EXPORT int jh_acnet_segment(const jh_acnet* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols) {
-  JH_ARG(n && i >= 0 && i < AC_SEG_COUNT && offset && rows && cols);
-  *offset = n->seg_off[i]; *rows = n->seg_rows[i]; *cols = n->seg_cols[i];
-  return JH_OK;
+  return seg_query(n, AC_SEG_COUNT, i, offset, rows, cols);
 }
 
 // actor(x) -> d_action [rows][A]; which 0 online / 1 target.  This is what acting uses.

@@ -1074,7 +1074,68 @@ class ControlVec:
         return next_obs, reward, done
 
 
-class RainbowNet:
+class _NetObject:
+    """What RainbowNet, IQNNet and _ActorCriticBuckets share below their architecture: library / device / context, zeroed flat float32
+    buckets, the segment table name -> (offset, rows, cols) read through the native entries `_SYM + name`, and destroy on collection."""
+
+    def _open(self, device):
+        self.lib = L.load()
+        self.device = torch.device(device)
+        self.ctx = L.ctx(self.device.index)
+
+    def _fn(self, name):
+        return getattr(self.lib, self._SYM + name)
+
+    def _zeros(self, n, count=5):
+        return [torch.zeros(n, dtype=torch.float32, device=self.device) for _ in range(count)]
+
+    def _segments(self, names, first=0):
+        seg = {}
+        for i, name in enumerate(names, first):
+            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
+            L.check(self._fn("segment")(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
+            seg[name] = (off.value, rows.value, cols.value)
+        return seg
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self._fn("destroy")(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+def _seg_pairs(flat, seg):
+    """[(name, view of its segment of `flat`: [rows, cols] for a .weight, flat otherwise)] in the table's order."""
+    out = []
+    for name, (off, rows, cols) in seg.items():
+        v = flat[off : off + rows * cols]
+        out.append((name, v.view(rows, cols) if name.endswith(".weight") else v))
+    return out
+
+
+def _export_pairs(pairs):
+    from collections import OrderedDict
+
+    return OrderedDict((k, v.clone(memory_format=torch.contiguous_format)) for k, v in pairs)
+
+
+@torch.no_grad()
+def _import_pairs(pairs, sd, device, shaped=lambda k, v, src: src):
+    """Copy sd[k] into the view v for every (k, v); `shaped` may re-view a source before its shape is checked."""
+    pairs = dict(pairs)
+    missing = [k for k in pairs if k not in sd]
+    if missing:
+        raise KeyError(f"state_dict is missing {missing}")
+    for k, v in pairs.items():
+        src = shaped(k, v, torch.as_tensor(sd[k]).to(device, torch.float32))
+        if tuple(src.shape) != tuple(v.shape):
+            raise ValueError(f"{k}: expected {tuple(v.shape)}, got {tuple(src.shape)}")
+        v.copy_(src)
+
+
+class RainbowNet(_NetObject):
     """jh_rbnet_*: the value networks of the DQN / Rainbow / Ape-X family -- kind "rainbow" (MLP or Nature-CNN
     head -> Linear -> noisy dueling categorical heads), "dueling" (head -> l1_a|l1_v -> l2_a, l2_v) and "q"
     (head -> l -> q) -- with the three learn() forwards, backward and the optimizer step as grouped MFMA GEMM
@@ -1086,12 +1147,11 @@ class RainbowNet:
 
     _SEG = ("w1", "b1", "w2", "b2", "w3", "b3", "wl", "bl", "mu_av1", "sig_av1", "mub_av1", "sigb_av1", "mu_a2", "sig_a2", "mub_a2", "sigb_a2",
             "mu_v2", "sig_v2", "mub_v2", "sigb_v2")
+    _SYM = "jh_rbnet_"
     _KIND = {"rainbow": 0, "dueling": 1, "q": 2, "pv": 2}  # "pv": the discrete policy-value net (policy_value.py:8-22) = head -> l -> (pi | v) stacked into ONE last layer of A + 1 rows
 
     def __init__(self, state_size, action_size, num_support, hidden, head, max_batch, device, kind="rainbow", noise_type="factorized"):
-        self.lib = L.load()
-        self.device = torch.device(device)
-        self.ctx = L.ctx(self.device.index)
+        self._open(device)
         self.kind = kind
         self.cnn = head == "cnn"
         if self.cnn:
@@ -1109,29 +1169,16 @@ class RainbowNet:
         if n <= 0:
             L.check(-2)
         self.n_params = n
-        mk = lambda: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.params, self.target, self.grads, self.m, self.v = mk(), mk(), mk(), mk(), mk()
+        self.params, self.target, self.grads, self.m, self.v = self._zeros(n)
         self.h = C.c_void_p()
         L.check(self.lib.jh_rbnet_create(self.ctx, kid, int(self.cnn), self.Cin, self.Hin, self.Win, self.H, self.A, self.K, self.maxB, L.ptr(self.params),
                                          L.ptr(self.target), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), C.byref(self.h)))
         self.noise_len = int(self.lib.jh_rbnet_noise_len(self.h)) if kind == "rainbow" else 0
-        self.seg = {}
-        for i, name in enumerate(self._SEG):
-            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
-            L.check(self.lib.jh_rbnet_segment(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
-            self.seg[name] = (off.value, rows.value, cols.value)
+        self.seg = self._segments(self._SEG)
         if self.cnn:
             d1 = ((self.Hin - 8) // 4 + 1, (self.Win - 8) // 4 + 1)
             d2 = ((d1[0] - 4) // 2 + 1, (d1[1] - 4) // 2 + 1)
             self.d3 = (d2[0] - 2, d2[1] - 2)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.jh_rbnet_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
     # ---- state_dict <-> private layout ---------------------------------------------------------
     def _v(self, bucket, name):
@@ -1185,29 +1232,17 @@ class RainbowNet:
                     ("q.weight", self._v(bucket, "mu_a2")), ("q.bias", self._v(bucket, "mub_a2").view(-1))]
         return out
 
+    @staticmethod
+    def _is_feat_cols(k, v):
+        return v.dim() == 4 and not k.startswith("head.")
+
     def export_state(self, bucket=None):
-        from collections import OrderedDict
-
         bucket = self.params if bucket is None else bucket
-        sd = OrderedDict()
-        for k, v in self._pairs(bucket):
-            sd[k] = (v.reshape(v.shape[0], -1) if (v.dim() == 4 and not k.startswith("head.")) else v).clone(memory_format=torch.contiguous_format)
-        return sd
+        return _export_pairs((k, v.reshape(v.shape[0], -1) if self._is_feat_cols(k, v) else v) for k, v in self._pairs(bucket))
 
-    @torch.no_grad()
     def import_state(self, sd, bucket=None):
         bucket = self.params if bucket is None else bucket
-        pairs = dict(self._pairs(bucket))
-        missing = [k for k in pairs if k not in sd]
-        if missing:
-            raise KeyError(f"state_dict is missing {missing}")
-        for k, v in pairs.items():
-            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-            if v.dim() == 4 and not k.startswith("head."):
-                src = src.view(v.shape[0], 64, self.d3[0], self.d3[1])
-            if tuple(src.shape) != tuple(v.shape):
-                raise ValueError(f"{k}: expected {tuple(v.shape)}, got {tuple(src.shape)}")
-            v.copy_(src)
+        _import_pairs(self._pairs(bucket), sd, self.device, lambda k, v, src: src.view(v.shape[0], 64, self.d3[0], self.d3[1]) if self._is_feat_cols(k, v) else src)
 
     # ---- engine ---------------------------------------------------------------------------------
     def set_hyper(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0, centered=False):
@@ -1318,7 +1353,7 @@ class RainbowNet:
         L.check(self.lib.jh_rbnet_optim_step(self.h, {"adam": 0, "rmsprop": 1}[optimizer], float(max_norm or 0.0), L.stream_ptr()))
 
 
-class IQNNet:
+class IQNNet(_NetObject):
     """jh_iqnnet_*: the implicit quantile network with an MLP head (network/iqn.py:9-47) -- head.l, state_embed, cosine features of the
     caller's tau draws, sample_embed, Hadamard product, l1, l2, q -- with the three learn() forwards, the backward and Adam as tile-engine
     launches plus the elementwise kernels of jh_iqn.hip.  It presents RainbowNet's surface (flat buckets, export / import in the
@@ -1330,75 +1365,43 @@ class IQNNet:
 
     _SEG = ("head.l.weight", "head.l.bias", "state_embed.weight", "state_embed.bias", "sample_embed.weight", "sample_embed.bias", "l1.weight", "l1.bias",
             "l2.weight", "l2.bias", "q.weight", "q.bias")
+    _SYM = "jh_iqnnet_"
     kind, cnn, noise_len = "iqn", False, 0
 
     def __init__(self, state_size, action_size, embedding_dim, num_sample, hidden, max_batch, device):
-        self.lib = L.load()
-        self.device = torch.device(device)
-        self.ctx = L.ctx(self.device.index)
+        self._open(device)
         self.S, self.A, self.E, self.N, self.H, self.maxB = int(state_size), int(action_size), int(embedding_dim), int(num_sample), int(hidden), int(max_batch)
         self.K = self.N
         self.tau_range, self.tau_inject = (0.0, 1.0), None
-        n = int(self.lib.jh_iqnnet_param_count_for(self.S, self.H, self.E, self.N, self.A))
+        n = int(self._fn("param_count_for")(self.S, self.H, self.E, self.N, self.A))
         if n <= 0:
             L.check(-2)
         self.n_params = n
-        mk = lambda: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.params, self.target, self.grads, self.m, self.v = mk(), mk(), mk(), mk(), mk()
+        self.params, self.target, self.grads, self.m, self.v = self._zeros(n)
         self.h = C.c_void_p()
-        L.check(self.lib.jh_iqnnet_create(self.ctx, self.S, self.H, self.E, self.N, self.A, self.maxB, L.ptr(self.params), L.ptr(self.target), L.ptr(self.grads),
-                                          L.ptr(self.m), L.ptr(self.v), C.byref(self.h)))
-        assert int(self.lib.jh_iqnnet_segment_count()) == len(self._SEG)
-        self.seg = {}
-        for i, name in enumerate(self._SEG):
-            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
-            L.check(self.lib.jh_iqnnet_segment(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
-            self.seg[name] = (off.value, rows.value, cols.value)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.jh_iqnnet_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        L.check(self._fn("create")(self.ctx, self.S, self.H, self.E, self.N, self.A, self.maxB, L.ptr(self.params), L.ptr(self.target), L.ptr(self.grads),
+                                   L.ptr(self.m), L.ptr(self.v), C.byref(self.h)))
+        assert int(self._fn("segment_count")()) == len(self._SEG)
+        self.seg = self._segments(self._SEG)
 
     def _pairs(self, bucket):
         """[(reference key, view of the bucket shaped like the reference tensor)] in the order of the reference module's state_dict."""
-        out = []
-        for name in self._SEG:
-            off, rows, cols = self.seg[name]
-            v = bucket[off : off + rows * cols]
-            out.append((name, v.view(rows, cols) if name.endswith(".weight") else v))
-        return out
+        return _seg_pairs(bucket, self.seg)
 
     def export_state(self, bucket=None):
-        from collections import OrderedDict
+        return _export_pairs(self._pairs(self.params if bucket is None else bucket))
 
-        bucket = self.params if bucket is None else bucket
-        return OrderedDict((k, v.clone()) for k, v in self._pairs(bucket))
-
-    @torch.no_grad()
     def import_state(self, sd, bucket=None):
-        bucket = self.params if bucket is None else bucket
-        pairs = dict(self._pairs(bucket))
-        missing = [k for k in pairs if k not in sd]
-        if missing:
-            raise KeyError(f"state_dict is missing {missing}")
-        for k, v in pairs.items():
-            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-            if tuple(src.shape) != tuple(v.shape):
-                raise ValueError(f"{k}: expected {tuple(v.shape)}, got {tuple(src.shape)}")
-            v.copy_(src)
+        _import_pairs(self._pairs(self.params if bucket is None else bucket), sd, self.device)
 
     def set_hyper(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0, centered=False):
-        L.check(self.lib.jh_iqnnet_set_hyper(self.h, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
+        L.check(self._fn("set_hyper")(self.h, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
 
     def set_lr(self, lr):
-        L.check(self.lib.jh_iqnnet_set_lr(self.h, float(lr), L.stream_ptr()))
+        L.check(self._fn("set_lr")(self.h, float(lr), L.stream_ptr()))
 
     def sync_target(self):
-        L.check(self.lib.jh_iqnnet_sync_target(self.h, L.stream_ptr()))
+        L.check(self._fn("sync_target")(self.h, L.stream_ptr()))
 
     def draw_tau(self, rows, lo=None, hi=None):
         """tau [rows, N] on the device: the injected draw, or uniform in [lo, hi] (default `tau_range`) like the reference's uniform_ (iqn.py:41-45)."""
@@ -1417,7 +1420,7 @@ class IQNNet:
         if out is None:
             out = torch.empty(rows, self.N, self.A, dtype=torch.float32, device=self.device)
         assert out.is_contiguous() and out.numel() == rows * self.N * self.A
-        L.check(self.lib.jh_iqnnet_forward(self.h, int(which), L.ptr(x), rows, L.ptr(tau), L.ptr(out), L.stream_ptr()))
+        L.check(self._fn("forward")(self.h, int(which), L.ptr(x), rows, L.ptr(tau), L.ptr(out), L.stream_ptr()))
         return out
 
     def learn_forward(self, x_all, B, tau, out):
@@ -1425,7 +1428,7 @@ class IQNNet:
         assert x_all.is_contiguous() and x_all.dtype == torch.float32 and int(x_all.shape[0]) == 2 * B
         assert tau.is_contiguous() and tau.dtype == torch.float32 and tau.numel() == 3 * B * self.N
         assert out.is_contiguous() and out.numel() == 3 * B * self.N * self.A
-        L.check(self.lib.jh_iqnnet_learn_forward(self.h, L.ptr(x_all), int(B), L.ptr(tau), L.ptr(out), L.stream_ptr()))
+        L.check(self._fn("learn_forward")(self.h, L.ptr(x_all), int(B), L.ptr(tau), L.ptr(out), L.stream_ptr()))
         return out
 
     def learn_forward_m(self, x_all, B, tau, out):
@@ -1434,19 +1437,19 @@ class IQNNet:
         assert x_all.is_contiguous() and x_all.dtype == torch.float32 and int(x_all.shape[0]) == 2 * B
         assert tau.is_contiguous() and tau.dtype == torch.float32 and tau.numel() == 3 * B * self.N
         assert out.is_contiguous() and out.numel() == 3 * B * self.N * self.A
-        L.check(self.lib.jh_iqnnet_learn_forward_m(self.h, L.ptr(x_all), int(B), L.ptr(tau), L.ptr(out), L.stream_ptr()))
+        L.check(self._fn("learn_forward_m")(self.h, L.ptr(x_all), int(B), L.ptr(tau), L.ptr(out), L.stream_ptr()))
         return out
 
     def backward(self, g, defer=False):
         """g = d(loss)/d(logits of online(state)) [B, N, A]."""
         assert g.is_contiguous() and g.dtype == torch.float32
-        L.check(self.lib.jh_iqnnet_backward(self.h, L.ptr(g), L.stream_ptr()))
+        L.check(self._fn("backward")(self.h, L.ptr(g), L.stream_ptr()))
 
     def optim_step(self, optimizer="adam", max_norm=None):
         """[clip_grad_norm_(max_norm)] + Adam's step."""
         if optimizer != "adam":
             raise ValueError(f"IQNNet has Adam only (every config.iqn.* uses it), got {optimizer!r}")
-        L.check(self.lib.jh_iqnnet_optim_step(self.h, float(max_norm or 0.0), L.stream_ptr()))
+        L.check(self._fn("optim_step")(self.h, float(max_norm or 0.0), L.stream_ptr()))
 
 
 def td3_next_action(z, eps=None, noise_std=0.0, noise_clip=0.0, out=None):
@@ -1499,7 +1502,7 @@ def td3_polyak(params, target, tau):
     return target
 
 
-class _ActorCriticBuckets:
+class _ActorCriticBuckets(_NetObject):
     """What ACNet and SACNet share: an actor and `nc` critics in flat float32 buckets (`self.actor[kind]` of n_actor floats,
     `self.critics[kind]` of nc * n_critic floats, critic c at c * n_critic), the segment tables `aseg` / `cseg` name -> (offset, rows, cols),
     export / import under the reference's state_dict keys, and every native entry the two objects have in common, called as `_SYM + name`.
@@ -1511,37 +1514,18 @@ class _ActorCriticBuckets:
     cnn = False
 
     def __init__(self, state_size, action_size, hidden, n_critics, max_batch, device):
-        self.lib = L.load()
-        self.device = torch.device(device)
-        self.ctx = L.ctx(self.device.index)
+        self._open(device)
         self.S, self.A, self.H, self.nc, self.maxB = int(state_size), int(action_size), int(hidden), int(n_critics), int(max_batch)
         na, ncr = C.c_int64(), C.c_int64()
         L.check(self._fn("param_counts_for")(self.S, self.H, self.A, C.byref(na), C.byref(ncr)))
         self.n_actor, self.n_critic = int(na.value), int(ncr.value)
-        mk = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.actor = {k: mk(self.n_actor) for k in self.AKINDS}
-        self.critics = {k: mk(self.nc * self.n_critic) for k in self.KINDS}
+        self.actor = dict(zip(self.AKINDS, self._zeros(self.n_actor, len(self.AKINDS))))
+        self.critics = dict(zip(self.KINDS, self._zeros(self.nc * self.n_critic)))
         self.h = C.c_void_p()
         L.check(self._fn("create")(self.ctx, *self._create_sizes(), *[L.ptr(self.actor[k]) for k in self.AKINDS], *[L.ptr(self.critics[k]) for k in self.KINDS],
                                    C.byref(self.h)))
-        names = self._ASEG + self._CSEG
-        assert int(self._fn("segment_count")()) == len(names)
-        self.aseg, self.cseg = {}, {}
-        for i, name in enumerate(names):
-            off, rows, cols = C.c_int64(), C.c_int32(), C.c_int32()
-            L.check(self._fn("segment")(self.h, i, C.byref(off), C.byref(rows), C.byref(cols)))
-            (self.aseg if i < len(self._ASEG) else self.cseg)[name] = (off.value, rows.value, cols.value)
-
-    def _fn(self, name):
-        return getattr(self.lib, self._SYM + name)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self._fn("destroy")(self.h)
-                self.h = None
-        except Exception:
-            pass
+        assert int(self._fn("segment_count")()) == len(self._ASEG + self._CSEG)
+        self.aseg, self.cseg = self._segments(self._ASEG), self._segments(self._CSEG, len(self._ASEG))
 
     def set_hyper(self, which, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
         """which: "actor" | "critic" (one Adam for both critics)."""
@@ -1586,29 +1570,13 @@ class _ActorCriticBuckets:
         return self.critics[kind][c * self.n_critic : (c + 1) * self.n_critic]
 
     def _pairs(self, net, kind):
-        flat, seg = self.flat(net, kind), (self.aseg if net == "actor" else self.cseg)
-        out = []
-        for name, (off, rows, cols) in seg.items():
-            v = flat[off : off + rows * cols]
-            out.append((name, v.view(rows, cols) if name.endswith(".weight") else v))
-        return out
+        return _seg_pairs(self.flat(net, kind), self.aseg if net == "actor" else self.cseg)
 
     def export_state(self, net, kind="params"):
-        from collections import OrderedDict
+        return _export_pairs(self._pairs(net, kind))
 
-        return OrderedDict((k, v.clone()) for k, v in self._pairs(net, kind))
-
-    @torch.no_grad()
     def import_state(self, sd, net, kind="params"):
-        pairs = dict(self._pairs(net, kind))
-        missing = [k for k in pairs if k not in sd]
-        if missing:
-            raise KeyError(f"state_dict is missing {missing}")
-        for k, v in pairs.items():
-            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-            if tuple(src.shape) != tuple(v.shape):
-                raise ValueError(f"{k}: expected {tuple(v.shape)}, got {tuple(src.shape)}")
-            v.copy_(src)
+        _import_pairs(self._pairs(net, kind), sd, self.device)
 
 
 class ACNet(_ActorCriticBuckets):

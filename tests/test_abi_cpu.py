@@ -222,3 +222,39 @@ def test_profile_name_mapping_follows_the_engine_tags():
     assert names.rename("void (anonymous namespace)::jh_tgemm_kernel<2, 1, 9>(TGemmBatch)", tags) == "jh_tgemm_stream1_bwd[64x32]"
     assert names.rename("void (anonymous namespace)::jh_tgemm_dma_kernel<16>(TGemmBatch)", tags) == "jh_tgemm_ppo_bwd[dma]"
     assert names.rename("jh_gae_kernel(int, int)", tags) == "jh_gae_kernel(int, int)"
+
+
+def test_param_counts_are_the_padded_sums_of_the_networks_segments(lib):
+    """The *_param_count(s)_for entries are host-only.  Each must return the sum over the network's tensors [rows][cols] of rows * cols
+    rounded up to 4 floats (every segment starts 16-byte aligned), with the tensors written out here from the network definitions
+    (network/{rainbow,dueling,q_network,iqn,policy}.py, head.py) at the smallest shapes that take every branch of each layout."""
+    up4 = lambda x: (x + 3) // 4 * 4
+    total = lambda shapes: sum(up4(r * c) for r, c in shapes)
+    lin = lambda out, inp: [(out, inp), (1, out)]  # weight, bias
+    S, H = 3, 8
+
+    def rbnet(kind, head, F, A, K):
+        if kind in (0, 3):  # rainbow: head -> l -> noisy a1 | v1 stacked -> noisy a2, v2, each a (mu, sig) pair of weights and of biases
+            return head + lin(H, F) + 2 * lin(2 * H, H) + 2 * lin(A * K, H) + 2 * lin(K, H)
+        if kind == 1:  # dueling: head -> l1_a | l1_v stacked -> l2_a, l2_v
+            return head + lin(2 * H, F) + lin(A, H) + lin(1, H)
+        return head + lin(H, F) + lin(A, H)  # q: head -> l -> q
+
+    A = 2
+    for kind, K in ((0, 3), (1, 1), (2, 1), (3, 3)):
+        assert lib.jh_rbnet_param_count_for(kind, 0, S, 0, 0, H, A, K) == total(rbnet(kind, lin(H, S), H, A, K)), kind
+    # Nature-CNN head on 1 x 36 x 36: 8 x 8 stride 4 -> 8 x 8, 4 x 4 stride 2 -> 3 x 3, 3 x 3 -> 1 x 1 x 64 features
+    cnn = lin(32, 1 * 8 * 8) + lin(64, 32 * 4 * 4) + lin(64, 64 * 3 * 3)
+    assert lib.jh_rbnet_param_count_for(0, 1, 1, 36, 36, H, A, 3) == total(rbnet(0, cnn, 64, A, 3))
+    # iqn: head.l, state_embed, sample_embed (reads E cosine features), l1, l2, q
+    E, N, A = 5, 2, 3
+    assert lib.jh_iqnnet_param_count_for(S, H, E, N, A) == total(lin(H, S) + lin(H, H) + lin(H, E) + lin(H, H) + lin(H, H) + lin(A, H))
+    # actor-critic: policy head.l -> l -> pi; critic head.l(s) | e(a) -> l on their concatenation -> q
+    A = 1
+    critic = lin(H, S) + lin(H, A) + lin(H, 2 * H) + lin(1, H)
+    na, nc = C.c_int64(), C.c_int64()
+    assert lib.jh_acnet_param_counts_for(S, H, A, C.byref(na), C.byref(nc)) == 0
+    assert (na.value, nc.value) == (total(lin(H, S) + lin(H, H) + lin(A, H)), total(critic))
+    # SAC's policy ends in mu and log_std, kept as ONE [2A][H] layer and one [2A] bias (include/jorldy_hip.h)
+    assert lib.jh_sacnet_param_counts_for(S, H, A, C.byref(na), C.byref(nc)) == 0
+    assert (na.value, nc.value) == (total(lin(H, S) + lin(H, H) + lin(2 * A, H)), total(critic))
