@@ -561,6 +561,34 @@ int jh_vmpo_loss_continuous(jh_ctx* ctx, int32_t B, int32_t A, const float* d_mu
                             const float* d_log_std_raw_old, float* d_block, const float* d_hyper, float* d_grad_mu_raw,
                             float* d_grad_log_std_raw, float* d_grad_value, float* d_stats, float* d_mask, jh_stream stream);
 
+/* ------------------------------------------------------------------ MPO, discrete policy
+ * core/agent/mpo.py:312-386 between the six forwards and the two backwards, ONE launch of ONE workgroup.  R = batch_size * T rows, row
+ * r = b * T + t (T = n_step with Retrace, 1 for 1step_TD).  float32 [R][A]: d_la / d_la_next / d_la_old = actor logits online(s),
+ * online(s'), target(s); d_q / d_qt / d_qt_next = critic online(s), target(s), target(s').  float32 [R]: d_action (clamped into [0, A)),
+ * d_reward, d_done, d_prob_b (the behaviour policy's probability of the taken action).  With pi = softmax(d_la), pi' = softmax(d_la_next),
+ * pi_old = softmax(d_la_old), every log pi a log-softmax:
+ *   c        = min(pi[a] / (prob_b + 1e-6), 1)                      the ONLINE policy, as the reference (mpo.py:324-330)
+ *   Qret     = reward + gamma sum_a pi' qt_next (1 - done)          (mpo.py:332-339)
+ *   retrace  for t = T - 2 .. 0: Qret[b,t] += gamma c[b,t+1] (Qret[b,t+1] - qt[b,t+1,a[b,t+1]]) (1 - done[b,t])   (mpo.py:347-355), one lane
+ *            per trajectory out of LDS; retrace == 0: skipped
+ *   critic   mean_r (q[r,a] - Qret)^2; d_grad_q[r][a] = 2 (q[r,a] - Qret) / R, zero elsewhere (every entry written)   (mpo.py:360)
+ *   V = sum pi_old qt, At = qt - V, w = softmax(At / eta) taken as a constant; actor = -mean_r sum_a w log pi      (mpo.py:363-368)
+ *   eta_loss = eta eps_eta + eta mean_r L_r, L_r = log sum_a pi_old exp(At / eta) formed around the row's largest At / eta: the reference's
+ *            formula (mpo.py:370-372) wherever its float32 exp is finite, and finite beyond
+ *   KLD = sum pi_old (log pi_old - log pi); alpha_loss = mean[alpha_mu (eps_alpha_mu - KLD) + alpha_mu KLD]          (mpo.py:379-384)
+ *   d_grad_la = ((pi - w) + alpha_mu (pi - pi_old)) / R
+ *   d eta = eps_eta + mean L_r - (1 / eta) mean sum_a u At, u = pi_old exp(At / eta) normalised; d alpha_mu = eps_alpha_mu - mean KLD
+ * d_block is V-MPO's multiplier block (JH_VMPO_BLOCK_FLOATS, layout above) and d_hyper the ACTOR's optimizer block (jh_rbnet_hyper_ptr,
+ * 8-byte aligned, only read): eta and alpha_mu take torch's single-tensor Adam step with its lr, betas, eps and t = step + 1, then their
+ * floors (reset_lgr_muls, mpo.py:416-419), by the code jh_vmpo_loss_* use; alpha_sigma has no gradient for a discrete policy and is left alone.
+ * d_stats optional float32[11] = {actor_loss, critic_loss, eta_loss, alpha_loss, eta', alpha_mu', alpha_sigma (after the step and the
+ * floors), min q, max q, min At, max At over all [R][A] entries}.  Per-row terms in double, every mean a double sum in a fixed order: the
+ * same bits every run.  JH_ERR_ARG, nothing launched: R < 1 or > 1024, T < 1, R % T != 0, A < 2 or A > 64.                         */
+int jh_mpo_loss_discrete(jh_ctx* ctx, int32_t R, int32_t T, int32_t A, const float* d_la, const float* d_la_next, const float* d_la_old,
+                         const float* d_q, const float* d_qt, const float* d_qt_next, const float* d_action, const float* d_reward,
+                         const float* d_done, const float* d_prob_b, float* d_block, const float* d_hyper, float gamma, int32_t retrace,
+                         float* d_grad_la, float* d_grad_q, float* d_stats, jh_stream stream);
+
 /* ------------------------------------------------------------------ native policy-value MLP
  * The encoder of the PPO configs (core/network/head.py:6-18 MLP head + policy_value.py:8-57):
  * S -> H relu -> H relu -> {A logits | A mu, A log_std} + value, as hand-written kernels
@@ -809,6 +837,14 @@ int jh_rbnet_learn_forward(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_
 int jh_rbnet_reserve_target_rows(jh_rbnet* n, int32_t rows);
 int jh_rbnet_learn_forward_m(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits,
                              jh_stream stream);
+/* The three forwards of MPO's discrete actor (mpo.py:312-313, 321): d_x as above -> d_logits [3][B][A][K] = online(state),
+ * online(next_state), target(state): jh_rbnet_learn_forward with the target trunk on the FIRST half of the batch, in as many launches;
+ * jh_rbnet_backward continues from it in the same way.  Kinds 1 and 2 (a noisy network: JH_ERR_ARG); d_noise is ignored.          */
+int jh_rbnet_learn_forward_p(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits,
+                             jh_stream stream);
+/* Device address of the optimizer's hyper block (16 floats: lr, beta1, beta2, eps, steps taken, ..., the betas as doubles at [10:14]),
+ * as jh_pponet_hyper_ptr: what jh_mpo_loss_discrete reads to step the multipliers that sit in the actor's optimizer (mpo.py:142-146). */
+void* jh_rbnet_hyper_ptr(jh_rbnet* n);
 /* jh_rbnet_learn_forward in two halves + the part that does not depend on the batch (rainbow.py:160-186: the three forwards of learn()):
  *   jh_rbnet_prepare_noise  W = mu + sig * eps of the three noisy weight sets (network/utils.py:55-86) for the draw d_noise [3][noise_len]
  *                           -- may run on another stream while the trunk runs (a 12-us launch off the critical path)

@@ -144,6 +144,7 @@ _PROTOS = {
     "jh_sacnet_actor_update": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "jh_vmpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_vmpo_loss_continuous": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_mpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 12 + [_f32, _i32, _vp, _vp, _vp, _vp]),
     "jh_pponet_param_count": (_i64, [_i32, _i32, _i32, _i32]),
     "jh_pponet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_uint64, _pp]),
     "jh_pponet_destroy": (None, [_vp]),
@@ -191,6 +192,8 @@ _PROTOS = {
     "jh_rbnet_learn_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "jh_rbnet_learn_forward_m": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "jh_rbnet_reserve_target_rows": (C.c_int, [_vp, _i32]),
+    "jh_rbnet_learn_forward_p": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "jh_rbnet_hyper_ptr": (_vp, [_vp]),
     "jh_rbnet_prepare_noise": (C.c_int, [_vp, _vp, _vp]),
     "jh_rbnet_learn_trunk": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "jh_rbnet_learn_heads": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),

@@ -6,6 +6,7 @@ from .dqn import DQN, ApeX, Double, Multistep, PER
 from .iqn import IQN
 from .mdqn import MDQN
 from .miqn import MIQN
+from .mpo import MPO
 from .ppo import PPO
 from .qrdqn import QRDQN
 from .rainbow import C51, Rainbow
@@ -14,7 +15,8 @@ from .td3 import TD3
 from .vmpo import VMPO
 
 agent_dict = {"dqn": DQN, "double": Double, "multistep": Multistep, "per": PER, "ape_x": ApeX, "c51": C51, "rainbow": Rainbow, "ppo": PPO, "qrdqn": QRDQN, "m_dqn": MDQN, "iqn": IQN,
-              "m_iqn": MIQN, "td3": TD3, "ddpg": DDPG, "sac": SAC, "vmpo": VMPO}
+              "m_iqn": MIQN, "td3": TD3, "ddpg": DDPG, "sac": SAC, "vmpo": VMPO,
+              "mpo": MPO}
 
 
 def Agent(name, *args, **kwargs):

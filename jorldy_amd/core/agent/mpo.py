@@ -1,0 +1,299 @@
+import os
+from collections import deque
+
+import numpy as np
+import torch
+
+from ... import ops
+from ..buffer import ReplayBuffer
+from ..buffer.base import h2d_small
+from ..network import Network
+from ..optimizer import Optimizer
+from .base import BaseAgent
+from .native_net import NativeNet
+
+MAX_ROWS = 1024  # jh_mpo_loss_discrete: one workgroup, one row of the batch_size x n_step trajectories per thread
+MAX_ACTIONS = 64  # logits per row the loss kernel loops over
+MPO_ELIGIBLE = ("MPO runs on libjorldy_hip only: actor 'discrete_policy' with critic 'discrete_q_network', head 'mlp' with a scalar state_size, "
+                "hidden_size % 4 == 0, optim_config {'name': 'adam', lr, betas, eps}, critic_loss_type in {'retrace', '1step_TD'}, "
+                f"2 <= action_size <= {MAX_ACTIONS} and batch_size * n_step <= {MAX_ROWS} (n_step counts as 1 with '1step_TD'): the Retrace scan and every "
+                "mean of a learn() run inside one workgroup (config.mpo.cartpole / mountaincar / pong_mlagent and their shapes); 'continuous_policy', "
+                "the cnn head and data-parallel learners (grad_sync) are not available for this agent")
+MULTIPLIERS = ("eta", "alpha_mu", "alpha_sigma")
+
+
+class MPO(BaseAgent):
+    """core/agent/mpo.py:14-484 for a discrete policy, on the native engine.
+
+      networks      actor (discrete_policy) and critic (discrete_q_network) have one shape: head -> l -> A outputs.  Each lives in an
+                    ops.RainbowNet of its own (kind "pi" / "q") with its online and target buckets, backward, clip and Adam.  Constructed in
+                    the reference's order (actor, target actor, critic, target critic: mpo.py:93-109), so that one torch.manual_seed gives
+                    the same initial weights.
+      replay        the reference's ReplayBuffer of whole trajectories: every column is [T, dim] per stored row (interact_callback stacks a
+                    sliding window of n_step transitions that is not reset at episode ends, mpo.py:477-484); np.random.randint draws the rows.
+      learn()       gather into ONE contiguous [s; s'] batch of 2R rows (R = batch_size * T) -> the actor's three forwards online(s), online(s'),
+                    target(s) (jh_rbnet_learn_forward_p) -> the critic's online(s), target(s), target(s') (jh_rbnet_learn_forward_m) ->
+                    jh_mpo_loss_discrete (Retrace, the four losses, both head gradients, AND the multipliers' Adam steps and floors on the
+                    device) -> two backwards -> two clip_grad_norm_ + Adam, each over its own network's parameters only (mpo.py:386-395).
+                    One hipGraph after a warm eager call.
+      multipliers   eta, alpha_mu, alpha_sigma live in V-MPO's device block (ops.vmpo_block), stepped by the loss kernel with the ACTOR's lr,
+                    betas, eps and step count (the actor's optimizer holds them, mpo.py:142-146; the cosine decay reaches them through the
+                    actor's hyper block).  Learn k sees them after k - 1 steps.  alpha_sigma has no gradient for a discrete policy.
+      process()     store, then n_epoch learns (each followed by the lr decay) and ONE hard target update of both nets (mpo.py:447-463); the
+                    statistics of the last learn are read back once.
+
+    Departures on purpose: log pi is a log-softmax and eta_loss's log-sum is formed around the row maximum (finite where the reference's float32
+    overflows or underflows, equal elsewhere); act() returns each row's OWN probability where the reference's np.take(pi, action) reads row 0's
+    for every row (identical at one row).  save() / load() are the reference's four keys; the multipliers' VALUES are not part of it (their
+    Adam moments are); save_full / load_full carry the whole block."""
+
+    action_type = "discrete"
+
+    def __init__(self, state_size, action_size, hidden_size=512, optim_config={"name": "adam"}, actor="discrete_policy", critic="discrete_q_network",
+                 head="mlp", buffer_size=50000, batch_size=64, start_train_step=2000, n_epoch=64, n_step=8, clip_grad_norm=1.0, gamma=0.99, run_step=1e6,
+                 lr_decay=True, device=None, critic_loss_type="retrace", num_sample=30, min_eta=1e-8, min_alpha_mu=1e-8, min_alpha_sigma=1e-8, eps_eta=0.01,
+                 eps_alpha_mu=0.01, eps_alpha_sigma=5 * 1e-5, eta=1.0, alpha_mu=1.0, alpha_sigma=1.0, use_graph=True, **kwargs):
+        T = n_step if critic_loss_type == "retrace" else 1
+        ok = (actor == "discrete_policy" and critic == "discrete_q_network" and head == "mlp" and np.isscalar(state_size)
+              and isinstance(hidden_size, (int, np.integer)) and hidden_size % 4 == 0 and isinstance(optim_config, dict)
+              and str(optim_config.get("name", "adam")).lower() == "adam" and set(optim_config) <= {"name", "lr", "betas", "eps"}
+              and critic_loss_type in ("retrace", "1step_TD") and isinstance(action_size, (int, np.integer)) and 2 <= action_size <= MAX_ACTIONS
+              and isinstance(batch_size, (int, np.integer)) and isinstance(T, (int, np.integer)) and batch_size >= 1 and T >= 1 and batch_size * T <= MAX_ROWS
+              and kwargs.get("grad_sync") is None)
+        if not ok:
+            raise ValueError(f"{MPO_ELIGIBLE}; got actor={actor!r}, critic={critic!r}, head={head!r}, state_size={state_size!r}, hidden_size={hidden_size!r}, "
+                             f"optim_config={optim_config!r}, critic_loss_type={critic_loss_type!r}, action_size={action_size!r}, batch_size={batch_size!r}, n_step={n_step!r}")
+        self.device = self._require_gpu(device)
+        self.use_graph = use_graph
+        self.grad_sync = None
+        self.head, self.action_size, self.state_size, self.hidden_size = head, int(action_size), int(state_size), int(hidden_size)
+        self.critic_loss_type = critic_loss_type
+        self.batch_size, self.n_step, self.clip_grad_norm = int(batch_size), int(T), clip_grad_norm
+        R = self.batch_size * self.n_step
+        # mpo.py:93-109: four constructions in this order; the targets' own initialisations are drawn and then overwritten
+        inits = [Network(name, state_size, action_size, D_hidden=hidden_size, head=head) for name in (actor, actor, critic, critic)]
+        self._actor = ops.RainbowNet(state_size, action_size, 1, hidden_size, head, R, self.device, kind="pi")
+        self._critic = ops.RainbowNet(state_size, action_size, 1, hidden_size, head, R, self.device, kind="q")
+        for net, init in ((self._actor, inits[0]), (self._critic, inits[2])):
+            net.import_state(init.state_dict())
+            net.sync_target()
+        self._critic.reserve_target_rows(2 * R)  # target(s) and target(s') share the target slot; allocated here, not inside a captured learn()
+        self._net = self._actor  # BaseAgent.load_full's marker of a native agent
+        self.actor, self.target_actor = NativeNet(self._actor, 0), NativeNet(self._actor, 1)
+        self.critic, self.target_critic = NativeNet(self._critic, 0), NativeNet(self._critic, 1)
+        self.num_learn, self.time_t = 0, 0
+        self.start_train_step, self.n_epoch, self.num_sample = start_train_step, int(n_epoch), num_sample
+        self.min_eta, self.min_alpha_mu, self.min_alpha_sigma = min_eta, min_alpha_mu, min_alpha_sigma
+        self.eps_eta, self.eps_alpha_mu, self.eps_alpha_sigma = eps_eta, eps_alpha_mu, eps_alpha_sigma
+        self._mult = ops.vmpo_block(eta, alpha_mu, alpha_sigma, min_eta, min_alpha_mu, min_alpha_sigma, eps_eta, eps_alpha_mu, eps_alpha_sigma, device=self.device)
+        self._optim_config = dict(optim_config)
+        d = Optimizer(**optim_config, params=[torch.nn.Parameter(torch.zeros(1))]).defaults
+        self._lr0, self._lr_now, self._adam_steps = float(d["lr"]), float(d["lr"]), 0
+        self._set_hyper(d, 0)
+        self.gamma = gamma
+        self.tmp_buffer = deque(maxlen=self.n_step)
+        self.buffer_size = buffer_size
+        self.memory = ReplayBuffer(buffer_size, device=self.device)
+        self.run_step, self.lr_decay = run_step, lr_decay
+        self._stats = torch.zeros(len(ops.MPO_STATS), dtype=torch.float32, device=self.device)
+        self._static, self._graph, self._warm = None, None, False
+
+    def _set_hyper(self, d, steps):
+        for net in (self._actor, self._critic):
+            net.set_hyper(d["lr"], d["betas"][0], d["betas"][1], d["eps"], steps)
+
+    # ---------------------------------------------------------------------------------- the multipliers
+    def multipliers(self):
+        """ops.vmpo_block_read of the device block (synchronises)."""
+        return ops.vmpo_block_read(self._mult)
+
+    eta = property(lambda self: self.multipliers()["eta"]["value"])
+    alpha_mu = property(lambda self: self.multipliers()["alpha_mu"]["value"])
+    alpha_sigma = property(lambda self: self.multipliers()["alpha_sigma"]["value"])
+
+    # ---------------------------------------------------------------------------------- acting
+    @torch.no_grad()
+    def act(self, state, training=True):
+        """mpo.py:158-181, discrete branch; `prob` is each row's own pi[action]."""
+        self.actor.train(training)
+        pi = torch.softmax(self.actor(self.as_tensor(state)), dim=-1)
+        action = torch.multinomial(pi, 1) if training else torch.argmax(pi, dim=-1, keepdim=True)
+        prob = pi.gather(1, action)
+        return {"action": action.cpu().numpy(), "prob": prob.cpu().numpy()}
+
+    def interact_callback(self, transition):
+        """mpo.py:477-484: a sliding window of n_step transitions, every key stacked on axis 1; not reset at episode ends."""
+        _transition = {}
+        self.tmp_buffer.append(transition)
+        if len(self.tmp_buffer) == self.n_step:
+            for key in self.tmp_buffer[0].keys():
+                _transition[key] = np.stack([t[key] for t in self.tmp_buffer], axis=1)
+        return _transition
+
+    # ---------------------------------------------------------------------------------- learn
+    def learning_rate_decay(self, step, optimizers=None, mode="cosine"):
+        """base.py:93-111 on both optimizers; the multipliers follow the actor's block, which the loss kernel reads."""
+        self._lr_now = self._lr0 * float(self._lr_weight(step, mode))
+        self._actor.set_lr(self._lr_now)  # device scalars: the captured graph reads them
+        self._critic.set_lr(self._lr_now)
+
+    def _alloc_static(self):
+        """Fixed-address buffers of one learn(): the sampled rows, the gathered batch as one [s; s'] block, the six outputs, the two gradients."""
+        B, R, A = self.batch_size, self.batch_size * self.n_step, self.action_size
+        idx = torch.zeros(B, dtype=torch.int64, device=self.device)
+        probe = self.memory.gather(idx, as_float=True)
+        for key in ("state", "action", "reward", "next_state", "done", "prob"):
+            if key not in probe:
+                raise KeyError(f"MPO.learn(): the replay has no column {key!r} (act() returns 'prob'; interact_callback stacks the window)")
+        if int(probe["state"].numel()) != R * self.state_size:
+            raise ValueError(f"MPO.learn(): stored trajectories are {tuple(probe['state'].shape[1:])} per row, expected ({self.n_step}, {self.state_size})")
+        x_all = torch.empty(2 * R, self.state_size, dtype=torch.float32, device=self.device)
+        tr = dict(probe)
+        tr["state"], tr["next_state"] = x_all[:R], x_all[R:]
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
+        return dict(idx=idx, tr=tr, store=self.memory._store, x_all=x_all, la=f(3, R, A, 1), lq=f(3, R, A, 1), g_la=f(R, A), g_q=f(R, A))
+
+    def _learn_body(self, st):
+        R, A = self.batch_size * self.n_step, self.action_size
+        tr = self.memory.gather(st["idx"], as_float=True, out=st["tr"])
+        la = self._actor.learn_forward_p(st["x_all"], R, None, st["la"])   # online(s), online(s'), target(s) in shared launches
+        lq = self._critic.learn_forward_m(st["x_all"], R, None, st["lq"])  # online(s), target(s), target(s')
+        g_la, g_q, _ = ops.mpo_loss_discrete(la[0].view(R, A), la[1].view(R, A), la[2].view(R, A), lq[0].view(R, A), lq[1].view(R, A), lq[2].view(R, A),
+                                             tr["action"], tr["reward"], tr["done"], tr["prob"], self.n_step, self._mult, self._actor.hyper_ptr(), self.gamma,
+                                             retrace=self.critic_loss_type == "retrace", stats=self._stats, out=(st["g_la"], st["g_q"]))
+        self._actor.backward(g_la)
+        self._critic.backward(g_q)
+        self._actor.optim_step("adam", self.clip_grad_norm)  # advances the step count the NEXT learn's multiplier step reads
+        self._critic.optim_step("adam", self.clip_grad_norm)
+
+    def _run_learn(self):
+        """DQN._run_learn: sample on the host (eager), then the body -- eagerly the first time, captured into a hipGraph the second, replayed after."""
+        if self.grad_sync is not None:
+            raise NotImplementedError(MPO_ELIGIBLE)
+        if self._static is None or self._static["store"] is not self.memory._store:
+            self._static, self._graph = self._alloc_static(), None
+        st = self._static
+        self.memory.flush()
+        st["idx"].copy_(h2d_small(self.memory.sample_indices(self.batch_size).astype(np.int64), self.device))
+        graphable = self.use_graph and not ops._PROF["lib"] and not getattr(self, "_graph_failed", False)
+        if graphable and self._graph is None and self._warm:
+            try:
+                g = torch.cuda.CUDAGraph()
+                torch.cuda.synchronize()
+                with ops.graph_capture(g):
+                    self._learn_body(st)
+                self._graph = g
+            except Exception as e:
+                self._graph, self._graph_failed, graphable = None, True, False
+                torch.cuda.synchronize()
+                print(f"[jorldy_amd] hipGraph capture of MPO.learn() failed ({type(e).__name__}: {e}); running eagerly")
+        if graphable and self._graph is not None:
+            self._graph.replay()
+        else:
+            self._learn_body(st)
+            self._warm = True
+        self.num_learn += 1
+        self._adam_steps += 1
+
+    def _result(self):
+        s = self._read_stats(self._stats)[0]
+        return {k: float(s[j]) for j, k in enumerate(ops.MPO_STATS)}
+
+    def learn(self):
+        self._run_learn()
+        return self._result()
+
+    def update_target(self):
+        self._actor.sync_target()
+        self._critic.sync_target()
+
+    def process(self, transitions, step):
+        """mpo.py:447-463."""
+        result = {}
+        if transitions:
+            self.memory.store(transitions)
+        self.time_t = step
+        if self.memory.size >= self.batch_size and self.time_t >= self.start_train_step:
+            for _ in range(self.n_epoch):
+                self._run_learn()
+                if self.lr_decay:
+                    self.learning_rate_decay(step)
+            self.update_target()
+            if self.n_epoch > 0:
+                result = self._result()  # the last learn's, as the reference returns; one read-back per process()
+        return result
+
+    # ---------------------------------------------------------------------------------- checkpoint, sync
+    def sync_in(self, weights):
+        self.actor.load_state_dict(weights)
+
+    def sync_out(self, device="cpu"):
+        return {"weights": {k: v.to(device) for k, v in self.actor.state_dict().items()}}
+
+    def _shadow_optimizers(self):
+        """The configured torch optimizers over copies of the parameters: the actor's also holds the three multipliers (mpo.py:142-149)."""
+        out = []
+        for net, extra in ((self._actor, True), (self._critic, False)):
+            sd = net.export_state()
+            params = [torch.nn.Parameter(v) for v in sd.values()]
+            mult = [torch.nn.Parameter(torch.tensor(float(v), device=self.device)) for v in self._mult[:3].tolist()] if extra else []
+            opt = Optimizer(**self._optim_config, params=params + mult)
+            for grp in opt.param_groups:
+                grp["lr"] = self._lr_now
+            out.append((net, opt, params, list(sd.keys()), mult))
+        return out
+
+    def save(self, path):
+        print(f"...Save model to {path}...")
+        ck = {"actor": self.actor.state_dict(), "critic": self.critic.state_dict()}
+        blk = self.multipliers()
+        t = lambda v: torch.tensor(float(v), dtype=torch.float32, device=self.device)
+        for (net, opt, params, keys, mult), name in zip(self._shadow_optimizers(), ("actor_optimizer", "critic_optimizer")):
+            if self._adam_steps > 0:
+                m, v = net.export_state(net.m), net.export_state(net.v)
+                for p, k in zip(params, keys):
+                    opt.state[p] = {"step": torch.tensor(float(self._adam_steps)), "exp_avg": m[k], "exp_avg_sq": v[k]}
+                for p, n in zip(mult, MULTIPLIERS):
+                    if blk[n]["has_state"]:  # alpha_sigma never takes a step: no entry, as in torch's own optimizer
+                        opt.state[p] = {"step": torch.tensor(float(self._adam_steps)), "exp_avg": t(blk[n]["m"]), "exp_avg_sq": t(blk[n]["v"])}
+            ck[name] = opt.state_dict()
+        torch.save(ck, os.path.join(path, "ckpt"))
+
+    def load(self, path):
+        print(f"...Load model from {path}...")
+        ck = torch.load(os.path.join(path, "ckpt"), map_location=self.device, weights_only=False)
+        for view, target, key in ((self.actor, self.target_actor, "actor"), (self.critic, self.target_critic, "critic")):
+            view.load_state_dict(ck[key])
+            target.load_state_dict(ck[key])
+        steps, g0 = 0, None
+        h = self._mult.detach().cpu().numpy().copy()
+        for (net, opt, params, keys, mult), name in zip(self._shadow_optimizers(), ("actor_optimizer", "critic_optimizer")):
+            opt.load_state_dict(ck[name])
+            net.m.zero_()
+            net.v.zero_()
+            if opt.state.get(params[0]):
+                net.import_state({k: opt.state[p]["exp_avg"] for p, k in zip(params, keys)}, net.m)
+                net.import_state({k: opt.state[p]["exp_avg_sq"] for p, k in zip(params, keys)}, net.v)
+                steps = int(float(opt.state[params[0]]["step"]))
+            for j, p in enumerate(mult):  # the moments go into the block; the VALUES are not in the reference's checkpoint and stay
+                stt = opt.state.get(p)
+                h[3 + j], h[6 + j], h[15 + j] = (float(stt["exp_avg"]), float(stt["exp_avg_sq"]), 1.0) if stt else (0.0, 0.0, 0.0)
+            g0 = g0 or opt.param_groups[0]
+        torch.cuda.current_stream().synchronize()
+        self._mult.copy_(torch.from_numpy(h))
+        self._adam_steps, self._lr_now = steps, float(g0["lr"])
+        d = dict(g0)
+        d["lr"] = self._lr_now
+        self._set_hyper(d, steps)
+
+    def _resume_extra_attrs(self):
+        return {"mpo_block": [float(v).hex() for v in self._mult.detach().cpu().numpy().astype(np.float64)]}  # hex: exact, and a NaN survives JSON
+
+    def _resume_load_extra_attrs(self, d):
+        if "mpo_block" in d:
+            h = np.asarray([float.fromhex(v) for v in d["mpo_block"]], dtype=np.float32)
+            torch.cuda.current_stream().synchronize()
+            self._mult.copy_(torch.from_numpy(h))
+
+    def _import_optim_state(self):  # BaseAgent.load_full(): load() already imported the moments
+        pass

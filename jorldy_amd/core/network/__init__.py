@@ -13,6 +13,7 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   deterministic_policy         core/network/policy.py:8-20
   continuous_q_network         core/network/q_network.py:23-39
   continuous_policy            core/network/policy.py:38-55
+  discrete_policy              core/network/policy.py:23-35
 """
 import torch
 
@@ -167,6 +168,18 @@ class DeterministicPolicy(BaseNetwork):
         orthogonal_init(self.pi, "tanh")
 
 
+class DiscretePolicy(BaseNetwork):
+    """The actor of discrete MPO (policy.py:23-35): head -> relu(l) -> softmax(pi).  The shape of discrete_q_network with the last layer
+    named pi and initialised with the policy gain 0.01."""
+
+    def __init__(self, D_in, D_out, D_hidden=512, head="mlp"):
+        super().__init__(D_in, D_hidden, head)
+        self.l = torch.nn.Linear(self.head.D_head_out, D_hidden)
+        self.pi = torch.nn.Linear(D_hidden, D_out)
+        orthogonal_init(self.l)
+        orthogonal_init(self.pi, "policy")
+
+
 class ContinuousPolicy(BaseNetwork):
     """The actor of SAC (policy.py:38-55): head -> relu(l) -> (clamp(mu, -5, 5), exp(tanh(log_std)))."""
 
@@ -204,6 +217,7 @@ network_dict = {
     "deterministic_policy": DeterministicPolicy,
     "continuous_q_network": ContinuousQ_Network,
     "continuous_policy": ContinuousPolicy,
+    "discrete_policy": DiscretePolicy,
 }
 
 

@@ -1161,6 +1161,37 @@ JH_EXPORT int jh_rbnet_learn_forward_m(jh_rbnet* n, const void* d_x, int32_t x_d
   return JH_OK;
 }
 
+// The three forwards of MPO's discrete actor (agent/mpo.py:312-313, 321): d_x = [state; next_state] as for jh_rbnet_learn_forward,
+//   logits[0] = online(state)   logits[1] = online(next_state)   logits[2] = target(state)
+// jh_rbnet_learn_forward with the target trunk on the FIRST half of the batch: the same grouped launches (two jobs per layer), the online
+// activations of the state rows at the start of slot 0, so that jh_rbnet_backward continues from here unchanged.
+JH_EXPORT int jh_rbnet_learn_forward_p(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits, jh_stream stream) {
+  JH_ARG(n && d_x && d_logits);
+  if (n->noisy) return jh_fail(JH_ERR_ARG, "jh_rbnet_learn_forward_p: kinds discrete_q_network and dueling only (a noisy network is no MPO actor)");
+  (void)d_noise;
+  JH_ARG(B > 0 && B <= n->maxB);
+  JH_ARG(x_dtype == JH_U8 || x_dtype == JH_F32);
+  TrunkJob tj[2] = {{n->params, d_x, 2 * B, 0}, {n->target, d_x, B, 1}};
+  int rc = rb_trunk(n, tj, 2, x_dtype == JH_U8, jh_s(stream));
+  if (rc) return rc;
+  n->last_x = d_x; n->last_x_u8 = x_dtype == JH_U8; n->last_B = B;
+  const size_t lsz = (size_t)B * n->NA;
+  float* const* sin = n->has_l ? n->h : n->feat;  // what the streams read
+  HeadJob hj[3] = {{n->params, nullptr, sin[0], d_logits},
+                   {n->params, nullptr, sin[0] + (size_t)B * n->in1, d_logits + lsz},
+                   {n->target, nullptr, sin[1], d_logits + 2 * lsz}};
+  rc = rb_heads(n, hj, 3, B, jh_s(stream));
+  if (rc) return rc;
+  n->last_noise = nullptr;
+  n->raw_heads = 0;
+  n->dx_ready = 0;
+  return JH_OK;
+}
+
+// Device address of the optimizer's hyper block (JH_HY_FLOATS floats: lr, betas, eps, the steps taken so far, ...): what a loss kernel that
+// steps scalars of the same optimizer reads (jh_mpo_loss_discrete: the multipliers sit in the actor's Adam, mpo.py:142-146).
+JH_EXPORT void* jh_rbnet_hyper_ptr(jh_rbnet* n) { return n ? (void*)n->opt.hyper : nullptr; }
+
 static int rb_noisy_grad(jh_rbnet* n, hipStream_t st) {
   int64_t blocks = (n->n_noisy + 255) / 256;
   if (blocks > 1024) blocks = 1024;  // (4096 blocks -- one element per thread -- measured 2.6 us SLOWER at Rainbow's 655 k noisy weights x 3 sets, round 5)

@@ -16,19 +16,9 @@
 // Empty top half (b == 1, or no advantage above the median): as the reference -- no actor gradient, eta_loss = log(mean of nothing) = NaN,
 // and so is the stepped eta (x < floor ? floor : x keeps a NaN, as torch.max does).
 #include "jh_common.h"
+#include "jh_mult.h"  // the multiplier block's layout, block_sums, multiplier_step: shared with jh_mpo.hip
 
 namespace {
-
-enum {
-  VB_VAL = 0,     // eta, alpha_mu, alpha_sigma
-  VB_M = 3,       // exp_avg of the three
-  VB_V = 6,       // exp_avg_sq
-  VB_FLOOR = 9,   // min_eta, min_alpha_mu, min_alpha_sigma
-  VB_EPS = 12,    // eps_eta, eps_alpha_mu, eps_alpha_sigma
-  VB_STATE = 15,  // 1: this multiplier has taken an Adam step (has optimizer state).  alpha_sigma of a discrete policy never does.
-  VB_GRAD = 18,   // the gradients of the last step
-  VB_FLOATS = 24
-};
 
 constexpr float kAtanhLo = -0.99999988f, kAtanhHi = 0.99999988f;  // (float)(1 - 1e-7): the reference clamps the float32 action tensor
 constexpr double kHalfLog2Pi = 0.91893853320467274178;
@@ -53,45 +43,6 @@ struct VmpoArgs {
   float* stats;             // [8] or null
   float* mask;              // [b] or null: 1 where the row is in the top half
 };
-
-// N sums over the workgroup: shuffle tree inside a wave, then the waves' partials in wave order.  Every thread returns with the totals.
-template <int N>
-__device__ __forceinline__ void block_sums(double (&v)[N], double (*red)[8]) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = jh_wave_sum(v[k]);
-  __syncthreads();  // `red` may still be read from the previous use
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) red[wid][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    double r = 0.0;
-    for (int w = 0; w < nw; ++w) r += red[w][k];
-    v[k] = r;
-  }
-}
-
-// torch.optim.Adam (single tensor) on one float32 scalar, then max(x, floor) (jh_sac_actor_seed_kernel's arithmetic: lerp of exp_avg, addcmul
-// of exp_avg_sq, bias corrections and step size in double, rounded once)
-__device__ __forceinline__ float multiplier_step(float* blk, int j, float grad, const float* hyper, float t) {
-  const double b1 = *reinterpret_cast<const double*>(hyper + JH_HY_B1D), b2 = *reinterpret_cast<const double*>(hyper + JH_HY_B2D);
-  const float m = blk[VB_M + j] + (grad - blk[VB_M + j]) * (float)(1.0 - b1);
-  const float v = blk[VB_V + j] * (float)b2 + (float)(1.0 - b2) * grad * grad;
-  const float step_size = (float)((double)hyper[JH_HY_LR] / (1.0 - pow(b1, (double)t)));
-  const float denom = sqrtf(v) / (float)sqrt(1.0 - pow(b2, (double)t)) + hyper[JH_HY_EPS];
-  float x = blk[VB_VAL + j] - step_size * (m / denom);
-  const float floor_j = blk[VB_FLOOR + j];
-  x = x < floor_j ? floor_j : x;  // a NaN stays a NaN (torch.max), which fmaxf would turn into the floor
-  blk[VB_VAL + j] = x;
-  blk[VB_M + j] = m;
-  blk[VB_V + j] = v;
-  blk[VB_STATE + j] = 1.f;
-  blk[VB_GRAD + j] = grad;
-  return x;
-}
 
 template <bool CONT>
 __global__ void __launch_bounds__(kMaxRows) jh_vmpo_loss_kernel(VmpoArgs<CONT> a) {
@@ -245,8 +196,6 @@ static int vmpo_launch(const VmpoArgs<CONT>& a, hipStream_t st) {
 }
 
 }  // namespace
-
-static_assert(VB_FLOATS == JH_VMPO_BLOCK_FLOATS, "the multiplier block of include/jorldy_hip.h");
 
 JH_EXPORT int jh_vmpo_loss_discrete(jh_ctx* ctx, int32_t B, int32_t A, const float* d_logits, const float* d_value_pred, const int64_t* d_idx,
                                     const float* d_action, const float* d_adv, const float* d_value_old, const float* d_logits_old, float* d_block,

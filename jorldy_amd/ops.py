@@ -633,6 +633,36 @@ def vmpo_loss_continuous(mu_raw, log_std_raw, value_pred, idx, action, adv, valu
     return g_mu, g_ls, g_v.view(-1, 1), stats
 
 
+# ============================================================================= MPO
+MPO_STATS = ("actor_loss", "critic_loss", "eta_loss", "alpha_loss", "eta", "alpha_mu", "alpha_sigma", "min_Q", "max_Q", "min_At", "max_At")
+
+
+def mpo_loss_discrete(la, la_next, la_old, q, qt, qt_next, action, reward, done, prob_b, T, block, hyper, gamma, retrace=True, stats=None, out=None):
+    """jh_mpo_loss_discrete: actor logits online(s), online(s'), target(s) and critic online(s), target(s), target(s'), each [R, A] with
+    R = batch * T rows (row b * T + t), the replayed columns [R]; `block` (vmpo_block) is advanced in place with the ACTOR's optimizer block
+    `hyper` (RainbowNet.hyper_ptr() or a vmpo_hyper tensor).  out = (grad_la, grad_q) to write into.
+    -> (grad_la [R, A], grad_q [R, A], stats f32[11] in the order of MPO_STATS)."""
+    t = [_f32(v) for v in (la, la_next, la_old, q, qt, qt_next)]
+    R, A = t[0].shape
+    assert all(tuple(v.shape) == (R, A) for v in t)
+    cols = [_f32(v).reshape(-1) for v in (action, reward, done, prob_b)]
+    assert all(v.numel() == R for v in cols)
+    assert block.dtype == torch.float32 and block.numel() == VMPO_BLOCK_FLOATS and block.is_contiguous()
+    if torch.is_tensor(hyper):
+        assert hyper.dtype == torch.float32 and hyper.numel() >= 16 and hyper.is_contiguous() and hyper.device == t[0].device
+        hyper_ptr = C.c_void_p(hyper.data_ptr())
+    else:
+        hyper_ptr = C.c_void_p(int(hyper))
+    g_la, g_q = out if out is not None else (torch.empty_like(t[0]), torch.empty_like(t[3]))
+    assert g_la.is_contiguous() and g_q.is_contiguous() and g_la.numel() == R * A and g_q.numel() == R * A and g_la.dtype == g_q.dtype == torch.float32
+    if stats is None:
+        stats = torch.zeros(len(MPO_STATS), dtype=torch.float32, device=t[0].device)
+    assert stats.dtype == torch.float32 and stats.numel() >= len(MPO_STATS) and stats.is_contiguous()
+    L.check(L.load().jh_mpo_loss_discrete(L.ctx(_dev(t[0])), R, int(T), A, *(L.ptr(v) for v in t), *(L.ptr(v) for v in cols), L.ptr(block), hyper_ptr, float(gamma),
+                                          int(bool(retrace)), L.ptr(g_la), L.ptr(g_q), L.ptr(stats), L.stream_ptr()))
+    return g_la, g_q, stats
+
+
 # ============================================================================= native policy-value MLP
 class PinnedBuffer:
     """Pinned host memory mapped into the device address space (jh_pinned_alloc): `.np` is the host
@@ -1148,7 +1178,7 @@ class RainbowNet(_NetObject):
     _SEG = ("w1", "b1", "w2", "b2", "w3", "b3", "wl", "bl", "mu_av1", "sig_av1", "mub_av1", "sigb_av1", "mu_a2", "sig_a2", "mub_a2", "sigb_a2",
             "mu_v2", "sig_v2", "mub_v2", "sigb_v2")
     _SYM = "jh_rbnet_"
-    _KIND = {"rainbow": 0, "dueling": 1, "q": 2, "pv": 2}  # "pv": the discrete policy-value net (policy_value.py:8-22) = head -> l -> (pi | v) stacked into ONE last layer of A + 1 rows
+    _KIND = {"rainbow": 0, "dueling": 1, "q": 2, "pv": 2, "pi": 2}  # "pv": the discrete policy-value net (policy_value.py:8-22) = head -> l -> (pi | v) stacked into ONE last layer of A + 1 rows
 
     def __init__(self, state_size, action_size, num_support, hidden, head, max_batch, device, kind="rainbow", noise_type="factorized"):
         self._open(device)
@@ -1227,9 +1257,10 @@ class RainbowNet(_NetObject):
             out += [("l.weight", self._feat_cols(self._v(bucket, "wl"))), ("l.bias", self._v(bucket, "bl").view(-1)),
                     ("pi.weight", w[:n]), ("pi.bias", b[:n]), ("v.weight", w[n:]), ("v.bias", b[n:])]
         else:
+            last = "pi" if self.kind == "pi" else "q"  # "pi": the discrete policy (policy.py:23-35) = a q-network whose last layer is named pi
             out += head
             out += [("l.weight", self._feat_cols(self._v(bucket, "wl"))), ("l.bias", self._v(bucket, "bl").view(-1)),
-                    ("q.weight", self._v(bucket, "mu_a2")), ("q.bias", self._v(bucket, "mub_a2").view(-1))]
+                    (f"{last}.weight", self._v(bucket, "mu_a2")), (f"{last}.bias", self._v(bucket, "mub_a2").view(-1))]
         return out
 
     @staticmethod
@@ -1294,6 +1325,17 @@ class RainbowNet(_NetObject):
         assert x_all.is_contiguous() and out.is_contiguous() and int(x_all.shape[0]) == 2 * B
         L.check(self.lib.jh_rbnet_learn_forward_m(self.h, L.ptr(x_all), self._xdt(x_all), int(B), L.ptr(noise), L.ptr(out), L.stream_ptr()))
         return out
+
+    def learn_forward_p(self, x_all, B, noise, out):
+        """x_all = [state; next_state] (2B rows) -> out [3, B, A, K] = online(state), online(next_state), target(state) (jh_rbnet_learn_forward_p):
+        the forwards of MPO's discrete actor; `backward` continues from it as after `learn_forward`.  q / dueling networks; `noise` is ignored."""
+        assert x_all.is_contiguous() and out.is_contiguous() and int(x_all.shape[0]) == 2 * B
+        L.check(self.lib.jh_rbnet_learn_forward_p(self.h, L.ptr(x_all), self._xdt(x_all), int(B), L.ptr(noise), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def hyper_ptr(self):
+        """Device address of the optimizer's hyper block (jh_rbnet_hyper_ptr): what ops.mpo_loss_discrete takes as `hyper`."""
+        return int(self.lib.jh_rbnet_hyper_ptr(self.h) or 0)
 
     def prepare_noise(self, noise):
         """The three noisy weight sets of learn()'s forwards for the draw `noise` [3, noise_len], on the CURRENT stream (may be a side stream)."""
