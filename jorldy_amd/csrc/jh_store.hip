@@ -188,7 +188,7 @@ bool jh_store_commit_is_one_launch(const jh_store* s, int64_t n) {
 // enqueued before the host has filled them.  Only the one-launch form can wait: bigger commits are refused when a gate is given.
 int jh_store_stage_commit_gated(jh_store* s, int n_extra, const void* const* x_src, void* const* x_dst, const int64_t* x_bytes, const unsigned* gate,
                                 unsigned gate_val, hipStream_t st) {
-  JH_ARG(s != nullptr && n_extra >= 0 && s->n_cols + n_extra <= kCopyJobs);
+  JH_ARG(s != nullptr && n_extra >= 0);
   if (!s->staged) return jh_fail(JH_ERR_STATE, "jh_store_stage_commit without begin");
   const int64_t n = s->staged_n;
   size_t bytes = 0;
@@ -196,6 +196,7 @@ int jh_store_stage_commit_gated(jh_store* s, int n_extra, const void* const* x_s
   const size_t kKernelCommitMax = store_kernel_commit_max();
   if (s->n_cols <= 8 && bytes <= kKernelCommitMax) {
     // small commits (a PPO rollout: 46 KB; Rainbow's 4 deferred rows: 226 KB): one kernel reads the slab in place
+    JH_ARG(s->n_cols + n_extra <= kCopyJobs);  // the launch's job table; the copy-engine form below has none (up to 16 columns)
     const void* src[8];
     for (int c = 0; c < s->n_cols; ++c) src[c] = (const char*)s->staged->dev + s->staged_off[c];
     int rc = store_append_kernel(s, n, src, st, n_extra, x_src, x_dst, x_bytes, gate, gate_val);

@@ -146,7 +146,7 @@ class DeviceStore:
         slots = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
         arrs = []
         for name, dt, elems, _ in self.columns:
-            a = np.ascontiguousarray(np.asarray(cols[name]).reshape(len(cols[name]), -1), dtype=_NP_OF[dt])
+            a = np.ascontiguousarray(np.asarray(cols[name]).reshape(-1, elems), dtype=_NP_OF[dt])  # (an empty call: zero rows)
             assert a.shape == (slots.size, elems)
             arrs.append(a)
         for o in range(0, slots.size, 32768):  # grid.y limit
@@ -203,6 +203,8 @@ class DeviceStore:
                 outs.append(torch.empty((B,) + tuple(shape), dtype=tdt, device=self.device))
             sel.append(i)
             odt.append(_DT[tdt])
+        if B == 0:  # nothing to launch (an empty idx has no device pointer to pass)
+            return dict(zip(names, outs))
         selc = (C.c_int32 * len(sel))(*sel)
         odtc = (C.c_int32 * len(sel))(*odt)
         ptrs = (C.c_void_p * len(sel))(*[o.data_ptr() for o in outs])
