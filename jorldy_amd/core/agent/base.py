@@ -69,6 +69,15 @@ class BaseAgent(ABC):
             for group in opt.param_groups:
                 group["lr"] = opt.defaults["lr"] * weight
 
+    # ---- learn() as hipGraphs: every agent's constructor makes self._learn_graphs = ops.LearnGraphs(...), which owns capture, replay
+    # and the eager fallback; these are read-only views of it
+    _graphs = property(lambda self: self._learn_graphs.graphs)  # {key: captured graph}
+    _graph = property(lambda self: self._learn_graphs.last)     # the graph most recently replayed (None: learn() is running eagerly)
+
+    def reset_graphs(self):
+        """The static buffers, the network or the gradient hook were replaced: the captured graphs hold the old ones' addresses."""
+        self._learn_graphs.reset()
+
     # ---- complete checkpoint (beyond the reference's {"network", "optimizer"} ckpt) -------------------
     _RESUME_ATTRS = ("time_t", "learn_stamp", "num_learn", "epsilon", "beta", "target_update_stamp", "learn_period_stamp",
                      "num_transitions", "_adam_steps")

@@ -62,8 +62,7 @@ class DQN(NativeValueNetMixin, BaseAgent):
         self.clip_grad_norm = None
         self._stats, self._stats_np = self._mapped_stats(4)
         self._static = None
-        self._graph = None
-        self._warm = False
+        self._learn_graphs = ops.LearnGraphs(f"{type(self).__name__}.learn()")
         self._noise = None
         # JH_LEARN_OVERLAP=1 (opt-in, measured SLOWER): learn() as a graph with BRANCHES -- work that nothing on the critical path waits for on
         # a side stream forked from / joined to the learner's stream inside the captured body: the PER priority write-back (per_delta + tree
@@ -149,30 +148,16 @@ class DQN(NativeValueNetMixin, BaseAgent):
 
     def _run_learn(self):
         """Sample on the host (eager), then run the body: eagerly the first time, captured into a hipGraph the second time,
-        replayed after."""
+        replayed after (ops.LearnGraphs)."""
         if self._static is None or self._static["store"] is not self.memory._store:
-            self._static, self._graph = self._alloc_static(), None
+            self._static = self._alloc_static()
+            self.reset_graphs()
         st = self._static
         self.memory.flush()  # held per-step stores -> HBM before anything (possibly a replayed graph) reads the ring
         extra = self._draw(st)
-        graphable = (self.use_graph and (self._noise is None or isinstance(self._noise, str)) and not ops._PROF["lib"] and not getattr(self, "_graph_failed", False)
+        graphable = (self.use_graph and (self._noise is None or isinstance(self._noise, str))
                      and (self.grad_sync is None or (self.graph_with_collective and getattr(self.grad_sync, "capturable", True))))
-        if graphable and self._graph is None and self._warm:
-            try:
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                with ops.graph_capture(g):  # thread_local capture, garbage collector held off, stream restored if it fails
-                    self._learn_body(st)
-                self._graph = g
-            except Exception as e:
-                self._graph, self._graph_failed, graphable = None, True, False
-                torch.cuda.synchronize()
-                print(f"[jorldy_amd] hipGraph capture of {type(self).__name__}.learn() failed ({type(e).__name__}: {e}); running eagerly")
-        if graphable and self._graph is not None:
-            self._graph.replay()
-        else:
-            self._learn_body(st)
-            self._warm = True
+        self._learn_graphs.run("learn", lambda: self._learn_body(st), graphable)
         self.num_learn += 1
         self._adam_steps += 1
         return extra

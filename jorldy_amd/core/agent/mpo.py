@@ -96,7 +96,7 @@ class MPO(BaseAgent):
         self.memory = ReplayBuffer(buffer_size, device=self.device)
         self.run_step, self.lr_decay = run_step, lr_decay
         self._stats = torch.zeros(len(ops.MPO_STATS), dtype=torch.float32, device=self.device)
-        self._static, self._graph, self._warm = None, None, False
+        self._static, self._learn_graphs = None, ops.LearnGraphs("MPO.learn()")
 
     def _set_hyper(self, d, steps):
         for net in (self._actor, self._critic):
@@ -167,31 +167,16 @@ class MPO(BaseAgent):
         self._critic.optim_step("adam", self.clip_grad_norm)
 
     def _run_learn(self):
-        """DQN._run_learn: sample on the host (eager), then the body -- eagerly the first time, captured into a hipGraph the second, replayed after."""
+        """Sample on the host (eager), then the body: eagerly the first time, captured into a hipGraph the second, replayed after (ops.LearnGraphs)."""
         if self.grad_sync is not None:
             raise NotImplementedError(MPO_ELIGIBLE)
         if self._static is None or self._static["store"] is not self.memory._store:
-            self._static, self._graph = self._alloc_static(), None
+            self._static = self._alloc_static()
+            self.reset_graphs()
         st = self._static
         self.memory.flush()
         st["idx"].copy_(h2d_small(self.memory.sample_indices(self.batch_size).astype(np.int64), self.device))
-        graphable = self.use_graph and not ops._PROF["lib"] and not getattr(self, "_graph_failed", False)
-        if graphable and self._graph is None and self._warm:
-            try:
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                with ops.graph_capture(g):
-                    self._learn_body(st)
-                self._graph = g
-            except Exception as e:
-                self._graph, self._graph_failed, graphable = None, True, False
-                torch.cuda.synchronize()
-                print(f"[jorldy_amd] hipGraph capture of MPO.learn() failed ({type(e).__name__}: {e}); running eagerly")
-        if graphable and self._graph is not None:
-            self._graph.replay()
-        else:
-            self._learn_body(st)
-            self._warm = True
+        self._learn_graphs.run("learn", lambda: self._learn_body(st), self.use_graph)
         self.num_learn += 1
         self._adam_steps += 1
 

@@ -105,7 +105,7 @@ class PPO(BaseAgent):
         # eager launches if the capture is refused)
         self.graph_with_collective = os.environ.get("JH_GRAPH_DP", "1") == "1"
         self._net = None
-        self._graph = None
+        self._learn_graphs = ops.LearnGraphs("learn()")
         self._static = None
         self._adam_steps = 0
         self._captured = 0            # rows whose heads / values the collector delivered for the next learn() (jh_collector_set_capture)
@@ -161,7 +161,8 @@ class PPO(BaseAgent):
         net.set_hyper(self.optimizer.param_groups[0]["lr"], d["betas"][0], d["betas"][1], d["eps"], step=float(self._adam_steps))
         torch.cuda.synchronize()
         self._drop_rides()
-        self._net, self._graph, self._static, self._graphs = net, None, None, {}
+        self._net, self._static = net, None
+        self.reset_graphs()
 
     # ---------------------------------------------------------------------------------- act
     @torch.no_grad()
@@ -240,7 +241,8 @@ class PPO(BaseAgent):
         self._grow_native(2 * M if 2 * M <= 8192 else M)
         if self._static is None or self._static["M"] != M:
             self._drop_rides()
-            self._static, self._graphs = self._alloc_static(M), {}
+            self._static = self._alloc_static(M)
+            self.reset_graphs()
         st = self._static
         return st["h0"], st["h1"], st["value"], st["next_value"]
 
@@ -275,10 +277,10 @@ class PPO(BaseAgent):
         st["idx_ev"][k] = ev
         return True
 
-    def _enqueue_learn(self, st):
+    def _enqueue_learn(self, st, captured=False):
         """Everything between `memory.sample()` and the result read-back, as stream work only (no host
         sync, no allocation outside torch's graph-private pool): capturable."""
-        self._enqueue_pre(st)
+        self._enqueue_pre(st, captured)
         self._enqueue_main(st)
 
     def _enqueue_pre(self, st, captured=False):
@@ -371,6 +373,12 @@ class PPO(BaseAgent):
                 net.adam_step(self.clip_grad_norm)
                 k += 1
 
+    @property
+    def _graph(self):
+        """What learn() last replayed: the shared "main" graph where one exists, else the key's own."""
+        last = self._learn_graphs.last
+        return None if last is None else self._graphs.get("main", last)
+
     def _learn_native(self):
         self._learn_launch()
         return self._learn_finish()
@@ -380,7 +388,7 @@ class PPO(BaseAgent):
         the begin / process_begin / loop / process_end form; before that, process() (capturing a graph synchronises the device, which
         must not happen while a rollout's acting kernel is waiting for this thread's observations)."""
         st = self._static
-        return bool(st is not None and st["idx_ready"] and ("one", True) in getattr(self, "_graphs", {}) and self._predraw is not None and self._predraw.valid)
+        return bool(st is not None and st["idx_ready"] and ("one", True) in self._graphs and self._predraw is not None and self._predraw.valid)
 
     def _learn_launch(self, allow_capture=True):
         """Enqueue one learn() (everything up to and including the launches); `_learn_finish` does the host work behind them and reads
@@ -390,7 +398,8 @@ class PPO(BaseAgent):
         self._grow_native(2 * M if 2 * M <= 8192 else M)
         if self._static is None or self._static["M"] != M:
             self._drop_rides()
-            self._static, self._graphs = self._alloc_static(M), {}
+            self._static = self._alloc_static(M)
+            self.reset_graphs()
         st = self._static
         E = self.n_epoch
         captured = self._captured == M
@@ -413,7 +422,7 @@ class PPO(BaseAgent):
         if pin is not None:  # arrival markers: one element of EACH 16-byte granule of the last update's row (critic and c2: means of squares, never -1)
             pin.np[st["n_upd"] - 1, 2] = -1.0
             pin.np[st["n_upd"] - 1, 7] = -1.0
-        graphable = (self.use_graph and not ops._PROF["on"] and not ops._PROF["lib"] and not getattr(self, "_graph_failed", False)
+        graphable = (self.use_graph and not ops._PROF["on"]
                      and (self.grad_sync is None or (self.graph_with_collective and getattr(self.grad_sync, "capturable", True))))
         # index lists: pre-drawn behind the previous learn() and already uploaded (np_rng.Predraw) when np.random has not been
         # touched since -- then ONE graph holds the whole learn(); otherwise drawn now, between the pre-phase and the minibatch
@@ -422,55 +431,24 @@ class PPO(BaseAgent):
         st["idx_ready"] = False
         split = not have_idx and os.environ.get("JH_PPO_SPLIT_GRAPH", "1") == "1"
         key = ("split" if split else "one", captured)
-        graphs = getattr(self, "_graphs", None)
-        if graphs is None:
-            graphs = self._graphs = {}
-        warm = getattr(self, "_warm_keys", None)
-        if warm is None:
-            warm = self._warm_keys = set()
-        if graphable and allow_capture and key not in graphs and key in warm:
-            try:
-                torch.cuda.synchronize()
-                if split:
-                    gp = torch.cuda.CUDAGraph()
-                    with ops.graph_capture(gp):
-                        self._enqueue_pre(st, captured)
-                    if "main" not in graphs:
-                        g = torch.cuda.CUDAGraph()
-                        with ops.graph_capture(g):  # thread_local: other threads (batched actors, staging ring) keep issuing HIP work on their own streams
-                            self._enqueue_main(st)
-                        graphs["main"] = g
-                    graphs[key] = gp
-                else:
-                    g = torch.cuda.CUDAGraph()
-                    with ops.graph_capture(g):
-                        self._enqueue_pre(st, captured)
-                        self._enqueue_main(st)
-                    graphs[key] = g  # capture does not execute: replay below runs this iteration's update
-            except Exception as e:  # e.g. a collective that cannot be captured: stay eager from now on
-                graphs.clear()
-                self._graph_failed, graphable = True, False
-                torch.cuda.synchronize()
-                import traceback
-
-                print(f"[jorldy_amd] hipGraph capture of learn() failed ({type(e).__name__}: {e}); running eagerly\n{traceback.format_exc()}")
-        if graphable and key in graphs:
+        # split: the pre-phase graph of this key and the "main" graph that every split key shares, captured together or not at all
+        lg, pre = self._learn_graphs, lambda: self._enqueue_pre(st, captured)
+        bodies = {key: pre, "main": lambda: self._enqueue_main(st)} if split else {key: lambda: self._enqueue_learn(st, captured)}
+        if lg.ready(key, bodies, graphable, warm_key=key, capture=allow_capture):
             if split:
-                graphs[key].replay()  # the GPU works on the no-grad passes / GAE ...
-                shuffles()            # ... while the host shuffles
-                graphs["main"].replay()
+                lg.replay(key)  # the GPU works on the no-grad passes / GAE ...
+                shuffles()      # ... while the host shuffles
+                lg.replay("main")
             else:
                 if not have_idx:
                     shuffles()
-                graphs[key].replay()
-            self._graph = graphs.get("main", graphs[key])
+                lg.replay(key)
         else:
-            self._enqueue_pre(st, captured)
+            pre()
             if not have_idx:
                 shuffles()
             self._enqueue_main(st)
-            warm.add(key)
-            self._warm = True
+            lg.warm.add(key)
         self.memory._store.clear()
         self._adam_steps += st["n_upd"]
         self._launched = (st, pin, M, E)

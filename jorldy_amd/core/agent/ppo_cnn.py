@@ -71,7 +71,7 @@ class PPOConv(NativeValueNetMixin, PPO):
         self.dp_exact_critic = os.environ.get("JH_DP_EXACT_CRITIC", "1") == "1"
         self.backend, self.use_graph = "native", use_graph
         self.graph_with_collective = os.environ.get("JH_GRAPH_DP", "1") == "1"
-        self._graph, self._graphs, self._static, self._stats = None, {}, None, None
+        self._learn_graphs, self._static, self._stats = ops.LearnGraphs("PPO(cnn).learn()"), None, None
         self._seed, self._act_ctr = int(seed), 0
         self._ride, self._ride_wait = None, {}  # (PPO._upload_idx: nothing rides on a collector's commit launch here)
         # the reference's initialisation (orthogonal, utils.py:110-124) drawn by the reference's module on the host, then moved into the library's bucket
@@ -174,34 +174,17 @@ class PPOConv(NativeValueNetMixin, PPO):
     def learn(self):
         M, E = self.memory.size, self.n_epoch
         if self._static is None or self._static["M"] != M:
-            self._static, self._graphs = self._alloc_static(M), {}
+            self._static = self._alloc_static(M)
+            self.reset_graphs()
         st = self._static
         if st.get("store") is not self.memory._store:  # the rollout store was replaced (it grows by doubling): a captured graph holds the old one's addresses
-            st["store"], self._graphs, self._graph = self.memory._store, {}, None
-        graphable = (self.use_graph and not ops._PROF["on"] and not ops._PROF["lib"] and not getattr(self, "_graph_failed", False)
+            st["store"] = self.memory._store
+            self.reset_graphs()
+        graphable = (self.use_graph and not ops._PROF["on"]
                      and (self.grad_sync is None or (self.graph_with_collective and getattr(self.grad_sync, "capturable", True))))
-        if graphable and "learn" not in self._graphs and getattr(self, "_warm", False):
-            try:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with ops.graph_capture(g):
-                    self._enqueue_pre(st)
-                    self._enqueue_main(st)
-                self._graphs["learn"] = g
-            except Exception as e:
-                self._graphs.clear()
-                self._graph_failed, graphable = True, False
-                torch.cuda.synchronize()
-                print(f"[jorldy_amd] hipGraph capture of PPO(cnn).learn() failed ({type(e).__name__}: {e}); running eagerly")
         # the reference's global-RNG shuffles (ppo.py:118) of all epochs, drawn before the launches (nothing else touches np.random inside learn())
         self._upload_idx(st, lambda out: np_rng.epoch_shuffles(M, E, out))
-        if graphable and "learn" in self._graphs:
-            self._graphs["learn"].replay()
-            self._graph = self._graphs["learn"]
-        else:
-            self._enqueue_pre(st)
-            self._enqueue_main(st)
-            self._warm = True
+        self._learn_graphs.run("learn", lambda: self._enqueue_learn(st), graphable)
         self.memory._store.clear()
         self._adam_steps += st["n_upd"]
         s = self._read_stats(st["stats"])[0].astype(np.float64)  # the only host sync of learn()

@@ -124,7 +124,7 @@ class DeterministicActorCritic(BaseAgent):
         self.lr_decay = lr_decay
         self._noise_inject = None  # test hook: the standard normals of the next learn() ([B, A]; SAC [2, B, A]) instead of torch.randn
         self._stats, self._stats_np = self._mapped_stats(self.N_STATS)  # critic: loss_1, loss_2, max_Q, mark; then the actor update's, its mark last
-        self._static, self._graphs, self._warm = None, {}, False
+        self._static, self._learn_graphs = None, ops.LearnGraphs(f"{type(self).__name__}.learn()")
 
     # ------------------------------------------------------------------------------------------ acting
     @torch.no_grad()
@@ -169,29 +169,13 @@ class DeterministicActorCritic(BaseAgent):
         """Sample on the host (eager), then run the body: eagerly the first time (and whenever `capture` is off for this variant), captured
         into a hipGraph of its own per variant on first use after that, replayed from then on."""
         if self._static is None or self._static["store"] is not self.memory._store:
-            self._static, self._graphs = self._alloc_static(), {}
+            self._static = self._alloc_static()
+            self.reset_graphs()
         st = self._static
         self.memory.flush()
         self._draw(st)
-        key = (actor_step, soft)
-        graphable = self.use_graph and capture and not ops._PROF["lib"] and not getattr(self, "_graph_failed", False)
-        if graphable and key not in self._graphs and self._warm:
-            try:
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                with ops.graph_capture(g):
-                    self._learn_body(st, actor_step, soft)
-                self._graphs[key] = g
-            except Exception as e:
-                self._graph_failed, graphable = True, False
-                self._graphs.pop(key, None)
-                torch.cuda.synchronize()
-                print(f"[jorldy_amd] hipGraph capture of {type(self).__name__}.learn() failed ({type(e).__name__}: {e}); running eagerly")
-        if graphable and key in self._graphs:
-            self._graphs[key].replay()
-        else:
-            self._learn_body(st, actor_step, soft)
-            self._warm = True
+        # one graph per variant; the variants share one warm-up (the first learn() of any of them)
+        self._learn_graphs.run((actor_step, soft), lambda: self._learn_body(st, actor_step, soft), self.use_graph and capture, warm_key="learn")
         self._adam_steps_critic += 1
         self._adam_steps_actor += int(actor_step)
 

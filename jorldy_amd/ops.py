@@ -913,6 +913,59 @@ def graph_capture(g):
             gc.enable()
 
 
+class LearnGraphs:
+    """The hipGraph lifecycle of an agent's learn(), the same for every agent: a body runs eagerly the first time (that warms it), is
+    captured the next time it is eligible, and is replayed from then on.  A capture that raises (e.g. a collective that refuses capture)
+    is synchronised away and reported once, and the agent stays eager for good.  A captured graph holds the addresses of the static
+    buffers it was captured on: whoever replaces them calls reset()."""
+
+    def __init__(self, what):
+        self.what, self.graphs, self.warm, self.failed, self.last = what, {}, set(), False, None  # last: the graph most recently replayed
+
+    def reset(self):
+        """Drop the graphs; what has run eagerly once stays warm."""
+        self.graphs.clear()
+        self.last = None
+
+    def ready(self, key, bodies, eligible, warm_key, capture=True):
+        """May this call replay `key`?  First captures `bodies` ({key: body}; those not held yet, all or none) when that is due: `key` is
+        eligible, warm and not captured, and `capture` is on (a capture synchronises the device; a caller that cannot have that now
+        still replays what it holds)."""
+        usable = eligible and not self.failed and not _PROF["lib"]
+        if usable and capture and key not in self.graphs and warm_key in self.warm:
+            try:
+                new = {}
+                torch.cuda.synchronize()
+                for k, body in bodies.items():
+                    if k not in self.graphs:
+                        new[k] = torch.cuda.CUDAGraph()
+                        with graph_capture(new[k]):  # capture does not execute: the replay that follows runs this call's update
+                            body()
+                self.graphs.update(new)
+            except Exception as e:
+                self.reset()
+                self.failed = True
+                torch.cuda.synchronize()
+                print(f"[jorldy_amd] hipGraph capture of {self.what} failed ({type(e).__name__}: {e}); running eagerly")
+                return False
+        return bool(usable and key in self.graphs)
+
+    def replay(self, key):
+        self.last = self.graphs[key]
+        self.last.replay()
+
+    def run(self, key, body, eligible=True, warm_key=None):
+        """Run `body` eagerly, or capture it and / or replay its graph; -> was it a replay.  `warm_key`: what the eager run warms and a
+        capture waits for (default: `key` itself; variants that share one warm-up pass one name)."""
+        warm_key = key if warm_key is None else warm_key
+        if self.ready(key, {key: body}, eligible, warm_key):
+            self.replay(key)
+            return True
+        body()
+        self.warm.add(warm_key)
+        return False
+
+
 def c51_loss(logit, target_logit, action, reward, done, v_min, v_max, gamma, next_logit_online=None, weights=None, alpha=0.0, n_step=0, shift_max=False, stats=None):
     """logit/target_logit/next_logit_online [B,A,K].  Returns (grad_logit, prio [B], kl [B], stats f32[8])."""
     lib = L.load()

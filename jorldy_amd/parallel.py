@@ -330,9 +330,7 @@ def attach_data_parallel(agent, dist, group=None):
         mem.attach_shards(dist, group, transport)
     agent.grad_sync = sync
     agent.graph_with_collective = bool(getattr(agent, "graph_with_collective", True)) and transport.capturable
-    agent._graph = None
-    if hasattr(agent, "_graphs"):
-        agent._graphs = {}
+    agent.reset_graphs()  # captured without the collective
     return sync
 
 

@@ -614,7 +614,8 @@ def test_rainbow_learn_at_atari_shapes_graph_replay(use_graph):
             d[tag] = (torch.randn(i).cuda(), torch.randn(o).cuda())
         noise.append(d)
     agent._noise = "static"
-    agent._static, agent._graph = agent._alloc_static(), None
+    agent._static = agent._alloc_static()
+    agent.reset_graphs()
     for rep in range(3):
         agent.network.load_state_dict(w0)
         agent.target_network.load_state_dict(wt)

@@ -432,18 +432,42 @@ def test_td3_graph_replay_equals_eager_over_all_three_variants():
         torch.manual_seed(0)
         agent = _loaded_agent(fx, use_graph=use_graph, run_step=1000)
         np.random.seed(7)
-        out = []
+        out, held = [], []
         for it in range(6):
             r = agent.learn()
             agent.learning_rate_decay(10 * (it + 1))
             out.append([r[k] for k in ("critic_loss1", "critic_loss2", "actor_loss", "max_Q")])
-        if use_graph:
-            assert set(agent._graphs) == {(False, False), (True, True)}, f"captured variants: {sorted(agent._graphs)}"
+            held.append(sorted(agent._graphs))
+        if use_graph:  # learn 0 eager (its variant never comes again), 1 and 2 captured, 3 onwards replayed
+            assert held == [[], [(False, False)]] + [[(False, False), (True, True)]] * 4, f"captured variants, learn by learn: {held}"
         else:
-            assert not agent._graphs
+            assert held == [[]] * 6
         res.append((out, torch.cat([agent._net.actor["params"], agent._net.actor["target"], agent._net.critics["params"], agent._net.critics["target"]]).clone()))
     np.testing.assert_allclose(res[0][0], res[1][0], rtol=1e-5)
     torch.testing.assert_close(res[0][1], res[1][1], rtol=1e-5, atol=1e-6)
+
+
+def test_failed_capture_falls_back_to_eager(monkeypatch, capsys):
+    """Four learns whose capture raises (before any stream enters capture) == four learns of an agent that never captures, bit for bit; the agent
+    says so once, holds no graph and stays eager."""
+    from jorldy_amd import ops
+    from tests.util import refuse_capture
+
+    monkeypatch.setattr(ops, "graph_capture", refuse_capture)
+    fx = D.Fixture(load("td3"))
+    res = []
+    for use_graph in (True, False):
+        torch.manual_seed(0)
+        agent = _loaded_agent(fx, use_graph=use_graph, run_step=1000)
+        np.random.seed(7)
+        out = [agent.learn() for _ in range(4)]
+        torch.cuda.synchronize()
+        assert not agent._graphs and agent._learn_graphs.failed == use_graph
+        res.append((out, torch.cat([agent._net.actor["params"], agent._net.actor["target"], agent._net.critics["params"], agent._net.critics["target"]]).clone()))
+    assert res[0][0] == res[1][0] and torch.equal(res[0][1], res[1][1])
+    printed = capsys.readouterr().out
+    assert printed.count("running eagerly") == 1
+    assert "[jorldy_amd] hipGraph capture of TD3.learn() failed (RuntimeError: capture refused); running eagerly" in printed
 
 
 def test_ddpg_graph_replay_equals_eager():
@@ -453,11 +477,12 @@ def test_ddpg_graph_replay_equals_eager():
         torch.manual_seed(0)
         agent = _loaded_agent(fx, use_graph=use_graph, run_step=1000)
         np.random.seed(7)
-        out = []
+        out, held = [], []
         for it in range(4):
             r = agent.process([fx.buffer()[it]], 10 * (it + 1))  # learn + lr decay + the soft update of process()
             out.append([r[k] for k in ("critic_loss", "actor_loss", "max_Q")])
-        assert set(agent._graphs) == ({(True, False)} if use_graph else set())
+            held.append(sorted(agent._graphs))
+        assert held == ([[]] + [[(True, False)]] * 3 if use_graph else [[]] * 4), f"captured variants, learn by learn: {held}"
         res.append((out, torch.cat([agent._net.actor["params"], agent._net.actor["target"], agent._net.critics["params"], agent._net.critics["target"]]).clone()))
     np.testing.assert_allclose(res[0][0], res[1][0], rtol=1e-5)
     torch.testing.assert_close(res[0][1], res[1][1], rtol=1e-5, atol=1e-6)

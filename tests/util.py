@@ -1,3 +1,4 @@
+import contextlib
 import os
 
 import numpy as np
@@ -26,3 +27,10 @@ def f32(a):
 
 def npy(t):
     return t.detach().cpu().numpy()
+
+
+@contextlib.contextmanager
+def refuse_capture(g):
+    """Stands in for ops.graph_capture: raises before any stream enters capture (nothing happens on the device)."""
+    raise RuntimeError("capture refused")
+    yield
