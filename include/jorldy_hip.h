@@ -784,6 +784,8 @@ int jh_normal_fill(jh_ctx* ctx, int64_t n, float* d_out, uint64_t* d_state, jh_s
  *   kind 3  rainbow with independent Gaussian noise (utils.py:72-79): one draw per weight instead of the outer product
  *   kind 1  dueling  core/network/dueling.py:8-35: head -> l1_a|l1_v -> l2_a, l2_v -> dueling combine  (K = 1)
  *   kind 2  q        core/network/q_network.py:8-20: head -> l -> q                                    (K = 1)
+ *   kind 4  noisy    core/network/noisy.py:8-50: head -> relu(noisy(F -> H)) -> noisy(H -> A), factorised noise   (K = 1)
+ *   kind 5  noisy with independent Gaussian noise (utils.py:72-79)
  * on core/network/head.py:6-61 (MLP or Nature-CNN head), plus the three forwards / backward / optimizer step
  * of the agents' learn() (rainbow.py:160-186,236-238; dqn.py:128-147; ape_x.py:96-131).  Convolutions are
  * implicit GEMMs on the fp32 MFMA; uint8 NCHW frames are read straight from the replay store (divide by 255
@@ -794,7 +796,11 @@ int jh_normal_fill(jh_ctx* ctx, int64_t n, float* d_out, uint64_t* d_state, jh_s
  *   6 l.weight [H][F] (cnn: F ordered (y,x,c))   7 l.bias                         (kinds 0, 2)
  *   8 first stream layer, a|v stacked [2H][in] (in = H, or F for kind 1; rainbow: mu_w^T)   9 sig_w   10 bias [2H]   11 sig_b
  *   12-15 a2 / l2_a / q: weight [A*K][H], sig_w, bias, sig_b        16-19 v2 / l2_v: weight [K][H], sig_w, bias, sig_b
- * (sig_* only for kind 0).                                                                              */
+ * (sig_* only for kinds 0, 3, 4, 5).
+ * Kinds 4 / 5 (network/noisy.py:15-20, utils.py:55-107) have no segment 6 / 7 and no 16-19; their two noisy layers use the slots
+ *   8 mu_w1^T [H][F] (F = H for the mlp head, 64 * P3 ordered (y,x,c) for the cnn head)   9 sig_w1^T   10 mu_b1 [H]   11 sig_b1
+ *   12 mu_w2^T [A][H]   13 sig_w2^T   14 mu_b2 [A]   15 sig_b2
+ * each padded up to 4 floats like every segment; jh_rbnet_param_count_for(4 | 5, ...) is the padded sum.               */
 typedef struct jh_rbnet jh_rbnet;
 int64_t jh_rbnet_param_count_for(int32_t kind, int32_t head_cnn, int32_t channels_or_state_size, int32_t height, int32_t width,
                                  int32_t hidden, int32_t action_size, int32_t num_support);
@@ -810,7 +816,10 @@ int32_t jh_rbnet_segment_count(void);
 int jh_rbnet_segment(const jh_rbnet* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols);
 /* Length of one noise set (kind 0): N(0,1) draws in the reference's draw order (utils.py:58-60, layers a1, v1,
  * a2, v2): [e_in a1 H][e_out a1 H][e_in v1 H][e_out v1 H][e_in a2 H][e_out a2 A*K][e_in v2 H][e_out v2 K];
- * kind 3: per layer [eps_w (in x out, row-major like the reference's mu_w)][eps_b (out)]                   */
+ * kind 3: per layer [eps_w (in x out, row-major like the reference's mu_w)][eps_b (out)]
+ * kind 4: [eps_i1 F][eps_j1 H][eps_i2 H][eps_j2 A];   kind 5: [eps_w1 F x H (in, out)][eps_b1 H][eps_w2 H x A][eps_b2 A].
+ *   eps_i1[k] and the rows of eps_w1 are indexed by the REFERENCE's feature index k (cnn head: (c, y, x), head.py:58), not by the stored
+ *   column (y, x, c): the kernels apply the permutation the weights' columns get on import.                              */
 int64_t jh_rbnet_noise_len(const jh_rbnet* n);
 /* Adam: (lr, beta1, beta2, eps).  RMSprop: (lr, alpha, unused, eps) + centered.  step = optimizer step counter. */
 int jh_rbnet_set_hyper(jh_rbnet* n, double lr, double beta1_or_alpha, double beta2, double eps, int64_t step, int32_t centered,
@@ -842,6 +851,15 @@ int jh_rbnet_learn_forward_m(jh_rbnet* n, const void* d_x, int32_t x_dtype, int3
  * jh_rbnet_backward continues from it in the same way.  Kinds 1 and 2 (a noisy network: JH_ERR_ARG); d_noise is ignored.          */
 int jh_rbnet_learn_forward_p(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits,
                              jh_stream stream);
+/* The two forwards of Noisy.learn() (agent/noisy.py:83-105), kinds 4 / 5 only: d_x as above, d_noise [2][noise_len] -> d_logits [2][B][A] =
+ * online(state; noise 0), target(next_state; noise 1).  The online trunk runs over the first B rows only and the target trunk over the last
+ * B rows only, in shared launches; jh_rbnet_backward[_deferred] continues from it.  jh_rbnet_learn_forward, _m, _p, jh_rbnet_learn_trunk /
+ * _heads, jh_rbnet_prepare_noise and jh_rbnet_c51_step answer JH_ERR_ARG for these kinds.                                            */
+int jh_rbnet_learn_forward_n(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits,
+                             jh_stream stream);
+/* Noisy.get_sig_w_mean (network/noisy.py:46-50) of the online parameters, kinds 4 / 5: d_out2 = {mean |sig_w1|, mean |sig_w2|} (device or
+ * device-mapped memory) in one launch whose summation order is fixed (a graph replay returns the bits of the eager call).           */
+int jh_rbnet_sig_abs_mean(jh_rbnet* n, float* d_out2, jh_stream stream);
 /* Device address of the optimizer's hyper block (16 floats: lr, beta1, beta2, eps, steps taken, ..., the betas as doubles at [10:14]),
  * as jh_pponet_hyper_ptr: what jh_mpo_loss_discrete reads to step the multipliers that sit in the actor's optimizer (mpo.py:142-146). */
 void* jh_rbnet_hyper_ptr(jh_rbnet* n);
@@ -869,7 +887,8 @@ int jh_rbnet_learn_heads_raw(jh_rbnet* n, int32_t B, const float* d_noise, jh_st
 int jh_rbnet_c51_step(jh_rbnet* n, jh_per* per, int32_t B, int32_t n_step, int32_t flags, const float* d_action, const float* d_reward,
                       const float* d_done, const float* d_weights, const int64_t* d_tree_idx, float v_min, float v_max, float gamma,
                       float alpha, float* d_logits, float* d_prio, float* d_kl, float* d_stats, jh_stream stream);
-/* jh_rbnet_backward that leaves two elementwise tails undone -- d(sigma) = d(mu) * eps of the noisy layers (network/utils.py:60-70) and
+/* (kinds 4 / 5: the tail left undone is d(sigma) = d(mu) * eps of the two noisy layers, one launch in jh_rbnet_flush_grads / jh_rbnet_optim_step.)
+ * jh_rbnet_backward that leaves two elementwise tails undone -- d(sigma) = d(mu) * eps of the noisy layers (network/utils.py:60-70) and
  * the sum of conv1's weight-gradient partials -- for jh_rbnet_optim_step to do inside the optimizer's own pass (no clipping) or as the
  * launches they were (clipping).  jh_rbnet_flush_grads completes the gradient bucket for anybody who reads it before the optimizer step
  * (a data-parallel all-reduce).                                                                                                       */

@@ -193,6 +193,8 @@ _PROTOS = {
     "jh_rbnet_learn_forward_m": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "jh_rbnet_reserve_target_rows": (C.c_int, [_vp, _i32]),
     "jh_rbnet_learn_forward_p": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "jh_rbnet_learn_forward_n": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "jh_rbnet_sig_abs_mean": (C.c_int, [_vp, _vp, _vp]),
     "jh_rbnet_hyper_ptr": (_vp, [_vp]),
     "jh_rbnet_prepare_noise": (C.c_int, [_vp, _vp, _vp]),
     "jh_rbnet_learn_trunk": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),

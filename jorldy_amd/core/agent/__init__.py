@@ -3,10 +3,12 @@ Keys match the reference's auto-registered snake_case class names."""
 from .base import BaseAgent
 from .ddpg import DDPG
 from .dqn import DQN, ApeX, Double, Multistep, PER
+from .dueling import Dueling
 from .iqn import IQN
 from .mdqn import MDQN
 from .miqn import MIQN
 from .mpo import MPO
+from .noisy import Noisy
 from .ppo import PPO
 from .qrdqn import QRDQN
 from .rainbow import C51, Rainbow
@@ -16,7 +18,7 @@ from .vmpo import VMPO
 
 agent_dict = {"dqn": DQN, "double": Double, "multistep": Multistep, "per": PER, "ape_x": ApeX, "c51": C51, "rainbow": Rainbow, "ppo": PPO, "qrdqn": QRDQN, "m_dqn": MDQN, "iqn": IQN,
               "m_iqn": MIQN, "td3": TD3, "ddpg": DDPG, "sac": SAC, "vmpo": VMPO,
-              "mpo": MPO}
+              "mpo": MPO, "noisy": Noisy, "dueling": Dueling}
 
 
 def Agent(name, *args, **kwargs):

@@ -78,7 +78,8 @@ class NativeNet:
     def pack_noise(self, noise, out=None):
         """{tag: (e_in, e_out)} / {tag: (eps_w [in, out], eps_b)} (the parity fixtures' injection format for factorised /
         independent noise) -> one flat noise set."""
-        flat = torch.cat([torch.cat([noise[t][0].reshape(-1), noise[t][1].reshape(-1)]) for t in ("a1", "v1", "a2", "v2")]).to(self._net.device, torch.float32)
+        tags = ("l1", "l2") if self._net.kind == "noisy" else ("a1", "v1", "a2", "v2")  # network/noisy.py's two layers | rainbow.py's four
+        flat = torch.cat([torch.cat([noise[t][0].reshape(-1), noise[t][1].reshape(-1)]) for t in tags]).to(self._net.device, torch.float32)
         assert flat.numel() == self._net.noise_len
         if out is not None:
             out.copy_(flat)
@@ -90,7 +91,7 @@ class NativeNet:
         net = self._net
         x = x.contiguous()
         nz = None
-        if net.kind == "rainbow" and is_train:
+        if net.noise_len > 0 and is_train:
             nz = self.pack_noise(noise) if noise is not None else torch.randn(net.noise_len, device=net.device)
         outs = [net.forward(x[o : o + net.maxB], self._which, nz) for o in range(0, x.shape[0], net.maxB)]  # one noise draw per call, like the reference
         out = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
@@ -163,7 +164,7 @@ class NativeValueNetMixin:
             self._actbuf = a
         np.copyto(a["x_pin"].numpy(), x, casting="same_kind")
         a["x_dev"].copy_(a["x_pin"], non_blocking=True)
-        nz = torch.randn(net.noise_len, device=net.device) if (net.kind == "rainbow" and is_train) else None
+        nz = torch.randn(net.noise_len, device=net.device) if (net.noise_len > 0 and is_train) else None
         net.forward(a["x_dev"], 0, nz, out=a["logits"])
         a["am"].np[:] = -1  # arrival marks (actions are >= 0)
         self._act_kernel(a["logits"].view(N, A, K), (a["act_dev"], a["q_dev"]))
@@ -197,7 +198,7 @@ class NativeValueNetMixin:
         tr["state"], tr["next_state"] = x_all[:B], x_all[B:]  # one contiguous [state; next_state] batch
         st = dict(idx=idx, w=torch.ones(B, dtype=torch.float32, device=self.device), tr=tr, store=self.memory._store, x_all=x_all,
                   logits=torch.empty(3, B, self._net.A, self._net.K, dtype=torch.float32, device=self.device))
-        if self._net.kind == "rainbow":
+        if self._net.noise_len > 0:
             st["noise"] = torch.zeros(3, self._net.noise_len, dtype=torch.float32, device=self.device)
         return st
 
@@ -255,3 +256,33 @@ class NativeValueNetMixin:
 
     def _import_optim_state(self):  # BaseAgent.load_full(): load() already imported the moments
         pass
+
+
+class NoiseDrawMixin:
+    """What the agents with NoisyNet layers (Rainbow, Noisy) share around their learn(): the independent noise draws of its forwards and the
+    noise stream's place in a resume checkpoint.  `self._noise`: None = the device source; a list of per-forward draws in NativeNet.pack_noise's
+    format (parity tests; forces the eager path); "static" = the test wrote st["noise"] itself (replayable)."""
+
+    def _draw_noise(self, st):
+        """One independent draw per forward of learn() -> st["noise"] [forwards, noise_len]."""
+        if self._noise is None:
+            if getattr(self, "_normal", None) is None:
+                self._normal = ops.NormalSource(self.device)
+            self._normal.fill(st["noise"])
+        elif self._noise != "static":  # "static": the test wrote the draws into st["noise"] itself (replayable: nothing to do here)
+            for i in range(st["noise"].shape[0]):
+                self.network.pack_noise(self._noise[i], st["noise"][i])
+
+    def _resume_extra_attrs(self):
+        """The learner's noise stream (ops.NormalSource: seed + call counter in device memory): without it a resumed run would
+        re-seed from torch's generator and draw other NoisyNet noise than the uninterrupted one."""
+        src = getattr(self, "_normal", None)
+        if src is None:
+            return {}
+        st = src.state.cpu().tolist()
+        return {"normal_source": [str(int(v)) for v in st]}
+
+    def _resume_load_extra_attrs(self, d):
+        if "normal_source" in d and self._net is not None:
+            self._normal = ops.NormalSource(self.device, seed=0)
+            self._normal.state.copy_(torch.tensor([int(v) for v in d["normal_source"]], dtype=torch.int64))

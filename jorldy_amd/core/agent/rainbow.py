@@ -8,7 +8,7 @@ from ... import ops
 from ..buffer import PERBuffer
 from ..network import Network
 from .dqn import DQN
-from .native_net import require_native
+from .native_net import NoiseDrawMixin, require_native
 
 
 class C51(DQN):
@@ -60,7 +60,7 @@ class C51(DQN):
         return {"loss": float(s[0]), "epsilon": self.epsilon, "max_Q": float(s[1]), "max_logit": float(s[2]), "min_logit": float(s[3])}
 
 
-class Rainbow(DQN):
+class Rainbow(NoiseDrawMixin, DQN):
     """core/agent/rainbow.py:14-308: noisy dueling categorical net, n-step double-Q projection, PER
     with priorities KL^alpha.  The projection + KL + backward-to-logits + priorities are one HIP
     kernel (jh_c51_loss); priorities go straight into the device sum tree (no B `.item()` syncs).
@@ -141,16 +141,8 @@ class Rainbow(DQN):
     def _idx_offset(self):
         return self.memory.first_leaf_index
 
-    # ---- plumbing: native_net.NativeValueNetMixin via DQN -------------------
-    def _draw_noise(self, st):
-        """Three independent draws: network(s), network(s'), target_network(s') (rainbow.py:160-186) -> st["noise"]."""
-        if self._noise is None:
-            if getattr(self, "_normal", None) is None:
-                self._normal = ops.NormalSource(self.device)
-            self._normal.fill(st["noise"])
-        elif self._noise != "static":  # "static": the test wrote the draws into st["noise"] itself (replayable: nothing to do here)
-            for i in range(3):
-                self.network.pack_noise(self._noise[i], st["noise"][i])
+    # ---- plumbing: native_net.NativeValueNetMixin via DQN; the noise draws (network(s), network(s'), target_network(s'), rainbow.py:160-186)
+    # and the noise stream's place in a resume checkpoint: native_net.NoiseDrawMixin
 
     def _learn_body(self, st):
         net, B = self._net, self.batch_size
@@ -189,20 +181,6 @@ class Rainbow(DQN):
         net.optim_step(self._opt_name, self.clip_grad_norm)
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
-
-    def _resume_extra_attrs(self):
-        """The learner's noise stream (ops.NormalSource: seed + call counter in device memory): without it a resumed run would
-        re-seed from torch's generator and draw other NoisyNet noise than the uninterrupted one."""
-        src = getattr(self, "_normal", None)
-        if src is None:
-            return {}
-        st = src.state.cpu().tolist()
-        return {"normal_source": [str(int(v)) for v in st]}
-
-    def _resume_load_extra_attrs(self, d):
-        if "normal_source" in d and self._net is not None:
-            self._normal = ops.NormalSource(self.device, seed=0)
-            self._normal.state.copy_(torch.tensor([int(v) for v in d["normal_source"]], dtype=torch.int64))
 
     def learn(self):
         s, p = self._learn_stats(self._stats8_np, (5, 7), self._stats8)

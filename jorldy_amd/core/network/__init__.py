@@ -9,6 +9,7 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   continuous_policy_value      core/network/policy_value.py:38-57
   dueling                      core/network/dueling.py:8-35
   rainbow                      core/network/rainbow.py:8-94 (+ utils.py:55-107 noisy linear)
+  noisy                        core/network/noisy.py:8-50 (+ utils.py:89-107 init_weights)
   iqn                          core/network/iqn.py:9-47
   deterministic_policy         core/network/policy.py:8-20
   continuous_q_network         core/network/q_network.py:23-39
@@ -141,6 +142,33 @@ class Rainbow(BaseNetwork):
         orthogonal_init(self.l)
 
 
+def _init_weights(shape, noise_type):
+    """core/network/utils.py:89-107 call for call: mu_w, mu_b, sig_w, sig_b are each filled by a `uniform_` in this order -- the constant sigma
+    fills draw from the generator too, so the next layer's mu sees the reference's stream."""
+    if noise_type == "factorized":
+        mu_init, sig_init = 1.0 / (shape[0] ** 0.5), 0.5 / (shape[0] ** 0.5)
+    else:
+        mu_init, sig_init = (3.0 / shape[0]) ** 0.5, 0.017
+    mu_w, sig_w = torch.nn.Parameter(torch.empty(shape)), torch.nn.Parameter(torch.empty(shape))
+    mu_b, sig_b = torch.nn.Parameter(torch.empty(shape[1])), torch.nn.Parameter(torch.empty(shape[1]))
+    mu_w.data.uniform_(-mu_init, mu_init)
+    mu_b.data.uniform_(-mu_init, mu_init)
+    sig_w.data.uniform_(sig_init, sig_init)
+    sig_b.data.uniform_(sig_init, sig_init)
+    return mu_w, sig_w, mu_b, sig_b
+
+
+class Noisy(BaseNetwork):
+    """NoisyNet Q-network (noisy.py:8-20): head -> noisy(D_head_out -> D_hidden) -> noisy(D_hidden -> D_out)."""
+
+    def __init__(self, D_in, D_out, noise_type="factorized", D_hidden=512, head="mlp"):
+        assert noise_type in ["independent", "factorized"]
+        super().__init__(D_in, D_hidden, head)
+        self.noise_type = noise_type
+        self.mu_w1, self.sig_w1, self.mu_b1, self.sig_b1 = _init_weights((self.head.D_head_out, D_hidden), noise_type)
+        self.mu_w2, self.sig_w2, self.mu_b2, self.sig_b2 = _init_weights((D_hidden, D_out), noise_type)
+
+
 class IQN(BaseNetwork):
     """Implicit quantile network (iqn.py:9-24).  The reference's orthogonal_init call names sample_embed twice and state_embed never
     (iqn.py:23): state_embed keeps nn.Linear's default initialisation, and so it does here."""
@@ -213,6 +241,7 @@ network_dict = {
     "continuous_policy_value": ContinuousPolicyValue,
     "dueling": Dueling,
     "rainbow": Rainbow,
+    "noisy": Noisy,
     "iqn": IQN,
     "deterministic_policy": DeterministicPolicy,
     "continuous_q_network": ContinuousQ_Network,

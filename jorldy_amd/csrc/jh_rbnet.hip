@@ -2,7 +2,8 @@
 //   kind 0 / 3  rainbow  -> Linear -> noisy dueling categorical heads (factorised / independent noise)
 //   kind 1      dueling  -> l1_a | l1_v -> l2_a, l2_v -> dueling combine
 //   kind 2      q        -> Linear -> q
-//   reference: core/network/rainbow.py:8-94, dueling.py:8-35, q_network.py:8-20, head.py:6-61 (MLP / CNN),
+//   kind 4 / 5  noisy    -> noisy(F -> H) -> noisy(H -> A) (factorised / independent noise; the two forwards of Noisy.learn)
+//   reference: core/network/rainbow.py:8-94, dueling.py:8-35, q_network.py:8-20, noisy.py:8-50, head.py:6-61 (MLP / CNN),
 //              utils.py:55-107 (noisy linear); the three forwards + backward + optimizer step of one learn()
 //              (core/agent/rainbow.py:154-253, dqn.py:128-147, ape_x.py:96-131).
 //
@@ -112,6 +113,149 @@ __global__ void __launch_bounds__(256) jh_rb_noisy_grad_kernel(NoisyDims d, cons
     float eps;
     noisy_locate(d, i, e, &pm, &ps, &wo, &eps);
     G[ps] = G[pm] * eps;
+  }
+}
+
+// ---------------------------------------------------------------------------------- the NoisyNet Q-network (kinds 4 / 5)
+// network/noisy.py:8-50: head -> relu(noisy(F -> H)) -> noisy(H -> A); the first noisy layer reads the head's FEATURES.  One noise set in the
+// reference's draw order (utils.py:58-60, 75-76, layer 1 then layer 2):
+//   factorised   [eps_i1 F][eps_j1 H][eps_i2 H][eps_j2 A]
+//   independent  [eps_w1 F x H (in, out)][eps_b1 H][eps_w2 H x A][eps_b2 A]
+// eps_i1 / the rows of eps_w1 are indexed by the REFERENCE's feature index: on the cnn head the stored column k = (y, x, c) of layer 1 is the
+// reference's feature c * P3 + (y, x) (head.py:58 flattens NCHW) -- the permutation ops.py applies to the weights' columns (_feat_cols).
+struct NzDims {
+  int H, F, A, P3, independent;                                             // P3 > 0: cnn head with P3 feature pixels
+  int64_t p_mu1, p_sig1, p_mub1, p_sigb1, p_mu2, p_sig2, p_mub2, p_sigb2;  // offsets in a parameter / gradient bucket
+  int64_t o_w1, o_b1, o_w2, o_b2;                                          // offsets in one effective-weight set
+};
+__device__ __forceinline__ int nz_ref_col(const NzDims& d, int k) { return d.P3 ? (k & 63) * d.P3 + (k >> 6) : k; }
+// eps of the stored weights [n][k .. k + 3] of layer 0 | 1 (e != null)
+__device__ __forceinline__ float4 nz_eps4(const NzDims& d, const float* __restrict__ e, int layer, int n, int k) {
+  float r[4];
+  if (layer == 0) {
+    if (d.independent) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r[q] = e[(int64_t)nz_ref_col(d, k + q) * d.H + n];
+    } else {
+      const float fj = noise_f(e[d.F + n]);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r[q] = noise_f(e[nz_ref_col(d, k + q)]) * fj;  // torch.outer(f_i, f_j)
+    }
+  } else {
+    if (d.independent) {
+      const float* w2 = e + (int64_t)d.F * d.H + d.H;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r[q] = w2[(int64_t)(k + q) * d.A + n];
+    } else {
+      const float fj = noise_f(e[d.F + 2 * d.H + n]);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r[q] = noise_f(e[d.F + d.H + k + q]) * fj;
+    }
+  }
+  return make_float4(r[0], r[1], r[2], r[3]);
+}
+// eps_b of bias i of [b1 H | b2 A]: f_j of the output unit (utils.py:68) / its own draw (utils.py:76)
+__device__ __forceinline__ float nz_eps_b(const NzDims& d, const float* __restrict__ e, int i) {
+  if (d.independent) return i < d.H ? e[(int64_t)d.F * d.H + i] : e[(int64_t)d.F * d.H + d.H + (int64_t)d.H * d.A + (i - d.H)];
+  return noise_f(i < d.H ? e[d.F + i] : e[d.F + 2 * d.H + (i - d.H)]);
+}
+// Items of one pass over the two layers: H F / 4 + A H / 4 float4s along the STORED rows (F, H % 4 == 0: a float4 never straddles a row, and
+// consecutive lanes take consecutive 16 bytes of mu / sig / W), then the H + A biases.
+struct NzItem {
+  int layer, n, k;       // weights: row, first of four columns
+  int64_t off;           // inside the layer's [rows][cols] matrix
+};
+__device__ __forceinline__ NzItem nz_item(const NzDims& d, int i, int n1) {
+  NzItem it;
+  it.layer = i >= n1;
+  const int j = it.layer ? i - n1 : i, c4 = (it.layer ? d.H : d.F) >> 2;
+  it.n = j / c4;
+  it.k = 4 * (j - it.n * c4);
+  it.off = 4 * (int64_t)j;
+  return it;
+}
+struct NzSets {
+  const float* params[2];
+  const float* noise[2];  // null: W = mu (is_train False)
+  float* weff[2];
+};
+// W = mu + sig * eps for the (parameter set, draw) pairs of a learn() (online | state, target | next_state) or the one of an act()
+__global__ void __launch_bounds__(256) jh_nz_weff_kernel(NzDims d, NzSets s, int n_w4, int n_items) {
+  const int set = blockIdx.y;
+  const float* __restrict__ P = s.params[set];
+  const float* __restrict__ e = s.noise[set];
+  float* __restrict__ W = s.weff[set];
+  const int n1 = d.H * (d.F >> 2);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n_items; i += gridDim.x * 256) {
+    if (i < n_w4) {
+      const NzItem it = nz_item(d, i, n1);
+      float4 w = *reinterpret_cast<const float4*>(P + (it.layer ? d.p_mu2 : d.p_mu1) + it.off);
+      if (e) {
+        const float4 sg = *reinterpret_cast<const float4*>(P + (it.layer ? d.p_sig2 : d.p_sig1) + it.off);
+        const float4 ep = nz_eps4(d, e, it.layer, it.n, it.k);
+        w.x = w.x + sg.x * ep.x; w.y = w.y + sg.y * ep.y; w.z = w.z + sg.z * ep.z; w.w = w.w + sg.w * ep.w;
+      }
+      *reinterpret_cast<float4*>(W + (it.layer ? d.o_w2 : d.o_w1) + it.off) = w;
+    } else {
+      const int b = i - n_w4, l2 = b >= d.H, bi = l2 ? b - d.H : b;
+      const float mu = P[(l2 ? d.p_mub2 : d.p_mub1) + bi];
+      W[(l2 ? d.o_b2 : d.o_b1) + bi] = e ? mu + P[(l2 ? d.p_sigb2 : d.p_sigb1) + bi] * nz_eps_b(d, e, b) : mu;
+    }
+  }
+}
+// d(sig) = d(W) * eps with the same indexing; d(mu) = d(W) was written in place by the weight-gradient GEMMs
+__global__ void __launch_bounds__(256) jh_nz_sig_grad_kernel(NzDims d, const float* __restrict__ e, float* __restrict__ G, int n_w4, int n_items) {
+  const int n1 = d.H * (d.F >> 2);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n_items; i += gridDim.x * 256) {
+    if (i < n_w4) {
+      const NzItem it = nz_item(d, i, n1);
+      const float4 g = *reinterpret_cast<const float4*>(G + (it.layer ? d.p_mu2 : d.p_mu1) + it.off);
+      const float4 ep = nz_eps4(d, e, it.layer, it.n, it.k);
+      *reinterpret_cast<float4*>(G + (it.layer ? d.p_sig2 : d.p_sig1) + it.off) = make_float4(g.x * ep.x, g.y * ep.y, g.z * ep.z, g.w * ep.w);
+    } else {
+      const int b = i - n_w4, l2 = b >= d.H, bi = l2 ? b - d.H : b;
+      G[(l2 ? d.p_sigb2 : d.p_sigb1) + bi] = G[(l2 ? d.p_mub2 : d.p_mub1) + bi] * nz_eps_b(d, e, b);
+    }
+  }
+}
+// Noisy.get_sig_w_mean (network/noisy.py:46-50): out2 = {mean |sig_w1|, mean |sig_w2|} in one launch.  Workgroups [0, g1) sum slices of sig_w1,
+// the others of sig_w2 (wave64 butterflies, then the waves in order); the last workgroup to arrive adds the partials -- thread t takes
+// partial t, the same butterflies --: the order of every addition is fixed by the grid alone, so a replay gives the bits of the eager call.
+__global__ void __launch_bounds__(256) jh_nz_sig_abs_mean_kernel(const float* __restrict__ sig1, int n1_4, const float* __restrict__ sig2, int n2_4, int g1,
+                                                                 float* __restrict__ partial, unsigned* __restrict__ ticket, float* __restrict__ out2) {
+  __shared__ float s_red[16];
+  __shared__ int s_last;
+  const int second = (int)blockIdx.x >= g1;
+  const float4* p = reinterpret_cast<const float4*>(second ? sig2 : sig1);
+  const int n4 = second ? n2_4 : n1_4, wg = second ? blockIdx.x - g1 : blockIdx.x, stride = (second ? (int)gridDim.x - g1 : g1) * 256;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  int i = wg * 256 + threadIdx.x;
+  for (; i + 3 * stride < n4; i += 4 * stride) {
+    const float4 v0 = p[i], v1 = p[i + stride], v2 = p[i + 2 * stride], v3 = p[i + 3 * stride];
+    a0 += (fabsf(v0.x) + fabsf(v0.y)) + (fabsf(v0.z) + fabsf(v0.w));
+    a1 += (fabsf(v1.x) + fabsf(v1.y)) + (fabsf(v1.z) + fabsf(v1.w));
+    a2 += (fabsf(v2.x) + fabsf(v2.y)) + (fabsf(v2.z) + fabsf(v2.w));
+    a3 += (fabsf(v3.x) + fabsf(v3.y)) + (fabsf(v3.z) + fabsf(v3.w));
+  }
+  for (; i < n4; i += stride) {
+    const float4 v = p[i];
+    a0 += (fabsf(v.x) + fabsf(v.y)) + (fabsf(v.z) + fabsf(v.w));
+  }
+  const float acc = jh_block_reduce((a0 + a1) + (a2 + a3), s_red, JhAdd(), 0.f);
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(partial + blockIdx.x, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  const int t = threadIdx.x;  // gridDim.x <= 256: one partial per thread
+  const float v = t < (int)gridDim.x ? __hip_atomic_load(partial + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+  const float s1 = jh_block_reduce(t < g1 ? v : 0.f, s_red, JhAdd(), 0.f);
+  const float s2 = jh_block_reduce(t < g1 ? 0.f : v, s_red, JhAdd(), 0.f);
+  if (t == 0) {
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    out2[0] = s1 / (float)(4 * (int64_t)n1_4);
+    out2[1] = s2 / (float)(4 * (int64_t)n2_4);
   }
 }
 
@@ -613,7 +757,9 @@ struct jh_rbnet {
   // kind 0 rainbow: head -> l -> noisy a1|v1 -> noisy a2, v2 -> dueling over K atoms   (network/rainbow.py:8-94)
   //      1 dueling: head -> l1_a|l1_v -> l2_a, l2_v -> dueling combine (K = 1)         (network/dueling.py:8-35)
   //      2 q:       head -> l -> q                                                      (network/q_network.py:8-20)
+  //      4 noisy:   head -> noisy(F -> H) -> noisy(H -> A) (K = 1; 5: independent noise)  (network/noisy.py:8-50)
   int kind = 0, noisy = 1, dueling = 1, has_l = 1, has_av1 = 1, in1 = 0, noise_independent = 0;
+  int R1 = 0;  // rows of the first stream layer: 2H (a1 | v1 stacked), H for the noisy network's single layer
   int NA4 = 0, K4 = 0;
   ConvGeom c1{}, c2{}, c3{};
   int P1 = 0, P2 = 0, P3 = 0;  // output pixels per sample
@@ -623,6 +769,11 @@ struct jh_rbnet {
   float *params = nullptr, *target = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr;
   NoisyDims nd{};
   int64_t n_noisy = 0;
+  NzDims nz{};                   // kind 4
+  int nz_w4 = 0, nz_items = 0;   // float4 items of the two weight matrices; those + the H + A biases
+  float* sig_partial = nullptr;  // jh_rbnet_sig_abs_mean: per-workgroup sums (256) ...
+  unsigned* sig_ticket = nullptr;  // ... and the arrival counter of its last-workgroup sum
+  int pend_sig = 0;              // d(sig) = d(mu) * eps of the last backward not yet formed (jh_rbnet_backward_deferred)
   float* weff = nullptr;                                // [3][set_stride]
   float *act1[2] = {nullptr, nullptr}, *act2[2] = {nullptr, nullptr}, *feat[2] = {nullptr, nullptr}, *h[2] = {nullptr, nullptr};
   float *hav = nullptr, *xa = nullptr, *xv = nullptr;  // [3][maxB][...]
@@ -640,14 +791,15 @@ struct jh_rbnet {
 
 static int rb_layout(jh_rbnet* n, int32_t kind, int32_t head_cnn, int32_t c_or_s, int32_t h_in, int32_t w_in, int32_t hidden, int32_t A, int32_t K,
                      int32_t max_batch) {
-  JH_ARG(kind >= 0 && kind <= 3);
-  if (kind == 3) {  // rainbow with independent Gaussian noise (utils.py:72-79)
+  JH_ARG(kind >= 0 && kind <= 5);
+  if (kind == 3 || kind == 5) {  // rainbow / noisy with independent Gaussian noise (utils.py:72-79)
     n->noise_independent = 1;
-    kind = 0;
+    kind = kind == 3 ? 0 : 4;
   }
   JH_ARG(hidden > 0 && hidden % 4 == 0 && A > 0 && max_batch > 0 && c_or_s > 0);
   JH_ARG(kind == 0 ? K > 1 : K == 1);
-  n->kind = kind; n->noisy = kind == 0; n->dueling = kind != 2; n->has_l = kind != 1; n->has_av1 = kind != 2;
+  n->kind = kind; n->noisy = kind == 0 || kind == 4; n->dueling = kind == 0 || kind == 1; n->has_l = kind == 0 || kind == 2; n->has_av1 = kind != 2;
+  n->R1 = kind == 4 ? hidden : 2 * hidden;
   n->cnn = head_cnn ? 1 : 0;
   n->Cin = c_or_s; n->Hin = h_in; n->Win = w_in; n->hidden = hidden; n->A = A; n->K = K; n->NA = A * K; n->maxB = max_batch;
   n->NA4 = (int)up4(n->NA); n->K4 = (int)up4(K);
@@ -673,8 +825,8 @@ static int rb_layout(jh_rbnet* n, int32_t kind, int32_t head_cnn, int32_t c_or_s
   n->in1 = n->has_l ? H : n->F;
   if (n->has_l) { seg(SEG_WL, H, n->F); seg(SEG_BL, 1, H); }
   if (n->has_av1) {
-    seg(SEG_MU_AV1, 2 * H, n->in1); seg(SEG_MUB_AV1, 1, 2 * H);
-    if (n->noisy) { seg(SEG_SIG_AV1, 2 * H, n->in1); seg(SEG_SIGB_AV1, 1, 2 * H); }
+    seg(SEG_MU_AV1, n->R1, n->in1); seg(SEG_MUB_AV1, 1, n->R1);
+    if (n->noisy) { seg(SEG_SIG_AV1, n->R1, n->in1); seg(SEG_SIGB_AV1, 1, n->R1); }
   }
   seg(SEG_MU_A2, n->NA, H); seg(SEG_MUB_A2, 1, n->NA);
   if (n->noisy) { seg(SEG_SIG_A2, n->NA, H); seg(SEG_SIGB_A2, 1, n->NA); }
@@ -683,6 +835,23 @@ static int rb_layout(jh_rbnet* n, int32_t kind, int32_t head_cnn, int32_t c_or_s
     if (n->noisy) { seg(SEG_SIG_V2, K, H); seg(SEG_SIGB_V2, 1, K); }
   }
   n->n_params = seg_pack(n->seg_rows, n->seg_cols, 0, SEG_COUNT, n->seg_off);
+  if (kind == 4) {  // the noisy network: layer 1 in the AV1 slots ([H][F]), layer 2 in the A2 slots; its own effective-weight set and noise format
+    const int F = n->F;
+    const int64_t w4 = (int64_t)H * (F / 4) + (int64_t)A * (H / 4);
+    if (w4 + H + A > 0x7fffffff) return jh_fail(JH_ERR_ARG, "noisy network (kind 4 / 5): %lld weights are more than 32-bit item indices cover", (long long)(4 * w4));
+    NzDims& z = n->nz;
+    z.H = H; z.F = F; z.A = A; z.P3 = n->cnn ? n->P3 : 0; z.independent = n->noise_independent;
+    z.p_mu1 = n->seg_off[SEG_MU_AV1]; z.p_sig1 = n->seg_off[SEG_SIG_AV1]; z.p_mub1 = n->seg_off[SEG_MUB_AV1]; z.p_sigb1 = n->seg_off[SEG_SIGB_AV1];
+    z.p_mu2 = n->seg_off[SEG_MU_A2]; z.p_sig2 = n->seg_off[SEG_SIG_A2]; z.p_mub2 = n->seg_off[SEG_MUB_A2]; z.p_sigb2 = n->seg_off[SEG_SIGB_A2];
+    z.o_w1 = 0; z.o_b1 = up4((int64_t)H * F); z.o_w2 = up4(z.o_b1 + H); z.o_b2 = up4(z.o_w2 + (int64_t)A * H);
+    n->nz_w4 = (int)w4; n->nz_items = (int)(w4 + H + A);
+    NoisyDims& d = n->nd;  // what stream_w and jh_rbnet_noise_len read
+    d.H = H; d.NA = A; d.K = 1; d.independent = n->noise_independent;
+    d.o_av1 = z.o_w1; d.o_bav1 = z.o_b1; d.o_a2 = z.o_w2; d.o_ba2 = z.o_b2; d.set_stride = up4(z.o_b2 + A);
+    d.noise_len = d.independent ? (int64_t)F * H + H + (int64_t)H * A + A : (int64_t)F + 2 * H + A;
+    n->n_noisy = 0;
+    return JH_OK;
+  }
   NoisyDims& d = n->nd;
   d.H = H; d.NA = n->NA; d.K = K;
   d.o_av1 = 0;
@@ -734,6 +903,10 @@ JH_EXPORT int jh_rbnet_create(jh_ctx* ctx, int32_t kind, int32_t head_cnn, int32
     }
     A4(&n->feat[s], rows * n->F);
     A4(&n->h[s], rows * H);
+  }
+  if (n->kind == 4) {
+    A4(&n->sig_partial, 256);
+    if (!rc) rc = core_alloc(&n->core, "jh_rbnet", (void**)&n->sig_ticket, 64, true);
   }
   A4(&n->hav, 3 * B * 2 * H); A4(&n->xa, 3 * B * n->NA4); A4(&n->xv, 3 * B * n->K4);
   A4(&n->dxa, B * n->NA4); A4(&n->dxv, B * n->K4); A4(&n->dhav, B * 2 * H); A4(&n->dh, B * H); A4(&n->dfeat, B * n->F);
@@ -914,7 +1087,18 @@ static int rb_heads(jh_rbnet* n, const HeadJob* jobs, int nj, int B, hipStream_t
   const NoisyDims& d = n->nd;
   const bool prepared = n->noisy && nj == 3 && n->prepared_noise != nullptr && n->prepared_noise == jobs[0].noise;
   n->prepared_noise = nullptr;
-  if (n->noisy && !prepared) {
+  const int R1 = n->R1;
+  if (n->kind == 4) {
+    if (nj > 2) return jh_fail(JH_ERR_ARG, "noisy network (kind 4 / 5): at most two forwards share a launch");
+    NzSets ns{};
+    for (int j = 0; j < nj; ++j) {
+      ns.params[j] = jobs[j].P; ns.noise[j] = jobs[j].noise; ns.weff[j] = n->weff + (size_t)j * d.set_stride;
+    }
+    int blocks = (n->nz_items + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    JH_LAUNCH(jh_nz_weff_kernel, dim3((unsigned)blocks, nj), dim3(256), 0, st, n->nz, ns, n->nz_w4, n->nz_items);
+    JH_LAUNCH_CHECK();
+  } else if (n->noisy && !prepared) {
     NoiseSets ns{};
     ns.n_sets = nj;
     for (int j = 0; j < nj; ++j) {
@@ -931,7 +1115,7 @@ static int rb_heads(jh_rbnet* n, const HeadJob* jobs, int nj, int B, hipStream_t
   if (n->has_av1) {
     for (int j = 0; j < nj; ++j) {
       const StreamW w = stream_w(n, jobs[j].P, j);
-      g[j] = mk_gemm(B, 2 * H, in1, op_dense(OP_KCONT, jobs[j].h, in1), op_dense(OP_KCONT, w.av1, in1), n->hav + j * B_ * 2 * H, 2 * H, TEPI_BIAS_RELU, w.bav1);
+      g[j] = mk_gemm(B, R1, in1, op_dense(OP_KCONT, jobs[j].h, in1), op_dense(OP_KCONT, w.av1, in1), n->hav + j * B_ * 2 * H, R1, TEPI_BIAS_RELU, w.bav1);
     }
     rc = core_tgemm(&n->core, "jh_tgemm_stream1_fwd", g, nj, st);
     if (rc) return rc;
@@ -940,7 +1124,7 @@ static int rb_heads(jh_rbnet* n, const HeadJob* jobs, int nj, int B, hipStream_t
   for (int j = 0; j < nj; ++j) {
     const StreamW w = stream_w(n, jobs[j].P, j);
     const float* in_a = n->has_av1 ? n->hav + j * B_ * 2 * H : jobs[j].h;  // q-network: the q layer reads h
-    const int ld_in = n->has_av1 ? 2 * H : H;
+    const int ld_in = n->has_av1 ? R1 : H;
     float* out_a = n->dueling ? n->xa + j * B_ * n->NA4 : jobs[j].logits;
     g[ng++] = mk_gemm(B, NA, H, op_dense(OP_KCONT, in_a, ld_in), op_dense(OP_KCONT, w.a2, H), out_a, n->dueling ? n->NA4 : NA, TEPI_BIAS, w.ba2);
     if (n->dueling)
@@ -993,8 +1177,16 @@ JH_EXPORT int jh_rbnet_forward_keep(jh_rbnet* n, const void* d_x, int32_t x_dtyp
 // The two halves separately, so that a caller can run what does not depend on the batch on ANOTHER stream meanwhile (round 4: the
 // NoisyNet weight sets W = mu + sig * eps of the three forwards only need the noise draw; materialising them costs a 12-us launch that
 // used to sit in front of the trunk): jh_rbnet_prepare_noise (any stream) || jh_rbnet_learn_trunk; join; jh_rbnet_learn_heads.
+// the noisy network (kind 4 / 5) has one learn() forward of its own, jh_rbnet_learn_forward_n: every other learn() entry refuses it by name
+static int rb_refuse_nz(const jh_rbnet* n, const char* fn) {
+  if (!n || n->kind != 4) return JH_OK;
+  return jh_fail(JH_ERR_ARG, "%s: not for kind %d (the noisy network, network/noisy.py: its learn() forwards are jh_rbnet_learn_forward_n)", fn,
+                 n->noise_independent ? 5 : 4);
+}
+
 JH_EXPORT int jh_rbnet_prepare_noise(jh_rbnet* n, const float* d_noise, jh_stream stream) {
   JH_ARG(n != nullptr);
+  if (int rf = rb_refuse_nz(n, "jh_rbnet_prepare_noise")) return rf;
   if (!n->noisy) return JH_OK;
   JH_ARG(d_noise != nullptr);
   const NoisyDims& d = n->nd;
@@ -1013,6 +1205,7 @@ JH_EXPORT int jh_rbnet_prepare_noise(jh_rbnet* n, const float* d_noise, jh_strea
 
 JH_EXPORT int jh_rbnet_learn_trunk(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, jh_stream stream) {
   JH_ARG(n && d_x);
+  if (int rf = rb_refuse_nz(n, "jh_rbnet_learn_forward / jh_rbnet_learn_trunk")) return rf;
   JH_ARG(B > 0 && B <= n->maxB);
   JH_ARG(x_dtype == JH_U8 || x_dtype == JH_F32);
   const size_t row_elems = n->cnn ? (size_t)n->Cin * n->Hin * n->Win : (size_t)n->Cin;
@@ -1027,6 +1220,7 @@ JH_EXPORT int jh_rbnet_learn_trunk(jh_rbnet* n, const void* d_x, int32_t x_dtype
 
 static int rb_learn_heads(jh_rbnet* n, int32_t B, const float* d_noise, float* d_logits, bool raw, jh_stream stream) {
   JH_ARG(n && (d_logits || raw));
+  if (int rf = rb_refuse_nz(n, "jh_rbnet_learn_heads")) return rf;
   JH_ARG(d_noise || !n->noisy);
   JH_ARG(B > 0 && B == n->last_B);
   if (raw && !n->dueling) return jh_fail(JH_ERR_ARG, "jh_rbnet_learn_heads_raw: a dueling network's call");
@@ -1064,6 +1258,7 @@ JH_EXPORT int jh_rbnet_c51_step(jh_rbnet* n, jh_per* per, int32_t B, int32_t n_s
                                 const float* d_done, const float* d_weights, const int64_t* d_tree_idx, float v_min, float v_max, float gamma,
                                 float alpha, float* d_logits, float* d_prio, float* d_kl, float* d_stats, jh_stream stream) {
   JH_ARG(n && d_action && d_reward && d_done && d_logits && d_prio);
+  if (int rf = rb_refuse_nz(n, "jh_rbnet_c51_step")) return rf;
   JH_ARG(n->dueling && n->K > 1 && n->K <= 256);
   JH_ARG(B > 0 && B <= 1024 && B == n->last_B && n_step >= 0);
   JH_ARG((flags & JH_C51_DOUBLE) != 0);
@@ -1094,6 +1289,7 @@ JH_EXPORT int jh_rbnet_c51_step(jh_rbnet* n, jh_per* per, int32_t B, int32_t n_s
 
 JH_EXPORT int jh_rbnet_learn_forward(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits, jh_stream stream) {
   JH_ARG(n && d_x && d_logits);
+  if (int rf = rb_refuse_nz(n, "jh_rbnet_learn_forward")) return rf;
   JH_ARG(d_noise || !n->noisy);
   int rc = jh_rbnet_learn_trunk(n, d_x, x_dtype, B, stream);
   if (rc) return rc;
@@ -1138,6 +1334,7 @@ JH_EXPORT int jh_rbnet_reserve_target_rows(jh_rbnet* n, int32_t rows) {
 // jh_rbnet_backward continues from here unchanged.
 JH_EXPORT int jh_rbnet_learn_forward_m(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits, jh_stream stream) {
   JH_ARG(n && d_x && d_logits);
+  if (int rf = rb_refuse_nz(n, "jh_rbnet_learn_forward_m")) return rf;
   if (n->noisy) return jh_fail(JH_ERR_ARG, "jh_rbnet_learn_forward_m: kinds discrete_q_network and dueling only (a noisy network has no Munchausen agent)");
   (void)d_noise;
   JH_ARG(B > 0 && B <= n->maxB);
@@ -1167,6 +1364,7 @@ JH_EXPORT int jh_rbnet_learn_forward_m(jh_rbnet* n, const void* d_x, int32_t x_d
 // activations of the state rows at the start of slot 0, so that jh_rbnet_backward continues from here unchanged.
 JH_EXPORT int jh_rbnet_learn_forward_p(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits, jh_stream stream) {
   JH_ARG(n && d_x && d_logits);
+  if (int rf = rb_refuse_nz(n, "jh_rbnet_learn_forward_p")) return rf;
   if (n->noisy) return jh_fail(JH_ERR_ARG, "jh_rbnet_learn_forward_p: kinds discrete_q_network and dueling only (a noisy network is no MPO actor)");
   (void)d_noise;
   JH_ARG(B > 0 && B <= n->maxB);
@@ -1185,6 +1383,45 @@ JH_EXPORT int jh_rbnet_learn_forward_p(jh_rbnet* n, const void* d_x, int32_t x_d
   n->last_noise = nullptr;
   n->raw_heads = 0;
   n->dx_ready = 0;
+  return JH_OK;
+}
+
+// The two forwards of Noisy.learn (agent/noisy.py:83-105): d_x = [state; next_state] as for jh_rbnet_learn_forward, d_noise [2][noise_len],
+//   logits[0] = online(state; noise 0)   logits[1] = target(next_state; noise 1)
+// The online trunk runs over the first B rows only, the target trunk over the last B rows only, in shared launches (two jobs per layer); the
+// two effective-weight sets come from one launch.  jh_rbnet_backward[_deferred] continues from it (noise set 0, the online activations of slot 0).
+JH_EXPORT int jh_rbnet_learn_forward_n(jh_rbnet* n, const void* d_x, int32_t x_dtype, int32_t B, const float* d_noise, float* d_logits, jh_stream stream) {
+  JH_ARG(n && d_x && d_logits && d_noise);
+  if (n->kind != 4) return jh_fail(JH_ERR_ARG, "jh_rbnet_learn_forward_n: kinds 4 and 5 only (the noisy network, network/noisy.py)");
+  JH_ARG(B > 0 && B <= n->maxB);
+  JH_ARG(x_dtype == JH_U8 || x_dtype == JH_F32);
+  const size_t row_elems = n->cnn ? (size_t)n->Cin * n->Hin * n->Win : (size_t)n->Cin;
+  const size_t esz = x_dtype == JH_U8 ? 1 : 4;
+  const void* x_next = (const char*)d_x + (size_t)B * row_elems * esz;
+  TrunkJob tj[2] = {{n->params, d_x, B, 0}, {n->target, x_next, B, 1}};
+  int rc = rb_trunk(n, tj, 2, x_dtype == JH_U8, jh_s(stream));
+  if (rc) return rc;
+  n->last_x = d_x; n->last_x_u8 = x_dtype == JH_U8; n->last_B = B;
+  HeadJob hj[2] = {{n->params, d_noise, n->feat[0], d_logits}, {n->target, d_noise + n->nd.noise_len, n->feat[1], d_logits + (size_t)B * n->NA}};
+  rc = rb_heads(n, hj, 2, B, jh_s(stream));
+  if (rc) return rc;
+  n->last_noise = d_noise;
+  n->raw_heads = 0;
+  n->dx_ready = 0;
+  return JH_OK;
+}
+
+// Noisy.get_sig_w_mean (network/noisy.py:46-50) of the ONLINE parameters: d_out2 = {mean |sig_w1|, mean |sig_w2|}, one launch on the stream.
+JH_EXPORT int jh_rbnet_sig_abs_mean(jh_rbnet* n, float* d_out2, jh_stream stream) {
+  JH_ARG(n && d_out2);
+  if (n->kind != 4) return jh_fail(JH_ERR_ARG, "jh_rbnet_sig_abs_mean: kinds 4 and 5 only (the noisy network, network/noisy.py)");
+  const int n1_4 = n->hidden * (n->F / 4), n2_4 = n->A * (n->hidden / 4);
+  int g1 = (n1_4 + 1023) / 1024, g2 = (n2_4 + 1023) / 1024;  // four float4s per lane and workgroup, up to 192 + 64 workgroups
+  g1 = g1 > 192 ? 192 : g1;
+  g2 = g2 > 64 ? 64 : g2;
+  JH_LAUNCH(jh_nz_sig_abs_mean_kernel, dim3(g1 + g2), dim3(256), 0, jh_s(stream), n->params + n->seg_off[SEG_SIG_AV1], n1_4, n->params + n->seg_off[SEG_SIG_A2],
+            n2_4, g1, n->sig_partial, n->sig_ticket, d_out2);
+  JH_LAUNCH_CHECK();
   return JH_OK;
 }
 
@@ -1207,10 +1444,19 @@ static int rb_parts_sum(jh_rbnet* n, int parts, hipStream_t st) {
   return JH_OK;
 }
 // what a deferred backward left undone (the gradient bucket is complete afterwards)
+static int rb_nz_sig_grad(jh_rbnet* n, hipStream_t st) {
+  int blocks = (n->nz_items + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  JH_LAUNCH(jh_nz_sig_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n->nz, n->last_noise, n->grads, n->nz_w4, n->nz_items);
+  JH_LAUNCH_CHECK();
+  return JH_OK;
+}
 static int rb_flush_grads(jh_rbnet* n, hipStream_t st) {
   int rc = JH_OK;
   if (n->pend_parts) rc = rb_parts_sum(n, n->pend_parts, st);
   n->pend_parts = 0;
+  if (!rc && n->pend_sig) rc = rb_nz_sig_grad(n, st);
+  n->pend_sig = 0;
   return rc;
 }
 
@@ -1222,8 +1468,9 @@ static int rb_backward(jh_rbnet* n, const float* d_g, bool defer, jh_stream stre
   if (!n->last_x) return jh_fail(JH_ERR_STATE, "jh_rbnet_backward without a preceding jh_rbnet_learn_forward");
   if (!d_g && !n->dx_ready) return jh_fail(JH_ERR_STATE, "jh_rbnet_backward(null gradient) without a preceding jh_rbnet_c51_step");
   n->pend_parts = 0;
+  n->pend_sig = 0;
   hipStream_t st = jh_s(stream);
-  const int B = n->last_B, H = n->hidden, NA = n->NA, K = n->K, F = n->F, in1 = n->in1;
+  const int B = n->last_B, H = n->hidden, NA = n->NA, K = n->K, F = n->F, in1 = n->in1, R1 = n->R1;
   const StreamW w0 = stream_w(n, n->params, 0);  // noise set 0 / the online parameters
   const float* hav0 = n->hav;
   const float* sin0 = n->has_l ? n->h[0] : n->feat[0];  // input of the streams (rows of `state`)
@@ -1244,11 +1491,11 @@ static int rb_backward(jh_rbnet* n, const float* d_g, bool defer, jh_stream stre
   int ng = 0, rc;
   // last stream layer(s): weight gradients (+ bias gradients as row sums) and data gradients (+ relu')
   const float* in_a = n->has_av1 ? hav0 : sin0;
-  const int ld_in = n->has_av1 ? 2 * H : H;
+  const int ld_in = n->has_av1 ? R1 : H;
   float* d_in = n->has_av1 ? n->dhav : dsin;
   // factorised NoisyNet layers: d(sig) = d(mu) * f(e_in) f(e_out)^T and d(sig_b) = d(mu_b) * f(e_out) leave the weight-gradient GEMMs' epilogues
   // beside d(mu), d(mu_b) (jh_tgemm.h: C2 / rowsum2).  Noise set 0 = [ei_a1 H][ej_a1 H][ei_v1 H][ej_v1 H][ei_a2 H][ej_a2 NA][ei_v2 H][ej_v2 K].
-  const bool sig_epi = n->noisy && !n->noise_independent;
+  const bool sig_epi = n->noisy && !n->noise_independent && n->kind != 4;  // (kind 4: the input-side noise of layer 1 is permuted on the cnn head)
   const float* e0 = n->last_noise;
   auto with_sigma = [&](TGemm& t, int seg_sig, int seg_sigb, const float* ej, const float* ei, int split, const float* ej2, const float* ei2) {
     if (!sig_epi) return;
@@ -1268,15 +1515,19 @@ static int rb_backward(jh_rbnet* n, const float* d_g, bool defer, jh_stream stre
   rc = core_tgemm(&n->core, "jh_tgemm_stream2_bwd", g, ng, st);
   if (rc) return rc;
   if (n->has_av1) {  // first stream layer (a1 | v1 stacked)
-    g[0] = mk_gemm(2 * H, in1, B, op_dense(OP_XCONT, n->dhav, 2 * H), op_dense(OP_XCONT, sin0, in1), G + n->seg_off[SEG_MU_AV1], in1, TEPI_NONE, nullptr, nullptr, 0,
+    g[0] = mk_gemm(R1, in1, B, op_dense(OP_XCONT, n->dhav, R1), op_dense(OP_XCONT, sin0, in1), G + n->seg_off[SEG_MU_AV1], in1, TEPI_NONE, nullptr, nullptr, 0,
                    G + n->seg_off[SEG_MUB_AV1]);
     // rows m < H are a1 (e_out at H + m, e_in at k), rows m >= H are v1 (e_out at 3H + (m - H) = 2H + m, e_in at 2H + k)
     with_sigma(g[0], SEG_SIG_AV1, SEG_SIGB_AV1, e0 + H, e0, H, e0 + 2 * H, e0 + 2 * H);
-    g[1] = mk_gemm(B, in1, 2 * H, op_dense(OP_KCONT, n->dhav, 2 * H), op_dense(OP_XCONT, w0.av1, in1), dsin, in1, TEPI_MASK, nullptr, sin0, in1);
+    g[1] = mk_gemm(B, in1, R1, op_dense(OP_KCONT, n->dhav, R1), op_dense(OP_XCONT, w0.av1, in1), dsin, in1, TEPI_MASK, nullptr, sin0, in1);
     rc = core_tgemm(&n->core, "jh_tgemm_stream1_bwd", g, 2, st);
     if (rc) return rc;
   }
-  if (n->noisy && !sig_epi) {  // independent noise (utils.py:73-76): eps is a matrix of its own, the elementwise kernel forms d(sig)
+  if (n->kind == 4) {  // d(sig) = d(mu) * eps: now, or left to jh_rbnet_flush_grads / jh_rbnet_optim_step
+    if (defer) n->pend_sig = 1;
+    else rc = rb_nz_sig_grad(n, st);
+    if (rc) return rc;
+  } else if (n->noisy && !sig_epi) {  // independent noise (utils.py:73-76): eps is a matrix of its own, the elementwise kernel forms d(sig)
     rc = rb_noisy_grad(n, st);
     if (rc) return rc;
   }

@@ -23,7 +23,7 @@ class BatchedValueActors:
 
     agent: a DQN-family / Rainbow / Ape-X agent with backend="native".  epsilons: per-actor exploration rates
     (default: Ape-X's schedule eps^(1 + i/(N-1) * alpha), ape_x.py:166-172, when the agent has one; else agent.epsilon
-    for all).  Rainbow acts through its noisy layers (a fresh noise draw per tick, rainbow.py:150) and epsilon = 0."""
+    for all).  Rainbow and Noisy act through their noisy layers (a fresh noise draw per tick, rainbow.py:150, noisy.py:76) and epsilon = 0."""
 
     def __init__(self, agent, n_actors, epsilons=None, stream=None):
         src = getattr(agent, "_net", None)
@@ -32,7 +32,7 @@ class BatchedValueActors:
         state_size = (src.Cin, src.Hin, src.Win) if src.cnn else src.Cin
         self.net = ops.RainbowNet(state_size, src.A, src.K, src.H, "cnn" if src.cnn else "mlp", self.N, self.device, kind=src.kind, noise_type=src.noise_type)
         self.stream = stream or torch.cuda.Stream(device=self.device)
-        self.noisy = src.kind == "rainbow"
+        self.noisy = self.net.noise_len > 0  # Rainbow, Noisy: explore through the noisy layers
         if epsilons is None:
             if self.noisy:
                 epsilons = np.zeros(self.N)

@@ -1233,7 +1233,7 @@ class RainbowNet(_NetObject):
     _SEG = ("w1", "b1", "w2", "b2", "w3", "b3", "wl", "bl", "mu_av1", "sig_av1", "mub_av1", "sigb_av1", "mu_a2", "sig_a2", "mub_a2", "sigb_a2",
             "mu_v2", "sig_v2", "mub_v2", "sigb_v2")
     _SYM = "jh_rbnet_"
-    _KIND = {"rainbow": 0, "dueling": 1, "q": 2, "pv": 2, "pi": 2}  # "pv": the discrete policy-value net (policy_value.py:8-22) = head -> l -> (pi | v) stacked into ONE last layer of A + 1 rows
+    _KIND = {"rainbow": 0, "dueling": 1, "q": 2, "pv": 2, "pi": 2, "noisy": 4}  # "noisy": network/noisy.py (head -> noisy -> noisy; 5 with independent noise); "pv": the discrete policy-value net (policy_value.py:8-22) = head -> l -> (pi | v) stacked into ONE last layer of A + 1 rows
 
     def __init__(self, state_size, action_size, num_support, hidden, head, max_batch, device, kind="rainbow", noise_type="factorized"):
         self._open(device)
@@ -1248,8 +1248,8 @@ class RainbowNet(_NetObject):
             self.n_actions, self.A = self.A, self.A + 1  # the library sees a q-network with one more output row: the value head
         kid = self._KIND[kind]
         self.noise_type = noise_type
-        if kind == "rainbow" and noise_type == "independent":
-            kid = 3
+        if kind in ("rainbow", "noisy") and noise_type == "independent":
+            kid += 3 if kind == "rainbow" else 1
         n = int(self.lib.jh_rbnet_param_count_for(kid, int(self.cnn), self.Cin, self.Hin, self.Win, self.H, self.A, self.K))
         if n <= 0:
             L.check(-2)
@@ -1258,7 +1258,7 @@ class RainbowNet(_NetObject):
         self.h = C.c_void_p()
         L.check(self.lib.jh_rbnet_create(self.ctx, kid, int(self.cnn), self.Cin, self.Hin, self.Win, self.H, self.A, self.K, self.maxB, L.ptr(self.params),
                                          L.ptr(self.target), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), C.byref(self.h)))
-        self.noise_len = int(self.lib.jh_rbnet_noise_len(self.h)) if kind == "rainbow" else 0
+        self.noise_len = int(self.lib.jh_rbnet_noise_len(self.h)) if kind in ("rainbow", "noisy") else 0
         self.seg = self._segments(self._SEG)
         if self.cnn:
             d1 = ((self.Hin - 8) // 4 + 1, (self.Win - 8) // 4 + 1)
@@ -1300,6 +1300,14 @@ class RainbowNet(_NetObject):
                         (f"mu_b_{tag}", self._v(bucket, f"mub_{tag}").view(-1)), (f"sig_b_{tag}", self._v(bucket, f"sigb_{tag}").view(-1))]
             out += head
             out += [("l.weight", self._feat_cols(self._v(bucket, "wl"))), ("l.bias", self._v(bucket, "bl").view(-1))]
+        elif self.kind == "noisy":  # network/noisy.py:15-20: mu_w1 / sig_w1 are [F][H] there (features (c, y, x)), [H][F] with (y, x, c) columns here
+            for i, tag in ((1, "av1"), (2, "a2")):
+                mu, sig = self._v(bucket, f"mu_{tag}"), self._v(bucket, f"sig_{tag}")
+                if i == 1:
+                    mu, sig = self._feat_cols(mu), self._feat_cols(sig)
+                out += [(f"mu_w{i}", self._rows_last(mu)), (f"sig_w{i}", self._rows_last(sig)),
+                        (f"mu_b{i}", self._v(bucket, f"mub_{tag}").view(-1)), (f"sig_b{i}", self._v(bucket, f"sigb_{tag}").view(-1))]
+            out += head
         elif self.kind == "dueling":
             av1, bav1 = self._v(bucket, "mu_av1"), self._v(bucket, "mub_av1").view(-1)
             out += head
@@ -1319,16 +1327,23 @@ class RainbowNet(_NetObject):
         return out
 
     @staticmethod
+    def _rows_last(w):
+        """The reference's [in][out] view of a noisy weight kept [out][in] ([out][c][y][x] on the cnn head's features -> [c][y][x][out])."""
+        return w.permute(*range(1, w.dim()), 0)
+
+    @staticmethod
     def _is_feat_cols(k, v):
         return v.dim() == 4 and not k.startswith("head.")
 
     def export_state(self, bucket=None):
         bucket = self.params if bucket is None else bucket
-        return _export_pairs((k, v.reshape(v.shape[0], -1) if self._is_feat_cols(k, v) else v) for k, v in self._pairs(bucket))
+        flat = (lambda v: v.reshape(-1, v.shape[-1])) if self.kind == "noisy" else (lambda v: v.reshape(v.shape[0], -1))
+        return _export_pairs((k, flat(v) if self._is_feat_cols(k, v) else v) for k, v in self._pairs(bucket))
 
     def import_state(self, sd, bucket=None):
         bucket = self.params if bucket is None else bucket
-        _import_pairs(self._pairs(bucket), sd, self.device, lambda k, v, src: src.view(v.shape[0], 64, self.d3[0], self.d3[1]) if self._is_feat_cols(k, v) else src)
+        shape4 = (lambda v: (64, self.d3[0], self.d3[1], v.shape[-1])) if self.kind == "noisy" else (lambda v: (v.shape[0], 64, self.d3[0], self.d3[1]))
+        _import_pairs(self._pairs(bucket), sd, self.device, lambda k, v, src: src.view(shape4(v)) if self._is_feat_cols(k, v) else src)
 
     # ---- engine ---------------------------------------------------------------------------------
     def set_hyper(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0, centered=False):
@@ -1386,6 +1401,24 @@ class RainbowNet(_NetObject):
         the forwards of MPO's discrete actor; `backward` continues from it as after `learn_forward`.  q / dueling networks; `noise` is ignored."""
         assert x_all.is_contiguous() and out.is_contiguous() and int(x_all.shape[0]) == 2 * B
         L.check(self.lib.jh_rbnet_learn_forward_p(self.h, L.ptr(x_all), self._xdt(x_all), int(B), L.ptr(noise), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def learn_forward_n(self, x_all, B, noise, out):
+        """x_all = [state; next_state] (2B rows), noise [2, noise_len] -> out [2, B, A, 1] = online(state; noise 0), target(next_state; noise 1)
+        (jh_rbnet_learn_forward_n: the two forwards of Noisy.learn, agent/noisy.py:83-105; the online trunk sees the first B rows only, the
+        target trunk the last B); `backward` continues from it.  The noisy network only."""
+        assert x_all.is_contiguous() and noise.is_contiguous() and out.is_contiguous() and int(x_all.shape[0]) == 2 * B
+        assert noise.numel() >= 2 * self.noise_len and out.numel() >= 2 * B * self.A * self.K
+        L.check(self.lib.jh_rbnet_learn_forward_n(self.h, L.ptr(x_all), self._xdt(x_all), int(B), L.ptr(noise), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def sig_abs_mean(self, out=None):
+        """Noisy.get_sig_w_mean (network/noisy.py:46-50) of the online parameters -> out f32[2] = {mean |sig_w1|, mean |sig_w2|}, one launch
+        with a fixed summation order (jh_rbnet_sig_abs_mean).  The noisy network only."""
+        if out is None:
+            out = torch.empty(2, dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= 2
+        L.check(self.lib.jh_rbnet_sig_abs_mean(self.h, L.ptr(out), L.stream_ptr()))
         return out
 
     def hyper_ptr(self):
