@@ -589,6 +589,57 @@ int jh_mpo_loss_discrete(jh_ctx* ctx, int32_t R, int32_t T, int32_t A, const flo
                          const float* d_done, const float* d_prob_b, float* d_block, const float* d_hyper, float gamma, int32_t retrace,
                          float* d_grad_la, float* d_grad_q, float* d_stats, jh_stream stream);
 
+/* ------------------------------------------------------------------ ICM-PPO's curiosity module
+ * core/network/icm.py:153-218 (ICM_MLP) with its helpers icm.py:8-34 (the feature trunk: fc1 -> bn1 -> ELU -> fc2 -> bn2 -> ELU on s; the
+ * SAME fc1 and fc2 on s' with bn1_next after fc1 and no batch norm after fc2), icm.py:99-142 (forward and inverse model), icm.py:145-150
+ * (ri_update), core/network/utils.py:6-52 (RewardForwardFilter, RunningMeanStd) and core/network/rnd.py:9-10 (normalize_obs), as
+ * icm_ppo.py:96-102 and icm_ppo.py:177-199 use them.  The feature size is 256.  Every batch norm uses BATCH statistics (the module is
+ * never put into eval mode): biased variance, eps 1e-5; the running statistics advance with momentum 0.1 and the unbiased variance.
+ * Caller-owned flat fp32 buckets (params, gradients, exp_avg, exp_avg_sq) of jh_icmnet_param_count_for floats (needs no GPU; -1 for bad
+ * sizes) hold the trainable tensors in the reference's registration order, weight then bias, every segment 16-byte aligned:
+ *   fc1 [H][S], fc2 [256][H], forward_fc1 [H][256 + a], forward_fc2 [256][H + a], inverse_fc1 [H][512], inverse_fc2 [A][H]
+ *   and, with JH_ICM_BATCH_NORM, bn1 [H], bn2 [256], bn1_next [H]         (a = 1, the action index as a float | A action columns)
+ * = 12 or 18 segments (jh_icmnet_segment_count / _segment).  continuous 0: 1 <= A <= 39, 1: 1 <= A <= 19; H % 4 == 0;
+ * max_batch <= 8192 rows per call.  The statistics block (device, jh_icmnet_stats_floats floats, _stats_get / _stats_set copy it whole and
+ * synchronise the stream): rms_obs mean [S], var [S], count | rms_ri mean, var, count | rewems [W] | running mean [C], var [C] of bn1
+ * (C = H), bn2 (256), bn1_next (H).  A fresh object holds a fresh module's values (counts 1e-4, running variances 1).              */
+typedef struct jh_icmnet jh_icmnet;
+#define JH_ICM_OBS_NORMALIZE 1
+#define JH_ICM_RI_NORMALIZE 2
+#define JH_ICM_BATCH_NORM 4
+int64_t jh_icmnet_param_count_for(int32_t S, int32_t H, int32_t A, int32_t continuous, int32_t batch_norm);
+int jh_icmnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int32_t continuous, int32_t num_workers, int32_t max_batch, int32_t flags,
+                     double eta, double gamma, float* d_params, float* d_grads, float* d_m, float* d_v, jh_icmnet** out);
+void jh_icmnet_destroy(jh_icmnet* n);
+int32_t jh_icmnet_segment_count(const jh_icmnet* n);
+int jh_icmnet_segment(const jh_icmnet* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols);
+/* the module's own Adam (icm_ppo.py:76); learning_rate_decay never reaches it (base.py:103-104)                     */
+int jh_icmnet_set_hyper(jh_icmnet* n, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream);
+int jh_icmnet_set_lr(jh_icmnet* n, double lr, jh_stream stream);
+int64_t jh_icmnet_stats_floats(const jh_icmnet* n);
+int jh_icmnet_stats_get(jh_icmnet* n, float* h_out, jh_stream stream);
+int jh_icmnet_stats_set(jh_icmnet* n, const float* h_in, jh_stream stream);
+/* icm.update_rms_obs(next_state) (icm_ppo.py:98): the per-feature mean and UNBIASED variance of d_next_state [rows][S] merged into
+ * rms_obs in float32, operation for operation (utils.py:31-52).  2 <= rows <= max_batch.  One launch.                  */
+int jh_icmnet_obs_update(jh_icmnet* n, const float* d_next_state, int32_t rows, jh_stream stream);
+/* r_i, _, _ = icm(state, action, next_state, update_ri=True) and the mix (icm_ppo.py:99-102) over a whole rollout, no gradient:
+ *   r_i = eta / 2 sum_j |x_forward - phi'|; the filter per worker w over its rows w T .. w T + T - 1 (T = rows / W); rms_ri merged with what
+ *   the reference's stack really holds -- RewardForwardFilter.update returns the Parameter itself, so T copies of the FINAL rewems:
+ *   batch count T W, mean mean_w rewems_w, unbiased variance over the T W entries --; with JH_ICM_RI_NORMALIZE r_i /= sqrt(rms_ri.var) +
+ *   1e-7 (the variance AFTER this update); d_reward [rows] <- extrinsic_coeff * d_reward + intrinsic_coeff * r_i in place.
+ * d_action [rows] (the index as a float) | [rows][A].  Optional outputs: d_ri_mean [1] = mean(r_i) as mixed, d_ri_raw [rows] before and
+ * d_ri [rows] after the normalisation.  The batch norms' running statistics advance once.  JH_ERR_ARG, nothing launched: rows < 2,
+ * rows > max_batch, rows % W != 0.  9 launches.                                                                         */
+int jh_icmnet_reward(jh_icmnet* n, const float* d_state, const float* d_next_state, const float* d_action, int32_t rows, float extrinsic_coeff,
+                     float intrinsic_coeff, float* d_reward, float* d_ri_mean, float* d_ri_raw, float* d_ri, jh_stream stream);
+/* One minibatch (icm_ppo.py:177, 185, 194-199) on rows d_idx[0 .. b) of the n_rows-row rollout arrays (NULL: rows 0 .. b - 1; an index is
+ * clamped into the rollout): forward, l_f = mse(x_forward, phi'.detach()), l_i = cross entropy against the action index | mse against the
+ * action, backward of beta l_f + (1 - beta) l_i, clip_grad_norm_(max_norm) over the trainable bucket (0: none), Adam.  d_stats optional
+ * float32[4] = {l_f, l_i, 0, arrival mark 0}, the mark written last behind a system-scope fence (device-mapped host memory may receive
+ * it).  JH_ERR_ARG, nothing launched: b < 1, b < 2 under batch norm, b > max_batch.  16 launches.                       */
+int jh_icmnet_update(jh_icmnet* n, const float* d_state, const float* d_next_state, const float* d_action, const int64_t* d_idx, int32_t b,
+                     int64_t n_rows, double beta, float max_norm, float* d_stats, jh_stream stream);
+
 /* ------------------------------------------------------------------ native policy-value MLP
  * The encoder of the PPO configs (core/network/head.py:6-18 MLP head + policy_value.py:8-57):
  * S -> H relu -> H relu -> {A logits | A mu, A log_std} + value, as hand-written kernels

@@ -287,10 +287,19 @@ class PPO(BaseAgent):
         """ppo.py:83-112: everything that does NOT depend on the epoch shuffles (replay rows, the no-grad passes,
         log pi_old, GAE, mean return).  Launched first so that the host's `np.random.shuffle` calls (ppo.py:118, ~12 us
         each at 1024 rows) run while the GPU is busy with this."""
+        self._enqueue_gather(st)
+        self._enqueue_pre_pass(st, captured)
+
+    def _enqueue_gather(self, st):
+        """The rollout's rows out of the store into the static buffers (ppo.py:85-93)."""
+        tr = st["tr"]
+        self.memory._store.gather(st["arange"], as_float=True, out={k: tr[k] for k in tr})
+
+    def _enqueue_pre_pass(self, st, captured=False):
+        """ppo.py:95-112 on the gathered rows (a subclass may have rewritten the reward column: ICM-PPO's intrinsic reward)."""
         net, M = self._net, st["M"]
         cont = net.cont
         tr = st["tr"]
-        self.memory._store.gather(st["arange"], as_float=True, out={k: tr[k] for k in tr})
         if captured:
             pass  # st["h0"] / ["h1"] / ["value"] / ["next_value"] were delivered with the rollout (acting-time capture): no forward pass
         elif 2 * M <= min(net.max_rows, 8192):

@@ -15,6 +15,7 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   continuous_q_network         core/network/q_network.py:23-39
   continuous_policy            core/network/policy.py:38-55
   discrete_policy              core/network/policy.py:23-35
+  icm_mlp                      core/network/icm.py:153-188 (+ utils.py:6-24 reward filter, running moments)
 """
 import torch
 
@@ -235,6 +236,52 @@ class ContinuousQ_Network(BaseNetwork):
         orthogonal_init(self.q, "linear")
 
 
+class RunningMeanStd(_Container):
+    """core/network/utils.py:18-24: running mean, variance and count as Parameters without gradient."""
+
+    def __init__(self, shape, epsilon=1e-4):
+        super().__init__()
+        self.mean = torch.nn.Parameter(torch.zeros(shape), requires_grad=False)
+        self.var = torch.nn.Parameter(torch.zeros(shape), requires_grad=False)
+        self.count = torch.nn.Parameter(torch.tensor(epsilon), requires_grad=False)
+
+
+class RewardForwardFilter(_Container):
+    """core/network/utils.py:6-10: the discounted sum of intrinsic rewards per worker."""
+
+    def __init__(self, gamma, num_workers):
+        super().__init__()
+        self.rewems = torch.nn.Parameter(torch.zeros(num_workers), requires_grad=False)
+        self.gamma = gamma
+
+
+class ICM_MLP(_Container):
+    """ICM-PPO's curiosity module (icm.py:153-188): module names, registration order and torch's default initialisation as the reference's,
+    so its state_dict has the reference's 34 keys (25 without batch norm) and, after the same torch.manual_seed, the reference's weights.
+    The feature size is 256 whatever D_hidden says (icm.py:181)."""
+
+    def __init__(self, D_in, D_out, num_workers, gamma, eta, action_type, ri_normalize=True, obs_normalize=True, batch_norm=True, D_hidden=256):
+        super().__init__()
+        assert action_type in ("discrete", "continuous")
+        self.D_in, self.D_out, self.num_workers, self.eta, self.action_type = D_in, D_out, num_workers, eta, action_type
+        self.rms_obs = RunningMeanStd(D_in)
+        self.rms_ri = RunningMeanStd(1)
+        self.rff = RewardForwardFilter(gamma, num_workers)
+        self.obs_normalize, self.ri_normalize, self.batch_norm = obs_normalize, ri_normalize, batch_norm
+        feature_size = 256
+        a = 1 if action_type == "discrete" else D_out
+        self.fc1 = torch.nn.Linear(D_in, D_hidden)
+        self.fc2 = torch.nn.Linear(D_hidden, feature_size)
+        self.forward_fc1 = torch.nn.Linear(feature_size + a, D_hidden)
+        self.forward_fc2 = torch.nn.Linear(D_hidden + a, feature_size)
+        self.inverse_fc1 = torch.nn.Linear(2 * feature_size, D_hidden)
+        self.inverse_fc2 = torch.nn.Linear(D_hidden, D_out)
+        if batch_norm:
+            self.bn1 = torch.nn.BatchNorm1d(D_hidden)
+            self.bn2 = torch.nn.BatchNorm1d(feature_size)
+            self.bn1_next = torch.nn.BatchNorm1d(D_hidden)
+
+
 network_dict = {
     "discrete_q_network": DiscreteQ_Network,
     "discrete_policy_value": DiscretePolicyValue,
@@ -247,6 +294,7 @@ network_dict = {
     "continuous_q_network": ContinuousQ_Network,
     "continuous_policy": ContinuousPolicy,
     "discrete_policy": DiscretePolicy,
+    "icm_mlp": ICM_MLP,
 }
 
 

@@ -1892,6 +1892,124 @@ class SACNet(_ActorCriticBuckets):
         L.check(self.lib.jh_sacnet_actor_update(self.h, L.ptr(x), L.ptr(eps), B, L.ptr(action), L.ptr(logp), L.ptr(q), L.ptr(stats), L.stream_ptr()))
 
 
+class ICMNet(_NetObject):
+    """jh_icmnet_*: ICM-PPO's curiosity module (network/icm.py:153-218) -- the feature trunk with batch norm under batch statistics and ELU,
+    the forward and the inverse model, the running moments of observations and intrinsic reward, the reward filter -- with the no-grad reward
+    pass over a rollout (`obs_update`, `reward`) and one minibatch update (`update`: forward, both losses, backward, clip, Adam) as tile-engine
+    launches plus the kernels of jh_icm.hip.  The trainable tensors live in flat buckets in the reference's registration order (`_SEG`);
+    everything that is a buffer-like Parameter in the reference (rms_obs, rms_ri, rff, the batch norms' running statistics) lives in the
+    device statistics block (`stats()` / `set_stats()`, the reference's state_dict keys)."""
+
+    _SEG = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "forward_fc1.weight", "forward_fc1.bias", "forward_fc2.weight", "forward_fc2.bias",
+            "inverse_fc1.weight", "inverse_fc1.bias", "inverse_fc2.weight", "inverse_fc2.bias", "bn1.weight", "bn1.bias", "bn2.weight", "bn2.bias",
+            "bn1_next.weight", "bn1_next.bias")
+    _SYM = "jh_icmnet_"
+    F = 256            # feature size (icm.py:181)
+    MAX_BATCH = 8192   # rows of one call (jh_icm.hip: kMaxBatch)
+
+    def __init__(self, state_size, hidden, action_size, continuous, num_workers, max_batch, device, eta=0.01, gamma=0.99, obs_normalize=True, ri_normalize=True,
+                 batch_norm=True, buckets=None):
+        self._open(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.S, self.H, self.A, self.cont, self.W, self.maxB = int(state_size), int(hidden), int(action_size), bool(continuous), int(num_workers), int(max_batch)
+        self.eta, self.gamma = float(eta), float(gamma)
+        self.obs_normalize, self.ri_normalize, self.batch_norm = bool(obs_normalize), bool(ri_normalize), bool(batch_norm)
+        n = int(self._fn("param_count_for")(self.S, self.H, self.A, int(self.cont), int(self.batch_norm)))
+        if n <= 0:
+            L.check(-2)
+        self.n_params = n
+        self.params, self.grads, self.m, self.v = self._zeros(n, 4) if buckets is None else buckets
+        assert all(t.numel() == n and t.is_contiguous() and t.dtype == torch.float32 for t in (self.params, self.grads, self.m, self.v))
+        flags = int(self.obs_normalize) | (int(self.ri_normalize) << 1) | (int(self.batch_norm) << 2)
+        self.h = C.c_void_p()
+        L.check(self._fn("create")(self.ctx, self.S, self.H, self.A, int(self.cont), self.W, self.maxB, flags, self.eta, self.gamma, L.ptr(self.params), L.ptr(self.grads),
+                                   L.ptr(self.m), L.ptr(self.v), C.byref(self.h)))
+        names = self._SEG[: int(self._fn("segment_count")(self.h))]
+        assert len(names) == (18 if self.batch_norm else 12)
+        self.seg = self._segments(names)
+        self.stats_floats = int(self._fn("stats_floats")(self.h))
+        self.ac = self.A if self.cont else 1
+
+    def _pairs(self, bucket):
+        """[(reference key, view of the bucket shaped like the reference tensor)] in the reference's registration order."""
+        out = []
+        for name, (off, rows, cols) in self.seg.items():
+            v = bucket[off : off + rows * cols]
+            out.append((name, v.view(rows, cols) if name.endswith(".weight") and not name.startswith("bn") else v))
+        return out
+
+    def export_state(self, bucket=None):
+        return _export_pairs(self._pairs(self.params if bucket is None else bucket))
+
+    def import_state(self, sd, bucket=None):
+        _import_pairs(self._pairs(self.params if bucket is None else bucket), sd, self.device)
+
+    def set_hyper(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
+        L.check(self._fn("set_hyper")(self.h, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
+
+    def set_lr(self, lr):
+        L.check(self._fn("set_lr")(self.h, float(lr), L.stream_ptr()))
+
+    def _stats_layout(self):
+        S, H, W, F = self.S, self.H, self.W, self.F
+        return (("rms_obs.mean", S), ("rms_obs.var", S), ("rms_obs.count", 0), ("rms_ri.mean", 1), ("rms_ri.var", 1), ("rms_ri.count", 0), ("rff.rewems", W),
+                ("bn1.running_mean", H), ("bn1.running_var", H), ("bn2.running_mean", F), ("bn2.running_var", F), ("bn1_next.running_mean", H),
+                ("bn1_next.running_var", H))
+
+    def stats(self):
+        """The statistics block as {reference state_dict key: float32 numpy array} (synchronises).  The batch norms' entries are there
+        whether or not batch_norm is on (a module without batch norm has no such keys: the caller drops them)."""
+        h = np.empty(self.stats_floats, np.float32)
+        L.check(self._fn("stats_get")(self.h, L.ptr(h), L.stream_ptr()))
+        out, o = {}, 0
+        for name, k in self._stats_layout():
+            out[name] = h[o : o + max(k, 1)].copy().reshape(() if k == 0 else (k,))
+            o += max(k, 1)
+        assert o == self.stats_floats
+        return out
+
+    def set_stats(self, d):
+        """Entries of `d` (keys as stats()) replace the block's; the others stay (synchronises)."""
+        cur = self.stats()
+        for k, v in d.items():
+            if k in cur:
+                v = (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)).astype(np.float32)
+                if v.size != cur[k].size:
+                    raise ValueError(f"{k}: expected {cur[k].size} values, got {v.size}")
+                cur[k] = v.reshape(cur[k].shape)
+        h = np.concatenate([cur[name].reshape(-1) for name, _ in self._stats_layout()]).astype(np.float32)
+        L.check(self._fn("stats_set")(self.h, L.ptr(h), L.stream_ptr()))
+
+    def _check_rows(self, state, next_state, action):
+        for t, w in ((state, self.S), (next_state, self.S), (action, self.ac)):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device and t.numel() == int(state.shape[0]) * w
+
+    def obs_update(self, next_state):
+        """icm.update_rms_obs(next_state) (icm_ppo.py:98)."""
+        assert next_state.is_contiguous() and next_state.dtype == torch.float32 and next_state.shape[1] == self.S
+        L.check(self._fn("obs_update")(self.h, L.ptr(next_state), int(next_state.shape[0]), L.stream_ptr()))
+
+    def reward(self, state, next_state, action, reward, extrinsic_coeff=1.0, intrinsic_coeff=1.0, ri_mean=None, ri_raw=None, ri=None):
+        """The no-grad pass of icm_ppo.py:99-102 over the whole rollout: `reward` [M] becomes ext * reward + int * r_i in place; optional outputs
+        ri_mean [1], ri_raw [M] (before the normalisation), ri [M] (after)."""
+        M = int(state.shape[0])
+        self._check_rows(state, next_state, action)
+        assert reward.is_contiguous() and reward.dtype == torch.float32 and reward.numel() == M
+        assert (ri_raw is None or ri_raw.numel() == M) and (ri is None or ri.numel() == M) and (ri_mean is None or ri_mean.numel() >= 1)
+        L.check(self._fn("reward")(self.h, L.ptr(state), L.ptr(next_state), L.ptr(action), M, float(extrinsic_coeff), float(intrinsic_coeff), L.ptr(reward), L.ptr(ri_mean),
+                                   L.ptr(ri_raw), L.ptr(ri), L.stream_ptr()))
+
+    def update(self, state, next_state, action, idx, beta, max_norm, stats=None, b=None):
+        """One minibatch (icm_ppo.py:177, 185, 194-199) on rows idx (int64) of the rollout arrays, or on rows 0 .. b - 1.  stats [4] = l_f, l_i, 0, mark."""
+        self._check_rows(state, next_state, action)
+        b = int(idx.numel()) if idx is not None else (int(state.shape[0]) if b is None else int(b))
+        assert idx is None or (idx.is_contiguous() and idx.dtype == torch.int64 and idx.device == self.device)
+        assert stats is None or stats.numel() >= 4
+        L.check(self._fn("update")(self.h, L.ptr(state), L.ptr(next_state), L.ptr(action), L.ptr(idx), b, int(state.shape[0]), float(beta),
+                                   float(max_norm if max_norm else 0.0), L.ptr(stats), L.stream_ptr()))
+
+
 class StagingRing:
     """jh_ring_*: bounded lock-free multi-producer / single-consumer ring of transitions in pinned host memory
     (the async Ape-X transport).  `produce` may be called from any number of actor threads (the GIL is released
