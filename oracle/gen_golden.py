@@ -7,7 +7,7 @@ tests/golden/ that pin (a) the CPU oracle in oracle/jorldy_oracle.py and
 (b) the HIP path, because the reference's own tests hold no golden vectors
 (SURVEY.md §4 / §8c).
 
-How the reference is exercised without editing it:
+How the reference is exercised without editing it (staging, the main and the tap are oracle/refkit.py's, shared with tools/gen_golden_*.py):
   * the tree is copied (minus Unity binaries) to a scratch dir and imported
     from there with PYTHONDONTWRITEBYTECODE (importing `core` rewrites
     `_*_dict.txt` files, SURVEY.md §8c "import trap");
@@ -19,88 +19,16 @@ How the reference is exercised without editing it:
 
 Usage:  python oracle/gen_golden.py [--ref /root/reference] [--out tests/golden]
 """
-import argparse
 import inspect
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
+from functools import partial
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import synth  # noqa: E402  (recipes shared with the tests: weights / frames regenerated from a seed)
-
-
-def _to_np(v):
-    import torch
-
-    if isinstance(v, torch.Tensor):
-        return v.detach().cpu().numpy().copy()
-    if isinstance(v, np.ndarray):
-        return v.copy()
-    if isinstance(v, (list, tuple)) and v and isinstance(v[0], (int, float, np.integer, np.floating)):
-        return np.asarray(v)
-    if isinstance(v, (int, float, bool, np.integer, np.floating)):
-        return np.asarray(v)
-    return None
-
-
-class LineTap:
-    """Snapshot named locals of `func` each time execution reaches a source line
-    containing one of the given marker substrings (BEFORE that line executes),
-    and once more at return (key '<return>')."""
-
-    def __init__(self, func, markers):
-        self.code = func.__code__
-        src, first = inspect.getsourcelines(func)
-        self.line_to_key = {}
-        for key, (needle, names) in markers.items():
-            hits = [i for i, s in enumerate(src) if needle in s]
-            assert hits, f"marker {needle!r} not found in {func.__qualname__}"
-            self.line_to_key[first + hits[0]] = (key, names)
-        self.ret_names = markers.get("<return>", (None, ()))[1] if "<return>" in markers else ()
-        self.records = {}  # key -> list of dict
-        self.on_line = {}  # key -> callback(frame)
-
-    def _local(self, frame, event, arg):
-        if event == "line" and frame.f_lineno in self.line_to_key:
-            key, names = self.line_to_key[frame.f_lineno]
-            if key in self.on_line:
-                self.on_line[key](frame)
-            snap = {}
-            for n in names:
-                if n in frame.f_locals:
-                    a = _to_np(frame.f_locals[n])
-                    if a is not None:
-                        snap[n] = a
-            self.records.setdefault(key, []).append(snap)
-        return self._local
-
-    def _global(self, frame, event, arg):
-        if event == "call" and frame.f_code is self.code:
-            return self._local
-        return None
-
-    def __enter__(self):
-        sys.settrace(self._global)
-        return self
-
-    def __exit__(self, *a):
-        sys.settrace(None)
-
-
-RECIPE_SEED = 20260925
-
-
-def flat(prefix, d, out):
-    for k, v in d.items():
-        out[f"{prefix}{k}"] = v
-
-
-def sd_to_np(sd):
-    return {k: v.detach().cpu().numpy().copy() for k, v in sd.items()}
+from oracle.refkit import RECIPE_SEED, LineTap, _fill, dump_rollout, flat, grad_norm, grads_of, last_outputs, retaining_hooks, run, sd_to_np, set_weights, store_step  # noqa: E402,F401
 
 
 # ----------------------------------------------------------------------------
@@ -223,39 +151,41 @@ def gen_buffers(out_dir):
 # ----------------------------------------------------------------------------
 # PPO
 # ----------------------------------------------------------------------------
+PPO_CASES = [
+    # name, S, A, hidden, W, T, batch, n_epoch, continuous, recipe
+    ("ppo_disc_small", 4, 3, 32, 4, 16, 16, 2, False, False),
+    ("ppo_disc_cartpole", 4, 2, 64, 8, 128, 256, 3, False, False),
+    ("ppo_cont_small", 5, 3, 32, 4, 16, 32, 2, True, False),
+    ("ppo_cont_hopper", 11, 3, 64, 4, 64, 64, 2, True, False),
+    # BASELINE widths (recipe = initial weights regenerated from a seed, big arrays stored thinned):
+    # config.ppo.cartpole exactly (hidden 512, 8 x 128, minibatch 256, 3 epochs; config/ppo/cartpole.py:9-40)
+    ("ppo_disc_cartpole_h512", 4, 2, 512, 8, 128, 256, 3, False, True),
+    # config.ppo.mujoco Hopper shapes (S=11, A=3, hidden 512, T=2048, distributed batch 2048;
+    # config/ppo/mujoco.py:8-41) with 2 workers x 2 epochs = 4 minibatches of 2048 rows
+    ("ppo_cont_hopper_real", 11, 3, 512, 2, 2048, 2048, 2, True, True),
+    # config.ppo.mujoco on its OTHER envs (config/ppo/mujoco.py:3-4 takes --env.name half_cheetah | walker | ant ...): more than 8 head
+    # outputs (2 A + 1 = 13 / 17).  HalfCheetah-v3 shapes (S=17, A=6) with minibatches of 1024 rows (the tiled engine), Ant shapes
+    # (S=27, A=8) with minibatches of 256 rows (the separate forward / backward calls)
+    # (11th element = the rollout seed, CHOSEN so that no ReLU pre-activation of any forward pass of this learn() lies within 3e-7
+    # of zero -- `relu_margin` in the fixture: two correct fp32 evaluations of a 512-term dot product differ by ~1e-7, and a unit whose
+    # pre-activation is that close to zero is on in one and off in the other: with seed 5 exactly ONE of HalfCheetah's 8 M ReLU
+    # decisions (row 297, unit 344 of minibatch 0: -3.2e-7 in float64, +6.0e-8 in torch's fp32) moved the trunk gradients by 1e-3 of
+    # their largest entry -- a property of the input, not of either implementation.  Among seeds 5..16 HalfCheetah's best margin is 3.7e-7
+    # (seed 15), Ant's 3.2e-6 (seed 5).  JH_GEN_ROLLOUT_SEED overrides for the search.)
+    ("ppo_cont_halfcheetah", 17, 6, 512, 2, 1024, 1024, 2, True, True, 15),
+    ("ppo_cont_ant_mb256", 27, 8, 512, 2, 256, 256, 2, True, True, 5),
+    # round 6: PPO on the CNN head (policy_value.py:8-22 over head.py:21-61).  A small image, and config.ppo.atari's shapes exactly
+    # ((4, 84, 84) uint8 frames, hidden 512, minibatch 32, lr 2.5e-4; config/ppo/atari.py:16-36) with A = 6 (Pong) on a 2 x 32 rollout
+    ("ppo_disc_cnn_small", (4, 44, 52), 4, 64, 2, 16, 16, 2, False, True),
+    ("ppo_disc_atari", (4, 84, 84), 6, 512, 2, 32, 32, 2, False, True),
+]
+
+
 def gen_ppo(out_dir, only=None):
     import torch
     from core.agent.ppo import PPO
 
-    cases = [
-        # name, S, A, hidden, W, T, batch, n_epoch, continuous, recipe
-        ("ppo_disc_small", 4, 3, 32, 4, 16, 16, 2, False, False),
-        ("ppo_disc_cartpole", 4, 2, 64, 8, 128, 256, 3, False, False),
-        ("ppo_cont_small", 5, 3, 32, 4, 16, 32, 2, True, False),
-        ("ppo_cont_hopper", 11, 3, 64, 4, 64, 64, 2, True, False),
-        # BASELINE widths (recipe = initial weights regenerated from a seed, big arrays stored thinned):
-        # config.ppo.cartpole exactly (hidden 512, 8 x 128, minibatch 256, 3 epochs; config/ppo/cartpole.py:9-40)
-        ("ppo_disc_cartpole_h512", 4, 2, 512, 8, 128, 256, 3, False, True),
-        # config.ppo.mujoco Hopper shapes (S=11, A=3, hidden 512, T=2048, distributed batch 2048;
-        # config/ppo/mujoco.py:8-41) with 2 workers x 2 epochs = 4 minibatches of 2048 rows
-        ("ppo_cont_hopper_real", 11, 3, 512, 2, 2048, 2048, 2, True, True),
-        # config.ppo.mujoco on its OTHER envs (config/ppo/mujoco.py:3-4 takes --env.name half_cheetah | walker | ant ...): more than 8 head
-        # outputs (2 A + 1 = 13 / 17).  HalfCheetah-v3 shapes (S=17, A=6) with minibatches of 1024 rows (the tiled engine), Ant shapes
-        # (S=27, A=8) with minibatches of 256 rows (the separate forward / backward calls)
-        # (11th element = the rollout seed, CHOSEN so that no ReLU pre-activation of any forward pass of this learn() lies within 3e-7
-        # of zero -- `relu_margin` in the fixture: two correct fp32 evaluations of a 512-term dot product differ by ~1e-7, and a unit whose
-        # pre-activation is that close to zero is on in one and off in the other: with seed 5 exactly ONE of HalfCheetah's 8 M ReLU
-        # decisions (row 297, unit 344 of minibatch 0: -3.2e-7 in float64, +6.0e-8 in torch's fp32) moved the trunk gradients by 1e-3 of
-        # their largest entry -- a property of the input, not of either implementation.  Among seeds 5..16 HalfCheetah's best margin is 3.7e-7
-        # (seed 15), Ant's 3.2e-6 (seed 5).  JH_GEN_ROLLOUT_SEED overrides for the search.)
-        ("ppo_cont_halfcheetah", 17, 6, 512, 2, 1024, 1024, 2, True, True, 15),
-        ("ppo_cont_ant_mb256", 27, 8, 512, 2, 256, 256, 2, True, True, 5),
-        # round 6: PPO on the CNN head (policy_value.py:8-22 over head.py:21-61).  A small image, and config.ppo.atari's shapes exactly
-        # ((4, 84, 84) uint8 frames, hidden 512, minibatch 32, lr 2.5e-4; config/ppo/atari.py:16-36) with A = 6 (Pong) on a 2 x 32 rollout
-        ("ppo_disc_cnn_small", (4, 44, 52), 4, 64, 2, 16, 16, 2, False, True),
-        ("ppo_disc_atari", (4, 84, 84), 6, 512, 2, 32, 32, 2, False, True),
-    ]
-    for case in cases:
+    for case in PPO_CASES:
         name, S, A, H, W, T, B, E, cont, recipe = case[:10]
         rollout_seed = int(os.environ.get("JH_GEN_ROLLOUT_SEED", case[10])) if len(case) > 10 else 5
         if only is not None and name not in only:
@@ -282,15 +212,8 @@ def gen_ppo(out_dir, only=None):
             num_workers=W,
             device="cpu",
         )
-        with torch.no_grad():
-            if recipe:
-                rec = synth.ppo_recipe({k: v.shape for k, v in agent.network.state_dict().items()}, RECIPE_SEED)
-                for k, p in agent.network.named_parameters():
-                    p.copy_(torch.from_numpy(rec[k]))
-            else:
-                # perturb the heads so pi is not ~uniform / value not ~0 (policy gain is 0.01)
-                for p in agent.network.parameters():
-                    p.add_(0.05 * torch.randn_like(p))
+        # without a recipe: perturb the heads so pi is not ~uniform / value not ~0 (policy gain is 0.01)
+        set_weights([agent.network], synth.ppo_recipe if recipe else None, RECIPE_SEED, 0.05)
         sd0 = sd_to_np(agent.network.state_dict())
 
         rng = np.random.RandomState(rollout_seed)
@@ -299,23 +222,8 @@ def gen_ppo(out_dir, only=None):
         agent.memory.first_store = False
 
         # capture pre-softmax / pre-clamp head outputs with grads
-        head_out = {}
-
-        def mk_hook(tag):
-            def hook(mod, inp, outp):
-                if outp.requires_grad:
-                    outp.retain_grad()
-                head_out.setdefault(tag, []).append(outp)
-
-            return hook
-
-        hooks = []
-        if cont:
-            hooks.append(agent.network.mu.register_forward_hook(mk_hook("mu_raw")))
-            hooks.append(agent.network.log_std.register_forward_hook(mk_hook("log_std_raw")))
-        else:
-            hooks.append(agent.network.pi.register_forward_hook(mk_hook("logits")))
-        hooks.append(agent.network.v.register_forward_hook(mk_hook("v")))
+        net = agent.network
+        head_out, hooks = retaining_hooks({"mu_raw": net.mu, "log_std_raw": net.log_std, "v": net.v} if cont else {"logits": net.pi, "v": net.v})
         relu_margin = [np.inf]
         if len(case) > 10:  # smallest |pre-activation| over every forward pass of this learn() (both hidden layers)
             def margin_hook(mod, inp, outp):
@@ -336,17 +244,12 @@ def gen_ppo(out_dir, only=None):
 
         def on_grad(frame):
             mbi = len(tap.records["mb_loss"]) - 1
-            grads_raw[mbi] = {k: p.grad.detach().numpy().copy() for k, p in agent.network.named_parameters()}
-            # the LAST two/three forward outputs are this minibatch's heads
-            hg = {}
-            for tag, lst in head_out.items():
-                hg[tag] = lst[-1].detach().numpy().copy()
-                hg["d_" + tag] = lst[-1].grad.detach().numpy().copy()
-            head_grads[mbi] = hg
+            grads_raw[mbi] = grads_of(agent.network)
+            head_grads[mbi] = last_outputs(head_out)  # the LAST two/three forward outputs are this minibatch's heads
 
         def on_step(frame):
             mbi = len(tap.records["mb_loss"]) - 1
-            grads_clip[mbi] = {k: p.grad.detach().numpy().copy() for k, p in agent.network.named_parameters()}
+            grads_clip[mbi] = grads_of(agent.network)
 
         tap.on_line["mb_grad"] = on_grad
         tap.on_line["mb_step"] = on_step
@@ -372,13 +275,11 @@ def gen_ppo(out_dir, only=None):
             out["rollout_seed"] = np.asarray(rollout_seed)
             if len(case) > 10:
                 out["relu_margin"] = np.asarray(relu_margin[0])
-            for k in ("state", "reward", "action"):
-                out[f"in_{k}_check"] = synth.row_checksum(np.concatenate([t[k] for t in trs], 0).astype(np.float32))[:: max(1, M // 64)]
+            dump_rollout(out, "", trs, recipe)
             flat("sd0_thin/", {k: th(v) for k, v in sd0.items()}, out)
             flat("sd1_thin/", {k: th(v) for k, v in sd_to_np(agent.network.state_dict()).items()}, out)
         else:
-            for k in ("state", "next_state", "reward", "done", "action"):
-                out[f"in_{k}"] = np.concatenate([t[k] for t in trs], 0)
+            dump_rollout(out, "", trs, recipe)
             flat("sd0/", sd0, out)
             flat("sd1/", sd_to_np(agent.network.state_dict()), out)
         flat("gae/", tap.records["gae_done"][0], out)
@@ -391,7 +292,7 @@ def gen_ppo(out_dir, only=None):
                 flat(f"mb{i}/grad_raw/", {k: th(v) for k, v in grads_raw[i].items()}, out)
                 flat(f"mb{i}/grad_clip/", {k: th(v) for k, v in grads_clip[i].items()}, out)
                 if recipe:
-                    out[f"mb{i}/grad_raw_norm"] = np.sqrt(sum(float((v.astype(np.float64) ** 2).sum()) for v in grads_raw[i].values()))
+                    out[f"mb{i}/grad_raw_norm"] = grad_norm(grads_raw[i])
                     for k, v in grads_raw[i].items():
                         out[f"mb{i}/grad_raw_absmax/{k}"] = np.abs(v).max()
         for k, v in result.items():
@@ -404,13 +305,7 @@ def gen_ppo(out_dir, only=None):
 # ----------------------------------------------------------------------------
 # DQN family
 # ----------------------------------------------------------------------------
-def _fill(agent, n, S, A, rng, n_step=None, with_q=False):
-    """Drive interact_callback + memory.store the way Actor.run / run_mode do."""
-    for i in range(n):
-        t = synth.raw_transition(rng, S, A, with_q)
-        t = agent.interact_callback(t)
-        if t:
-            agent.memory.store([t])
+BIG = ("rainbow_cnn", "rainbow_cnn_atari", "dqn_h512", "ape_x_cnn_atari", "ape_x_cnn_clip")  # on request only
 
 
 def gen_dqn_family(out_dir, only=None):
@@ -474,9 +369,8 @@ def gen_dqn_family(out_dir, only=None):
                        over=dict(state_size=(4, 44, 52), action_size=6, hidden_size=64, network="dueling", head="cnn", batch_size=8, buffer_size=64,
                                  optim_config={"name": "rmsprop", "lr": 2.5e-4 / 4, "eps": 1.5e-7, "centered": True}),
                        fill=40, recipe=True, opt_state=("square_avg", "grad_avg"))))
-    big = ("rainbow_cnn", "rainbow_cnn_atari", "dqn_h512", "ape_x_cnn_atari", "ape_x_cnn_clip")
     for name, cls, extra, opt in specs:
-        if (only is None and name in big) or (only is not None and name != only):
+        if (only is None and name in BIG) or (only is not None and name != only):
             continue
         torch.manual_seed(3)
         np.random.seed(3)
@@ -486,19 +380,8 @@ def gen_dqn_family(out_dir, only=None):
         S, B, A, H = kw["state_size"], kw["batch_size"], kw["action_size"], kw["hidden_size"]
         recipe = opt.get("recipe", False)
         agent = cls(**kw)
-        with torch.no_grad():
-            if recipe:
-                shapes = {k: v.shape for k, v in agent.network.state_dict().items()}
-                for net, seed in ((agent.network, RECIPE_SEED), (agent.target_network, RECIPE_SEED + 1)):
-                    rec = synth.recipe_state_dict(shapes, seed)
-                    for k, p in net.named_parameters():
-                        p.copy_(torch.from_numpy(rec[k]))
-            else:
-                for p in agent.network.parameters():
-                    p.add_(0.1 * torch.randn_like(p))
-                # target differs from online so double-Q is not degenerate
-                for p in agent.target_network.parameters():
-                    p.add_(0.1 * torch.randn_like(p))
+        # (perturbed: the target differs from online so double-Q is not degenerate)
+        set_weights([agent.network, agent.target_network], synth.recipe_state_dict if recipe else None, RECIPE_SEED, 0.1)
         agent.memory.first_store = False
         rng = np.random.RandomState(17)
         _fill(agent, opt.get("fill", 200), S, A, rng, with_q=opt.get("with_q", False))
@@ -548,7 +431,7 @@ def gen_dqn_family(out_dir, only=None):
         head = {}
 
         def on_step(frame):
-            graw.update({k: p.grad.detach().numpy().copy() for k, p in agent.network.named_parameters()})
+            graw.update(grads_of(agent.network))
             for nm in ("q", "logit"):
                 if nm in frame.f_locals and frame.f_locals[nm].grad is not None:
                     head["d_" + nm] = frame.f_locals[nm].grad.detach().numpy().copy()
@@ -561,7 +444,7 @@ def gen_dqn_family(out_dir, only=None):
         tap.on_line["step"] = on_step
         tap.on_line["pre_step"] = on_pre
         if "pre_clip" in markers:
-            tap.on_line["pre_clip"] = lambda frame: gpre.update({k: p.grad.detach().numpy().copy() for k, p in agent.network.named_parameters()})
+            tap.on_line["pre_clip"] = lambda frame: gpre.update(grads_of(agent.network))
 
         net64 = tgt64 = None
         if opt.get("grad64"):  # float64 twins of both networks (before the step) for a ground-truth gradient
@@ -597,26 +480,11 @@ def gen_dqn_family(out_dir, only=None):
                 out[f"grad64_thin/{k}"] = synth.thin(p64.grad.numpy())
         flat("learn/", rec, out)
         flat("learn/", head, out)
-        if recipe:
-            if gpre:  # gradients BEFORE clip_grad_norm_; graw (taken at optimizer.step()) holds the clipped ones
-                out["grad_clip_norm"] = np.sqrt(sum(float((v.astype(np.float64) ** 2).sum()) for v in graw.values()))
-                graw = gpre
-            flat("grad_thin/", {k: synth.thin(v) for k, v in graw.items()}, out)
-            out["grad_norm"] = np.sqrt(sum(float((v.astype(np.float64) ** 2).sum()) for v in graw.values()))
-            for k, v in graw.items():
-                out[f"grad_absmax/{k}"] = np.abs(v).max()
-            flat("sd0_thin/", {k: synth.thin(v) for k, v in sd0.items()}, out)
-            flat("sdt_thin/", {k: synth.thin(v) for k, v in sdt.items()}, out)
-            flat("sd1_thin/", {k: synth.thin(v) for k, v in sd_to_np(agent.network.state_dict()).items()}, out)
-            # optimizer moments after the step (Adam exp_avg / exp_avg_sq, RMSprop square_avg / grad_avg), per parameter name
-            for st_key in opt.get("opt_state", ()):
-                for k, p in agent.network.named_parameters():
-                    out[f"opt1_thin/{st_key}/{k}"] = synth.thin(agent.optimizer.state[p][st_key].detach().numpy())
-        else:
-            flat("grad/", graw, out)
-            flat("sd0/", sd0, out)
-            flat("sdt/", sdt, out)
-            flat("sd1/", sd_to_np(agent.network.state_dict()), out)
+        if recipe and gpre:  # gradients BEFORE clip_grad_norm_; graw (taken at optimizer.step()) holds the clipped ones
+            out["grad_clip_norm"] = grad_norm(graw)
+            graw = gpre
+        # optimizer moments after the step (Adam exp_avg / exp_avg_sq, RMSprop square_avg / grad_avg), per parameter name
+        store_step(out, agent, graw, sd0, sdt, thin=synth.thin if recipe else None, moments=opt.get("opt_state", ()) if recipe else ())
         for k, v in result.items():
             out[f"result/{k}"] = np.asarray(v)
         if is_per:
@@ -679,44 +547,10 @@ def gen_nstep(out_dir):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"))
-    ap.add_argument("--only", default="")
-    args = ap.parse_args()
-    out_dir = os.path.abspath(args.out)
-    os.makedirs(out_dir, exist_ok=True)
-
-    scratch = tempfile.mkdtemp(prefix="jref_")
-    subprocess.check_call(
-        f"cd {args.ref} && tar --exclude='jorldy/core/env/mlagents' -cf - jorldy | (cd {scratch} && tar xf -)",
-        shell=True,
-    )
-    os.chdir(os.path.join(scratch, "jorldy"))
-    sys.path.insert(0, os.getcwd())
-    sys.dont_write_bytecode = True
-    import torch
-
-    torch.set_num_threads(1)  # deterministic reductions in the fixtures
-    try:
-        todo = args.only.split(",") if args.only else ["buffers", "ppo", "dqn", "nstep"]  # + rainbow_cnn, rainbow_cnn_atari, dqn_h512, ape_x_cnn_atari on request
-        if "buffers" in todo:
-            gen_buffers(out_dir)
-        if "ppo" in todo:
-            gen_ppo(out_dir)
-        ppo_only = [t for t in todo if t.startswith("ppo_")]
-        if ppo_only:
-            gen_ppo(out_dir, only=ppo_only)
-        if "dqn" in todo:
-            gen_dqn_family(out_dir)
-        if "nstep" in todo:
-            gen_nstep(out_dir)
-        for nm in ("rainbow_cnn", "rainbow_cnn_atari", "dqn_h512", "ape_x_cnn_atari", "ape_x_cnn_clip"):
-            if nm in todo:
-                gen_dqn_family(out_dir, only=nm)
-    finally:
-        shutil.rmtree(scratch, ignore_errors=True)
-    print("golden fixtures written to", out_dir)
+    parts = {"buffers": gen_buffers, "ppo": gen_ppo, "dqn": gen_dqn_family, "nstep": gen_nstep}
+    parts.update({case[0]: partial(gen_ppo, only=[case[0]]) for case in PPO_CASES})
+    parts.update({name: partial(gen_dqn_family, only=name) for name in BIG})
+    run(parts, ref="/root/reference", default="buffers,ppo,dqn,nstep")
 
 
 if __name__ == "__main__":

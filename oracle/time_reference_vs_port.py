@@ -11,16 +11,14 @@ Rainbow.learn (config.rainbow.atari shapes) vs RainbowPort.learn.  and DQN.learn
 import argparse
 import json
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from oracle.refkit import staged_reference  # noqa: E402
 
 
 def main():
@@ -36,13 +34,7 @@ def main():
     from oracle.rainbow_port import RainbowPort
 
     torch.set_num_threads(args.threads)
-    scratch = tempfile.mkdtemp(prefix="jref_")
-    subprocess.check_call(f"cd {args.ref} && tar --exclude='jorldy/core/env/mlagents' -cf - jorldy | (cd {scratch} && tar xf -)", shell=True)
-    cwd = os.getcwd()
-    os.chdir(os.path.join(scratch, "jorldy"))
-    sys.path.insert(0, os.getcwd())
-    sys.dont_write_bytecode = True
-    try:
+    with staged_reference(args.ref):
         from core.agent.ppo import PPO
         from core.agent.rainbow import Rainbow
 
@@ -118,9 +110,6 @@ def main():
         out["threads"], out["host"] = args.threads, f"{os.cpu_count()} logical cores (build container)"
         out["note"] = "same process, same torch thread count, alternating calls, medians; the port is what bench.py's cpu_baseline times on the GPU box"
         print(json.dumps(out, indent=1))
-    finally:
-        os.chdir(cwd)
-        shutil.rmtree(scratch, ignore_errors=True)
 
 
 if __name__ == "__main__":

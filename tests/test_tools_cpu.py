@@ -151,3 +151,78 @@ def test_bench_dump_thins_a_rollout_over_the_budget_to_a_seeded_sample(monkeypat
     rows = a["rollout_action"][:, 0].astype(int)
     assert len(rows) == 40 and np.all(np.diff(rows) > 0) and rows.max() < 60 and np.array_equal(a["rollout_state"], c["rollout_state"])
     assert np.array_equal(a["rollout_state"], cols["state"].numpy()[rows])
+
+
+# ---------------------------------------------------------------------------------- oracle/refkit.py, the fixture generators' toolkit
+def _fake_reference(tmp_path):
+    ref = tmp_path / "checkout"
+    (ref / "jorldy" / "core" / "env" / "mlagents").mkdir(parents=True)
+    (ref / "jorldy" / "core" / "__pycache__").mkdir()
+    (ref / "jorldy" / "core" / "__init__.py").write_text("")
+    (ref / "jorldy" / "core" / "__pycache__" / "stale.pyc").write_bytes(b"\0")
+    (ref / "jorldy" / "core" / "env" / "mlagents" / "x.bin").write_bytes(b"\0" * 16)
+    (ref / "jorldy" / "refkit_probe.py").write_text("import core\nWHERE = __file__\nCORE = core.__file__\n")
+    return str(ref)
+
+
+def _check_inside_the_copy(copy):
+    import refkit_probe
+
+    assert os.path.samefile(os.getcwd(), copy) and sys.path[0] == copy and sys.dont_write_bytecode
+    assert os.path.samefile(refkit_probe.WHERE, os.path.join(copy, "refkit_probe.py")) and os.path.samefile(refkit_probe.CORE, os.path.join(copy, "core", "__init__.py"))
+    assert os.path.isdir(os.path.join(copy, "core", "env")) and not os.path.exists(os.path.join(copy, "core", "env", "mlagents"))
+    assert not [d for d, sub, _ in os.walk(copy) if "__pycache__" in sub]
+
+
+def test_staged_reference_imports_from_a_scratch_copy_and_undoes_itself_also_on_an_exception(tmp_path):
+    from oracle import refkit
+
+    ref = _fake_reference(tmp_path)
+    before = (os.getcwd(), list(sys.path), sys.dont_write_bytecode)
+    with refkit.staged_reference(ref) as copy:
+        _check_inside_the_copy(copy)
+    assert (os.getcwd(), sys.path, sys.dont_write_bytecode) == before and not os.path.exists(os.path.dirname(copy))
+    assert "refkit_probe" not in sys.modules and "core" not in sys.modules
+    seen = []
+    with pytest.raises(RuntimeError):
+        with refkit.staged_reference(ref) as copy2:
+            seen.append(copy2)
+            _check_inside_the_copy(copy2)  # imported afresh, from the second copy
+            raise RuntimeError("inside the block")
+    assert seen[0] != copy and (os.getcwd(), sys.path, sys.dont_write_bytecode) == before and not os.path.exists(os.path.dirname(seen[0]))
+    assert "refkit_probe" not in sys.modules and os.path.exists(os.path.join(ref, "jorldy", "core", "env", "mlagents", "x.bin"))
+
+
+def test_line_tap_snapshots_named_locals_in_front_of_the_marked_line():
+    from oracle import refkit
+
+    def three_lines(x):
+        a = x + 1
+        b = a * 2  # the marked line
+        return b
+
+    tracer = sys.gettrace()
+    try:
+        tap = refkit.LineTap(three_lines, {"m": ("# the marked line", ["x", "a", "b", "absent"])})
+        calls = []
+        tap.on_line["m"] = lambda frame: calls.append(sorted(frame.f_locals))
+        with tap:
+            assert three_lines(3) == 8 and three_lines(5) == 12
+        assert sys.gettrace() is None
+        assert calls == [["a", "x"], ["a", "x"]], "on_line runs in front of the marked line: b is not bound yet"
+        assert [sorted(r) for r in tap.records["m"]] == [["a", "x"], ["a", "x"]] and [int(r["a"]) for r in tap.records["m"]] == [4, 6]
+        assert isinstance(tap.records["m"][0]["x"], np.ndarray)
+        with pytest.raises(AssertionError, match="not found"):
+            refkit.LineTap(three_lines, {"m": ("a line this function does not have", [])})
+    finally:
+        sys.settrace(tracer)
+
+
+def test_keeper_is_the_identity_at_zero_and_synths_thin_above():
+    from oracle import refkit, synth
+
+    big, small = np.arange(20000, dtype=np.float32).reshape(100, 200), np.arange(12.0)
+    assert refkit.keeper(0)(big) is big
+    for limit in (100, 8192):
+        assert np.array_equal(refkit.keeper(limit)(big), synth.thin(big, limit)) and refkit.keeper(limit)(big).size < big.size
+        assert np.array_equal(refkit.keeper(limit)(small), small)

@@ -2,8 +2,8 @@
 """Golden vectors and the reference learning curves of ICM-PPO, from the UNMODIFIED reference agent (core/agent/icm_ppo.py).
 
 TEST INFRASTRUCTURE ONLY, for the build machine (where a checkout of the reference exists); nothing on a GPU machine runs this or
-reads the reference.  The reference is staged exactly as oracle/gen_golden.py stages it (scratch copy, no bytecode, one torch thread
-for the fixtures) and `learn()` runs under gen_golden's line tap; this file holds none of the reference's code.
+reads the reference.  Staging, the main, the line tap under which `learn()` runs, the storage helpers and the on-policy curve loop are
+oracle/refkit.py's; this file holds none of the reference's code.
 
   tests/golden/icm_discrete.npz     S 4, A 2, H 32, 5 workers x 8 steps (M 40), B 16: minibatches of 16, 16 and 8.  All three switches on, lr 3e-3,
                                     perturbed weights, the starting weights in full, recorded arrays over 4096 entries thinned; TWO CONSECUTIVE learns l0, l1 (the carry-over of rms_obs, rms_ri,
@@ -29,21 +29,16 @@ The generator checks itself and fails otherwise:
 
 Usage:  python tools/gen_golden_icm.py --ref <reference checkout> [--out tests/golden] [--only fixtures|curves] [--threads 4]
 """
-import argparse
-import json
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from oracle import synth  # noqa: E402
-from oracle.gen_golden import RECIPE_SEED, LineTap, flat, sd_to_np  # noqa: E402
+from oracle import refkit, synth  # noqa: E402
+from oracle.refkit import RECIPE_SEED, LineTap, flat, grads_of, sd_to_np  # noqa: E402
 
 SPECS = {
     "icm_discrete": dict(S=4, A=2, H=32, W=5, T=8, B=16, cont=False, lr=3e-3, n_epoch=1, on=True, learns=2, recipe=False, thin_limit=4096, std=True, eta=0.1),
@@ -101,13 +96,11 @@ def record_learn(agent, spec, trs, np_seed, keep):
     tap = LineTap(type(agent).learn, markers)
     raw, clipped = {}, {}
     mbi = lambda: len(tap.records.get("mb", [])) - 1
-    named = [(k, p) for k, p in icm.named_parameters() if p.requires_grad]
-    tap.on_line["clip"] = lambda frame: raw.__setitem__(mbi(), {k: p.grad.detach().numpy().copy() for k, p in named})
-    tap.on_line["step"] = lambda frame: clipped.__setitem__(mbi(), {k: p.grad.detach().numpy().copy() for k, p in named})
+    tap.on_line["clip"] = lambda frame: raw.__setitem__(mbi(), grads_of(icm, trainable_only=True))
+    tap.on_line["step"] = lambda frame: clipped.__setitem__(mbi(), grads_of(icm, trainable_only=True))
     blk0 = sd_to_np(icm.state_dict())
     icm0 = {k: v.copy() for k, v in blk0.items()}
-    np.random.seed(np_seed)
-    torch.manual_seed(np_seed)
+    refkit.seed_rngs(np_seed)
     with tap:
         result = agent.process(trs, agent.time_t + spec["T"])
     for h in hooks:
@@ -139,7 +132,7 @@ def record_learn(agent, spec, trs, np_seed, keep):
         if i in (0, nmb - 1):
             flat(f"mb{i}/grad_raw/", {k: keep(v) for k, v in raw[i].items()}, out)
             flat(f"mb{i}/grad_clip/", {k: keep(v) for k, v in clipped[i].items()}, out)
-            out[f"mb{i}/grad_raw_norm"] = np.sqrt(sum(float((v.astype(np.float64) ** 2).sum()) for v in raw[i].values()))
+            out[f"mb{i}/grad_raw_norm"] = refkit.grad_norm(raw[i])
             if spec["on"]:  # forward 0 of each batch norm is the pre-pass over the whole rollout, forward 1 + i is minibatch i
                 flat(f"mb{i}/bn_in/", {k: keep(seen["bn_in"][k][1 + i]) for k in BNS}, out)
     flat("result/", {k: np.asarray(v) for k, v in result.items()}, out)
@@ -196,22 +189,15 @@ def try_fixture(name):
 
     spec = SPECS[name]
     S, A, M, cont, recipe, limit = spec["S"], spec["A"], spec["W"] * spec["T"], spec["cont"], spec["recipe"], spec["thin_limit"]
-    keep = (lambda v: synth.thin(v, limit)) if limit else (lambda v: v)
-    torch.manual_seed(INIT_SEED)
-    np.random.seed(INIT_SEED)
+    keep = refkit.keeper(limit)
+    refkit.seed_rngs(INIT_SEED)
     agent = ICM_PPO(**agent_kwargs(spec))
-    with torch.no_grad():
-        if recipe:
-            rec = synth.ppo_recipe({k: v.shape for k, v in agent.network.state_dict().items()}, RECIPE_SEED)
-            for k, p in agent.network.named_parameters():
-                p.copy_(torch.from_numpy(rec[k]))
-            rec = D.icm_recipe({k: tuple(p.shape) for k, p in agent.icm.named_parameters() if p.requires_grad}, RECIPE_SEED)
-            for k, p in agent.icm.named_parameters():
-                if p.requires_grad:
-                    p.copy_(torch.from_numpy(rec[k]))
-        else:
-            for p in list(agent.network.parameters()) + [p for p in agent.icm.parameters() if p.requires_grad]:
-                p.add_(PERTURB * torch.randn_like(p))
+    refkit.set_weights([agent.network], synth.ppo_recipe if recipe else None, RECIPE_SEED, PERTURB)
+    with torch.no_grad():  # then the ICM's trainable tensors alone: its statistics block starts as the reference builds it
+        rec = D.icm_recipe({k: tuple(p.shape) for k, p in agent.icm.named_parameters() if p.requires_grad}, RECIPE_SEED) if recipe else None
+        for k, p in agent.icm.named_parameters():
+            if p.requires_grad:
+                p.copy_(torch.from_numpy(rec[k])) if recipe else p.add_(PERTURB * torch.randn_like(p))
     agent.memory.first_store = False
     out = {}
     sd0, icm0 = sd_to_np(agent.network.state_dict()), sd_to_np(agent.icm.state_dict())
@@ -227,12 +213,7 @@ def try_fixture(name):
         rec, icm_before, icm_after, idx_lists = record_learn(agent, spec, trs, NP_SEED + k, keep)
         flat(f"l{k}/", rec, out)
         out[f"l{k}/rollout_seed"] = np.asarray(seed_k)
-        if recipe:
-            for key in ("state", "reward", "action"):
-                out[f"l{k}/in_{key}_check"] = synth.row_checksum(np.concatenate([t[key] for t in trs], 0).astype(np.float32))[:: max(1, M // 64)]
-        else:
-            for key in ("state", "next_state", "reward", "done", "action"):
-                out[f"l{k}/in_{key}"] = np.concatenate([t[key] for t in trs], 0)
+        refkit.dump_rollout(out, f"l{k}/", trs, recipe)
         # the float64 truth over the same learn, continued from its own previous end: within half of the GPU test's caps
         start = dict(icm_before) if t_w is None else {**{kk: np.asarray(v, np.float64) for kk, v in t_blk.items()}, **t_w}
         if t_opt is not None:
@@ -255,74 +236,29 @@ def try_fixture(name):
                  recipe=int(recipe), recipe_seed=RECIPE_SEED, thin_limit=limit, init_seed=INIT_SEED, perturb=PERTURB, n_epoch=spec["n_epoch"], epsilon_clip=EPS_CLIP,
                  vf_coef=VF, ent_coef=ENT, beta=BETA, eta=spec["eta"], switches=int(spec["on"]), use_standardization=int(spec["std"]))
     hyper["lambda"] = LAMBDA
-    for k, v in hyper.items():
-        out[f"hyper/{k}"] = np.asarray(v)
+    refkit.put_hyper(out, hyper)
     return out
 
 
+def gen_fixture(name, out_dir):
+    refkit.save_fixture(out_dir, name, try_fixture(name))
+
+
 def reference_curve(seed):
-    import torch
     from core.agent.icm_ppo import ICM_PPO
 
-    from oracle import ppo_port as P
-
     c = CURVE_CONFIG
-    np.random.seed(seed)
-    torch.manual_seed(seed)
+    refkit.seed_rngs(seed)
     agent = ICM_PPO(run_step=c["run_step"], num_workers=c["workers"], device="cpu", **c["agent"])
-    envs = [P._OneEnv(seed=1000 * seed + w) for w in range(c["workers"])]
-    states = [e.reset_obs() for e in envs]
-    curve, step = [], 0
-    for _ in range(c["iterations"]):
-        trs = P.sync_iteration(agent, envs, states, c["n_step"])
-        curve.append(len(trs) / max(1, sum(int(t["done"][0, 0]) for t in trs)))
-        step += c["n_step"]
-        agent.process(trs, step)
-    return curve
+    return refkit.sync_cartpole_curve(agent, seed, c["workers"], c["n_step"], c["iterations"])
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", required=True, help="checkout of the reference (the directory that holds jorldy/)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--only", default="fixtures,curves")
-    ap.add_argument("--threads", type=int, default=4, help="torch threads of the curve runs (the fixtures always use one)")
-    args = ap.parse_args()
-    out_dir = os.path.abspath(args.out)
-    os.makedirs(out_dir, exist_ok=True)
-    scratch = tempfile.mkdtemp(prefix="jref_")
-    subprocess.check_call(f"cd {args.ref} && tar --exclude='jorldy/core/env/mlagents' -cf - jorldy | (cd {scratch} && tar xf -)", shell=True)
-    cwd = os.getcwd()
-    os.chdir(os.path.join(scratch, "jorldy"))
-    sys.path.insert(0, os.getcwd())
-    sys.dont_write_bytecode = True
-    import torch
-
-    try:
-        todo = args.only.split(",")
-        if "fixtures" in todo:
-            torch.set_num_threads(1)  # deterministic reductions in the fixtures
-            for name in SPECS:
-                out = try_fixture(name)
-                path = os.path.join(out_dir, f"{name}.npz")
-                np.savez_compressed(path, **out)
-                print(name, os.path.getsize(path), "bytes")
-        if "curves" in todo:
-            torch.set_num_threads(args.threads)
-            doc = {"generator": "tools/gen_golden_icm.py --only curves (the unmodified reference ICM-PPO, CPU, scratch copy)", "seeds": list(CURVE_CONFIG["seeds"]),
-                   "torch_threads": args.threads, "config": CURVE_CONFIG, "metric": "mean episode length per iteration (transitions / episode ends, 8 x 128 per iteration)"}
-            curves = []
-            for s in CURVE_CONFIG["seeds"]:
-                curves.append(reference_curve(s))
-                print("icm_ppo curve seed", s, [round(v, 1) for v in curves[-1]], flush=True)
-            doc["icm_ppo_cartpole"] = {"reference": curves}
-            with open(os.path.join(out_dir, "curves_reference_icm_ppo.json"), "w") as f:
-                json.dump(doc, f, indent=1)
-    finally:
-        os.chdir(cwd)
-        shutil.rmtree(scratch, ignore_errors=True)
-    print("written to", out_dir)
+def gen_curves(out_dir, threads):
+    doc = refkit.curve_doc("tools/gen_golden_icm.py --only curves (the unmodified reference ICM-PPO, CPU, scratch copy)", CURVE_CONFIG["seeds"], threads,
+                           config=CURVE_CONFIG, metric="mean episode length per iteration (transitions / episode ends, 8 x 128 per iteration)")
+    doc["icm_ppo_cartpole"] = {"reference": refkit.seeded_curves(reference_curve, CURVE_CONFIG["seeds"], "icm_ppo")}
+    refkit.write_curves(os.path.join(out_dir, "curves_reference_icm_ppo.json"), doc)
 
 
 if __name__ == "__main__":
-    main()
+    refkit.run(refkit.each(gen_fixture, SPECS), gen_curves, threads=4)

@@ -2,8 +2,8 @@
 """Golden vectors and the reference learning curves of discrete MPO, from the UNMODIFIED reference agent (core/agent/mpo.py).
 
 TEST INFRASTRUCTURE ONLY, for the build machine (where a checkout of the reference exists); nothing on a GPU machine runs this or
-reads the reference.  The reference is staged exactly as oracle/gen_golden.py stages it (scratch copy, no bytecode, one torch thread
-for the fixtures) and `learn()` runs under gen_golden's line tap; this file holds none of the reference's code.
+reads the reference.  Staging, the main, the line tap under which `learn()` runs, the hooks, the storage helpers and the on-policy curve loop are
+oracle/refkit.py's; this file holds none of the reference's code.
 
   tests/golden/mpo_discrete.npz   S 4, A 3, H 32, B 5 trajectories of T 4 (R 20) out of 12 stored, Retrace.  Multipliers 2.0 / 0.1 / 1.0, lr 3e-3 (one
                                   multiplier step is visible), perturbed weights (the targets a little away from their online nets), every tensor in
@@ -24,13 +24,8 @@ trajectories, one of them at position T - 2 (Retrace fixtures); c clipped in som
 
 Usage:  python tools/gen_golden_mpo.py --ref <reference checkout> [--out tests/golden] [--only fixtures|curves] [--threads 4]
 """
-import argparse
-import json
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -38,8 +33,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mpo_truth as D  # noqa: E402  (the replay recipe, the recipe weights and the curve configuration are shared with the tests)
-from oracle import synth  # noqa: E402
-from oracle.gen_golden import RECIPE_SEED, LineTap, flat, sd_to_np  # noqa: E402
+from oracle import refkit, synth  # noqa: E402
+from oracle.refkit import RECIPE_SEED, LineTap, flat, grads_of, sd_to_np  # noqa: E402
 
 SPECS = {
     "mpo_discrete": dict(S=4, A=3, H=32, B=5, T=4, N=12, retrace=True, lr=3e-3, mult=(2.0, 0.1, 1.0), floors=(1e-8, 1e-8, 1e-8), eps=(0.01, 0.01, 5e-5), learns=2,
@@ -64,32 +59,12 @@ def agent_kwargs(spec):
 
 
 def multiplier_state(agent):
-    out = {}
-    for k in D.NAMES:
-        p = getattr(agent, k)
-        st = agent.actor_optimizer.state.get(p)
-        out[k] = np.asarray(float(p.detach()), np.float32)
-        out[k + "/has_state"] = np.asarray(int(bool(st)))
-        out[k + "/exp_avg"] = np.asarray(float(st["exp_avg"]) if st else 0.0, np.float32)
-        out[k + "/exp_avg_sq"] = np.asarray(float(st["exp_avg_sq"]) if st else 0.0, np.float32)
-        out[k + "/step"] = np.asarray(int(float(st["step"])) if st else 0)
-    return out
+    return refkit.multiplier_state(agent, D.NAMES, agent.actor_optimizer)
 
 
 def record_learn(agent, spec, keep):
     """One learn() of the reference agent (IN PLACE) under the line tap -> flat dict."""
-    outs = {}
-
-    def mk_hook(tag):
-        def hook(mod, inp, outp):
-            if outp.requires_grad:
-                outp.retain_grad()
-            outs.setdefault(tag, []).append(outp)
-
-        return hook
-
-    mods = {"actor": agent.actor.pi, "target_actor": agent.target_actor.pi, "critic": agent.critic.q, "target_critic": agent.target_critic.q}
-    hooks = [mod.register_forward_hook(mk_hook(tag)) for tag, mod in mods.items()]
+    outs, hooks = refkit.retaining_hooks({"actor": agent.actor.pi, "target_actor": agent.target_actor.pi, "critic": agent.critic.q, "target_critic": agent.target_critic.q})
     markers = {
         "scan": ("reversed(\n", ["Qret"]),  # the discrete branch's loop header (the continuous branch writes it on one line): first hit = before the scan
         "target": ("critic_loss = F.mse_loss(Q_a, Qret)", ["Qret", "c", "action", "reward", "prob_b", "state", "next_state"]),
@@ -103,15 +78,14 @@ def record_learn(agent, spec, keep):
     got = {}
 
     def on_grad(frame):
-        got["raw"] = {n: {k: p.grad.detach().numpy().copy() for k, p in net.named_parameters()} for n, net in nets.items()}
+        got["raw"] = {n: grads_of(net) for n, net in nets.items()}
         got["d_la"], got["d_q"] = outs["actor"][0].grad.detach().numpy().copy(), outs["critic"][0].grad.detach().numpy().copy()
         assert outs["actor"][1].grad is None, "online(s') carries no gradient"
-        got["mult_grad"] = {k: np.asarray(float(getattr(agent, k).grad) if getattr(agent, k).grad is not None else np.nan, np.float32) for k in D.NAMES}
-        got["mult_grad"].update({k + "/has_grad": np.asarray(int(getattr(agent, k).grad is not None)) for k in D.NAMES})
+        got["mult_grad"] = refkit.multiplier_grads(agent, D.NAMES)
         got["mult0"] = multiplier_state(agent)
 
     def on_step(frame):
-        got["clip"] = {n: {k: p.grad.detach().numpy().copy() for k, p in net.named_parameters()} for n, net in nets.items()}
+        got["clip"] = {n: grads_of(net) for n, net in nets.items()}
 
     def on_after(frame):
         got["mult1"] = multiplier_state(agent)  # after reset_lgr_muls
@@ -141,7 +115,7 @@ def record_learn(agent, spec, keep):
     for net in nets:
         flat(f"grad_raw/{net}/", {k: keep(v) for k, v in got["raw"][net].items()}, out)
         flat(f"grad_clip/{net}/", {k: keep(v) for k, v in got["clip"][net].items()}, out)
-        out[f"grad_raw_norm/{net}"] = np.sqrt(sum(float((v.astype(np.float64) ** 2).sum()) for v in got["raw"][net].values()))
+        out[f"grad_raw_norm/{net}"] = refkit.grad_norm(got["raw"][net])
         for k, v in got["raw"][net].items():
             out[f"grad_raw_absmax/{net}/{k}"] = np.abs(v).max()
         flat(f"sd1/{net}/", {k: keep(v) for k, v in sd_to_np(nets[net].state_dict()).items()}, out)
@@ -155,9 +129,8 @@ def try_fixture(name, replay_seed):
 
     spec = SPECS[name]
     S, A, B, T, N, recipe, limit = spec["S"], spec["A"], spec["B"], spec["T"], spec["N"], spec["recipe"], spec["thin_limit"]
-    keep = lambda v: D.thin(v, limit)
-    torch.manual_seed(INIT_SEED)
-    np.random.seed(INIT_SEED)
+    keep = refkit.keeper(limit)
+    refkit.seed_rngs(INIT_SEED)
     agent = MPO(**agent_kwargs(spec))
     assert agent.n_step == T
     nets = {n: getattr(agent, n) for n in D.NETS}
@@ -183,8 +156,7 @@ def try_fixture(name, replay_seed):
             flat(f"sd0/{n}/", sd0, out)
         for k, v in sd0.items():
             out[f"shape/{n}/{k}"] = np.asarray(v.shape)
-    np.random.seed(NP_SEED)
-    torch.manual_seed(NP_SEED)
+    refkit.seed_rngs(NP_SEED)
     ok = True
     for k in range(spec["learns"]):
         state = np.random.get_state()
@@ -214,8 +186,7 @@ def try_fixture(name, replay_seed):
                  done_rows=np.asarray(done_rows, np.int64))
     for j, k in enumerate(D.NAMES):
         hyper[k], hyper["min_" + k], hyper["eps_" + k] = spec["mult"][j], spec["floors"][j], spec["eps"][j]
-    for k, v in hyper.items():
-        out[f"hyper/{k}"] = np.asarray(v)
+    refkit.put_hyper(out, hyper)
     return out, ok
 
 
@@ -227,22 +198,18 @@ def gen_fixture(name, out_dir):
         print(name, f"replay seed {seed}: the sampled batch misses a condition, next seed")
     else:
         raise SystemExit(f"{name}: no replay seed meets the conditions")
-    path = os.path.join(out_dir, f"{name}.npz")
-    np.savez_compressed(path, **out)
-    print(name, f"replay seed {seed}, {os.path.getsize(path)} bytes")
+    refkit.save_fixture(out_dir, name, out, note=f"replay seed {seed}")
 
 
 def reference_curve(seed):
     """The reference's single-mode loop (run_mode.py: act, step, interact_callback, process) with its MPO on the oracle's CartPole.
     -> mean reward per step in bins of BIN steps."""
-    import torch
     from core.agent.mpo import MPO
 
     from oracle.dqn_port import make_env
 
     c = D.CURVE_CONFIG
-    np.random.seed(seed)
-    torch.manual_seed(seed)
+    refkit.seed_rngs(seed)
     agent = MPO(run_step=c["run_step"], device="cpu", **c["agent"])
     agent.memory.first_store = False
     env, state = make_env(1000 + seed)
@@ -263,46 +230,15 @@ def reference_curve(seed):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", required=True, help="checkout of the reference (the directory that holds jorldy/)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--only", default="fixtures,curves")
-    ap.add_argument("--threads", type=int, default=4, help="torch threads of the curve runs (the fixtures always use one)")
-    args = ap.parse_args()
-    out_dir = os.path.abspath(args.out)
-    os.makedirs(out_dir, exist_ok=True)
-    scratch = tempfile.mkdtemp(prefix="jref_")
-    subprocess.check_call(f"cd {args.ref} && tar --exclude='jorldy/core/env/mlagents' -cf - jorldy | (cd {scratch} && tar xf -)", shell=True)
-    cwd = os.getcwd()
-    os.chdir(os.path.join(scratch, "jorldy"))
-    sys.path.insert(0, os.getcwd())
-    sys.dont_write_bytecode = True
-    import torch
-
-    try:
-        todo = args.only.split(",")
-        if "fixtures" in todo:
-            torch.set_num_threads(1)  # deterministic reductions in the fixtures
-            for name in SPECS:
-                gen_fixture(name, out_dir)
-        if "curves" in todo:
-            torch.set_num_threads(args.threads)
-            doc = {"generator": "tools/gen_golden_mpo.py --only curves (the unmodified reference MPO, CPU, scratch copy)", "seeds": list(D.CURVE_CONFIG["seeds"]),
-                   "torch_threads": args.threads, "config": D.CURVE_CONFIG, "bin": BIN, "metric": f"mean reward per step in bins of {BIN} steps (single mode)"}
-            curves = []
-            for s in D.CURVE_CONFIG["seeds"]:
-                c = reference_curve(s)
-                curves.append(c)
-                print("mpo curve seed", s, [round(v, 3) for v in c], "first / last tenth:", D.curve_tenths(c), flush=True)
-            doc["mpo_cartpole"] = {"reference": curves}
-            with open(os.path.join(out_dir, "curves_reference_mpo.json"), "w") as f:
-                json.dump(doc, f, indent=1)
-    finally:
-        os.chdir(cwd)
-        shutil.rmtree(scratch, ignore_errors=True)
-    print("written to", out_dir)
+def gen_curves(out_dir, threads):
+    seeds = D.CURVE_CONFIG["seeds"]
+    doc = refkit.curve_doc("tools/gen_golden_mpo.py --only curves (the unmodified reference MPO, CPU, scratch copy)", seeds, threads,
+                           config=D.CURVE_CONFIG, bin=BIN, metric=f"mean reward per step in bins of {BIN} steps (single mode)")
+    curves = refkit.seeded_curves(reference_curve, seeds, "mpo", digits=3)
+    print("first / last tenth:", [D.curve_tenths(c) for c in curves])
+    doc["mpo_cartpole"] = {"reference": curves}
+    refkit.write_curves(os.path.join(out_dir, "curves_reference_mpo.json"), doc)
 
 
 if __name__ == "__main__":
-    main()
+    refkit.run(refkit.each(gen_fixture, SPECS), gen_curves, threads=4)

@@ -2,8 +2,8 @@
 """Golden vectors and the reference learning curves of the continuous SAC, from the UNMODIFIED reference agent (core/agent/sac.py).
 
 TEST INFRASTRUCTURE ONLY, for the build machine (where a checkout of the reference exists); nothing on a GPU machine runs this or
-reads the reference.  The reference is staged exactly as oracle/gen_golden.py stages it (scratch copy, no bytecode, one torch thread
-for the fixtures) and `learn()` runs under gen_golden's line tap; this file holds none of the reference's code.
+reads the reference.  Staging, the main, the line tap under which `learn()` runs and the actor-critic family's starting point, record layout and curve
+loop are oracle/refkit.py's; this file holds none of the reference's code.
 
   tests/golden/sac.npz            S 4, A 3, H 32, B 32, dynamic alpha with alpha_lr 5e-2 (one alpha step is visible), perturbed online and
                                   target weights, every tensor stored in full; TWO CONSECUTIVE learns r0 and r1 -- r1 starts where r0 ended,
@@ -21,21 +21,16 @@ r<i>/unchanged/<net> = 1 instead of a copy of its weights.
 
 Usage:  python tools/gen_golden_sac.py --ref <reference checkout> [--out tests/golden] [--only fixtures|curves] [--threads 4]
 """
-import argparse
 import copy
-import json
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from oracle import synth  # noqa: E402
-from oracle.gen_golden import RECIPE_SEED, LineTap, flat, sd_to_np  # noqa: E402
+from oracle import refkit  # noqa: E402
+from oracle.refkit import FILL_SEED, RECIPE_SEED, LineTap, flat, sd_to_np  # noqa: E402
 
 SPECS = {
     "sac": dict(state_size=4, action_size=3, hidden_size=32, batch_size=32, actor_lr=5e-4, critic_lr=1e-3, alpha_lr=5e-2, tau=5e-3, dynamic=True, records=2,
@@ -47,7 +42,7 @@ SPECS = {
 }
 NETS = ("actor", "critic1", "target_critic1", "critic2", "target_critic2")  # the reference's construction order; recipe seed RECIPE_SEED + position
 OPTS = (("actor", "actor_optimizer"), ("critic1", "critic_optimizer1"), ("critic2", "critic_optimizer2"))
-FILL, FILL_SEED, INIT_SEED, NP_SEED, TORCH_SEED, PERTURB, STATIC_LOG_ALPHA = 200, 17, 5, 42, 42, 0.05, -2.0
+FILL, INIT_SEED, NP_SEED, TORCH_SEED, PERTURB, STATIC_LOG_ALPHA = 200, 5, 42, 42, 0.05, -2.0
 HEAD_SCALE = 0.2  # the actor's mu / log_std matrices are scaled down (as synth.ppo_recipe does) so that the fixtures' samples stay clear of tanh's saturation
 BATCH_KEYS = ["state", "action", "reward", "next_state", "done"]
 
@@ -55,17 +50,6 @@ CURVE_SEEDS = (1, 2, 3)
 CURVE_CONFIG = dict(S=11, A=3, steps=12000, chunk=1000, run_step=15000, hidden=256, batch=128, buffer=50000, start=1000, tau=5e-3, gamma=0.99, lr_decay=True,
                     sac=dict(use_dynamic_alpha=True, actor_lr=5e-4, critic_lr=1e-3, alpha_lr=3e-4),
                     note="12000 steps, not TD3's 8000: over 8000 the reference's own three seeds rise by 0.27, short of the 0.3 that 'learns' asks for")
-
-
-def fill_transitions(n, S, A, seed):
-    """n synthetic continuous-control transitions (also what the tests store into the HIP agent's buffer: the fixture keeps them as buf_*)."""
-    rng = np.random.RandomState(seed)
-    out = []
-    for _ in range(n):
-        out.append({"state": rng.randn(1, S).astype(np.float32), "action": np.tanh(rng.randn(1, A)).astype(np.float32),
-                    "reward": rng.choice([-1.0, 0.0, 1.0, 0.5], size=(1, 1)), "next_state": rng.randn(1, S).astype(np.float32),
-                    "done": np.asarray([[rng.rand() < 0.1]])})
-    return out
 
 
 def _alpha_state(agent):
@@ -96,7 +80,7 @@ def record_learn(agent, B, A, np_seed, torch_seed):
         extra["q1_pi"], extra["q2_pi"] = loc["q1"].detach().numpy().copy(), loc["q2"].detach().numpy().copy()
 
     def grab(net):
-        return lambda frame: grads.update({f"{net}/{k}": p.grad.detach().numpy().copy() for k, p in getattr(agent, net).named_parameters()})
+        return lambda frame: grads.update({f"{net}/{k}": g for k, g in refkit.grads_of(getattr(agent, net)).items()})
 
     tap.on_line["actor"], tap.on_line["cstep1"], tap.on_line["cstep2"], tap.on_line["astep"] = on_actor, grab("critic1"), grab("critic2"), grab("actor")
     before = copy.deepcopy(agent.actor)
@@ -125,81 +109,33 @@ def agent_kwargs(spec):
                 optim_config={"actor": "adam", "critic": "adam", "alpha": "adam", "actor_lr": spec["actor_lr"], "critic_lr": spec["critic_lr"], "alpha_lr": spec["alpha_lr"]})
 
 
+def scale_heads(agent):
+    for layer in (agent.actor.mu, agent.actor.log_std):
+        layer.weight.mul_(float(np.float32(HEAD_SCALE)))
+
+
 def gen_fixture(name, out_dir):
-    import torch
     from core.agent.sac import SAC
 
     spec = dict(SPECS[name])
     recipe, limit = spec["recipe"], spec["thin_limit"]
     S, A, H, B = spec["state_size"], spec["action_size"], spec["hidden_size"], spec["batch_size"]
-    kw = agent_kwargs(spec)
     out = {}
-    # the initial weights of a fresh agent under a recorded seed (construction order, orthogonal_init gains)
-    torch.manual_seed(INIT_SEED)
-    fresh = SAC(**kw)
-    for net in NETS:
-        flat(f"init_thin/{net}/", {k: synth.thin(v) for k, v in sd_to_np(getattr(fresh, net).state_dict()).items()}, out)
-    torch.manual_seed(3)
-    np.random.seed(3)
-    agent = SAC(**kw)
-    with torch.no_grad():
-        for i, net in enumerate(NETS):
-            mod = getattr(agent, net)
-            if recipe:
-                rec = synth.recipe_state_dict({k: v.shape for k, v in mod.state_dict().items()}, RECIPE_SEED + i)
-                for k, p in mod.named_parameters():
-                    p.copy_(torch.from_numpy(rec[k]))
-            else:  # independent draws: every target differs from its online net
-                for p in mod.parameters():
-                    p.add_(PERTURB * torch.randn_like(p))
-            if net == "actor":
-                for layer in (mod.mu, mod.log_std):
-                    layer.weight.mul_(float(np.float32(HEAD_SCALE)))
-    agent.memory.first_store = False
-    agent.memory.store(fill_transitions(FILL, S, A, FILL_SEED))
-    n = agent.memory.size
-    for k in agent.memory.buffer[0].keys():
-        out[f"buf_{k}"] = np.concatenate([agent.memory.buffer[i][k] for i in range(n)], 0)
-    keep = (lambda v: synth.thin(v, limit)) if limit else (lambda v: v)
-    keep0 = keep if recipe else (lambda v: v)  # starting weights without a recipe cannot be regenerated: always in full
-    sd0 = {net: sd_to_np(getattr(agent, net).state_dict()) for net in NETS}
-    for net in NETS:
-        flat(f"sd0/{net}/", {k: keep0(v) for k, v in sd0[net].items()}, out)
+    agent, _, keep = refkit.actor_critic_agent(SAC, agent_kwargs(spec), NETS, out, recipe, PERTURB, limit, INIT_SEED, FILL, tweak=scale_heads)
     for r in range(spec["records"]):  # consecutive: record r + 1 starts where record r ended
         start = {net: sd_to_np(getattr(agent, net).state_dict()) for net in NETS}
         flat(f"r{r}/alpha0/", _alpha_state(agent), out)
         rec, grads, result = record_learn(agent, B, A, NP_SEED + r, TORCH_SEED + r)
-        flat(f"r{r}/learn/", rec, out)
-        flat(f"r{r}/result/", result, out)
-        flat(f"r{r}/alpha1/", _alpha_state(agent), out)
-        flat(f"r{r}/grad/", {k: keep(v) for k, v in grads.items()}, out)
-        for k, v in grads.items():
-            out[f"r{r}/grad_absmax/{k}"] = np.abs(v).max()
-        for net in NETS:  # a network that learn() left bit-unchanged is stored as that statement, not as a copy
-            sd1 = sd_to_np(getattr(agent, net).state_dict())
-            same = all(np.array_equal(sd1[k], start[net][k]) for k in sd1)
-            out[f"r{r}/unchanged/{net}"] = np.asarray(int(same))
-            if not same:
-                flat(f"r{r}/sd1/{net}/", {k: keep(v) for k, v in sd1.items()}, out)
-        for net, oname in OPTS:
-            opt = getattr(agent, oname)
-            for k, p in getattr(agent, net).named_parameters():
-                st = opt.state.get(p)
-                if st:
-                    out[f"r{r}/opt/{net}/exp_avg/{k}"] = keep(st["exp_avg"].detach().numpy().copy())
-                    out[f"r{r}/opt/{net}/exp_avg_sq/{k}"] = keep(st["exp_avg_sq"].detach().numpy().copy())
+        alpha1 = {f"alpha1/{k}": v for k, v in _alpha_state(agent).items()}
+        refkit.store_actor_critic_record(out, r, agent, NETS, OPTS, start, rec, grads, result, keep, then=alpha1)
         out[f"r{r}/np_seed"], out[f"r{r}/torch_seed"] = np.asarray(NP_SEED + r), np.asarray(TORCH_SEED + r)
         sat = float(1 - np.abs(np.concatenate([rec["next_action"].reshape(-1), rec["sample_action"].reshape(-1)])).max() ** 2)
         print(name, f"r{r}", {k: float(v) for k, v in result.items()}, f"min 1 - a^2 = {sat:.3e}")
     hyper = dict(gamma=0.99, actor_lr=spec["actor_lr"], critic_lr=spec["critic_lr"], alpha_lr=spec["alpha_lr"], tau=spec["tau"], B=B, S=S, A=A, H=H, init_seed=INIT_SEED,
                  fill=FILL, fill_seed=FILL_SEED, recipe=int(recipe), recipe_seed=RECIPE_SEED, thin_limit=limit, use_dynamic_alpha=int(spec["dynamic"]),
-                 static_log_alpha=STATIC_LOG_ALPHA, target_entropy=float(agent.target_entropy), perturb=PERTURB, head_scale=HEAD_SCALE)
-    for k, v in hyper.items():
-        out[f"hyper/{k}"] = np.asarray(v)
-    out["hyper/agent"] = np.asarray("sac")
-    path = os.path.join(out_dir, f"{name}.npz")
-    np.savez_compressed(path, **out)
-    print(name, f"{os.path.getsize(path)} bytes")
+                 static_log_alpha=STATIC_LOG_ALPHA, target_entropy=float(agent.target_entropy), perturb=PERTURB, head_scale=HEAD_SCALE, agent="sac")
+    refkit.put_hyper(out, hyper)
+    refkit.save_fixture(out_dir, name, out)
 
 
 def curve_agent_kwargs():
@@ -211,78 +147,18 @@ def curve_agent_kwargs():
                 optim_config={"actor": "adam", "critic": "adam", "alpha": "adam", "actor_lr": t["actor_lr"], "critic_lr": t["critic_lr"], "alpha_lr": t["alpha_lr"]})
 
 
-def control_curve(agent, env, steps, chunk):
-    """The single-mode loop (act, step, process([transition], step)) -> mean reward per `chunk` env steps."""
-    out, acc = [], []
-    state = env.obs()
-    for step in range(1, steps + 1):
-        a = agent.act(state, True)
-        nxt, rew, done = env.step(np.asarray(a["action"], dtype=np.float32).reshape(1, -1))
-        tr = {"state": state, "next_state": np.asarray(nxt, dtype=np.float32), "reward": np.asarray(rew, dtype=np.float64).reshape(1, 1),
-              "done": np.asarray(done).astype(bool).reshape(1, 1)}
-        tr.update(a)
-        agent.process([tr], step)
-        state = env.obs()
-        acc.append(float(np.asarray(rew).reshape(-1)[0]))
-        if step % chunk == 0:
-            out.append(float(np.mean(acc)))
-            acc = []
-    return out
-
-
 def reference_curve(seed):
-    import torch
     from core.agent.sac import SAC
 
-    from oracle.jorldy_oracle import ControlOracle
-
-    c = CURVE_CONFIG
-    np.random.seed(seed)
-    torch.manual_seed(seed)
-    agent = SAC(device="cpu", **curve_agent_kwargs())
-    agent.memory.first_store = False
-    return control_curve(agent, ControlOracle(1, c["S"], c["A"], seed=1000 + seed), c["steps"], c["chunk"])
+    refkit.seed_rngs(seed)
+    return refkit.control_oracle_curve(SAC(device="cpu", **curve_agent_kwargs()), seed, CURVE_CONFIG)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", required=True, help="checkout of the reference (the directory that holds jorldy/)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--only", default="fixtures,curves")
-    ap.add_argument("--threads", type=int, default=4, help="torch threads of the curve runs (the fixtures always use one)")
-    args = ap.parse_args()
-    out_dir = os.path.abspath(args.out)
-    os.makedirs(out_dir, exist_ok=True)
-    scratch = tempfile.mkdtemp(prefix="jref_")
-    subprocess.check_call(f"cd {args.ref} && tar --exclude='jorldy/core/env/mlagents' -cf - jorldy | (cd {scratch} && tar xf -)", shell=True)
-    cwd = os.getcwd()
-    os.chdir(os.path.join(scratch, "jorldy"))
-    sys.path.insert(0, os.getcwd())
-    sys.dont_write_bytecode = True
-    import torch
-
-    try:
-        todo = args.only.split(",")
-        if "fixtures" in todo:
-            torch.set_num_threads(1)  # deterministic reductions in the fixtures
-            for name in SPECS:
-                gen_fixture(name, out_dir)
-        if "curves" in todo:
-            torch.set_num_threads(args.threads)
-            doc = {"generator": "tools/gen_golden_sac.py --only curves (the unmodified reference SAC, CPU, scratch copy)", "seeds": list(CURVE_SEEDS),
-                   "torch_threads": args.threads, "config": CURVE_CONFIG, "metric": "mean reward per 1000 env steps"}
-            curves = []
-            for s in CURVE_SEEDS:
-                curves.append(reference_curve(s))
-                print("sac curve seed", s, [round(v, 3) for v in curves[-1]], flush=True)
-            doc["sac"] = {"reference": curves}
-            with open(os.path.join(out_dir, "curves_reference_sac.json"), "w") as f:
-                json.dump(doc, f, indent=1)
-    finally:
-        os.chdir(cwd)
-        shutil.rmtree(scratch, ignore_errors=True)
-    print("written to", out_dir)
+def gen_curves(out_dir, threads):
+    doc = refkit.curve_doc("tools/gen_golden_sac.py --only curves (the unmodified reference SAC, CPU, scratch copy)", CURVE_SEEDS, threads,
+                           config=CURVE_CONFIG, metric="mean reward per 1000 env steps", sac={"reference": refkit.seeded_curves(reference_curve, CURVE_SEEDS, "sac", digits=3)})
+    refkit.write_curves(os.path.join(out_dir, "curves_reference_sac.json"), doc)
 
 
 if __name__ == "__main__":
-    main()
+    refkit.run(refkit.each(gen_fixture, SPECS), gen_curves, threads=4)

@@ -2,8 +2,8 @@
 """Golden vectors and the reference learning curves of TD3 and DDPG, from the UNMODIFIED reference agents (core/agent/td3.py, core/agent/ddpg.py).
 
 TEST INFRASTRUCTURE ONLY, for the build machine (where a checkout of the reference exists); nothing on a GPU machine runs this or
-reads the reference.  The reference is staged exactly as oracle/gen_golden.py stages it (scratch copy, no bytecode, one torch thread
-for the fixtures) and `learn()` runs under gen_golden's line tap; this file holds none of the reference's code.
+reads the reference.  Staging, the main, the line tap under which `learn()` runs and the actor-critic family's starting point, record layout and curve
+loop are oracle/refkit.py's; this file holds none of the reference's code.
 
   tests/golden/td3.npz            S 4, A 3, H 32, B 32, perturbed online and target weights: every tensor stored in full
   tests/golden/td3_odd.npz        S 3, A 1, H 64, B 7
@@ -20,21 +20,16 @@ learn() left bit-unchanged is recorded as r<i>/unchanged/<net> = 1 instead of a 
 
 Usage:  python tools/gen_golden_td3.py --ref <reference checkout> [--out tests/golden] [--only fixtures|curves] [--threads 4]
 """
-import argparse
 import copy
-import json
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from oracle import synth  # noqa: E402
-from oracle.gen_golden import RECIPE_SEED, LineTap, flat, sd_to_np  # noqa: E402
+from oracle import refkit  # noqa: E402
+from oracle.refkit import FILL_SEED, RECIPE_SEED, LineTap  # noqa: E402
 
 SPECS = {
     "td3": dict(agent="td3", state_size=4, action_size=3, hidden_size=32, batch_size=32, actor_lr=1e-3, critic_lr=1e-3, tau=5e-3, recipe=False, thin_limit=0),
@@ -47,23 +42,12 @@ NETS = {"td3": ("actor", "target_actor", "critic1", "target_critic1", "critic2",
         "ddpg": ("actor", "target_actor", "critic", "target_critic")}
 OPTS = {"td3": (("actor", "actor_optimizer"), ("critic1", "critic_optimizer1"), ("critic2", "critic_optimizer2")),
         "ddpg": (("actor", "actor_optimizer"), ("critic", "critic_optimizer"))}
-FILL, FILL_SEED, INIT_SEED, NP_SEED, TORCH_SEED = 200, 17, 5, 42, 42
+FILL, INIT_SEED, NP_SEED, TORCH_SEED = 200, 5, 42, 42
 BATCH_KEYS = ["state", "action", "reward", "next_state", "done"]
 
 CURVE_SEEDS = (1, 2, 3)
 CURVE_CONFIG = dict(S=11, A=3, steps=8000, chunk=1000, run_step=10000, hidden=256, batch=128, buffer=50000, start=1000, tau=5e-3, gamma=0.99, lr_decay=True,
                     td3=dict(initial_random_step=1000, actor_lr=1e-3, critic_lr=1e-3), ddpg=dict())
-
-
-def fill_transitions(n, S, A, seed):
-    """n synthetic continuous-control transitions (also what the tests store into the HIP agent's buffer: the fixture keeps them as buf_*)."""
-    rng = np.random.RandomState(seed)
-    out = []
-    for _ in range(n):
-        out.append({"state": rng.randn(1, S).astype(np.float32), "action": np.tanh(rng.randn(1, A)).astype(np.float32),
-                    "reward": rng.choice([-1.0, 0.0, 1.0, 0.5], size=(1, 1)), "next_state": rng.randn(1, S).astype(np.float32),
-                    "done": np.asarray([[rng.rand() < 0.1]])})
-    return out
 
 
 def _agent_class(kind):
@@ -100,7 +84,7 @@ def record_learn(agent, kind, B, A, num_learn):
                 extra["q2"] = agent.critic2(loc["state"], loc["action"]).numpy().copy()
 
     def grab(net):
-        return lambda frame: grads.update({f"{net}/{k}": p.grad.detach().numpy().copy() for k, p in getattr(agent, net).named_parameters()})
+        return lambda frame: grads.update({f"{net}/{k}": g for k, g in refkit.grads_of(getattr(agent, net)).items()})
 
     tap.on_line["target"], tap.on_line["cstep1"], tap.on_line["astep"] = on_target, grab(c1), grab("actor")
     if kind == "td3":
@@ -122,78 +106,25 @@ def record_learn(agent, kind, B, A, num_learn):
 
 
 def gen_fixture(name, out_dir):
-    import torch
-
     spec = dict(SPECS[name])
     kind, recipe, limit = spec.pop("agent"), spec.pop("recipe"), spec.pop("thin_limit")
     S, A, H, B = spec["state_size"], spec["action_size"], spec["hidden_size"], spec["batch_size"]
     kw = dict(state_size=S, action_size=A, hidden_size=H, batch_size=B, gamma=0.99, buffer_size=256, start_train_step=0, tau=spec["tau"], run_step=100000, device="cpu",
               optim_config={"actor": "adam", "critic": "adam", "actor_lr": spec["actor_lr"], "critic_lr": spec["critic_lr"]})
-    cls = _agent_class(kind)
     out = {}
-    # the initial weights of a fresh agent under a recorded seed (construction order, orthogonal_init gains)
-    torch.manual_seed(INIT_SEED)
-    fresh = cls(**kw)
-    for net in NETS[kind]:
-        flat(f"init_thin/{net}/", {k: synth.thin(v) for k, v in sd_to_np(getattr(fresh, net).state_dict()).items()}, out)
-    torch.manual_seed(3)
-    np.random.seed(3)
-    agent = cls(**kw)
-    with torch.no_grad():
-        for i, net in enumerate(NETS[kind]):
-            mod = getattr(agent, net)
-            if recipe:
-                rec = synth.recipe_state_dict({k: v.shape for k, v in mod.state_dict().items()}, RECIPE_SEED + i)
-                for k, p in mod.named_parameters():
-                    p.copy_(torch.from_numpy(rec[k]))
-            else:  # independent draws: every target differs from its online net
-                for p in mod.parameters():
-                    p.add_(0.1 * torch.randn_like(p))
-    agent.memory.first_store = False
-    agent.memory.store(fill_transitions(FILL, S, A, FILL_SEED))
-    n = agent.memory.size
-    for k in agent.memory.buffer[0].keys():
-        out[f"buf_{k}"] = np.concatenate([agent.memory.buffer[i][k] for i in range(n)], 0)
-    # thin_limit > 0: arrays larger than that are stored as synth.thin(v, limit) samples.  The starting weights of a fixture WITHOUT recipe
-    # weights cannot be regenerated and are always stored in full.
-    keep = (lambda v: synth.thin(v, limit)) if limit else (lambda v: v)
-    keep0 = keep if recipe else (lambda v: v)
-    sd0 = {net: sd_to_np(getattr(agent, net).state_dict()) for net in NETS[kind]}
-    for net in NETS[kind]:
-        flat(f"sd0/{net}/", {k: keep0(v) for k, v in sd0[net].items()}, out)
-    for r, num_learn in enumerate((0, 1, 2) if kind == "td3" else (0,)):
+    agent, sd0, keep = refkit.actor_critic_agent(_agent_class(kind), kw, NETS[kind], out, recipe, 0.1, limit, INIT_SEED, FILL)
+    for r, num_learn in enumerate((0, 1, 2) if kind == "td3" else (0,)):  # independent records: each from a copy of the same starting state
         a = copy.deepcopy(agent)
         rec, grads, result = record_learn(a, kind, B, A, num_learn)
-        flat(f"r{r}/learn/", rec, out)
-        flat(f"r{r}/result/", result, out)
-        flat(f"r{r}/grad/", {k: keep(v) for k, v in grads.items()}, out)
-        for k, v in grads.items():
-            out[f"r{r}/grad_absmax/{k}"] = np.abs(v).max()
-        for net in NETS[kind]:  # a network that learn() left bit-unchanged is stored as that statement, not as a copy
-            sd1 = sd_to_np(getattr(a, net).state_dict())
-            same = all(np.array_equal(sd1[k], sd0[net][k]) for k in sd1)
-            out[f"r{r}/unchanged/{net}"] = np.asarray(int(same))
-            if not same:
-                flat(f"r{r}/sd1/{net}/", {k: keep(v) for k, v in sd1.items()}, out)
-        for net, oname in OPTS[kind]:
-            opt = getattr(a, oname)
-            for k, p in getattr(a, net).named_parameters():
-                st = opt.state.get(p)
-                if st:
-                    out[f"r{r}/opt/{net}/exp_avg/{k}"] = keep(st["exp_avg"].detach().numpy())
-                    out[f"r{r}/opt/{net}/exp_avg_sq/{k}"] = keep(st["exp_avg_sq"].detach().numpy())
+        refkit.store_actor_critic_record(out, r, a, NETS[kind], OPTS[kind], sd0, rec, grads, result, keep)
         out[f"r{r}/num_learn"] = np.asarray(num_learn)
         print(name, f"num_learn={num_learn}", {k: float(v) for k, v in result.items()})
     hyper = dict(gamma=0.99, actor_lr=spec["actor_lr"], critic_lr=spec["critic_lr"], tau=spec["tau"], B=B, S=S, A=A, H=H, np_seed=NP_SEED, torch_seed=TORCH_SEED,
                  init_seed=INIT_SEED, fill=FILL, fill_seed=FILL_SEED, recipe=int(recipe), recipe_seed=RECIPE_SEED, thin_limit=limit)
     if kind == "td3":
         hyper.update(target_noise_std=agent.target_noise_std, target_noise_clip=agent.target_noise_clip, update_delay=agent.update_delay)
-    for k, v in hyper.items():
-        out[f"hyper/{k}"] = np.asarray(v)
-    out["hyper/agent"] = np.asarray(kind)
-    path = os.path.join(out_dir, f"{name}.npz")
-    np.savez_compressed(path, **out)
-    print(name, f"{os.path.getsize(path)} bytes")
+    refkit.put_hyper(out, dict(hyper, agent=kind))
+    refkit.save_fixture(out_dir, name, out)
 
 
 def curve_agent_kwargs(kind):
@@ -207,78 +138,18 @@ def curve_agent_kwargs(kind):
     return kw
 
 
-def control_curve(agent, env, steps, chunk):
-    """The single-mode loop (act, step, process([transition], step)) -> mean reward per `chunk` env steps."""
-    out, acc = [], []
-    state = env.obs()
-    for step in range(1, steps + 1):
-        a = agent.act(state, True)
-        nxt, rew, done = env.step(np.asarray(a["action"], dtype=np.float32).reshape(1, -1))
-        tr = {"state": state, "next_state": np.asarray(nxt, dtype=np.float32), "reward": np.asarray(rew, dtype=np.float64).reshape(1, 1),
-              "done": np.asarray(done).astype(bool).reshape(1, 1)}
-        tr.update(a)
-        agent.process([tr], step)
-        state = env.obs()
-        acc.append(float(np.asarray(rew).reshape(-1)[0]))
-        if step % chunk == 0:
-            out.append(float(np.mean(acc)))
-            acc = []
-    return out
-
-
 def reference_curve(kind, seed):
-    import torch
-
-    from oracle.jorldy_oracle import ControlOracle
-
-    c = CURVE_CONFIG
-    np.random.seed(seed)
-    torch.manual_seed(seed)
-    agent = _agent_class(kind)(device="cpu", **curve_agent_kwargs(kind))
-    agent.memory.first_store = False
-    return control_curve(agent, ControlOracle(1, c["S"], c["A"], seed=1000 + seed), c["steps"], c["chunk"])
+    refkit.seed_rngs(seed)
+    return refkit.control_oracle_curve(_agent_class(kind)(device="cpu", **curve_agent_kwargs(kind)), seed, CURVE_CONFIG)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", required=True, help="checkout of the reference (the directory that holds jorldy/)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--only", default="fixtures,curves")
-    ap.add_argument("--threads", type=int, default=4, help="torch threads of the curve runs (the fixtures always use one)")
-    args = ap.parse_args()
-    out_dir = os.path.abspath(args.out)
-    os.makedirs(out_dir, exist_ok=True)
-    scratch = tempfile.mkdtemp(prefix="jref_")
-    subprocess.check_call(f"cd {args.ref} && tar --exclude='jorldy/core/env/mlagents' -cf - jorldy | (cd {scratch} && tar xf -)", shell=True)
-    cwd = os.getcwd()
-    os.chdir(os.path.join(scratch, "jorldy"))
-    sys.path.insert(0, os.getcwd())
-    sys.dont_write_bytecode = True
-    import torch
-
-    try:
-        todo = args.only.split(",")
-        if "fixtures" in todo:
-            torch.set_num_threads(1)  # deterministic reductions in the fixtures
-            for name in SPECS:
-                gen_fixture(name, out_dir)
-        if "curves" in todo:
-            torch.set_num_threads(args.threads)
-            doc = {"generator": "tools/gen_golden_td3.py --only curves (the unmodified reference TD3 / DDPG, CPU, scratch copy)", "seeds": list(CURVE_SEEDS),
-                   "torch_threads": args.threads, "config": CURVE_CONFIG, "metric": "mean reward per 1000 env steps"}
-            for kind in ("td3", "ddpg"):
-                curves = []
-                for s in CURVE_SEEDS:
-                    curves.append(reference_curve(kind, s))
-                    print(kind, "curve seed", s, [round(v, 3) for v in curves[-1]], flush=True)
-                doc[kind] = {"reference": curves}
-            with open(os.path.join(out_dir, "curves_reference_td3.json"), "w") as f:
-                json.dump(doc, f, indent=1)
-    finally:
-        os.chdir(cwd)
-        shutil.rmtree(scratch, ignore_errors=True)
-    print("written to", out_dir)
+def gen_curves(out_dir, threads):
+    doc = refkit.curve_doc("tools/gen_golden_td3.py --only curves (the unmodified reference TD3 / DDPG, CPU, scratch copy)", CURVE_SEEDS, threads,
+                           config=CURVE_CONFIG, metric="mean reward per 1000 env steps")
+    for kind in ("td3", "ddpg"):
+        doc[kind] = {"reference": refkit.seeded_curves(lambda s: reference_curve(kind, s), CURVE_SEEDS, kind, digits=3)}
+    refkit.write_curves(os.path.join(out_dir, "curves_reference_td3.json"), doc)
 
 
 if __name__ == "__main__":
-    main()
+    refkit.run(refkit.each(gen_fixture, SPECS), gen_curves, threads=4)

@@ -2,8 +2,8 @@
 """Golden vectors and the reference learning curves of V-MPO, from the UNMODIFIED reference agent (core/agent/vmpo.py).
 
 TEST INFRASTRUCTURE ONLY, for the build machine (where a checkout of the reference exists); nothing on a GPU machine runs this or
-reads the reference.  The reference is staged exactly as oracle/gen_golden.py stages it (scratch copy, no bytecode, one torch thread
-for the fixtures) and `learn()` runs under gen_golden's line tap; this file holds none of the reference's code.
+reads the reference.  Staging, the main, the line tap under which `learn()` runs, the hooks, the storage helpers and the on-policy curve loop are
+oracle/refkit.py's; this file holds none of the reference's code.
 
   tests/golden/vmpo_discrete.npz     S 4, A 2, H 32, n_step 8, 5 workers (M 40), B 16: minibatches of 16, 16 and 8 rows.  Multipliers 2.0 / 0.1 / 5.0,
                                      lr 3e-3 (one multiplier step is visible), perturbed weights, every tensor in full; TWO CONSECUTIVE learns l0, l1
@@ -24,20 +24,15 @@ records the smallest relative gap met.
 
 Usage:  python tools/gen_golden_vmpo.py --ref <reference checkout> [--out tests/golden] [--only fixtures|curves] [--threads 4]
 """
-import argparse
-import json
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from oracle import synth  # noqa: E402
-from oracle.gen_golden import RECIPE_SEED, LineTap, flat, sd_to_np  # noqa: E402
+from oracle import refkit, synth  # noqa: E402
+from oracle.refkit import RECIPE_SEED, LineTap, flat, grads_of, sd_to_np  # noqa: E402
 
 NAMES = ("eta", "alpha_mu", "alpha_sigma")
 SPECS = {
@@ -65,36 +60,14 @@ def agent_kwargs(spec):
 
 
 def multiplier_state(agent):
-    out = {}
-    for k in NAMES:
-        p = getattr(agent, k)
-        st = agent.optimizer.state.get(p)
-        out[k] = np.asarray(float(p.detach()), np.float32)
-        out[k + "/has_state"] = np.asarray(int(bool(st)))
-        out[k + "/exp_avg"] = np.asarray(float(st["exp_avg"]) if st else 0.0, np.float32)
-        out[k + "/exp_avg_sq"] = np.asarray(float(st["exp_avg_sq"]) if st else 0.0, np.float32)
-        out[k + "/step"] = np.asarray(int(float(st["step"])) if st else 0)
-    return out
+    return refkit.multiplier_state(agent, NAMES, agent.optimizer)
 
 
 def record_learn(agent, spec, trs, np_seed, keep):
     """One process() = one learn() of the reference agent (IN PLACE) under the line tap -> (flat dict, smallest relative median gap)."""
-    import torch
-
-    cont = spec["cont"]
-    head_out = {}
-
-    def mk_hook(tag):
-        def hook(mod, inp, outp):
-            if outp.requires_grad:
-                outp.retain_grad()
-            head_out.setdefault(tag, []).append(outp)
-
-        return hook
-
     net = agent.network
-    tags = {"mu_raw": net.mu, "log_std_raw": net.log_std, "v": net.v} if cont else {"logits": net.pi, "v": net.v}
-    hooks = [mod.register_forward_hook(mk_hook(tag)) for tag, mod in tags.items()]
+    tags = {"mu_raw": net.mu, "log_std_raw": net.log_std, "v": net.v} if spec["cont"] else {"logits": net.pi, "v": net.v}
+    head_out, hooks = refkit.retaining_hooks(tags)
     markers = {
         "pre": ("ret = adv + value", ["value", "next_value", "adv", "reward", "done"]),
         "mb_loss": ("self.optimizer.zero_grad", ["idx", "_adv", "idx_tophalf", "psi", "actor_loss", "critic_loss", "eta_loss", "alpha_loss", "log_prob"]),
@@ -111,24 +84,16 @@ def record_learn(agent, spec, trs, np_seed, keep):
 
     def on_grad(frame):
         i = mbi()
-        grads_raw[i] = {k: p.grad.detach().numpy().copy() for k, p in net.named_parameters()}
-        hg = {}
-        for tag, lst in head_out.items():
-            hg[tag] = lst[-1].detach().numpy().copy()
-            hg["d_" + tag] = lst[-1].grad.detach().numpy().copy()
-        head_grads[i] = hg
-        mult_grads[i] = {k: np.asarray(float(getattr(agent, k).grad) if getattr(agent, k).grad is not None else np.nan, np.float32) for k in NAMES}
-        mult_grads[i].update({k + "/has_grad": np.asarray(int(getattr(agent, k).grad is not None)) for k in NAMES})
+        grads_raw[i], head_grads[i], mult_grads[i] = grads_of(net), refkit.last_outputs(head_out), refkit.multiplier_grads(agent, NAMES)
 
     def on_step(frame):
-        grads_clip[mbi()] = {k: p.grad.detach().numpy().copy() for k, p in net.named_parameters()}
+        grads_clip[mbi()] = grads_of(net)
 
     def on_after(frame):
         after[mbi()] = multiplier_state(agent)
 
     tap.on_line["mb_loss"], tap.on_line["mb_grad"], tap.on_line["mb_step"], tap.on_line["mb_after"] = on_loss, on_grad, on_step, on_after
-    np.random.seed(np_seed)
-    torch.manual_seed(np_seed)
+    refkit.seed_rngs(np_seed)
     with tap:
         result = agent.process(trs, agent.time_t + spec["T"])
     for h in hooks:
@@ -160,7 +125,7 @@ def record_learn(agent, spec, trs, np_seed, keep):
         if i in (0, nmb - 1):
             flat(f"mb{i}/grad_raw/", {k: keep(v) for k, v in grads_raw[i].items()}, out)
             flat(f"mb{i}/grad_clip/", {k: keep(v) for k, v in grads_clip[i].items()}, out)
-            out[f"mb{i}/grad_raw_norm"] = np.sqrt(sum(float((v.astype(np.float64) ** 2).sum()) for v in grads_raw[i].values()))
+            out[f"mb{i}/grad_raw_norm"] = refkit.grad_norm(grads_raw[i])
             for k, v in grads_raw[i].items():
                 out[f"mb{i}/grad_raw_absmax/{k}"] = np.abs(v).max()
     flat("result/", {k: np.asarray(v) for k, v in result.items()}, out)
@@ -170,23 +135,15 @@ def record_learn(agent, spec, trs, np_seed, keep):
 
 
 def try_fixture(name, rollout_seed):
-    import torch
     from core.agent.vmpo import VMPO
 
     spec = SPECS[name]
     S, A, M, cont, recipe, limit = spec["S"], spec["A"], spec["W"] * spec["T"], spec["cont"], spec["recipe"], spec["thin_limit"]
-    keep = (lambda v: synth.thin(v, limit)) if limit else (lambda v: v)
-    torch.manual_seed(INIT_SEED)
-    np.random.seed(INIT_SEED)
+    keep = refkit.keeper(limit)
+    refkit.seed_rngs(INIT_SEED)
     agent = VMPO(**agent_kwargs(spec))
-    with torch.no_grad():
-        if recipe:
-            rec = synth.ppo_recipe({k: v.shape for k, v in agent.network.state_dict().items()}, RECIPE_SEED)
-            for k, p in agent.network.named_parameters():
-                p.copy_(torch.from_numpy(rec[k]))
-        else:  # perturb the heads so that pi is not ~uniform and the value not ~0 (the policy gain is 0.01)
-            for p in agent.network.parameters():
-                p.add_(PERTURB * torch.randn_like(p))
+    # without a recipe: perturb the heads so that pi is not ~uniform and the value not ~0 (the policy gain is 0.01)
+    refkit.set_weights([agent.network], synth.ppo_recipe if recipe else None, RECIPE_SEED, PERTURB)
     agent.memory.first_store = False
     out = {}
     sd0 = sd_to_np(agent.network.state_dict())
@@ -201,20 +158,14 @@ def try_fixture(name, rollout_seed):
         worst = min(worst, gap)
         flat(f"l{k}/", rec, out)
         out[f"l{k}/rollout_seed"] = np.asarray(seed_k)
-        if recipe:
-            for key in ("state", "reward", "action"):
-                out[f"l{k}/in_{key}_check"] = synth.row_checksum(np.concatenate([t[key] for t in trs], 0).astype(np.float32))[:: max(1, M // 64)]
-        else:
-            for key in ("state", "next_state", "reward", "done", "action"):
-                out[f"l{k}/in_{key}"] = np.concatenate([t[key] for t in trs], 0)
+        refkit.dump_rollout(out, f"l{k}/", trs, recipe)
         print(name, f"l{k}", {key: float(v) for key, v in rec.items() if key.startswith("result/")}, f"median gap {gap:.3e}")
     hyper = dict(S=S, A=A, H=spec["H"], W=spec["W"], T=spec["T"], B=spec["B"], continuous=int(cont), lr=spec["lr"], gamma=GAMMA, clip_grad_norm=CLIP, learns=spec["learns"],
                  recipe=int(recipe), recipe_seed=RECIPE_SEED, thin_limit=limit, init_seed=INIT_SEED, perturb=PERTURB, median_gap=worst, clamp_every=0 if recipe else 17)
     hyper["lambda"] = spec["lam"]
     for j, k in enumerate(NAMES):
         hyper[k], hyper["min_" + k], hyper["eps_" + k] = spec["mult"][j], spec["floors"][j], spec["eps"][j]
-    for k, v in hyper.items():
-        out[f"hyper/{k}"] = np.asarray(v)
+    refkit.put_hyper(out, hyper)
     return out, worst
 
 
@@ -226,74 +177,36 @@ def gen_fixture(name, out_dir):
         print(name, f"rollout seed {seed}: median gap {worst:.3e} < {MEDIAN_GAP}, next seed")
     else:
         raise SystemExit(f"{name}: no rollout seed meets the median condition")
-    path = os.path.join(out_dir, f"{name}.npz")
-    np.savez_compressed(path, **out)
-    print(name, f"rollout seed {seed}, {os.path.getsize(path)} bytes")
+    refkit.save_fixture(out_dir, name, out, note=f"rollout seed {seed}")
 
 
 def reference_curve(seed):
-    import torch
+    """-> (curve, whether alpha_mu reached its floor after some iteration)"""
     from core.agent.vmpo import VMPO
 
-    from oracle import ppo_port as P
-
     c = CURVE_CONFIG
-    np.random.seed(seed)
-    torch.manual_seed(seed)
+    refkit.seed_rngs(seed)
     agent = VMPO(run_step=c["run_step"], num_workers=c["workers"], device="cpu", **c["agent"])
-    envs = [P._OneEnv(seed=1000 * seed + w) for w in range(c["workers"])]
-    states = [e.reset_obs() for e in envs]
-    curve, step, floor_hit = [], 0, False
-    for _ in range(c["iterations"]):
-        trs = P.sync_iteration(agent, envs, states, c["n_step"])
-        curve.append(len(trs) / max(1, sum(int(t["done"][0, 0]) for t in trs)))
-        step += c["n_step"]
-        agent.process(trs, step)
-        floor_hit = floor_hit or float(agent.alpha_mu.detach()) <= 1e-8
-    return curve, floor_hit
+    floor = []
+    curve = refkit.sync_cartpole_curve(agent, seed, c["workers"], c["n_step"], c["iterations"], per_iter=lambda a: floor.append(float(a.alpha_mu.detach()) <= 1e-8))
+    return curve, any(floor)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", required=True, help="checkout of the reference (the directory that holds jorldy/)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--only", default="fixtures,curves")
-    ap.add_argument("--threads", type=int, default=4, help="torch threads of the curve runs (the fixtures always use one)")
-    args = ap.parse_args()
-    out_dir = os.path.abspath(args.out)
-    os.makedirs(out_dir, exist_ok=True)
-    scratch = tempfile.mkdtemp(prefix="jref_")
-    subprocess.check_call(f"cd {args.ref} && tar --exclude='jorldy/core/env/mlagents' -cf - jorldy | (cd {scratch} && tar xf -)", shell=True)
-    cwd = os.getcwd()
-    os.chdir(os.path.join(scratch, "jorldy"))
-    sys.path.insert(0, os.getcwd())
-    sys.dont_write_bytecode = True
-    import torch
+def gen_curves(out_dir, threads):
+    doc = refkit.curve_doc("tools/gen_golden_vmpo.py --only curves (the unmodified reference V-MPO, CPU, scratch copy)", CURVE_CONFIG["seeds"], threads,
+                           config=CURVE_CONFIG, metric="mean episode length per iteration (transitions / episode ends, 8 x 128 per iteration)")
+    floors = []
 
-    try:
-        todo = args.only.split(",")
-        if "fixtures" in todo:
-            torch.set_num_threads(1)  # deterministic reductions in the fixtures
-            for name in SPECS:
-                gen_fixture(name, out_dir)
-        if "curves" in todo:
-            torch.set_num_threads(args.threads)
-            doc = {"generator": "tools/gen_golden_vmpo.py --only curves (the unmodified reference V-MPO, CPU, scratch copy)", "seeds": list(CURVE_CONFIG["seeds"]),
-                   "torch_threads": args.threads, "config": CURVE_CONFIG, "metric": "mean episode length per iteration (transitions / episode ends, 8 x 128 per iteration)"}
-            curves, floors = [], []
-            for s in CURVE_CONFIG["seeds"]:
-                c, hit = reference_curve(s)
-                curves.append(c)
-                floors.append(bool(hit))
-                print("vmpo curve seed", s, [round(v, 1) for v in c], "alpha_mu reached its floor:", hit, flush=True)
-            doc["vmpo_cartpole"] = {"reference": curves, "alpha_mu_reached_floor": floors}
-            with open(os.path.join(out_dir, "curves_reference_vmpo.json"), "w") as f:
-                json.dump(doc, f, indent=1)
-    finally:
-        os.chdir(cwd)
-        shutil.rmtree(scratch, ignore_errors=True)
-    print("written to", out_dir)
+    def curve(seed):
+        c, hit = reference_curve(seed)
+        floors.append(bool(hit))
+        print("alpha_mu reached its floor:", hit)
+        return c
+
+    curves = refkit.seeded_curves(curve, CURVE_CONFIG["seeds"], "vmpo")
+    doc["vmpo_cartpole"] = {"reference": curves, "alpha_mu_reached_floor": floors}
+    refkit.write_curves(os.path.join(out_dir, "curves_reference_vmpo.json"), doc)
 
 
 if __name__ == "__main__":
-    main()
+    refkit.run(refkit.each(gen_fixture, SPECS), gen_curves, threads=4)
