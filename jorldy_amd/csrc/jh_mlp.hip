@@ -546,7 +546,7 @@ __global__ void __launch_bounds__(256) jh_gradnorm_kernel(int64_t n, const float
 // of squares of the gradient tiles the backward's workgroups wrote (dW2 | db2 | head weights and biases), and the
 // (dW1 | db1) head of the bucket still is `tiles_m` per-row-tile slabs in `part`: EVERY workgroup sums all slabs (in
 // row-tile order: the same bits everywhere, so all workgroups derive the same clip coefficient) for the norm, and keeps
-// the elements it is about to update.  164 KB of L2 reads per workgroup for CartPole against a 7 us launch.
+// the elements it is about to update.  164 KB of L2 reads per workgroup (kNormBlocks = 256 of them) for CartPole against an 8 us launch.
 template <bool FUSED>
 __global__ void __launch_bounds__(256) jh_adam_kernel(int64_t n, float* __restrict__ p, float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ v,
@@ -563,8 +563,23 @@ __global__ void __launch_bounds__(256) jh_adam_kernel(int64_t n, float* __restri
   float4 *p4 = reinterpret_cast<float4*>(p), *g4 = reinterpret_cast<float4*>(g), *m4 = reinterpret_cast<float4*>(m), *v4 = reinterpret_cast<float4*>(v);
   const int64_t i_first = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t i_fc = i_first < n4 ? i_first : 0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
   const float4 pp0 = p4[i_fc], mm0 = m4[i_fc], vv0 = v4[i_fc], gg0 = g4[i_fc];
   float acc = 0.f;
+  // round 7: everything the update reads from the hyper block is requested IN FRONT of the block reduction and travels during it.  Read where it is
+  // used, behind the reduction, it was the launch's first touch of the block (the loss launch wrote it: a miss) as two dependent scalar round trips
+  // between the norm and the first store -- the compiler moves no load across a barrier, and nothing here depends on the norm.  As VECTOR fetches behind the
+  // slab and partial-sum fetches: a scalar fetch at kernel entry was measured first and bought nothing (8.38 -> 8.44 us) -- scalar loads return out of
+  // order, so the next wait for a kernel argument also waited for the missing block, in front of the slab fetches.  Vector fetches retire in issue
+  // order: nothing older waits for them (8.38 -> 8.13 us).
+  float4 hy0 = make_float4(0.f, 0.f, 0.f, 0.f), hy1 = hy0;
+  float hy8 = 0.f;
+  auto fetch_hyper = [&]() {  // (jh_pponet's hyper block is an allocation of its own: 16-byte fetches are aligned)
+    int lane_zero;  // a zero the compiler cannot prove uniform or loop invariant: the fetches stay vector fetches, and stay where they are written
+    asm volatile("v_mov_b32 %0, 0" : "=v"(lane_zero));
+    const float4* hy4 = reinterpret_cast<const float4*>(hyper + lane_zero);
+    hy0 = hy4[0]; hy1 = hy4[1]; hy8 = hyper[lane_zero + 8];
+  };
   bool partials_added = false;
   // the partial sums of squares, called once BEHIND the slab fetches below: issued in front of them, the first use of a partial is a
   // wait for everything older in the queue, i.e. a round trip before the 48 slab fetches even start.  Two per thread together
@@ -595,6 +610,7 @@ __global__ void __launch_bounds__(256) jh_adam_kernel(int64_t n, float* __restri
         for (int tu = 0; tu < TU; ++tu) w[ju][tu] = part4[(size_t)(tu < tiles_m ? tu : tiles_m - 1) * h4 + ic];
       }
       if (!partials_added) add_partials();
+      fetch_hyper();  // youngest in the queue (unconditional: behind an `if` the block ends in copies = a wait; the compiler issues it once, behind the last pass)
 #pragma unroll
       for (int ju = 0; ju < JU; ++ju) {
         const int64_t i = threadIdx.x + 256 * (j0 + ju);
@@ -610,14 +626,17 @@ __global__ void __launch_bounds__(256) jh_adam_kernel(int64_t n, float* __restri
     }
   }
   if (!partials_added) add_partials();
+  if (!FUSED) fetch_hyper();
+  // the kernel arguments of the update are in scalar registers BEFORE the reduction's barriers and stay there (an empty statement that names
+  // them: without it the compiler fetches them again, or for the first time, behind the last barrier)
+  asm volatile("" ::"s"(max_norm), "s"(norm_out), "s"(n), "s"(p), "s"(g), "s"(m), "s"(v), "s"(stride));
   const float total = sqrtf(jh_block_reduce(acc, s_red, JhAdd(), 0.f));
-  const float bc1 = hyper[5], bc2s = hyper[6];
+  const float lr = hy0.x, b2 = hy0.z, eps = hy0.w, bc1 = hy1.y, bc2s = hy1.z;  // JH_HY_LR, _B2, _EPS, _BC1, _BC2S
+  const float omb1 = hy1.w, omb2 = hy8;                                          // JH_HY_OMB1, _OMB2: (float)(1.0 - beta), torch derives them in double
   // torch.nn.utils.clip_grad_norm_: coef = max_norm / (total + 1e-6), clamped to 1
   float coef = 1.f;
   if (max_norm > 0.f) coef = fminf(max_norm / (total + 1e-6f), 1.f);
   if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) *norm_out = total;
-  const float lr = hyper[JH_HY_LR], b2 = hyper[JH_HY_B2], eps = hyper[JH_HY_EPS];
-  const float omb1 = hyper[JH_HY_OMB1], omb2 = hyper[JH_HY_OMB2];  // (float)(1.0 - beta): torch derives them in double
   const float step_size = lr / bc1;
   auto upd = [&](float& pi, float& gi_, float& mi_, float& vi_) {
     const float gi = gi_ * coef;
@@ -629,7 +648,7 @@ __global__ void __launch_bounds__(256) jh_adam_kernel(int64_t n, float* __restri
     const float denom = sqrtf(vi) / bc2s + eps;
     pi = pi - step_size * (mi / denom);
   };
-  for (int64_t i = i_first; i < n4; i += (int64_t)gridDim.x * 256) {
+  for (int64_t i = i_first; i < n4; i += stride) {
     const bool first = i == i_first;
     float4 pp = first ? pp0 : p4[i], mm = first ? mm0 : m4[i], vv = first ? vv0 : v4[i];
     float4 gg = (FUSED && i < h4) ? mine : (first ? gg0 : g4[i]);  // h4 <= gridDim.x * 256 (host): a head element is met in the first pass only

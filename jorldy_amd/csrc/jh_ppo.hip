@@ -310,6 +310,46 @@ __device__ __forceinline__ void disc_terms(const float* __restrict__ z, int k, c
   lg = logf(c);
 }
 
+// The discrete row in REGISTERS for A <= kDiscCache (round 7; the continuous policy's ContPre is the same idea): the logits are fetched once, the
+// loops over the actions are unrolled at compile time under static indices, and p / pn / c / lg / inr of each action are evaluated ONCE -- the loop
+// form reads z[k] through a pointer (a generic one in the single-workgroup kernel: a flat load and a full wait at every use) and re-evaluates
+// disc_terms (an exp and a log) in the forward loop and in each of the three backward loops.  Same terms, same order of every sum: same bits.
+// 4 = one 16-byte granule of partial heads; 14 more registers per row than the loop form.
+constexpr int kDiscCache = 4;
+struct DiscReg {
+  float z[kDiscCache];
+  float m, lse, s;
+  float p[kDiscCache], pn[kDiscCache], c[kDiscCache], lg[kDiscCache];
+  bool inr[kDiscCache];
+};
+
+__device__ __forceinline__ void disc_reg_prepare(DiscReg& t, int A) {
+  float m = t.z[0];
+#pragma unroll
+  for (int k = 1; k < kDiscCache; ++k)
+    if (k < A) m = fmaxf(m, t.z[k]);
+  float se = 0.f;
+#pragma unroll
+  for (int k = 0; k < kDiscCache; ++k)
+    if (k < A) se += expf(t.z[k] - m);
+  t.m = m;
+  t.lse = logf(se);
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < kDiscCache; ++k) {
+    t.p[k] = 0.f;
+    if (k < A) { t.p[k] = expf((t.z[k] - m) - t.lse); s += t.p[k]; }
+  }
+  t.s = s;
+#pragma unroll
+  for (int k = 0; k < kDiscCache; ++k) {  // disc_terms, once per action
+    t.pn[k] = t.p[k] / s;
+    t.inr[k] = (t.pn[k] >= JH_EPS32) && (t.pn[k] <= 1.f - JH_EPS32);
+    t.c[k] = fminf(fmaxf(t.pn[k], JH_EPS32), 1.f - JH_EPS32);
+    t.lg[k] = logf(t.c[k]);
+  }
+}
+
 // ============================================================================ log pi_old
 __global__ void __launch_bounds__(256) jh_logp_discrete_kernel(int64_t M, int A, const float* __restrict__ logits,
                                                                const float* __restrict__ action,
@@ -488,10 +528,27 @@ __device__ __forceinline__ ContPre ppo_cont_prefetch(const PpoArgs<CONT>& a, con
 template <bool CONT>
 __device__ __forceinline__ void ppo_row_fwd(const PpoArgs<CONT>& a, const RowIn& in, const float* z0, const float* z1, float v,
                                             RowCommon& rc, float& ent_row, float& minp_row, DiscRow& dr, int& act_k,
-                                            const ContPre* pre = nullptr) {
+                                            const ContPre* pre = nullptr, DiscReg* dreg = nullptr) {
   const int64_t r = in.r;
   const float adv = in.adv, ret = in.ret, vold = in.vold;
-  if (!CONT) {
+  if (!CONT && dreg) {  // discrete, A <= kDiscCache, dreg->z filled: the loop form below with everything in registers
+    disc_reg_prepare(*dreg, a.A);
+    dr.m = dreg->m; dr.lse = dreg->lse; dr.s = dreg->s;
+    int ak = (int)in.action;
+    ak = ak < 0 ? 0 : (ak >= a.A ? a.A - 1 : ak);
+    act_k = ak;
+    float ent = 0.f, logp = 0.f;
+#pragma unroll
+    for (int k = 0; k < kDiscCache; ++k) {
+      if (k < a.A) {
+        ent += dreg->pn[k] * dreg->lg[k];
+        if (k == ak) logp = dreg->lg[k];
+      }
+    }
+    ent_row = -ent;
+    rc = row_common(logp - in.logp_old, adv, v, vold, ret, a.eps);
+    minp_row = expf(logp);
+  } else if (!CONT) {
     const float* z = z0;
     dr = disc_prepare(z, a.A);
     int ak = (int)in.action;
@@ -537,7 +594,7 @@ __device__ __forceinline__ void ppo_row_fwd(const PpoArgs<CONT>& a, const RowIn&
 template <bool CONT>
 __device__ __forceinline__ void ppo_row_bwd(const PpoArgs<CONT>& a, int i, const float* z0, const float* z1,
                                             const RowCommon& rc, const DiscRow& dr, int act_k, float w1, float w2,
-                                            const ContPre* pre = nullptr) {
+                                            const ContPre* pre = nullptr, const DiscReg* dreg = nullptr) {
   const float invB = 1.f / (float)a.B;
   const float d_ratio = -invB * (rc.g1 * rc.adv + (rc.in_clip ? rc.g2 * rc.adv : 0.f));
   const float d_logp = d_ratio * rc.ratio;
@@ -549,7 +606,26 @@ __device__ __forceinline__ void ppo_row_bwd(const PpoArgs<CONT>& a, int i, const
     const float dv = a.vf * (w1 * 2.f * (rc.v - rc.ret) * invB + (rc.in_v ? w2 * 2.f * (rc.vclip - rc.ret) * invB : 0.f));
     a.gv[(size_t)i * a.ldv] = dv;
   }
-  if (!CONT) {
+  if (!CONT && dreg) {  // the three loops below on the forward half's terms (g_lg, g_pn, g_p: one evaluation per action instead of three, two)
+    const float ce = a.ent * invB;
+    const float s = dr.s;
+    float g_pn[kDiscCache], T1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kDiscCache; ++k) {
+      const float g_lg = (k == act_k ? d_logp : 0.f) + ce * dreg->pn[k];
+      g_pn[k] = ce * dreg->lg[k] + (dreg->inr[k] ? g_lg / dreg->c[k] : 0.f);
+      if (k < a.A) T1 += g_pn[k] * dreg->p[k];
+    }
+    float g_p[kDiscCache], T2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kDiscCache; ++k) {
+      g_p[k] = g_pn[k] / s - T1 / (s * s);
+      if (k < a.A) T2 += g_p[k] * dreg->p[k];
+    }
+#pragma unroll
+    for (int k = 0; k < kDiscCache; ++k)
+      if (k < a.A) a.g0[(size_t)i * a.ldg + k] = g_p[k] * dreg->p[k] - dreg->p[k] * T2;  // log_softmax backward
+  } else if (!CONT) {
     const float* z = z0;
     const float ce = a.ent * invB;  // loss += ent_coef * (-mean(H)) = ent_coef/B * sum pn*lg
     float T1 = 0.f;
@@ -609,8 +685,9 @@ __device__ __forceinline__ void ppo_row_bwd(const PpoArgs<CONT>& a, int i, const
 }
 
 // {sum, sum, sum, sum, max, min} over the workgroup (<= 16 waves)
-__device__ __forceinline__ void ppo_block_reduce6(float (&v)[6], float (*red)[6]) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+// nw: the waves that take part (the single-workgroup kernel's extra wave does not: it has left before the barrier)
+__device__ __forceinline__ void ppo_block_reduce6(float (&v)[6], float (*red)[6], int nw) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll
@@ -636,21 +713,39 @@ __device__ __forceinline__ void ppo_block_reduce6(float (&v)[6], float (*red)[6]
 
 // B <= 1024: one workgroup does forward, the 6 block reductions and backward with the row terms
 // still in registers (one launch per minibatch instead of two).
-// MAXT: the launch's thread limit (256-row minibatches get the 512-VGPR budget: all 32 tiles of a 512-wide net in flight at once)
+// MAXT: the rows' thread limit (256-row minibatches get one wave per SIMD: all 32 tiles of a 512-wide net in flight at once)
+// Round 7, MAXT <= 256 with a.hyper_advance: the launch carries ONE MORE WAVE behind the rows' waves.  It advances Adam's step counter and the bias
+// corrections (two double-precision pow + a sqrt: ~400 dependent instructions that depend on the step counter alone) and leaves; it owns no row and
+// takes no part in the reductions (a wave that has ended is not waited for at a barrier).  The same code used to run in one lane of the LAST rows' wave:
+// in front of the partial sums it held that wave's arrival at the barrier back by ~1 us (rounds 2-4), behind its rows (rounds 5-6) the launch ended ~1 us
+// after the other waves had.  Nobody reads hyper in this launch.
+constexpr int ppo_fused_threads(int maxt) { return maxt <= 256 ? maxt + 64 : maxt; }
 template <bool CONT, int MAXT>
-__global__ void __launch_bounds__(MAXT) jh_ppo_fused_kernel(PpoArgs<CONT> a) {
+__global__ void __launch_bounds__(ppo_fused_threads(MAXT)) jh_ppo_fused_kernel(PpoArgs<CONT> a) {
   __shared__ float s_red6[16][6];
-  extern __shared__ __attribute__((aligned(16))) float s_z[];  // [B][8] when the heads come as partials
+  extern __shared__ __attribute__((aligned(16))) float s_z[];  // [B][8] when the heads come as partials and the row form reads them through a pointer
   const int i = threadIdx.x;
+  int nw = (blockDim.x + 63) >> 6;  // the rows' waves
+  if (MAXT <= 256 && a.hyper_advance) {
+    --nw;
+    if (i >= nw * 64) {
+      if (i == nw * 64) jh_adam_advance(a.hyper_advance);
+      return;
+    }
+  }
   const bool on = i < a.B;
+  const bool reg = !CONT && a.A <= kDiscCache;  // the discrete row in registers (DiscReg)
   const float *z0 = nullptr, *z1 = nullptr;
   float vpred = 0.f;
+  DiscReg dreg;
+#pragma unroll
+  for (int k = 0; k < kDiscCache; ++k) dreg.z[k] = 0.f;
   // first in the queue (round 5), the partial heads behind them.  Unconditional (threads beyond B re-read row 0): behind `if (on)` the
   // block ends in copies of the fetched values = a wait before the partial heads are even requested
   const RowIn rin = ppo_row_load<CONT>(a, on ? i : 0);
   if (a.hpart) {
+    float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (on) {
-      float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       const bool wide = a.hp_ld == 8;
       if (!wide) {  // <= 4 head outputs (CartPole: 2 logits + value): TU tiles' float4 per round trip, sums in tile order
         constexpr int TU = MAXT <= 256 ? 32 : 16;
@@ -685,38 +780,62 @@ __global__ void __launch_bounds__(MAXT) jh_ppo_fused_kernel(PpoArgs<CONT> a) {
           }
         }
       }
-      float4* dst = reinterpret_cast<float4*>(s_z + (size_t)i * 8);
-      dst[0] = make_float4(z[0], z[1], z[2], z[3]);
-      dst[1] = make_float4(z[4], z[5], z[6], z[7]);
     }
-    __syncthreads();
-    z0 = s_z + (size_t)i * 8;
-    z1 = z0 + a.A;
-    if (on) vpred = z0[CONT ? 2 * a.A : a.A];
+    if (reg) {
+      // the row's sums stay with the thread that formed them (round 7): through the LDS staging below, every later use was a flat load
+      // (z0 may point at global memory) and a full wait, behind a barrier that no thread needs -- each reads its own row only
+#pragma unroll
+      for (int k = 0; k < kDiscCache; ++k) dreg.z[k] = z[k];
+#pragma unroll
+      for (int k = 1; k <= kDiscCache; ++k)
+        if (k == a.A) vpred = z[k];
+    } else {
+      if (on) {
+        float4* dst = reinterpret_cast<float4*>(s_z + (size_t)i * 8);
+        dst[0] = make_float4(z[0], z[1], z[2], z[3]);
+        dst[1] = make_float4(z[4], z[5], z[6], z[7]);
+      }
+      __syncthreads();
+      z0 = s_z + (size_t)i * 8;
+      z1 = z0 + a.A;
+      if (on) vpred = z0[CONT ? 2 * a.A : a.A];
+    }
   } else if (on) {
     z0 = a.h0 + (size_t)i * a.ldh;
     z1 = CONT ? a.h1 + (size_t)i * a.ldh : nullptr;
+    if (reg) {  // one batch with the value prediction (actions past A re-read action A - 1: never used)
+#pragma unroll
+      for (int k = 0; k < kDiscCache; ++k) dreg.z[k] = z0[k < a.A ? k : a.A - 1];
+    }
     vpred = a.value_pred[(size_t)i * a.ldvp];
   }
   RowCommon rc{};
   DiscRow dr{};
   int act_k = 0;
   float ent_row = 0.f, minp = 3.4e38f;
-  if (on) ppo_row_fwd<CONT>(a, rin, z0, z1, vpred, rc, ent_row, minp, dr, act_k);
+  if (on) {  // (two calls, not a selected pointer: dreg stays in registers only if its address never becomes a value)
+    if (reg) ppo_row_fwd<CONT>(a, rin, z0, z1, vpred, rc, ent_row, minp, dr, act_k, nullptr, &dreg);
+    else ppo_row_fwd<CONT>(a, rin, z0, z1, vpred, rc, ent_row, minp, dr, act_k);
+  }
   const float e1 = on ? (rc.v - rc.ret) * (rc.v - rc.ret) : 0.f;
   const float e2 = on ? (rc.vclip - rc.ret) * (rc.vclip - rc.ret) : 0.f;
+  // the kernel arguments of the second half are in scalar registers BEFORE the barrier (an empty statement that names them): the compiler
+  // fetched them behind it, in six dependent groups
+  asm volatile("" ::"s"(a.B), "s"(a.A), "s"(a.vf), "s"(a.ent), "s"(a.stats), "s"(a.critic_sums), "s"(a.defer_dv2), "s"(a.g0), "s"(a.g1), "s"(a.gv), "s"(a.ldg), "s"(a.ldv));
   // the six block reductions share one shuffle tree pass and ONE LDS exchange (same arithmetic order as six
   // jh_block_reduce calls: fixed tree inside a wave, wave partials combined in wave order)
   float v6[6] = {on ? rc.smin : 0.f, e1, e2, on ? ent_row : 0.f, on ? rc.ratio : -3.4e38f, on ? minp : 3.4e38f};
-  ppo_block_reduce6(v6, s_red6);
+  ppo_block_reduce6(v6, s_red6, nw);
   float w1, w2;
   ppo_finish_stats(v6[0], v6[1], v6[2], v6[3], v6[4], v6[5], a.B, CONT ? a.B * a.A : a.B, a.vf, a.ent, w1, w2,
                    threadIdx.x == 0 ? a.stats : nullptr);
   if (a.critic_sums && threadIdx.x == 0) { a.critic_sums[0] = v6[1]; a.critic_sums[1] = v6[2]; }
-  if (on) ppo_row_bwd<CONT>(a, i, z0, z1, rc, dr, act_k, w1, w2);
-  // Adam's step counter + bias corrections (two double-precision pow: ~400 instructions) by the LAST wave, AFTER its rows: in front of
-  // the partial sums (rounds 2-4) that wave reached the barrier ~1 us behind the others, every minibatch (nobody reads hyper here)
-  if (a.hyper_advance && threadIdx.x == blockDim.x - 1) jh_adam_advance(a.hyper_advance);
+  if (on) {
+    if (reg) ppo_row_bwd<CONT>(a, i, z0, z1, rc, dr, act_k, w1, w2, nullptr, &dreg);
+    else ppo_row_bwd<CONT>(a, i, z0, z1, rc, dr, act_k, w1, w2);
+  }
+  // more than 256 rows: Adam's step counter + bias corrections by the LAST wave, AFTER its rows (nobody reads hyper here)
+  if (MAXT > 256 && a.hyper_advance && threadIdx.x == blockDim.x - 1) jh_adam_advance(a.hyper_advance);
 }
 
 // B > 1024: pass 1 writes per-block partials, pass 2 re-reduces them in every block (deterministic,
@@ -744,7 +863,7 @@ __global__ void __launch_bounds__(256) jh_ppo_fwd_kernel(PpoArgs<CONT> a) {
   const float e1 = on ? (rc.v - rc.ret) * (rc.v - rc.ret) : 0.f;
   const float e2 = on ? (rc.vclip - rc.ret) * (rc.vclip - rc.ret) : 0.f;
   float v6[6] = {on ? rc.smin : 0.f, e1, e2, on ? ent_row : 0.f, on ? rc.ratio : -3.4e38f, on ? minp : 3.4e38f};
-  ppo_block_reduce6(v6, s_red6);
+  ppo_block_reduce6(v6, s_red6, (blockDim.x + 63) >> 6);
   if (threadIdx.x == 0) {
     float* p = a.partial + (size_t)blockIdx.x * PPO_NPART;
     p[0] = v6[0]; p[1] = v6[1]; p[2] = v6[2]; p[3] = v6[3]; p[4] = v6[4]; p[5] = v6[5];
@@ -837,7 +956,7 @@ __global__ void __launch_bounds__(256) jh_ppo_onepass_kernel(PpoArgs<CONT> a, un
   const float e1 = on ? (rc.v - rc.ret) * (rc.v - rc.ret) : 0.f;
   const float e2 = on ? (rc.vclip - rc.ret) * (rc.vclip - rc.ret) : 0.f;
   float v6[6] = {on ? rc.smin : 0.f, e1, e2, on ? ent_row : 0.f, on ? rc.ratio : -3.4e38f, on ? minp : 3.4e38f};
-  ppo_block_reduce6(v6, s_red6);
+  ppo_block_reduce6(v6, s_red6, (blockDim.x + 63) >> 6);
   if (threadIdx.x < PPO_NPART && threadIdx.x < 6) {
     float mine = v6[0];
 #pragma unroll
@@ -941,7 +1060,8 @@ static int ppo_launch(jh_ctx* ctx, PpoArgs<CONT>& a, hipStream_t st) {
     const int threads = ((a.B + 63) / 64) * 64;
     a.nb = 1;
     const size_t lds = a.hpart ? sizeof(float) * 8 * (size_t)a.B : 0;
-    if (threads <= 256) JH_LAUNCH((jh_ppo_fused_kernel<CONT, 256>), dim3(1), dim3(threads), lds, st, a);
+    // (<= 256 rows with the step to advance: one more wave, which does nothing else -- see the kernel)
+    if (threads <= 256) JH_LAUNCH((jh_ppo_fused_kernel<CONT, 256>), dim3(1), dim3(threads + (a.hyper_advance ? 64 : 0)), lds, st, a);
     else JH_LAUNCH((jh_ppo_fused_kernel<CONT, 1024>), dim3(1), dim3(threads), lds, st, a);
     JH_LAUNCH_CHECK();
     return JH_OK;

@@ -117,9 +117,19 @@ __global__ void __launch_bounds__(256) jh_pmb_fwd_kernel(PmbFwd g) {
     bw[u] = *reinterpret_cast<const float4*>(g.W2 + (size_t)n * K + kc);
   }
   const float b2 = g.b2[n];
-  float whv[8];
+  // round 7: the head rows and biases through UNCONDITIONAL static pointers (the host fills the unused slots of g.wh / g.hb with slot 0): behind
+  // `o < g.n_out` every pointer was a scalar fetch of its own from the argument segment + a wait + one weight fetch, in front of the first
+  // operand batch's wait; now the pointer array arrives as one block and the weights travel with the W2 rows.  Slots >= n_out are never used.
+  // The biases (tile 0's epilogue, behind the split-K barrier: a pointer fetch + a dependent fetch there) come along.
+  float whv[8], hbv[8];
 #pragma unroll
-  for (int o = 0; o < 8; ++o) whv[o] = o < g.n_out ? g.wh[o][n] : 0.f;
+  for (int o = 0; o < 4; ++o) { whv[o] = g.wh[o][n]; hbv[o] = *g.hb[o]; }
+#pragma unroll
+  for (int o = 4; o < 8; ++o) whv[o] = hbv[o] = 0.f;
+  if (g.part_ld == 8) {  // more than four head outputs
+#pragma unroll
+    for (int o = 4; o < 8; ++o) { whv[o] = g.wh[o][n]; hbv[o] = *g.hb[o]; }
+  }
   if (GEN) {
     if (VEC) {
       // UNCONDITIONAL stores: a lane beyond the slice fetched element 0 and rewrites it with the same bits -- behind an `if` LLVM
@@ -254,7 +264,7 @@ __global__ void __launch_bounds__(256) jh_pmb_fwd_kernel(PmbFwd g) {
       p += __shfl_xor(p, 8, 64);
       const int mm = m0 + kq * 4 + i;
       if (r == 0 && mm < g.M) {
-        if (tn == 0) p += *g.hb[o];
+        if (tn == 0) p += hbv[o];
         g.part[((size_t)tn * g.part_rows + mm) * g.part_ld + o] = p;
       }
     }
@@ -701,7 +711,7 @@ int jh_pmb_forward(jh_pponet* n, int M, const float* d_x, const int64_t* d_idx, 
   g.M = M; g.H = n->H; g.S = n->S; g.x = d_x; g.x_rows = d_idx;
   g.W1 = n->params + n->o_w1; g.b1 = n->params + n->o_b1; g.W2 = n->params + n->o_w2; g.b2 = n->params + n->o_b2;
   g.h1_in = h1_in; g.h1_out = store_act ? n->h1 : nullptr; g.h2_out = store_act ? n->h2 : nullptr;
-  for (int o = 0; o < hd.n_out; ++o) { g.wh[o] = hd.w[o]; g.hb[o] = hd.b[o]; }
+  for (int o = 0; o < 8; ++o) { g.wh[o] = hd.w[o < hd.n_out ? o : 0]; g.hb[o] = hd.b[o < hd.n_out ? o : 0]; }  // unused slots: valid, never used (the kernel fetches all of a granule)
   g.n_out = hd.n_out; g.part = n->fwd_part; g.part_rows = n->max_rows; g.part_ld = hd.n_out <= 4 ? 4 : 8;
   if (h1_in) return pmb_fwd_launch<0, false>(g, st);
   const bool al = (((uintptr_t)d_x) & 15) == 0 && (((uintptr_t)g.W1) & 15) == 0;
