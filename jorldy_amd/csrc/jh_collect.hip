@@ -2,8 +2,8 @@
 // for W host envs (behind a jh_env_vtbl) and T timesteps in ONE call, no Python per step.  A run is
 //   run_prepare  staging rows of the rollout store, the capture slab, the persistent acting kernel (jh_persist.hip)
 //   run_loop     the collector's persistent form, fixed when it is created:
-//                  run_loop_lookahead  forkable envs with two actions: two timesteps per exchange with the kernel
-//                  run_loop_split      32 rows of a built-in env: two independent exchanges of 16 per timestep
+//                  run_loop_lookahead  forkable envs with two actions: two timesteps per exchange with the kernel, in two independent halves of the envs
+//                  run_loop_split      2 .. 32 rows of a built-in env: two independent exchanges of half the rows per timestep
 //                  run_loop_exchange   otherwise: one exchange of the W rows per timestep
 //                then run_loop_per_launch, one acting launch per timestep, for the timesteps the form did not complete (all of
 //                them when the kernel is unavailable, the rest when it gave up)
@@ -19,11 +19,12 @@
 struct jh_persist;
 int jh_persist_create(jh_pponet* n, jh_persist** out);
 void jh_persist_destroy(jh_persist* p);
-int jh_persist_begin(jh_persist* p, int W, int T, hipStream_t st, int split = 0);
+bool jh_persist_can_split(const jh_persist* p, int rows0, int rows1);
+int jh_persist_begin(jh_persist* p, int W, int T, hipStream_t st, const int* half_rows);
 unsigned jh_persist_publish(jh_persist* p, int W, const float* h_obs);
 unsigned jh_persist_seq(const jh_persist* p);
-void jh_persist_publish_rows(jh_persist* p, int r0, int r1, const float* h_obs, unsigned tag);
-int jh_persist_collect_range(jh_persist* p, int r0, int n_rows, unsigned tag, float* h_heads);
+void jh_persist_publish_rows(jh_persist* p, int row0, int n, const float* h_obs, unsigned tag);
+int jh_persist_collect_range(jh_persist* p, int r0, int n_rows, unsigned tag, float* h_heads, int pf_rows);
 int jh_persist_collect(jh_persist* p, int W, unsigned tag, float* h_heads);
 int jh_persist_collect_rows(jh_persist* p, const int* rows, int n_rows, unsigned tag, float* h_heads);
 void jh_persist_abort(jh_persist* p);
@@ -43,13 +44,14 @@ struct Level {  // 2^k W forked envs: row 2 i + a = env i of the level above aft
     for (int i = 0; i < rows; ++i) act[i] = i & 1;
   }
 };
-// dst rows 2 i + a <- src row i stepped with action a (auto-reset included: the row then holds the reset state)
+// dst rows 2 i + a <- src row i stepped with action a (auto-reset included: the row then holds the reset state), for src rows i0 .. i1-1
 // -> the env table's first error (jh_env_vtbl: obs / step return a negative JH_ERR_* and the run stops)
-inline int fork_step(const jh_env_vtbl& vt, Level& dst, const void* src, int n_src) {
-  for (int i = 0; i < n_src; ++i) { vt.copy_row(dst.env, 2 * i, src, i); vt.copy_row(dst.env, 2 * i + 1, src, i); }
-  int rc = vt.step(dst.env, 0, 2 * n_src, dst.act.data(), dst.next.data(), dst.rw.data(), dst.dn.data());
+inline int fork_step(const jh_env_vtbl& vt, Level& dst, const void* src, int i0, int i1) {
+  for (int i = i0; i < i1; ++i) { vt.copy_row(dst.env, 2 * i, src, i); vt.copy_row(dst.env, 2 * i + 1, src, i); }
+  const size_t r0 = 2 * (size_t)i0, S = (size_t)dst.S;
+  int rc = vt.step(dst.env, 2 * i0, 2 * i1, dst.act.data() + r0, dst.next.data() + S * r0, dst.rw.data() + r0, dst.dn.data() + r0);
   if (rc) return rc;
-  return vt.obs(dst.env, 0, 2 * n_src, dst.obs.data());
+  return vt.obs(dst.env, 2 * i0, 2 * i1, dst.obs.data() + S * r0);
 }
 inline void copy_level_row(const jh_env_vtbl& vt, Level& d, int di, const Level& s_, int si) {
   vt.copy_row(d.env, di, s_.env, si);
@@ -84,9 +86,11 @@ struct jh_collector {
   // lookahead = 2 (discrete two-action envs that can be forked on the host, 3 W <= 32 rows): every PCIe round trip carries each
   // env's state AND both successor states, and serves two timesteps (run_loop_lookahead).  1: one timestep per round trip.
   int lookahead = 1;
-  // 32 rows of an env that steps row ranges (the built-in envs) are exchanged as two INDEPENDENT halves of 16 (run_loop_split): one half's round
-  // trip through the acting kernel runs under the other half's sampling, env steps and bookkeeping.  JH_COLLECT_SPLIT=0: one exchange of 32 rows.
+  // The rows are exchanged as two INDEPENDENT halves, one per row tile of the acting kernel: one half's round trip through the kernel runs under the other
+  // half's sampling, env steps and bookkeeping.  Half h is envs w0[h] .. w0[h+1]-1 (ceil(W/2) and floor(W/2) of them): 2 .. 32 rows of an env that steps row
+  // ranges of itself (the built-in envs; run_loop_split), or the look-ahead's 3 rows per env (run_loop_lookahead).  JH_COLLECT_SPLIT=0: one exchange of all rows.
   bool split = false;
+  int w0[3] = {0, 0, 0};
   Level lv[4];  // L1, L2, L3 and the one-step exchange's scratch level
   void *spec = nullptr, *spec2 = nullptr, *spec3 = nullptr;  // 2 W / 4 W / 8 W scratch envs (vt.fork_alloc): successors one, two and three steps ahead
   // acting-time capture (jh_collector_set_capture): device destinations of the raw heads / values of the states acted on
@@ -149,11 +153,15 @@ static int collector_create(jh_ctx* ctx, jh_pponet* net, const jh_env_vtbl* vt, 
       if (!c->spec || !c->spec2 || !c->spec3) c->lookahead = 1;
     }
   }
-  // two independent halves per timestep: 32 rows, one timestep per exchange, an env that steps row ranges of ITSELF (the vtbl's contract promises that for
-  // scratch envs only: the built-in envs do)
+  // two independent halves (W >= 2): of a look-ahead exchange -- only scratch envs are stepped there, on row ranges, which the vtbl's contract promises --
+  // or of one timestep per exchange, for an env that steps row ranges of ITSELF (the contract does not promise that: the built-in envs do)
   {
     const char* e = getenv("JH_COLLECT_SPLIT");
-    c->split = c->persist && c->lookahead != 2 && W == 32 && (vt->obs == cart_obs || vt->obs == ctl_obs) && !(e && atoi(e) == 0);
+    c->w0[1] = (W + 1) / 2;
+    c->w0[2] = W;
+    const int per_env = c->lookahead == 2 ? 3 : 1;
+    c->split = c->persist && W >= 2 && (c->lookahead == 2 || vt->obs == cart_obs || vt->obs == ctl_obs) && !(e && atoi(e) == 0) &&
+               jh_persist_can_split(c->persist, per_env * c->w0[1], per_env * (W - c->w0[1]));
   }
   c->obs.resize((size_t)S * W);
   c->next_obs.resize((size_t)S * W);
@@ -168,9 +176,10 @@ static int collector_create(jh_ctx* ctx, jh_pponet* net, const jh_env_vtbl* vt, 
 }
 
 // ---- the two built-in envs as function tables
-static int cart_obs(void* e, int32_t r0, int32_t r1, float* o) { jh_cartpole_obs_rows((const jh_cartpole*)e, r0, r1, o); return JH_OK; }
+// (jh_env_vtbl: the arrays of obs / step hold the rows of the RANGE, [r1 - r0][..]; the built-in envs' *_rows index full arrays by absolute row)
+static int cart_obs(void* e, int32_t r0, int32_t r1, float* o) { jh_cartpole_obs_rows((const jh_cartpole*)e, r0, r1, o - 4 * (ptrdiff_t)r0); return JH_OK; }
 static int cart_step(void* e, int32_t r0, int32_t r1, const void* a, float* nx, float* rw, uint8_t* dn) {
-  jh_cartpole_step_rows((jh_cartpole*)e, r0, r1, (const int64_t*)a, nx, rw, dn);
+  jh_cartpole_step_rows((jh_cartpole*)e, r0, r1, (const int64_t*)a - r0, nx - 4 * (ptrdiff_t)r0, rw - r0, dn - r0);
   return JH_OK;
 }
 static void* cart_fork_alloc(void*, int32_t rows) {
@@ -188,13 +197,13 @@ static void cart_copy_row(void* d_, int32_t di, const void* s_, int32_t si) {
 static int ctl_obs(void* e, int32_t r0, int32_t r1, float* o) {
   const jh_control* c = (const jh_control*)e;
   if (r0 < 0 || r1 > c->W || r0 >= r1) return jh_fail(JH_ERR_ARG, "jh_control: rows %d..%d of %d", r0, r1, c->W);
-  jh_control_obs_rows(c, r0, r1, o);
+  jh_control_obs_rows(c, r0, r1, o - (ptrdiff_t)c->S * r0);
   return JH_OK;
 }
 static int ctl_step(void* e, int32_t r0, int32_t r1, const void* a, float* nx, float* rw, uint8_t* dn) {
   jh_control* c = (jh_control*)e;
   if (r0 < 0 || r1 > c->W || r0 >= r1) return jh_fail(JH_ERR_ARG, "jh_control: rows %d..%d of %d", r0, r1, c->W);
-  jh_control_step_rows(c, r0, r1, (const float*)a, nx, rw, dn);
+  jh_control_step_rows(c, r0, r1, (const float*)a - (ptrdiff_t)c->A * r0, nx - (ptrdiff_t)c->S * r0, rw - r0, dn - r0);
   return JH_OK;
 }
 
@@ -272,6 +281,12 @@ static int collector_steps(const jh_collector* c, int T) {
   return (c->lookahead == 2 ? (T + 1) / 2 : T) + extra;
 }
 static int collector_rows(const jh_collector* c) { return c->lookahead == 2 ? 3 * c->W : c->W; }
+// rows of half h in its row tile of the acting kernel (split)
+static int half_rows(const jh_collector* c, int h) { return (c->lookahead == 2 ? 3 : 1) * (c->w0[h + 1] - c->w0[h]); }
+static int collector_begin_kernel(jh_collector* c, int steps, hipStream_t st) {
+  const int hr[2] = {half_rows(c, 0), half_rows(c, 1)};
+  return jh_persist_begin(c->persist, collector_rows(c), steps, st, c->split ? hr : nullptr);
+}
 
 // Enqueue the persistent acting kernel of the NEXT jh_collector_run(T) now (e.g. right behind the learner's last launch): it starts
 // when the stream reaches it, loads the then-current weights and waits for the first observations (bounded: ~0.2 s, after which it
@@ -281,7 +296,7 @@ JH_EXPORT int jh_collector_prelaunch(jh_collector* c, int32_t T, jh_stream strea
   JH_ARG(c != nullptr && T > 0);
   if (!c->persist || c->prelaunched_T) return JH_OK;
   const int steps = collector_steps(c, T);
-  int rc = jh_persist_begin(c->persist, collector_rows(c), steps, jh_s(stream), c->split);
+  int rc = collector_begin_kernel(c, steps, jh_s(stream));
   if (rc == JH_OK) c->prelaunched_T = steps;
   return rc;
 }
@@ -302,8 +317,8 @@ struct RunState {
   float* ac_f = nullptr;
   jh_pinned_slab* cap_slab = nullptr;
   float *ch0 = nullptr, *ch1 = nullptr, *cv = nullptr, *cnv = nullptr;
-  // test hook (tests/test_agents_gpu.py): JH_COLLECT_TEST_STALL="<timestep>,<half>" makes run_loop_split sit idle for 0.35 s in front of
-  // that half's read, which is what a stalled environment looks like to the acting kernel (it gives up after ~0.2 s without
+  // test hook (tests/test_agents_gpu.py, tests/test_collector_halves_gpu.py): JH_COLLECT_TEST_STALL="<timestep>,<half>" makes the split forms
+  // (run_loop_split, run_loop_lookahead in two halves) sit idle for 0.35 s in front of that half's read, which is what a stalled environment looks like to the acting kernel (it gives up after ~0.2 s without
   // observations): exercises the hand-over to one launch per step
   int stall_t = -1, stall_h = -1;
 };
@@ -389,7 +404,7 @@ static int run_prepare(jh_collector* c, int T, hipStream_t st) {
         jh_persist_abort(c->persist);
         (void)hipStreamSynchronize(st);
       }
-      rc = jh_persist_begin(c->persist, collector_rows(c), r.steps, st, c->split);
+      rc = collector_begin_kernel(c, r.steps, st);
       if (rc) r.persistent = false;
     }
   }
@@ -448,9 +463,9 @@ static void store_row(const jh_collector* c, const RunState& r, int w, int t, co
 
 // env rows w0 .. w1-1 take their sampled actions; their transitions go to the staging rows of timestep t.  -> the env's status
 static int step_rows(jh_collector* c, const RunState& r, int w0, int w1, int t) {
-  const int rc = c->vt.step(c->env, w0, w1, act_of(c, 0), c->next_obs.data(), c->reward.data(), c->done.data());
-  if (rc) return rc;
   const size_t S = (size_t)c->S;
+  const int rc = c->vt.step(c->env, w0, w1, act_of(c, w0), c->next_obs.data() + S * w0, c->reward.data() + w0, c->done.data() + w0);
+  if (rc) return rc;
   for (int w = w0; w < w1; ++w) store_row(c, r, w, t, &c->obs[S * w], &c->next_obs[S * w], act_of(c, w), c->reward[w], c->done[w]);
   return JH_OK;
 }
@@ -540,37 +555,38 @@ static int run_loop_exchange(jh_collector* c, int training, hipStream_t st, int*
   return JH_OK;
 }
 
-// ---- split: the 32 rows of a timestep as two INDEPENDENT exchanges of 16.
+// ---- split: the rows of a timestep as two INDEPENDENT exchanges of half of them (round 8: any 2 <= W <= 32, not only 32).
 // One timestep of config.ppo.mujoco's 32 workers was exchange (19.4 us: publication, PCIe polling, 3.9 us of kernel, 48 KB of partial heads back, the host's
 // sampling) + env steps and bookkeeping (11 us), one after the other.  The acting kernel's two row tiles are two sets of workgroups that never talk to each
 // other, so with tags per row tile (jh_persist.hip: PersistArgs::split) the host runs them out of phase: while half A's observations are on their way through
 // the kernel, the host samples, steps and stores half B, publishes B's next observations, and only then comes back for A's heads.  Nothing is speculated: the
-// same rows go through the same arithmetic (a row's position inside its tile is unchanged), the sampling stream is keyed by (seed, timestep, row), every env
-// row advances on its own state -- the rollout, the captured heads / values and every stored transition are bit-identical to the one-exchange path (tested).
+// same rows go through the same arithmetic (a row's bits do not depend on its tile or its slot in it), the sampling stream is keyed by (seed, timestep, row),
+// every env row advances on its own state -- the rollout, the captured heads / values and every stored transition are bit-identical to the one-exchange path
+// (tested).  Half h: envs w0[h] .. w0[h+1]-1 as rows 16 h .. of the kernel.
 static int run_loop_split(jh_collector* c, int training, hipStream_t st, int* t_done) {
   RunState& r = run_state(c);
-  const int W = c->W, T = r.T, steps = T + (r.cap ? 1 : 0), HR = 16;
+  const int W = c->W, S = c->S, T = r.T, steps = T + (r.cap ? 1 : 0);
   const unsigned base = jh_persist_seq(c->persist);  // the kernel's tags are base + 1 .. base + steps, for each half on its own
   bool dead = false;  // the kernel gave up while half 1 of a timestep was owed: that half is finished by hand, then the per-step path takes over
   int rc = c->vt.obs(c->env, 0, W, c->obs.data());
   if (rc) return env_failed(c, rc);
-  for (int h = 0; h < 2; ++h) jh_persist_publish_rows(c->persist, h * HR, (h + 1) * HR, c->obs.data(), base + 1);
+  for (int h = 0; h < 2; ++h) jh_persist_publish_rows(c->persist, 16 * h, c->w0[h + 1] - c->w0[h], c->obs.data() + (size_t)S * c->w0[h], base + 1);
   for (int t = 0; t < steps; ++t) {
     const bool extra = t == T;  // capture: one value-only query of the states the rollout ended in
     for (int h = 0; h < 2; ++h) {
-      const int r0 = h * HR, r1 = r0 + HR;
+      const int r0 = c->w0[h], r1 = c->w0[h + 1];
       const auto t0 = Clock::now();
       if (t == r.stall_t && h == r.stall_h) {
         // (the OTHER half's workgroups are the ones starved: this half's observations are out already)
         while (secs(t0, Clock::now()) < 0.35) {}
       }
-      rc = jh_persist_collect_range(c->persist, r0, HR, base + (unsigned)t + 1, c->heads.data() + (size_t)r0 * c->no);
+      rc = jh_persist_collect_range(c->persist, 16 * h, r1 - r0, base + (unsigned)t + 1, c->heads.data() + (size_t)r0 * c->no, 0);
       if (rc) {
         rc = kernel_gave_up(c, r, t, st, t_done);
         if (rc || h == 0) return rc;  // (both halves stand at step t: the per-step path takes over from here)
-        // half 1 of step t is still owed (half 0 has moved on): its raw heads from one launch over its 16 rows, sampled below with the rows' own stream keys
+        // half 1 of step t is still owed (half 0 has moved on): its raw heads from one launch over its rows, sampled below with the rows' own stream keys
         const uint64_t ctr = c->net->act_ctr;
-        rc = act_launch(c, r0, HR, 0, st);
+        rc = act_launch(c, r0, r1 - r0, 0, st);
         if (rc) return rc;
         c->net->act_ctr = ctr;  // (the launch counted a sampling step; this timestep's count comes below)
         dead = true;
@@ -587,9 +603,9 @@ static int run_loop_split(jh_collector* c, int training, hipStream_t st, int* t_
       rc = step_rows(c, r, r0, r1, t);
       if (rc) return env_failed(c, rc);
       if (t + 1 < steps && !dead) {  // this half's next observations (the reset state where an episode just ended) go out NOW: their round trip runs under the other half's work
-        rc = c->vt.obs(c->env, r0, r1, c->obs.data());
+        rc = c->vt.obs(c->env, r0, r1, c->obs.data() + (size_t)S * r0);
         if (rc) return env_failed(c, rc);
-        jh_persist_publish_rows(c->persist, r0, r1, c->obs.data(), base + (unsigned)t + 2);
+        jh_persist_publish_rows(c->persist, 16 * h, r1 - r0, c->obs.data() + (size_t)S * r0, base + (unsigned)t + 2);
       }
       c->t_env += secs(t1, Clock::now());
     }
@@ -620,124 +636,190 @@ static int run_loop_split(jh_collector* c, int training, hipStream_t st, int* t_
 // rollout, the captured heads / values and every stored transition are bit-identical to the one-step-per-exchange path
 // (tests/test_agents_gpu.py: lookahead vs JH_COLLECT_LOOKAHEAD=1); what changes is that the GPU also evaluates the successor that
 // was not taken (8 wasted rows per exchange) and the host steps env copies that are thrown away.
+// Round 8: the exchange in two INDEPENDENT halves of the envs (c->split), like run_loop_split's: half h = envs w0[h] .. w0[h+1]-1 lives in row tile h of the
+// kernel in the same layout (its n roots, then n + 2 i + a), under its own tags.  Per exchange the host handles half A, then half B -- read, sample, publish
+// the half's next rows at once, bookkeeping, its speculative env steps -- so that one half's round trip runs under the other half's host work.  Both halves
+// draw timestep t under the same sampling step (the stream is keyed by (seed, step, env row)), the levels' rows of an env do not depend on the half it is in:
+// bit-identical again (JH_COLLECT_SPLIT=0: one exchange of all rows, the schedule above).
 static int run_loop_lookahead(jh_collector* c, int training, hipStream_t st, int* t_done) {
   RunState& r = run_state(c);
   const int W = c->W, S = c->S, T = r.T, steps = T + (r.cap ? 1 : 0), no = c->no;
+  const int NP = c->split ? 2 : 1;
   void* e = c->env;
   const jh_env_vtbl& vt = c->vt;
   Level &L1 = c->lv[0], &L2 = c->lv[1], &L3 = c->lv[2], &tmp = c->lv[3];
   L1.env = c->spec; L2.env = c->spec2; L3.env = c->spec3;
   L1.init(2 * W, S); L2.init(4 * W, S); L3.init(8 * W, S);
-  std::vector<float> pub((size_t)3 * W * S), pub_next((size_t)3 * W * S), hz((size_t)W * no), hz2((size_t)W * no);
+  std::vector<float> pub_a((size_t)3 * W * S), pub_b((size_t)3 * W * S), hz((size_t)W * no), hz2((size_t)W * no);
   std::vector<int> pick(W);
   std::vector<int64_t> a0(W), a1(W);
-  int t = 0;
-  // JH_COLLECT_DEBUG: where the host's time per exchange goes (summed over the run, printed every 16th run): fork = stepping the
+  // part h: envs e0 .. e1-1 as rows rb .. rb + 3 n - 1 of the kernel; its published rows [3 n][S] and the next exchange's
+  int e0s[2] = {0, 0}, e1s[2] = {W, W};
+  float *pub[2], *pub_next[2];
+  Clock::time_point t0[2];
+  for (int h = 0; h < NP; ++h) {
+    if (NP == 2) { e0s[h] = c->w0[h]; e1s[h] = c->w0[h + 1]; }
+    pub[h] = pub_a.data() + (size_t)3 * S * e0s[h];
+    pub_next[h] = pub_b.data() + (size_t)3 * S * e0s[h];
+  }
+  const unsigned base = jh_persist_seq(c->persist);  // the kernel's tags are base + 1 .. , per exchange (and per half on its own)
+  uint64_t ctr = c->net->act_ctr;                    // the sampling step of timestep t: the same for both halves
+  int t = 0, k = 0;
+  bool dead = false;  // the kernel gave up while half 1 of an exchange was owed: that half is finished by hand, then the per-step path takes over
+  // JH_COLLECT_DEBUG: where the host's time per (half-)exchange goes (summed over the run, printed every 16th run): fork = stepping the
   // speculative copies, wait = polling for the root rows' heads, sample = both samplings + the chosen successors' heads,
   // publish = assembling and publishing the next exchange, book = transitions / captured heads / moving the envs on
   const bool dbg = c->dbg;
   double d_fork = 0, d_wait = 0, d_sample = 0, d_publish = 0, d_book = 0;
   int n_ex = 0;
-  // rows 0 .. W-1: the envs' current states; rows W + 2 w + a: the state env w acts on next if it takes action a now
-  int rc = fork_step(vt, L1, e, W);
-  if (!rc) rc = vt.obs(e, 0, W, pub.data());
+  // While the GPU works on part h's exchange of timestep t_at: its env model two levels further (nothing for the value-only query)
+  auto speculate = [&](int h, int t_at) -> int {
+    if (t_at == T) return JH_OK;
+    const bool two = t_at + 1 < T;
+    const auto q0 = dbg ? Clock::now() : Clock::time_point();
+    int rc = fork_step(vt, L2, L1.env, 2 * e0s[h], 2 * e1s[h]);
+    if (!rc && two && t_at + 2 < steps) rc = fork_step(vt, L3, L2.env, 4 * e0s[h], 4 * e1s[h]);
+    if (dbg) d_fork += secs(q0, Clock::now());
+    return rc;
+  };
+  // raw heads of part h's n rows with observations x(i), i = 0 .. n-1, from one acting launch (the kernel is gone) -> out [n][no]
+  auto heads_by_launch = [&](int h, auto x, float* out) -> int {
+    const int n = e1s[h] - e0s[h];
+    for (int i = 0; i < n; ++i) memcpy(&c->obs[(size_t)S * (e0s[h] + i)], x(i), sizeof(float) * S);
+    const uint64_t keep = c->net->act_ctr;
+    const int rc = act_launch(c, e0s[h], n, 0, st);
+    c->net->act_ctr = keep;  // (the launch counted a sampling step and sampled under its own row keys: the rows are sampled below, under theirs)
+    if (!rc) memcpy(out, c->heads.data() + (size_t)e0s[h] * no, sizeof(float) * (size_t)n * no);
+    return rc;
+  };
+  // rows 0 .. n-1 of a part: its envs' current states; rows n + 2 i + a: the state its env i acts on next if it takes action a now
+  int rc = fork_step(vt, L1, e, 0, W);
+  if (!rc) rc = vt.obs(e, 0, W, c->obs.data());
   if (rc) return env_failed(c, rc);
-  memcpy(pub.data() + (size_t)W * S, L1.obs.data(), sizeof(float) * (size_t)2 * W * S);
-  auto t0 = Clock::now();
-  unsigned tag = jh_persist_publish(c->persist, 3 * W, pub.data());
+  for (int h = 0; h < NP; ++h) {
+    const int n = e1s[h] - e0s[h];
+    memcpy(pub[h], &c->obs[(size_t)S * e0s[h]], sizeof(float) * (size_t)n * S);
+    memcpy(pub[h] + (size_t)n * S, &L1.obs[(size_t)S * 2 * e0s[h]], sizeof(float) * (size_t)2 * n * S);
+    t0[h] = Clock::now();
+    jh_persist_publish_rows(c->persist, 16 * h, 3 * n, pub[h], base + 1);
+  }
+  auto last_t1 = t0[0];  // the acting time of a (half-)exchange runs from its publication, or from the previous sampling where that came later
+  for (int h = 0; h < NP; ++h) {
+    rc = speculate(h, 0);
+    if (rc) return env_failed(c, rc);
+  }
   while (t < steps) {
     const bool extra = t == T;
     const bool two = !extra && t + 1 < T;
     const int t_next = t + (two ? 2 : 1);
-    const auto q0 = dbg ? Clock::now() : Clock::time_point();
-    if (!extra) {  // the GPU is busy for ~5 us: run the env model two levels further meanwhile
-      rc = fork_step(vt, L2, L1.env, 2 * W);
-      if (!rc && two && t_next < steps) rc = fork_step(vt, L3, L2.env, 4 * W);
-      if (rc) return env_failed(c, rc);
-    }
-    const auto q1 = dbg ? Clock::now() : q0;
-    rc = jh_persist_collect_rows(c->persist, nullptr, W, tag, hz.data());
-    const auto q2 = dbg ? Clock::now() : q0;
-    if (rc) return kernel_gave_up(c, r, t, st, t_done);
-    if (!extra) {
-      for (int w = 0; w < W; ++w) {
-        a0[w] = jh_sample_discrete(c->net, hz.data() + (size_t)w * no, w, training);
-        pick[w] = W + 2 * w + (int)a0[w];
+    const unsigned tag = base + (unsigned)k + 1;
+    for (int h = 0; h < NP; ++h) {
+      const int w0 = e0s[h], w1 = e1s[h], n = w1 - w0, rb = 16 * h;
+      const float* roots = pub[h];
+      if (t == r.stall_t && h == r.stall_h) {  // (test hook: see run_loop_split)
+        const auto s0 = Clock::now();
+        while (secs(s0, Clock::now()) < 0.35) {}
       }
-      c->net->act_ctr += 1;
-      if (two) {  // timestep t + 1: the heads of the chosen successors arrived with the same exchange
-        rc = jh_persist_collect_rows(c->persist, pick.data(), W, tag, hz2.data());
-        if (rc) return rc;  // (the kernel answers a tag for all rows or for none)
-        for (int w = 0; w < W; ++w) a1[w] = jh_sample_discrete(c->net, hz2.data() + (size_t)w * no, w, training);
-        c->net->act_ctr += 1;
+      const auto q1 = dbg ? Clock::now() : Clock::time_point();
+      c->net->act_ctr = ctr;
+      rc = jh_persist_collect_range(c->persist, rb, n, tag, hz.data() + (size_t)w0 * no, 2 * n);
+      const auto q2 = dbg ? Clock::now() : q1;
+      if (rc) {
+        rc = kernel_gave_up(c, r, t, st, t_done);
+        if (rc || h == 0) return rc;  // (both halves stand at timestep t: the per-step path takes over from here)
+        // half 1 still owes this exchange's timesteps (half 0 has stored them): one acting launch per timestep over its rows, the successors it had computed
+        dead = true;
+        rc = heads_by_launch(h, [&](int i) { return roots + (size_t)S * i; }, hz.data() + (size_t)w0 * no);
+        if (rc) return rc;
       }
-    }
-    const auto t1 = Clock::now();
-    if (dbg) { d_fork += secs(q0, q1); d_wait += secs(q1, q2); d_sample += secs(q2, t1); ++n_ex; }
-    // ---- the next exchange first: its rows are already computed; everything else happens while the GPU works on it
-    unsigned tag_next = 0;
-    auto t0_next = t1;
-    if (!extra && t_next < steps) {
-      for (int w = 0; w < W; ++w) {
+      if (!extra) {
+        for (int w = w0; w < w1; ++w) {
+          a0[w] = jh_sample_discrete(c->net, hz.data() + (size_t)w * no, w, training);
+          pick[w] = rb + n + 2 * (w - w0) + (int)a0[w];
+        }
+        if (two) {  // timestep t + 1, one sampling step on: the heads of the chosen successors arrived with the same exchange
+          c->net->act_ctr = ctr + 1;
+          rc = dead ? heads_by_launch(h, [&](int i) { return &L1.obs[(size_t)S * (2 * (w0 + i) + (int)a0[w0 + i])]; }, hz2.data() + (size_t)w0 * no)
+                    : jh_persist_collect_rows(c->persist, pick.data() + w0, n, tag, hz2.data() + (size_t)w0 * no);
+          if (rc) return rc;  // (the kernel answers a tag for all rows of a row tile or for none)
+          for (int w = w0; w < w1; ++w) a1[w] = jh_sample_discrete(c->net, hz2.data() + (size_t)w * no, w, training);
+        }
+      }
+      const auto t1 = Clock::now();
+      if (dbg) { d_wait += secs(q1, q2); d_sample += secs(q2, t1); ++n_ex; }
+      // ---- the part's next exchange first: its rows are already computed; everything else happens while the GPU works on it
+      auto t0_next = t1;
+      if (!extra && t_next < steps && !dead) {
+        float* pn = pub_next[h];
+        for (int w = w0; w < w1; ++w) {
+          const int i = w - w0, k1 = 2 * w + (int)a0[w];
+          if (two) {
+            const int k2 = 2 * k1 + (int)a1[w];
+            memcpy(&pn[(size_t)S * i], &L2.obs[(size_t)S * k2], sizeof(float) * S);
+            memcpy(&pn[(size_t)S * (n + 2 * i)], &L3.obs[(size_t)S * 2 * k2], sizeof(float) * 2 * S);
+          } else {
+            memcpy(&pn[(size_t)S * i], &L1.obs[(size_t)S * k1], sizeof(float) * S);
+            memcpy(&pn[(size_t)S * (n + 2 * i)], &L2.obs[(size_t)S * 2 * k1], sizeof(float) * 2 * S);
+          }
+        }
+        t0_next = Clock::now();
+        jh_persist_publish_rows(c->persist, rb, 3 * n, pn, tag + 1);
+      }
+      const auto q3 = dbg ? Clock::now() : t1;
+      if (dbg) d_publish += secs(t1, q3);
+      // ---- bookkeeping of this (half-)exchange: captured heads / values, transitions, the envs move on
+      for (int w = w0; w < w1; ++w) {
+        capture_row(c, r, w, t, hz.data() + (size_t)w * no);
+        if (two) capture_row(c, r, w, t + 1, hz2.data() + (size_t)w * no);
+      }
+      count_act(c, r, t, secs(t0[h] > last_t1 ? t0[h] : last_t1, t1));
+      last_t1 = t1;
+      if (extra) continue;
+      const bool on = t_next < steps && !dead;  // another exchange follows: the levels move up
+      if (!two) { tmp.env = L3.env; tmp.init(2 * W, S); }  // one-step exchange: L3 is free, the successors move up through it
+      for (int w = w0; w < w1; ++w) {
         const int k1 = 2 * w + (int)a0[w];
+        store_row(c, r, w, t, roots + (size_t)S * (w - w0), &L1.next[(size_t)S * k1], &a0[w], L1.rw[k1], L1.dn[k1]);
         if (two) {
           const int k2 = 2 * k1 + (int)a1[w];
-          memcpy(&pub_next[(size_t)S * w], &L2.obs[(size_t)S * k2], sizeof(float) * S);
-          memcpy(&pub_next[(size_t)S * (W + 2 * w)], &L3.obs[(size_t)S * 2 * k2], sizeof(float) * 2 * S);
+          store_row(c, r, w, t + 1, &L1.obs[(size_t)S * k1], &L2.next[(size_t)S * k2], &a1[w], L2.rw[k2], L2.dn[k2]);
+          vt.copy_row(e, w, L2.env, k2);
+          if (on) {  // (L1's rows of env w are read above before they are overwritten)
+            copy_level_row(vt, L1, 2 * w, L3, 2 * k2);
+            copy_level_row(vt, L1, 2 * w + 1, L3, 2 * k2 + 1);
+          }
         } else {
-          memcpy(&pub_next[(size_t)S * w], &L1.obs[(size_t)S * k1], sizeof(float) * S);
-          memcpy(&pub_next[(size_t)S * (W + 2 * w)], &L2.obs[(size_t)S * 2 * k1], sizeof(float) * 2 * S);
+          vt.copy_row(e, w, L1.env, k1);
+          if (on) {
+            copy_level_row(vt, tmp, 2 * w, L2, 2 * k1);
+            copy_level_row(vt, tmp, 2 * w + 1, L2, 2 * k1 + 1);
+          }
         }
       }
-      t0_next = Clock::now();
-      tag_next = jh_persist_publish(c->persist, 3 * W, pub_next.data());
-    }
-    const auto q3 = dbg ? Clock::now() : t1;
-    if (dbg) d_publish += secs(t1, q3);
-    // ---- bookkeeping of this exchange: captured heads / values, transitions, the envs move on
-    for (int w = 0; w < W; ++w) {
-      capture_row(c, r, w, t, hz.data() + (size_t)w * no);
-      if (two) capture_row(c, r, w, t + 1, hz2.data() + (size_t)w * no);
-    }
-    count_act(c, r, t, secs(t0, t1));
-    if (extra) {
-      t = t_next;
-      break;
-    }
-    if (!two) { tmp.env = L3.env; tmp.init(2 * W, S); }  // one-step exchange: L3 is free, the successors move up through it
-    for (int w = 0; w < W; ++w) {
-      const int k1 = 2 * w + (int)a0[w];
-      store_row(c, r, w, t, &pub[(size_t)S * w], &L1.next[(size_t)S * k1], &a0[w], L1.rw[k1], L1.dn[k1]);
-      if (two) {
-        const int k2 = 2 * k1 + (int)a1[w];
-        store_row(c, r, w, t + 1, &L1.obs[(size_t)S * k1], &L2.next[(size_t)S * k2], &a1[w], L2.rw[k2], L2.dn[k2]);
-        vt.copy_row(e, w, L2.env, k2);
-        if (t_next < steps) {  // (L1's rows of env w are read above before they are overwritten)
-          copy_level_row(vt, L1, 2 * w, L3, 2 * k2);
-          copy_level_row(vt, L1, 2 * w + 1, L3, 2 * k2 + 1);
-        }
-      } else {
-        vt.copy_row(e, w, L1.env, k1);
-        copy_level_row(vt, tmp, 2 * w, L2, 2 * k1);
-        copy_level_row(vt, tmp, 2 * w + 1, L2, 2 * k1 + 1);
+      if (!two && on)
+        for (int i = 2 * w0; i < 2 * w1; ++i) copy_level_row(vt, L1, i, tmp, i);
+      const auto t2 = Clock::now();
+      if (dbg) d_book += secs(q3, t2);
+      c->t_env += secs(t1, t2);
+      t0[h] = t0_next;
+      std::swap(pub[h], pub_next[h]);
+      if (on) {
+        rc = speculate(h, t_next);
+        if (rc) return env_failed(c, rc);
       }
     }
-    if (!two)
-      for (int i = 0; i < 2 * W; ++i) copy_level_row(vt, L1, i, tmp, i);
-    c->steps += two ? 2 : 1;
-    const auto t2 = Clock::now();
-    if (dbg) d_book += secs(q3, t2);
-    c->t_env += secs(t1, t2);
+    ctr += extra ? 0 : two ? 2 : 1;
+    c->net->act_ctr = ctr;
+    c->steps += extra ? 0 : two ? 2 : 1;
     t = t_next;
-    tag = tag_next;
-    t0 = t0_next;
-    pub.swap(pub_next);
+    ++k;
+    if (dead) break;
   }
   *t_done = t;
   if (dbg && n_ex > 0 && (c->runs % 16) == 15)
-    fprintf(stderr, "[jh_collect] host us per exchange (%d exchanges): fork %.2f  wait %.2f  sample %.2f  publish %.2f  book %.2f\n", n_ex, d_fork / n_ex * 1e6,
-            d_wait / n_ex * 1e6, d_sample / n_ex * 1e6, d_publish / n_ex * 1e6, d_book / n_ex * 1e6);
-  if (c->dbg_persist && (c->runs % 16) == 15) jh_persist_dump_debug(c->persist, collector_steps(c, T));
+    fprintf(stderr, "[jh_collect] host us per %s (%d of them): fork %.2f  wait %.2f  sample %.2f  publish %.2f  book %.2f\n", NP == 2 ? "half-exchange" : "exchange", n_ex,
+            d_fork / n_ex * 1e6, d_wait / n_ex * 1e6, d_sample / n_ex * 1e6, d_publish / n_ex * 1e6, d_book / n_ex * 1e6);
+  if (c->dbg_persist && (c->runs % 16) == 15 && !dead) jh_persist_dump_debug(c->persist, collector_steps(c, T));
   return JH_OK;
 }
 

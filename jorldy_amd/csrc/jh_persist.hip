@@ -28,6 +28,8 @@
 // actions lead to (the envs are host objects that can be forked), so that one PCIe round trip serves TWO timesteps: the host samples
 // a_t from the root row, picks that child and samples a_{t+1} from the child's row, which is already there.  The second row tile
 // is a second set of 32 workgroups (grid = column tiles x row tiles): a step's compute stays the one-tile 1.65 us.
+// Round 6 / 8: the two row tiles can be exchanged INDEPENDENTLY (PersistArgs::split): each polls, relays and answers its own rows under its own tags -- half h
+// of the rows is rows_rt[h] <= 16 rows of row tile h, whatever the row count (two halves of 16 workers, of 4, of a look-ahead exchange's 12 rows).
 // Heads: G = ceil(n_out / 3) granules per (tile, row), n_out = A logits (or mu / log_std of a continuous policy) + the value
 // head (last output; handed to the learner by the collector's capture): discrete A <= 11, continuous A <= 5.
 #if defined(__x86_64__)
@@ -53,8 +55,9 @@ struct PersistArgs {
   int period;                          // spacing of the polls in flight, wall_clock64 ticks (10 ns)
   unsigned long long* mbox;            // device memory [64] granules: relay of the observations (null: every workgroup polls the host)
   float4* dpart;                       // device memory [row tiles][G][16 rows][tiles] granules, or null: round 6, the partial heads are summed ON THE DEVICE
-  int split;                           // round 6: the two row tiles are exchanged INDEPENDENTLY (W = 32): a workgroup waits for, polls and relays only ITS row tile's
+  int split;                           // round 6: the two row tiles are exchanged INDEPENDENTLY: a workgroup waits for, polls and relays only ITS row tile's
                                        // observation granules, so the host can publish one half's step t + 1 while the other half's step t is still in flight
+  int rows_rt[2];                      // rows in use of each row tile: min(W, 16) and the rest, or (split, round 8) the two halves' row counts -- half h is rows 16 h .. 16 h + rows_rt[h] - 1
 };
 
 // One poll: lanes 0..n16-1 of the calling wave each fetch 16 bytes (two granules) of the observation area
@@ -126,8 +129,9 @@ __global__ void __launch_bounds__(256, 1) jh_act_persist_kernel(PersistArgs p) {
   __syncthreads();
 
   // the window of observation granules this workgroup waits for: all of them, or (split) its row tile's rows -- S x 16 x 8 bytes = a multiple of 16
+  const int rows_mine = p.rows_rt[rt];  // rows of this workgroup's row tile that are in use (read once: not a kernel-argument fetch per step)
   const int g0 = p.split ? rt * 16 * S : 0;
-  const int n_gran = p.split ? (p.W - 16 * rt < 16 ? p.W - 16 * rt : 16) * S : p.W * S;  // <= 128 PI: lane l owns granules g0 + l + 64 j
+  const int n_gran = p.split ? rows_mine * S : p.W * S;  // <= 128 PI: lane l owns granules g0 + l + 64 j
   const int n16 = (n_gran + 1) >> 1;     // 16-byte pieces per poll (two granules each); instruction q fetches pieces 64 q .. 64 q + 63
   const char* my_src = reinterpret_cast<const char*>(p.obs_gran + g0) + 16 * (lane < n16 ? lane : 0);
   const bool poller = !p.mbox || (p.split ? tile == 0 : blockIdx.x == 0);  // polls the HOST (and relays to its row tile / to everybody)
@@ -311,7 +315,7 @@ __global__ void __launch_bounds__(256, 1) jh_act_persist_kernel(PersistArgs p) {
       // 16-byte row granules {out 3g, out 3g+1, out 3g+2, tag}: the partial IS its own flag.  Lanes (g, row) store
       // W consecutive granules per g with ONE instruction; fire and forget (no fence, no acknowledgement wait)
       const int g = lane >> 4, row = lane & 15;
-      if (g < p.G && 16 * rt + row < p.W) {
+      if (g < p.G && row < rows_mine) {
         const f32x4 gq = (f32x4){s_out[row][3 * g], s_out[row][3 * g + 1], s_out[row][3 * g + 2], __uint_as_float(tag)};
         // write-through 16-byte store (a plain store lingers in L2 for milliseconds); hipcc does not track asm stores: the s_nop keeps
         // the data registers intact until the store has read them (CDNA guide §5.7).  Host memory, or -- round 6 -- the device-side
@@ -333,7 +337,7 @@ __global__ void __launch_bounds__(256, 1) jh_act_persist_kernel(PersistArgs p) {
     // them IN TILE ORDER (the host's order: the same bits) and sends one granule per (row, g) to the host, into tile 0's slots.
     if (p.dpart && tile == 0) {
       const int g = lane >> 4, row = lane & 15;
-      const bool mine = g < p.G && 16 * rt + row < p.W;
+      const bool mine = g < p.G && row < rows_mine;
       const int per = tiles_n / 4;  // tiles per wave: 1, 2, 4, 8 (hidden 64 .. 512)
       bool ok = true;
       if (mine) {
@@ -473,12 +477,20 @@ static void persist_launch(int depth, int pi, int grid, hipStream_t st, const Pe
 }
 
 // Launch the persistent kernel for T steps of W <= 32 rows (W * S <= 512 observation granules).
-// split: the two row tiles of a W = 32 exchange advance independently (tags per row tile; jh_persist_publish_rows / jh_persist_collect_rows).
-int jh_persist_begin(jh_persist* p, int W, int T, hipStream_t st, int split) {
+// half_rows (or null): the two row tiles advance independently (tags per row tile; jh_persist_publish_rows / jh_persist_collect_range / _rows): half h is
+// half_rows[h] <= 16 rows of row tile h, rows 16 h .. 16 h + half_rows[h] - 1 (W is then their sum).
+static int persist_poll_instructions(int granules) { return ((granules + 1) / 2 + 63) / 64; }
+bool jh_persist_can_split(const jh_persist* p, int rows0, int rows1) {
+  // both row tiles run the same kernel instance: every poll instruction of a poll must have a lane to fetch for in BOTH windows
+  const int S = p->net->S;
+  return rows0 >= 1 && rows0 <= 16 && rows1 >= 1 && rows1 <= 16 && persist_poll_instructions(rows0 * S) == persist_poll_instructions(rows1 * S);
+}
+int jh_persist_begin(jh_persist* p, int W, int T, hipStream_t st, const int* half_rows) {
   jh_pponet* n = p->net;
-  JH_ARG(W > 0 && W <= 32 && W * n->S <= kPersistMaxGranules && T > 0 && (!split || W == 32));
-  const int win = split ? 16 * n->S : W * n->S;  // observation granules a workgroup polls
-  const int pi = ((win + 1) / 2 + 63) / 64;  // exactly the instructions that have a lane to fetch for (see the kernel)
+  const bool split = half_rows != nullptr;
+  JH_ARG(T > 0 && (split ? jh_persist_can_split(p, half_rows[0], half_rows[1]) && W == half_rows[0] + half_rows[1] : W > 0 && W <= 32 && W * n->S <= kPersistMaxGranules));
+  const int win = split ? half_rows[0] * n->S : W * n->S;  // observation granules a workgroup polls
+  const int pi = persist_poll_instructions(win);  // exactly the instructions that have a lane to fetch for (see the kernel)
   PersistArgs a{};
   a.W = W; a.S = n->S; a.H = n->H; a.T = T; a.G = p->G;
   a.W1 = n->params + n->o_w1; a.b1 = n->params + n->o_b1; a.W2 = n->params + n->o_w2; a.b2 = n->params + n->o_b2;
@@ -503,16 +515,20 @@ int jh_persist_begin(jh_persist* p, int W, int T, hipStream_t st, int split) {
   // 15.8 us reduced; 8 workers: 6.9 vs 8.4 us).  The cross-XCD visibility of a store is the price, not the bytes.
   // ... but ON by default for SPLIT exchanges (end of round 6): there the extra hand-off latency hides under the other half's host work, and what is left on the
   // host's critical path -- reading 48 KB of partial heads per timestep (~4 us) -- shrinks to 1.5 KB: configs[4] end to end 0.79 -> 0.88 M env transitions/s.
-  const int reduce = getenv("JH_PERSIST_REDUCE") ? atoi(getenv("JH_PERSIST_REDUCE")) : (split ? 1 : 0);  // (read per launch: the tests switch it)
+  // ... and only for two FULL halves (round 8): a narrower split exchange -- a look-ahead half of 12 rows, 4 workers of a continuous policy -- is bound by its
+  // round trip, not by the host's reading, and the hand-off would lengthen exactly that.
+  const int reduce = getenv("JH_PERSIST_REDUCE") ? atoi(getenv("JH_PERSIST_REDUCE")) : (split && W == 32 ? 1 : 0);  // (read per launch: the tests switch it)
   p->reduced = reduce == 1;
   a.dpart = p->reduced ? p->dpart : nullptr;
   a.split = split ? 1 : 0;
-  p->split = split != 0;
+  p->split = split;
   a.max_polls = 600000;  // x (>= 0.3 us per consumed poll) = >= 0.2 s without observations -> give up
   p->flag_h[0] = 0;
   const int nch = n->H / 64;
   const int sp = (n->S + 3) / 4 * 4;  // 4, 8: W1 fragments in registers; 12, 16: in LDS
-  const int rt = W > 16 ? 2 : 1;  // row tiles = workgroups per column tile
+  const int rt = split || W > 16 ? 2 : 1;  // row tiles = workgroups per column tile
+  a.rows_rt[0] = split ? half_rows[0] : (W < 16 ? W : 16);
+  a.rows_rt[1] = split ? half_rows[1] : (W > 16 ? W - 16 : 0);
   p->rows_ld = 16 * rt;
   a.rows_ld = p->rows_ld;
   const int grid = p->tiles * rt;
@@ -542,28 +558,33 @@ unsigned jh_persist_publish(jh_persist* p, int W, const float* h_obs) {
   return tag;
 }
 
-// Split exchanges: publish rows r0 .. r1-1 (h_obs: the FULL [W][S] array) under `tag` = the persist's sequence number at jh_persist_begin + the step (1 ..).
+// Split exchanges: publish h_obs [n][S] as the kernel's rows row0 .. row0 + n - 1 (a half's rows start at 16 h) under `tag` = the persist's sequence number at
+// jh_persist_begin + the step (1 ..).
 unsigned jh_persist_seq(const jh_persist* p) { return p->seq; }
-void jh_persist_publish_rows(jh_persist* p, int r0, int r1, const float* h_obs, unsigned tag) {
+void jh_persist_publish_rows(jh_persist* p, int row0, int n, const float* h_obs, unsigned tag) {
   const int S = p->net->S;
-  if (r1 > p->rows_published) p->rows_published = r1;
-  for (int i = r0 * S; i < r1 * S; ++i) {
+  unsigned long long* dst = p->gran_h + (size_t)row0 * S;
+  for (int i = 0; i < n * S; ++i) {
     unsigned bits;
     memcpy(&bits, h_obs + i, 4);
-    __atomic_store_n(p->gran_h + i, ((unsigned long long)tag << 32) | bits, __ATOMIC_RELEASE);
+    __atomic_store_n(dst + i, ((unsigned long long)tag << 32) | bits, __ATOMIC_RELEASE);
   }
   if ((int)(tag - p->seq) > 0) p->seq = tag;
 }
 
 // Wait until every tile's granules of the listed rows (rows == NULL: rows 0 .. n_rows-1) carry `tag`, then sum the per-tile partials
 // in tile order: h_heads [n_rows][n_out] raw head outputs (logits | mu_raw, log_std_raw; value last).  JH_ERR_STATE if the kernel gave up.
-static int persist_collect(jh_persist* p, const int* rows, int n_rows, unsigned tag, float* h_heads, int r_first, bool block_order);
+static int persist_collect(jh_persist* p, const int* rows, int n_rows, unsigned tag, float* h_heads, int r_first, bool block_order, int pf_rows);
 int jh_persist_collect_rows(jh_persist* p, const int* rows, int n_rows, unsigned tag, float* h_heads) {
-  return persist_collect(p, rows, n_rows, tag, h_heads, 0, !rows && n_rows > 16);
+  return persist_collect(p, rows, n_rows, tag, h_heads, 0, !rows && n_rows > 16, (!rows && p->rows_published > n_rows) ? p->rows_published - n_rows : 0);
 }
-// rows r0 .. r0 + n_rows - 1 in the blocks' storage order (a split exchange's half: 16 consecutive row granules per (tile, g) block)
-int jh_persist_collect_range(jh_persist* p, int r0, int n_rows, unsigned tag, float* h_heads) { return persist_collect(p, nullptr, n_rows, tag, h_heads, r0, true); }
-static int persist_collect(jh_persist* p, const int* rows, int n_rows, unsigned tag, float* h_heads, int r_first, bool block_order) {
+// rows r0 .. r0 + n_rows - 1 (a split exchange's half, or the first rows of one: r0 = 16 h).  A full tile of 16 is read in the blocks' storage order (16
+// consecutive row granules per (tile, g) block), fewer rows keep the row-major walk (see persist_collect).  pf_rows: rows behind them that the same
+// exchange carries and a later jh_persist_collect_rows will ask for (the successors of a look-ahead half): prefetched while the first rows are read
+int jh_persist_collect_range(jh_persist* p, int r0, int n_rows, unsigned tag, float* h_heads, int pf_rows) {
+  return persist_collect(p, nullptr, n_rows, tag, h_heads, r0, n_rows == 16 && pf_rows == 0, pf_rows);
+}
+static int persist_collect(jh_persist* p, const int* rows, int n_rows, unsigned tag, float* h_heads, int r_first, bool block_order, int pf_rows) {
   const int n_out = p->n_out, G = p->G, ld = p->rows_ld, tiles = p->reduced ? 1 : p->tiles;  // (reduced: the device summed the tiles; tile 0's slots hold the answer)
   volatile unsigned* abort_w = p->flag_h;
   // [tiles][G][ld] granules of 16 bytes {out, out, out, tag}: ONE 16-byte load per granule serves the tag check and the sum (the
@@ -613,12 +634,11 @@ static int persist_collect(jh_persist* p, const int* rows, int n_rows, unsigned 
     return JH_OK;
   }
   int missing = n_rows;
-  const int pf_rows = (!rows && p->rows_published > n_rows) ? p->rows_published - n_rows : 0;
   for (int k = 0; k < n_rows; ++k) have[k] = 0;
   for (long spin = 0; spin < 40000000L && missing; ++spin) {
     for (int k = 0; k < n_rows; ++k) {
       if (have[k]) continue;
-      const int wq = rows ? rows[k] : k;
+      const int wq = rows ? rows[k] : r_first + k;
       float acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       bool ok = true;
       for (int t = 0; t < tiles && ok; ++t)
@@ -630,14 +650,15 @@ static int persist_collect(jh_persist* p, const int* rows, int n_rows, unsigned 
           const Gran16* gp = part + ((size_t)t * G + g) * ld + wq;
           if (__atomic_load_n(reinterpret_cast<const unsigned*>(gp) + 3, __ATOMIC_ACQUIRE) != tag) { ok = false; break; }
 #if defined(__x86_64__)
-          // the first read of a two-timestep exchange (rows 0 .. W-1 of 3 W): this workgroup wrote its granules of ALL rows with the same
+          // the first read of a two-timestep exchange (rows 0 .. W-1 of 3 W, or a half's roots): this workgroup wrote its granules of ALL rows with the same
           // store instruction, so the successors' rows of this (tile, g) are in host memory too -- pull them towards the cache now; the
           // second read (the chosen successors, right after the sampling) then finds them there instead of missing 32 times per row
           // (round 5: 3.10 -> 2.92 us per timestep, 0.901 -> 0.882 ms per PPO step; also prefetching the first read's own rows 4 .. 7
           // added nothing: profiles/r05_ab_host_prefetch_ppo.txt)
           if (pf_rows > 0 && k == 0) {
-            const char* q = reinterpret_cast<const char*>(part + ((size_t)t * G + g) * ld + n_rows);
-            for (int b = 0; b < pf_rows * 16; b += 64) _mm_prefetch(q + b, _MM_HINT_T0);
+            const char* q = reinterpret_cast<const char*>(part + ((size_t)t * G + g) * ld + r_first + n_rows);
+            // (every 64-byte line the rows touch: a half of 3 or 5 envs does not start on one)
+            for (int b = -(int)(reinterpret_cast<uintptr_t>(q) & 63); b < pf_rows * 16; b += 64) _mm_prefetch(q + b, _MM_HINT_T0);
           }
 #endif
           alignas(16) unsigned w4[4];
