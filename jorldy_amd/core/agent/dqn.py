@@ -60,7 +60,7 @@ class DQN(NativeValueNetMixin, BaseAgent):
         self.run_step = run_step
         self.lr_decay = lr_decay
         self.clip_grad_norm = None
-        self._stats, self._stats_np = self._mapped_stats(4)
+        self._stats = self._mapped_stats(4)
         self._static = None
         self._learn_graphs = ops.LearnGraphs(f"{type(self).__name__}.learn()")
         self._noise = None
@@ -105,7 +105,6 @@ class DQN(NativeValueNetMixin, BaseAgent):
         from ..buffer.base import h2d_small
 
         st["idx"].copy_(h2d_small(self.memory.sample_indices(self.batch_size).astype(np.int64), self.device))
-        return None
 
     def _idx_offset(self):
         return 0
@@ -137,7 +136,7 @@ class DQN(NativeValueNetMixin, BaseAgent):
         q, next_q, next_target_q = lg[0].view(B, A), lg[1].view(B, A), lg[2].view(B, A)
         g, prio, _ = ops.td_loss(q, next_target_q, tr["action"], tr["reward"], tr["done"], self.gamma, q_next_online=next_q if self._td["double"] else None,
                                  weights=st["w"] if self._td["per"] else None, alpha=getattr(self, "alpha", 0.0),
-                                 n_step=self._td["n_step"] and self.n_step, stats=self._stats)
+                                 n_step=self._td["n_step"] and self.n_step, stats=self._stats.dev)
         side = self._write_back_priorities(st, prio) if self._td["per"] else None
         net.backward(g)
         if self.grad_sync is not None:  # data-parallel learners: one all-reduce of the flat gradient bucket
@@ -154,32 +153,23 @@ class DQN(NativeValueNetMixin, BaseAgent):
             self.reset_graphs()
         st = self._static
         self.memory.flush()  # held per-step stores -> HBM before anything (possibly a replayed graph) reads the ring
-        extra = self._draw(st)
+        self._draw(st)
         graphable = (self.use_graph and (self._noise is None or isinstance(self._noise, str))
                      and (self.grad_sync is None or (self.graph_with_collective and getattr(self.grad_sync, "capturable", True))))
         self._learn_graphs.run("learn", lambda: self._learn_body(st), graphable)
         self.num_learn += 1
         self._adam_steps += 1
-        return extra
 
-    def _learn_stats(self, view, marks, tensor):
-        """Run one learn(); -> (loss statistics, PER statistics or None) as host arrays."""
-        tree_np = getattr(getattr(self.memory, "_tree", None), "stats_np", None) if self._td["per"] else None
-        mapped = view is not None and (not self._td["per"] or tree_np is not None)
-        if mapped:
-            for m in marks:
-                view[m] = -1.0
-        stats64 = self._run_learn()
-        if mapped:
-            self._await_marks(view, marks, type(self).__name__ + ".learn()")
-            # the sampling kernel ran (and ended) in front of the kernels that wrote `view`: its statistics are there too
-            return view.copy(), (tree_np.copy() if self._td["per"] else None)
-        if self._td["per"]:
-            return tuple(self._read_stats(tensor, stats64))
-        return self._read_stats(tensor)[0], None
+    def _learn_stats(self, buf, marks):
+        """Run one learn() whose loss kernel writes `buf` (elements `marks` last); -> (loss statistics, PER statistics or None) as host arrays."""
+        buf.arm(marks)
+        self._run_learn()
+        buf.wait(marks, type(self).__name__ + ".learn(): the statistics")
+        # the sampling kernel ran (and ended) in front of the kernels that wrote `buf`: its statistics are there too
+        return buf.np.copy(), (self.memory._tree.stats_np.copy() if self._td["per"] else None)
 
     def learn(self):
-        s, p = self._learn_stats(self._stats_np, (3,), self._stats)
+        s, p = self._learn_stats(self._stats, (3,))
         result = {"loss": float(s[0]), "epsilon": self.epsilon, "max_Q": float(s[1])}
         if self._td["per"]:
             result.update({"sampled_p": float(p[0]), "mean_p": float(p[1])})
@@ -272,7 +262,7 @@ class PER(DQN):
         self.learn_period_stamp = 0
 
     def _draw(self, st):
-        return self.memory.sample_into(self.beta, self.batch_size, st["idx"], st["w"])
+        self.memory.sample_into(self.beta, self.batch_size, st["idx"], st["w"])
 
     def _idx_offset(self):
         return self.memory.first_leaf_index
@@ -342,7 +332,7 @@ class ApeX(DQN):
         return {"action": action, "q": q}
 
     def _draw(self, st):
-        return self.memory.sample_into(self.beta, self.batch_size, st["idx"], st["w"])
+        self.memory.sample_into(self.beta, self.batch_size, st["idx"], st["w"])
 
     def _idx_offset(self):
         return self.memory.first_leaf_index

@@ -128,14 +128,8 @@ class ICM_PPO(PPO):
         st = super()._alloc_static(M)
         n_upd = st["n_upd"]
         # the ICM's rows {l_f, l_i, 0, mark} and, in row n_upd, mean(r_i) of the pre-pass: a mapped buffer of their own
-        if "stats_pin" in st:
-            pin = ops.PinnedBuffer((n_upd + 1, 4), np.float32, self.device.index)
-            pin.np[:] = 0.0
-            pin.np[n_upd - 1, 3] = -1.0  # arrival marker; set again by _result once a learn() has been read
-            st["icm_pin"] = pin
-            st["icm_stats"] = ops._wrap_device(pin.dev_ptr.value, (n_upd + 1, 4), torch.float32, self.device, owner=pin)
-        else:
-            st["icm_stats"] = torch.zeros(n_upd + 1, 4, dtype=torch.float32, device=self.device)
+        st["icm_pin"] = self._mapped_stats(n_upd + 1, 4)
+        st["icm_stats"] = st["icm_pin"].dev
         return st
 
     def _enqueue_pre(self, st, captured=False):
@@ -159,18 +153,11 @@ class ICM_PPO(PPO):
                            stats=st["icm_stats"][k])
                 k += 1
 
-    def _await_mapped_stats(self, a, n_upd):
-        s = super()._await_mapped_stats(a, n_upd)
-        self._await_marks(self._static["icm_pin"].np, ((n_upd - 1) * 4 + 3,), "ICM_PPO.learn()")  # jh_icm.hip writes [3] last, behind a system-scope fence
-        return s
+    def _stat_marks(self, n_upd):
+        return {**super()._stat_marks(n_upd), "icm_pin": ((n_upd - 1) * 4 + 3,)}  # jh_icm.hip writes [3] last, behind a system-scope fence
 
     def _result(self, s, n_upd):
-        st = self._static
-        if "icm_pin" in st:
-            a = st["icm_pin"].np.astype(np.float64)
-            st["icm_pin"].np[n_upd - 1, 3] = -1.0  # the next learn()'s arrival marker
-        else:
-            a = self._read_stats(st["icm_stats"])[0].astype(np.float64)
+        a = self._static["icm_pin"].np.astype(np.float64)
         result = super()._result(s, n_upd)
         result.update({"r_i": float(a[n_upd, 0]), "l_f": float(a[n_upd - 1, 0]), "l_i": float(a[n_upd - 1, 1])})  # the LAST minibatch's losses (icm_ppo.py:215-216)
         return result

@@ -51,7 +51,7 @@ class IQN(DQN):
         self.sample_max = float(sample_max)
         self._tau_inject = None  # test hook: the tau draws of the next learn() ([3, B, N]) / act() ([rows, N]) instead of torch.rand
         super().__init__(state_size, action_size, network=network, head=head, optim_config=optim_config, **kwargs)
-        self._stats8, self._stats8_np = self._mapped_stats(8)
+        self._stats8 = self._mapped_stats(8)
 
     # ---- the construction hooks of DQN / NativeValueNetMixin: the network is IQN's own, no q-network is built and thrown away (iqn.py:41-49 does)
     def _require_native(self, backend, network, head, state_size, hidden_size, optim_config):
@@ -105,24 +105,23 @@ class IQN(DQN):
     def _draw(self, st):
         """The sampled rows, then the three tau sets of this learn() (iqn.py:90, 100, 103: one uniform draw per forward), eagerly into the
         static buffer the captured body reads: a replayed graph sees fresh draws."""
-        extra = super()._draw(st)
+        super()._draw(st)
         if self._tau_inject is not None:
             st["tau"].copy_(torch.as_tensor(self._tau_inject).to(self.device, torch.float32).reshape(st["tau"].shape))
         else:
             torch.rand(st["tau"].shape, out=st["tau"])
-        return extra
 
     def _learn_body(self, st):
         B = self.batch_size
         net = self._net
         tr = self.memory.gather(st["idx"], as_float=self._as_float(), out=st["tr"])
         lg = net.learn_forward(st["x_all"], B, st["tau"], st["logits"])
-        g, _ = ops.iqn_loss(lg[0], lg[1], lg[2], tr["action"], tr["reward"], tr["done"], st["tau"][0], self.gamma, stats=self._stats8)
+        g, _ = ops.iqn_loss(lg[0], lg[1], lg[2], tr["action"], tr["reward"], tr["done"], st["tau"][0], self.gamma, stats=self._stats8.dev)
         net.backward(g)
         if self.grad_sync is not None:
             self.grad_sync.reduce_flat(net.grads)
         net.optim_step(self._opt_name, self.clip_grad_norm)
 
     def learn(self):
-        s, _ = self._learn_stats(self._stats8_np, (5, 7), self._stats8)
+        s, _ = self._learn_stats(self._stats8, (5, 7))
         return {"loss": float(s[0]), "epsilon": self.epsilon, "max_Q": float(s[1]), "max_logit": float(s[2]), "min_logit": float(s[3])}

@@ -32,12 +32,12 @@ class MDQN(DQN):
         tr = self.memory.gather(st["idx"], as_float=self._as_float(), out=st["tr"])
         lg = net.learn_forward_m(st["x_all"], B, None, st["logits"])  # online(s), target(s), target(s') in shared launches
         g, _ = ops.mdqn_loss(lg[0].view(B, A), lg[1].view(B, A), lg[2].view(B, A), tr["action"], tr["reward"], tr["done"], self.gamma, self.alpha, self.tau,
-                             self.l_0, stats=self._stats)
+                             self.l_0, stats=self._stats.dev)
         net.backward(g)
         if self.grad_sync is not None:  # data-parallel learners: one all-reduce of the flat gradient bucket
             self.grad_sync.reduce_flat(net.grads)
         net.optim_step(self._opt_name, self.clip_grad_norm)
 
     def learn(self):
-        s, _ = self._learn_stats(self._stats_np, (3,), self._stats)
+        s, _ = self._learn_stats(self._stats, (3,))
         return {"loss": float(s[0]), "epsilon": self.epsilon, "max_Q": float(s[1])}

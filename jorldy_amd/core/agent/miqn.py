@@ -28,7 +28,7 @@ class MIQN(IQN):
         net = self._net
         tr = self.memory.gather(st["idx"], as_float=self._as_float(), out=st["tr"])
         lg = net.learn_forward_m(st["x_all"], B, st["tau"], st["logits"])
-        g, _ = ops.miqn_loss(lg[0], lg[1], lg[2], tr["action"], tr["reward"], tr["done"], st["tau"][0], self.gamma, self.alpha, self.tau, self.l_0, stats=self._stats8)
+        g, _ = ops.miqn_loss(lg[0], lg[1], lg[2], tr["action"], tr["reward"], tr["done"], st["tau"][0], self.gamma, self.alpha, self.tau, self.l_0, stats=self._stats8.dev)
         net.backward(g)
         if self.grad_sync is not None:
             self.grad_sync.reduce_flat(net.grads)

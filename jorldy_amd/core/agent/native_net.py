@@ -7,7 +7,6 @@ import os
 import numpy as np
 import torch
 
-from ... import _lib as L
 from ... import ops
 from ..optimizer import Optimizer
 
@@ -131,7 +130,7 @@ class NativeValueNetMixin:
     def _act_greedy(self, state, is_train=False):
         """The network branch of act() (dqn.py:100-115, rainbow.py:140-152) without torch in the loop: observations -> pinned slab -> one
         async H2D -> forward of the live online network -> jh_value_act (Q from the outputs, first-maximum argmax) writing the actions
-        into device-mapped memory -> the host waits for their arrival (jh_host_wait_words).  The generic form -- as_tensor (a pageable,
+        into device-mapped memory -> the host waits for their arrival (ops.PinnedBuffer.wait).  The generic form -- as_tensor (a pageable,
         synchronous copy), five torch kernels for logits2Q + argmax, `.cpu()` -- was most of a single-mode env step.
         Rainbow in training mode draws its noise exactly as NativeNet.__call__ does (torch.randn on the device: the same stream of
         draws).  -> int64 [N, 1]; None when this form does not apply (list-valued states, more rows than the network's batch)."""
@@ -155,23 +154,17 @@ class NativeValueNetMixin:
         a = self.__dict__.get("_actbuf")
         if a is None or a["key"] != key:
             dt = torch.uint8 if u8 else torch.float32
-            am, qm = ops.PinnedBuffer((N,), np.int64, self.device.index), ops.PinnedBuffer((N,), np.float32, self.device.index)
             a = dict(key=key, x_pin=torch.empty((N,) + tuple(x.shape[1:]), dtype=dt, pin_memory=True), x_dev=torch.empty((N,) + tuple(x.shape[1:]), dtype=dt, device=self.device),
-                     logits=torch.empty(N, net.A, net.K, dtype=torch.float32, device=self.device), am=am, qm=qm,  # (viewed [N, A, K] for the act kernel)
-                     act_dev=ops._wrap_device(am.dev_ptr.value, (N,), torch.int64, self.device, owner=am),
-                     q_dev=ops._wrap_device(qm.dev_ptr.value, (N,), torch.float32, self.device, owner=qm), words=am.np.view(np.uint32),
-                     marks=np.arange(0, 2 * N, 2, dtype=np.int32))  # low words of the int64 actions
+                     logits=torch.empty(N, net.A, net.K, dtype=torch.float32, device=self.device),  # (viewed [N, A, K] for the act kernel)
+                     am=ops.PinnedBuffer((N,), np.int64, self.device), qm=ops.PinnedBuffer((N,), np.float32, self.device))
             self._actbuf = a
         np.copyto(a["x_pin"].numpy(), x, casting="same_kind")
         a["x_dev"].copy_(a["x_pin"], non_blocking=True)
         nz = torch.randn(net.noise_len, device=net.device) if (net.noise_len > 0 and is_train) else None
         net.forward(a["x_dev"], 0, nz, out=a["logits"])
-        a["am"].np[:] = -1  # arrival marks (actions are >= 0)
-        self._act_kernel(a["logits"].view(N, A, K), (a["act_dev"], a["q_dev"]))
-        if L.load().jh_host_wait_words(L.ptr(a["words"]), L.ptr(a["marks"]), N, 0xFFFFFFFF, 5.0) != 0:
-            torch.cuda.current_stream(self.device).synchronize()
-            if (a["am"].np < 0).any():
-                raise RuntimeError("act(): the actions never arrived (failed launch?)")
+        a["am"].arm()
+        self._act_kernel(a["logits"].view(N, A, K), (a["am"].dev, a["qm"].dev))
+        a["am"].wait(what="act(): the actions", timeout_s=ops.ACT_WAIT_S)
         return a["am"].np.reshape(N, 1).copy()
 
     def _act_kernel(self, logits, out):

@@ -29,7 +29,7 @@ class Noisy(NoiseDrawMixin, DQN):
                  **kwargs):
         self.noise_type = noise_type
         super().__init__(state_size, action_size, hidden_size=hidden_size, network=network, head=head, optim_config=optim_config, **kwargs)
-        self._stats8, self._stats8_np = self._mapped_stats(8)  # [0:4] jh_td_loss's, [4:6] the sigma means (written last)
+        self._stats8 = self._mapped_stats(8)  # [0:4] jh_td_loss's, [4:6] the sigma means (written last)
 
     def _require_native(self, backend, network, head, state_size, hidden_size, optim_config):
         if backend not in (None, "auto", "native"):
@@ -77,15 +77,15 @@ class Noisy(NoiseDrawMixin, DQN):
         tr = self.memory.gather(st["idx"], idx_offset=0, as_float=self._as_float(), out=st["tr"])
         self._draw_noise(st)
         lg = net.learn_forward_n(st["x_all"], B, st["noise"], st["logits"])  # online(s; noise 0), target(s'; noise 1)
-        g, _, _ = ops.td_loss(lg[0].view(B, A), lg[1].view(B, A), tr["action"], tr["reward"], tr["done"], self.gamma, stats=self._stats8[:4])
+        g, _, _ = ops.td_loss(lg[0].view(B, A), lg[1].view(B, A), tr["action"], tr["reward"], tr["done"], self.gamma, stats=self._stats8.dev[:4])
         net.backward(g, defer=self.grad_sync is None)  # d(sig) = d(mu) * eps and conv1's partial sums wait for the optimizer step
         if self.grad_sync is not None:  # data-parallel learners: one all-reduce of the flat gradient bucket
             self.grad_sync.reduce_flat(net.grads)
         net.optim_step(self._opt_name, self.clip_grad_norm)
-        net.sig_abs_mean(self._stats8[4:6])  # after the step, like the reference (noisy.py:113)
+        net.sig_abs_mean(self._stats8.dev[4:6])  # after the step, like the reference (noisy.py:113)
 
     def learn(self):
-        s, _ = self._learn_stats(self._stats8_np, (5,), self._stats8)
+        s, _ = self._learn_stats(self._stats8, (5,))
         return {"loss": float(s[0]), "max_Q": float(s[1]), "sig_w1": float(s[4]), "sig_w2": float(s[5])}
 
     def process(self, transitions, step):

@@ -208,17 +208,13 @@ class PPO(BaseAgent):
             h0=h0_all[:M], h1=h1_all[:M] if cont else None, value=v_all[:M], nh0=h0_all[M:], nh1=h1_all[M:] if cont else None, next_value=v_all[M:],
             logp_old=f(M, A if cont else 1), adv=f(M, 1), ret=f(M, 1),
             mb_h0=f(B, A), mb_h1=f(B, A) if cont else None, mb_v=f(B, 1),
-            stats=torch.zeros(n_upd + 1, 8, dtype=torch.float32, device=self.device),
-        )
-        if os.environ.get("JH_PPO_MAPPED_STATS", "1") == "1":
             # the [n_upd + 1][8] statistics live in device-MAPPED pinned host memory: the loss kernels write them across
             # PCIe themselves (32 bytes per update, flushed when the kernel ends), and learn() waits for the last row to
             # arrive instead of for the stream -- no D2H copy, no hipStreamSynchronize wake-up, and the host is already
             # preparing the next rollout while the last backward + Adam are still running (stream order keeps that correct)
-            pin = ops.PinnedBuffer((n_upd + 1, 8), np.float32, self.device.index)
-            pin.np[:] = 0.0
-            st["stats_pin"] = pin
-            st["stats"] = ops._wrap_device(pin.dev_ptr.value, (n_upd + 1, 8), torch.float32, self.device, owner=pin)
+            stats_pin=self._mapped_stats(n_upd + 1, 8),
+        )
+        st["stats"], st["marks"] = st["stats_pin"].dev, self._stat_marks(n_upd)  # what the kernels write, what learn() arms and awaits
         # rows of every minibatch of every epoch, gathered once per learn() (jh_ppo_minibatch_rows) when all
         # minibatches take the four- / five-launch update
         E = self.n_epoch
@@ -228,13 +224,15 @@ class PPO(BaseAgent):
             st["rows"] = ops.MinibatchRows(srcs, st["mb"])
         # the epochs' index lists are drawn straight into pinned memory (two buffers: the next learn()'s lists are drawn and
         # uploaded while this one's may still be in flight)
-        st["idx_pin"] = [ops.PinnedBuffer((self.n_epoch * M,), np.int64, self.device.index) for _ in range(2)]  # device-mapped: a kernel may read them in place
-        st["idx_alias"] = [ops._wrap_device(p.dev_ptr.value, (self.n_epoch * M,), torch.int64, self.device, owner=p) for p in st["idx_pin"]]
+        self._alloc_idx_lists(st, E * M)
+        self._stats = st["stats"]
+        return st
+
+    def _alloc_idx_lists(self, st, n):
+        st["idx_pin"] = [ops.PinnedBuffer((n,), np.int64, self.device) for _ in range(2)]  # device-mapped: a kernel may read them in place
         st["idx_ev"] = [None, None]
         st["idx_k"] = 0
         st["idx_ready"] = False  # st["idx"] already holds the (pre-drawn, uploaded) lists of the coming learn()
-        self._stats = st["stats"]
-        return st
 
     def _capture_targets(self, M):
         """Device tensors the collector's acting-time capture writes for a rollout of M rows (raw policy head(s), V(s), V(s'))."""
@@ -271,7 +269,7 @@ class PPO(BaseAgent):
             self._ride_wait["idx"] = k
             return True
         self._ride_wait.pop("idx", None)
-        st["idx"].copy_(st["idx_alias"][k])
+        st["idx"].copy_(st["idx_pin"][k].dev)
         ev = torch.cuda.Event()
         ev.record()
         st["idx_ev"][k] = ev
@@ -419,7 +417,7 @@ class PPO(BaseAgent):
             if "lr" in self._ride_wait:
                 self._net.set_lr(float(self._lr_word.np[0]))
             if "idx" in self._ride_wait and st["idx_ready"]:
-                st["idx"].copy_(st["idx_alias"][self._ride_wait["idx"]])
+                st["idx"].copy_(st["idx_pin"][self._ride_wait["idx"]].dev)
         self._ride_wait.clear()
 
         def shuffles():
@@ -427,10 +425,8 @@ class PPO(BaseAgent):
             # (np_rng.epoch_shuffles) straight into pinned memory, uploaded at once
             self._upload_idx(st, lambda out: np_rng.epoch_shuffles(M, E, out))
 
-        pin = st.get("stats_pin")
-        if pin is not None:  # arrival markers: one element of EACH 16-byte granule of the last update's row (critic and c2: means of squares, never -1)
-            pin.np[st["n_upd"] - 1, 2] = -1.0
-            pin.np[st["n_upd"] - 1, 7] = -1.0
+        for key, marks in st["marks"].items():  # arrival markers, before anything that writes them is enqueued
+            st[key].arm(marks)
         graphable = (self.use_graph and not ops._PROF["on"]
                      and (self.grad_sync is None or (self.graph_with_collective and getattr(self.grad_sync, "capturable", True))))
         # index lists: pre-drawn behind the previous learn() and already uploaded (np_rng.Predraw) when np.random has not been
@@ -460,10 +456,10 @@ class PPO(BaseAgent):
             lg.warm.add(key)
         self.memory._store.clear()
         self._adam_steps += st["n_upd"]
-        self._launched = (st, pin, M, E)
+        self._launched = (st, M, E)
 
     def _learn_finish(self):
-        st, pin, M, E = self._launched
+        st, M, E = self._launched
         self._launched = None
         # ---- behind the launches, while the GPU works: next learning rate, next index lists, the next rollout's acting kernel
         if self._lr_step is not None:
@@ -475,16 +471,14 @@ class PPO(BaseAgent):
         hook, self._post_launch_hook = self._post_launch_hook, None
         if hook is not None:
             hook()
-        if pin is not None:
-            s = self._await_mapped_stats(pin.np, st["n_upd"])
-        else:
-            s = self._read_stats(st["stats"])[0].astype(np.float64)  # the only host sync of learn()
-        return self._result(s, st["n_upd"])
+        for key, marks in st["marks"].items():  # until the last loss kernel's row has landed in the mapped host buffer
+            st[key].wait(marks, type(self).__name__ + ".learn(): the statistics")
+        return self._result(st["stats_pin"].np.astype(np.float64), st["n_upd"])
 
-    def _await_mapped_stats(self, a, n_upd):
-        """Wait until the last loss kernel's row has landed in the mapped host buffer (BaseAgent._await_marks)."""
-        self._await_marks(a, ((n_upd - 1) * 8 + 2, (n_upd - 1) * 8 + 7), "PPO.learn()")  # jh_ppo.hip: jh_ppo_stats_row
-        return a.astype(np.float64)
+    def _stat_marks(self, n_upd):
+        """{statistics buffer of _static: the flat elements its last kernel writes last} -- armed before learn()'s launches, awaited after.
+        jh_ppo.hip (jh_ppo_stats_row): one element of EACH 16-byte granule of the last update's row (critic and c2: means of squares, never -1)."""
+        return {"stats_pin": ((n_upd - 1) * 8 + 2, (n_upd - 1) * 8 + 7)}
 
     def learning_rate_decay(self, step, optimizers=None, mode="cosine"):
         super().learning_rate_decay(step, optimizers, mode)
@@ -492,7 +486,7 @@ class PPO(BaseAgent):
             lr = self.optimizer.param_groups[0]["lr"]
             if self._ride is not None and self._lr_step is not None:  # from inside learn(): the next run's commit launch delivers it
                 if self._lr_word is None:
-                    self._lr_word = ops.PinnedBuffer((1,), np.float32, self.device.index)
+                    self._lr_word = ops.PinnedBuffer((1,), np.float32, self.device)
                 self._lr_word.np[0] = lr
                 self._ride.ride_along(1, self._lr_word.dev_ptr.value, self._net.hyper_ptr(), 4, keep=(self._lr_word, self._net))
                 self._ride_wait["lr"] = True

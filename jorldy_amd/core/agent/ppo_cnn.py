@@ -3,7 +3,6 @@ import os
 import numpy as np
 import torch
 
-from ... import _lib as L
 from ... import np_rng, ops
 from ..buffer import RolloutBuffer
 from ..network import Network
@@ -101,23 +100,17 @@ class PPOConv(NativeValueNetMixin, PPO):
         a = self.__dict__.get("_actbuf")
         if a is None or a["key"] != key:
             dt = torch.uint8 if key[2] else torch.float32
-            am = ops.PinnedBuffer((N,), np.int64, self.device.index)
             a = dict(key=key, x_pin=torch.empty((N,) + key[1], dtype=dt, pin_memory=True), x_dev=torch.empty((N,) + key[1], dtype=dt, device=self.device),
-                     heads=torch.empty(N, net.A, dtype=torch.float32, device=self.device), am=am,
-                     act_dev=ops._wrap_device(am.dev_ptr.value, (N,), torch.int64, self.device, owner=am), words=am.np.view(np.uint32),
-                     marks=np.arange(0, 2 * N, 2, dtype=np.int32))
+                     heads=torch.empty(N, net.A, dtype=torch.float32, device=self.device), am=ops.PinnedBuffer((N,), np.int64, self.device))
             self._actbuf = a
         np.copyto(a["x_pin"].numpy(), x)
         a["x_dev"].copy_(a["x_pin"], non_blocking=True)
         for o in range(0, N, net.maxB):
             net.forward(a["x_dev"][o : o + net.maxB], 0, None, out=a["heads"][o : o + net.maxB])
-        a["am"].np[:] = -1  # arrival marks (actions are >= 0)
-        ops.policy_act_discrete(a["heads"], net.n_actions, self._seed, self._act_ctr, training, a["act_dev"])
+        a["am"].arm()
+        ops.policy_act_discrete(a["heads"], net.n_actions, self._seed, self._act_ctr, training, a["am"].dev)
         self._act_ctr += 1
-        if L.load().jh_host_wait_words(L.ptr(a["words"]), L.ptr(a["marks"]), N, 0xFFFFFFFF, 5.0) != 0:
-            torch.cuda.current_stream(self.device).synchronize()
-            if (a["am"].np < 0).any():
-                raise RuntimeError("act(): the actions never arrived (failed launch?)")
+        a["am"].wait(what="act(): the actions", timeout_s=ops.ACT_WAIT_S)
         return {"action": a["am"].np.reshape(N, 1).copy()}
 
     # ---------------------------------------------------------------------------------- learn
@@ -133,9 +126,7 @@ class PPOConv(NativeValueNetMixin, PPO):
                   packed=f(2 * M, net.A), h0=f(2 * M, net.n_actions), v=f(2 * M), logp_old=f(M, 1), adv=f(M, 1), ret=f(M, 1),
                   x_mb=torch.empty((B,) + frame, dtype=dt, device=self.device), heads_mb=f(B, net.A), grad_mb=torch.zeros(B, net.A, dtype=torch.float32, device=self.device),
                   stats=torch.zeros(n_upd + 1, 8, dtype=torch.float32, device=self.device), dp_work=torch.zeros(n_upd, B + 16, dtype=torch.float32, device=self.device))
-        st["idx_pin"] = [ops.PinnedBuffer((E * M,), np.int64, self.device.index) for _ in range(2)]
-        st["idx_alias"] = [ops._wrap_device(p.dev_ptr.value, (E * M,), torch.int64, self.device, owner=p) for p in st["idx_pin"]]
-        st["idx_ev"], st["idx_k"], st["idx_ready"] = [None, None], 0, False
+        self._alloc_idx_lists(st, E * M)
         self._stats = st["stats"]
         return st
 

@@ -43,7 +43,7 @@ class QRDQN(DQN):
         self.num_support = num_support
         self.tau = tau.to(self.device).view(1, num_support)
         self.inv_tau = 1 - self.tau
-        self._stats8, self._stats8_np = self._mapped_stats(8)
+        self._stats8 = self._mapped_stats(8)
 
     def logits2Q(self, logits):
         _logits = logits.view(logits.shape[0], self.action_size, self.num_support)
@@ -72,12 +72,12 @@ class QRDQN(DQN):
         tr = self.memory.gather(st["idx"], as_float=self._as_float(), out=st["tr"])
         lg = net.learn_forward(st["x_all"], B, None, st["logits"])
         g, _ = ops.qr_loss(lg[0].view(B, A, N), lg[1].view(B, A, N), lg[2].view(B, A, N), tr["action"], tr["reward"], tr["done"], self.tau, self.gamma,
-                           stats=self._stats8)
+                           stats=self._stats8.dev)
         net.backward(g.view(B, A * N))
         if self.grad_sync is not None:
             self.grad_sync.reduce_flat(net.grads)
         net.optim_step(self._opt_name, self.clip_grad_norm)
 
     def learn(self):
-        s, _ = self._learn_stats(self._stats8_np, (5, 7), self._stats8)
+        s, _ = self._learn_stats(self._stats8, (5, 7))
         return {"loss": float(s[0]), "epsilon": self.epsilon, "max_Q": float(s[1]), "max_logit": float(s[2]), "min_logit": float(s[3])}

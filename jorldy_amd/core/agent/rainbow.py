@@ -21,7 +21,7 @@ class C51(DQN):
         self.v_min, self.v_max, self.num_support = v_min, v_max, num_support
         self.delta_z = (v_max - v_min) / (num_support - 1)
         self.z = torch.linspace(v_min, v_max, num_support, device=self.device).view(1, -1)
-        self._stats8, self._stats8_np = self._mapped_stats(8)
+        self._stats8 = self._mapped_stats(8)
 
     def logits2Q(self, logits):
         _logits = logits.view(logits.shape[0], self.action_size, self.num_support)
@@ -49,14 +49,14 @@ class C51(DQN):
         tr = self.memory.gather(st["idx"], as_float=self._as_float(), out=st["tr"])
         lg = net.learn_forward(st["x_all"], B, None, st["logits"])
         g, _, _, _ = ops.c51_loss(lg[0].view(B, A, K), lg[2].view(B, A, K), tr["action"], tr["reward"], tr["done"], self.v_min, self.v_max, self.gamma,
-                                  shift_max=True, stats=self._stats8)
+                                  shift_max=True, stats=self._stats8.dev)
         net.backward(g.view(B, A * K))
         if self.grad_sync is not None:
             self.grad_sync.reduce_flat(net.grads)
         net.optim_step(self._opt_name, self.clip_grad_norm)
 
     def learn(self):
-        s, _ = self._learn_stats(self._stats8_np, (5, 7), self._stats8)
+        s, _ = self._learn_stats(self._stats8, (5, 7))
         return {"loss": float(s[0]), "epsilon": self.epsilon, "max_Q": float(s[1]), "max_logit": float(s[2]), "min_logit": float(s[3])}
 
 
@@ -113,8 +113,8 @@ class Rainbow(NoiseDrawMixin, DQN):
         self.delta_z = (v_max - v_min) / (num_support - 1)
         self.z = torch.linspace(v_min, v_max, num_support, device=self.device).view(1, -1)
         self.epsilon = 0.0
-        self._stats8, self._stats8_np = self._mapped_stats(8)
-        self._stats, self._stats_np = self._mapped_stats(4)
+        self._stats8 = self._mapped_stats(8)
+        self._stats = self._mapped_stats(4)
         self._noise = None  # parity tests inject the Gaussian draws here (a list forces the eager path; "static" = already in st["noise"], graph allowed)
 
     def logits2Q(self, logits):
@@ -136,7 +136,7 @@ class Rainbow(NoiseDrawMixin, DQN):
         return {"action": action}
 
     def _draw(self, st):
-        return self.memory.sample_into(self.beta, self.batch_size, st["idx"], st["w"])
+        self.memory.sample_into(self.beta, self.batch_size, st["idx"], st["w"])
 
     def _idx_offset(self):
         return self.memory.first_leaf_index
@@ -164,7 +164,7 @@ class Rainbow(NoiseDrawMixin, DQN):
             net.learn_heads_raw(B, st["noise"])
             self.memory.flush()
             net.c51_step(self.memory._tree, st["idx"], tr["action"], tr["reward"], tr["done"], st["w"], self.v_min, self.v_max, self.gamma, self.alpha,
-                         self.n_step, st["logits"], stats=self._stats8)
+                         self.n_step, st["logits"], stats=self._stats8.dev)
             # d(sigma) = d(mu) * eps and conv1's partial sums ride in the optimizer's pass unless somebody reads the bucket first
             net.backward(None, defer=self.grad_sync is None)
             if self.grad_sync is not None:
@@ -173,7 +173,7 @@ class Rainbow(NoiseDrawMixin, DQN):
             return
         lg = net.learn_heads(B, st["noise"], st["logits"])
         g, prio, _, _ = ops.c51_loss(lg[0], lg[2], tr["action"], tr["reward"], tr["done"], self.v_min, self.v_max, self.gamma,
-                                     next_logit_online=lg[1], weights=st["w"], alpha=self.alpha, n_step=self.n_step, stats=self._stats8)
+                                     next_logit_online=lg[1], weights=st["w"], alpha=self.alpha, n_step=self.n_step, stats=self._stats8.dev)
         side = self._write_back_priorities(st, prio)  # rainbow.py:230-231; branch 2: beside the backward pass + optimizer
         net.backward(g)
         if self.grad_sync is not None:  # data-parallel learners: one all-reduce of the flat gradient bucket
@@ -183,7 +183,7 @@ class Rainbow(NoiseDrawMixin, DQN):
             torch.cuda.current_stream().wait_stream(side)
 
     def learn(self):
-        s, p = self._learn_stats(self._stats8_np, (5, 7), self._stats8)
+        s, p = self._learn_stats(self._stats8, (5, 7))
         return {"loss": float(s[0]), "beta": self.beta, "max_Q": float(s[1]), "max_logit": float(s[2]), "min_logit": float(s[3]),
                 "sampled_p": float(p[0]), "mean_p": float(p[1])}
 

@@ -100,9 +100,9 @@ class SAC(DeterministicActorCritic):
     def _learn_body(self, st, actor_step, soft):
         B, net = self.batch_size, self._net
         tr = self.memory.gather(st["idx"], as_float=True, out=st["tr"])
-        net.critic_update(st["x_all"], tr["action"], tr["reward"], tr["done"], st["noise"][0], self.gamma, self._stats, y=st["y"], q=st["q"], a_next=st["a_next"],
+        net.critic_update(st["x_all"], tr["action"], tr["reward"], tr["done"], st["noise"][0], self.gamma, self._stats.dev, y=st["y"], q=st["q"], a_next=st["a_next"],
                           logp_next=st["logp_next"])
-        net.actor_update(st["x_all"][:B], st["noise"][1], self._stats[4:10], action=st["a_pred"], logp=st["logp"], q=st["q_pi"])
+        net.actor_update(st["x_all"][:B], st["noise"][1], self._stats.dev[4:10], action=st["a_pred"], logp=st["logp"], q=st["q_pi"])
         if soft:
             net.soft_update(self.tau)
 

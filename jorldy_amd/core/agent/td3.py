@@ -123,7 +123,7 @@ class DeterministicActorCritic(BaseAgent):
         self.run_step = run_step
         self.lr_decay = lr_decay
         self._noise_inject = None  # test hook: the standard normals of the next learn() ([B, A]; SAC [2, B, A]) instead of torch.randn
-        self._stats, self._stats_np = self._mapped_stats(self.N_STATS)  # critic: loss_1, loss_2, max_Q, mark; then the actor update's, its mark last
+        self._stats = self._mapped_stats(self.N_STATS)  # critic: loss_1, loss_2, max_Q, mark; then the actor update's, its mark last
         self._static, self._learn_graphs = None, ops.LearnGraphs(f"{type(self).__name__}.learn()")
 
     # ------------------------------------------------------------------------------------------ acting
@@ -159,9 +159,9 @@ class DeterministicActorCritic(BaseAgent):
         B, net = self.batch_size, self._net
         tr = self.memory.gather(st["idx"], as_float=True, out=st["tr"])
         net.critic_update(st["x_all"], tr["action"], tr["reward"], tr["done"], st["noise"] if self.TARGET_NOISE else None, self.gamma,
-                          self.target_noise_std, self.target_noise_clip, self._stats, y=st["y"], q=st["q"])
+                          self.target_noise_std, self.target_noise_clip, self._stats.dev, y=st["y"], q=st["q"])
         if actor_step:
-            net.actor_update(st["x_all"][:B], self._stats[4:6], action_pred=st["a_pred"])
+            net.actor_update(st["x_all"][:B], self._stats.dev[4:6], action_pred=st["a_pred"])
         if soft:
             net.soft_update(self.tau)
 
@@ -181,15 +181,10 @@ class DeterministicActorCritic(BaseAgent):
 
     def _learn_stats(self, actor_step, soft, capture=True):
         marks = (3, self.ACTOR_MARK) if actor_step else (3,)
-        view = self._stats_np
-        if view is not None:
-            for m in marks:
-                view[m] = -1.0
+        self._stats.arm(marks)
         self._run_learn(actor_step, soft, capture)
-        if view is not None:
-            self._await_marks(view, marks, type(self).__name__ + ".learn()")
-            return view.copy()
-        return self._read_stats(self._stats)[0].copy()
+        self._stats.wait(marks, type(self).__name__ + ".learn(): the statistics")
+        return self._stats.np.copy()
 
     def learning_rate_decay(self, step, optimizers=None, mode="cosine"):
         """base.py:93-111 on the actor's and the critics' optimizers: one weight for both (td3.py:219-226)."""

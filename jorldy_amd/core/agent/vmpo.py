@@ -99,9 +99,8 @@ class VMPO(PPO):
         return {"actor_loss": np.mean(s[:n_upd, 0]), "critic_loss": np.mean(s[:n_upd, 1]), "eta_loss": np.mean(s[:n_upd, 2]), "alpha_loss": np.mean(s[:n_upd, 3]),
                 "eta": float(s[n_upd - 1, 4]), "alpha_mu": float(s[n_upd - 1, 5]), "alpha_sigma": float(s[n_upd - 1, 6])}
 
-    def _await_mapped_stats(self, a, n_upd):
-        self._await_marks(a, ((n_upd - 1) * 8 + 7,), "VMPO.learn()")  # jh_vmpo.hip writes [7] last, behind a system-scope fence
-        return a.astype(np.float64)
+    def _stat_marks(self, n_upd):
+        return {"stats_pin": ((n_upd - 1) * 8 + 7,)}  # jh_vmpo.hip writes [7] last, behind a system-scope fence
 
     def _enqueue_pre(self, st, captured=False):
         """vmpo.py:111-153 without log pi_old and without ret."""

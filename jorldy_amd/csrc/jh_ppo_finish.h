@@ -6,7 +6,7 @@
 #define PPO_NPART 6
 
 // One statistics row [8] = two 16-byte granules {loss, actor, critic, entropy} | {max_ratio, min_prob, c1, c2}.  The host may be
-// spinning on the row in device-mapped memory (the last update of a learn(), core/agent/ppo.py: _await_mapped_stats): it waits for
+// spinning on the row in device-mapped memory (the last update of a learn(), core/agent/ppo.py: _stat_marks): it waits for
 // ONE element of EACH granule to change -- critic [2] and c2 [7], means of squares, never the -1 the host arms them with -- and each
 // granule is one 16-byte store, which lands whole (MI355X_MICROARCH.md, hand-off granules).  Rounds 1-4 wrote eight scalars with a
 // __threadfence_system() in front of [7]: an L2 write-back + invalidate (~2-3.5 us) on the critical path of EVERY minibatch's loss

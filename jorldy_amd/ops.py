@@ -324,15 +324,8 @@ class SumTree:
         L.check(self.lib.jh_per_create(self.ctx, self.capacity, self.usp, C.byref(self.h)))
         # {sampled_p, mean_p, root, max_w} of the last sample: device-mapped pinned memory, so that a learner can read
         # them without a copy + stream sync once it knows the sampling kernel has finished (`stats_np`)
-        import os
-
-        if os.environ.get("JH_MAPPED_STATS", "1") == "1":
-            self._stats_pin = PinnedBuffer((4,), np.float64, self.device.index)
-            self._stats_pin.np[:] = 0
-            self._stats = _wrap_device(self._stats_pin.dev_ptr.value, (4,), torch.float64, self.device, owner=self._stats_pin)
-            self.stats_np = self._stats_pin.np
-        else:
-            self._stats, self.stats_np = torch.zeros(4, dtype=torch.float64, device=self.device), None
+        self._stats = PinnedBuffer((4,), np.float64, self.device)
+        self.stats_np = self._stats.np
 
     def __del__(self):
         try:
@@ -373,8 +366,8 @@ class SumTree:
         w64 = torch.empty(B, dtype=torch.float64, device=self.device) if want_w64 else None
         w32 = torch.empty(B, dtype=torch.float32, device=self.device) if out_w32 is None else out_w32
         assert idx.numel() == B and w32.numel() == B
-        L.check(self.lib.jh_per_sample(self.h, B, float(beta), int(uniform_slot.size), L.ptr(uniform_slot), L.ptr(u), L.ptr(idx), L.ptr(w64), L.ptr(w32), L.ptr(self._stats), L.stream_ptr()))
-        return idx, w64, w32, self._stats
+        L.check(self.lib.jh_per_sample(self.h, B, float(beta), int(uniform_slot.size), L.ptr(uniform_slot), L.ptr(u), L.ptr(idx), L.ptr(w64), L.ptr(w32), L.ptr(self._stats.dev), L.stream_ptr()))
+        return idx, w64, w32, self._stats.dev
 
     def shard_stats(self, B, out3):
         """out3 (float64 [3], device) <- {root, count, min priority of the last sample of B}."""
@@ -666,28 +659,76 @@ def mpo_loss_discrete(la, la_next, la_old, q, qt, qt_next, action, reward, done,
 
 
 # ============================================================================= native policy-value MLP
-class PinnedBuffer:
-    """Pinned host memory mapped into the device address space (jh_pinned_alloc): `.np` is the host
-    view, `.dev_ptr` the address kernels use."""
+class _PinnedBlock:
+    """One jh_pinned_alloc allocation, freed when the last reference goes: a PinnedBuffer and the holder of its device alias
+    each keep one, neither keeps the other (no reference cycle, so plain reference counting releases the block)."""
 
-    def __init__(self, shape, dtype, device_index=None):
+    def __init__(self, device_index, nbytes):
         self.lib = L.load()
-        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        h, d = C.c_void_p(), C.c_void_p()
-        L.check(self.lib.jh_pinned_alloc(L.ctx(device_index), max(n, 8), C.byref(h), C.byref(d)))
-        self._h = h
-        self.dev_ptr = C.c_void_p(d.value)
-        buf = (C.c_char * max(n, 8)).from_address(h.value)
-        self.np = np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
+        self.host, self.dev = C.c_void_p(), C.c_void_p()
+        L.check(self.lib.jh_pinned_alloc(L.ctx(device_index), nbytes, C.byref(self.host), C.byref(self.dev)))
 
     def __del__(self):
         try:
-            if getattr(self, "_h", None):
-                self.np = None
-                self.lib.jh_pinned_free(self._h)
-                self._h = None
+            if getattr(self, "host", None):
+                self.lib.jh_pinned_free(self.host)
+                self.host = None
         except Exception:
             pass
+
+
+STATS_WAIT_S, ACT_WAIT_S = 2.0, 5.0  # bounds of PinnedBuffer.wait: learn() statistics, per-env-step actions
+
+
+class PinnedBuffer:
+    """Pinned host memory mapped into the device address space (jh_pinned_alloc), zero-filled: `.np` is the host view, `.dev` the
+    CUDA tensor aliasing it for the kernels, `.dev_ptr` its raw device address.
+
+    Small results come back through it without a D2H copy or a hipStreamSynchronize wake-up: the host arms the elements that the
+    finishing kernel writes last (behind a system-scope fence) with a sentinel BEFORE it enqueues the launch, and waits for the
+    sentinels to go; everything it enqueues meanwhile is stream-ordered behind that kernel.  float32 buffers: sentinel -1.0 at the
+    marks (values that are never -1).  int64 buffers: -1 (actions are >= 0), the mark is the low 32-bit word of each element."""
+
+    def __init__(self, shape, dtype, device=None):
+        dtype = np.dtype(dtype)
+        device = device if isinstance(device, torch.device) else torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+        count = int(np.prod(shape))
+        nbytes = max(count * dtype.itemsize, 8)
+        self._block = _PinnedBlock(device.index, nbytes)
+        self.dev_ptr = C.c_void_p(self._block.dev.value)
+        self.np = np.frombuffer((C.c_char * nbytes).from_address(self._block.host.value), dtype=dtype, count=count).reshape(shape)
+        self.np[...] = 0
+        self.dev = _wrap_device(self._block.dev.value, shape, _TORCH_OF[_NP_DT[dtype]], device, owner=self._block)
+        self._flat = self.np.reshape(-1)
+        if dtype == np.int64:
+            self._wait_fn, self._base, self._sentinel = self._block.lib.jh_host_wait_words, self._flat.view(np.uint32), 0xFFFFFFFF
+        else:
+            self._wait_fn, self._base, self._sentinel = self._block.lib.jh_host_wait_marks, self._flat, -1.0
+        self._waits = {}  # marks -> (elements, pointer to _base, their int32 indices into _base, pointer to those, count): wait() is a per-env-step path
+
+    def arm(self, marks=None):
+        """Write the sentinel at the flat element indices `marks` (None: every element), before the launch that overwrites them."""
+        if marks is None:
+            self._flat.fill(-1)
+        else:
+            for m in marks:
+                self._flat[m] = -1
+
+    def wait(self, marks=None, what="PinnedBuffer.wait(): the results", stream=None, timeout_s=STATS_WAIT_S):
+        """Wait until no element of `marks` (as armed) holds the sentinel.  One ctypes call: a C spin, i.e. without the GIL (a Python spin
+        loop here cost the batched actors of an Ape-X process a third of their throughput).  Bounded: after `timeout_s` a synchronise
+        of `stream` (default: torch's current stream of the buffer's device), which also surfaces asynchronous errors, then an error if
+        the marks are still there."""
+        w = self._waits.get(marks)
+        if w is None:
+            assert self.np.dtype in (np.float32, np.int64), "arrival marks are float32 elements or the low words of int64 elements"
+            el = np.arange(self._flat.size, dtype=np.int32) if marks is None else np.asarray(marks, dtype=np.int32)
+            idx = el * (self._base.size // self._flat.size)  # int64: the low word (little endian) of each element
+            w = self._waits[marks] = (el, L.ptr(self._base), idx, L.ptr(idx), int(idx.size))
+        if self._wait_fn(w[1], w[3], w[4], self._sentinel, timeout_s) != 0:
+            (torch.cuda.current_stream(self.dev.device) if stream is None else stream).synchronize()
+            if (self._flat[w[0]] == -1).any():
+                raise RuntimeError(f"{what} never arrived (failed launch?)")
 
 
 class PPONet:

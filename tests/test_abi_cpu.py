@@ -258,3 +258,52 @@ def test_param_counts_are_the_padded_sums_of_the_networks_segments(lib):
     # SAC's policy ends in mu and log_std, kept as ONE [2A][H] layer and one [2A] bias (include/jorldy_hip.h)
     assert lib.jh_sacnet_param_counts_for(S, H, A, C.byref(na), C.byref(nc)) == 0
     assert (na.value, nc.value) == (total(lin(H, S) + lin(H, H) + lin(2 * A, H)), total(critic))
+
+
+# ---- the host-side arrival wait (jh_host_wait_marks / jh_host_wait_words) on plain numpy arrays: what ops.PinnedBuffer.wait calls
+def _wait_marks(lib, a, marks, timeout_s):
+    idx = np.asarray(marks, dtype=np.int32)
+    return lib.jh_host_wait_marks(C.c_void_p(a.ctypes.data), C.c_void_p(idx.ctypes.data), int(idx.size), -1.0, timeout_s)
+
+
+def test_host_wait_marks_returns_at_once_when_the_marks_are_clear(lib):
+    a = np.zeros(8, np.float32)
+    assert _wait_marks(lib, a, (3, 7), 5.0) == 0
+
+
+def test_host_wait_marks_times_out_no_earlier_than_its_bound(lib):
+    import time
+
+    a = np.zeros(8, np.float32)
+    a[3] = -1.0
+    t0 = time.perf_counter()
+    rc = _wait_marks(lib, a, (3, 7), 0.05)
+    dt = time.perf_counter() - t0
+    assert rc != 0
+    assert dt >= 0.05, f"returned after {dt * 1e3:.1f} ms, before the 50 ms bound"
+
+
+def test_host_wait_marks_spins_without_the_gil(lib):
+    """A Python thread clears the mark while the main thread is inside the C wait: it can only run if the wait does not hold the GIL."""
+    import threading
+
+    a = np.zeros(8, np.float32)
+    a[3] = -1.0
+    t = threading.Timer(0.02, lambda: a.__setitem__(3, 0.5))
+    t.start()
+    try:
+        rc = _wait_marks(lib, a, (3,), 5.0)
+    finally:
+        t.join()
+    assert rc == 0 and a[3] == 0.5
+
+
+def test_host_wait_words_watches_the_low_words_of_int64_elements(lib):
+    a = np.full(3, -1, np.int64)
+    words, idx = a.view(np.uint32), np.arange(0, 6, 2, dtype=np.int32)
+    wait = lambda: lib.jh_host_wait_words(C.c_void_p(words.ctypes.data), C.c_void_p(idx.ctypes.data), 3, 0xFFFFFFFF, 0.05)
+    assert wait() != 0
+    a[0], a[2] = 4, 0
+    assert wait() != 0, "element 1 is still -1"
+    a[1] = 1
+    assert wait() == 0
