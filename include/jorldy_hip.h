@@ -589,6 +589,90 @@ int jh_mpo_loss_discrete(jh_ctx* ctx, int32_t R, int32_t T, int32_t A, const flo
                          const float* d_done, const float* d_prob_b, float* d_block, const float* d_hyper, float gamma, int32_t retrace,
                          float* d_grad_la, float* d_grad_q, float* d_stats, jh_stream stream);
 
+/* ------------------------------------------------------------------ R2D2: the LSTM recurrence and the sequence loss
+ * torch.nn.LSTM(H + A -> H, one layer) as core/network/r2d2.py:13-15, 38 runs it, one time step per launch.  Gate order i, f, g, o.
+ * jh_lstm_step, for every segment s < n_segs (up to JH_LSTM_MAX_SEGS row groups in ONE launch, each with weights and buffers of its own:
+ * the online rows and the target rows of R2D2.learn(), r2d2.py:117-129; a segment of 0 rows is skipped):
+ *   gates = xproj + h_prev W_hh^T      xproj [rows] rows of 4H floats, ld_x floats apart: the input projection x_t W_ih^T + b_ih + b_hh,
+ *                                      which does not depend on the recurrence; w_hh [4H][H]; h_prev, c_prev [rows][H]
+ *   i, f, o = sigmoid, g = tanh;  c_out = f c_prev + i g;  h_out = o tanh(c_out)            [rows][H]
+ *   gates_out [rows][4H] (NULL ok) = the ACTIVATED gates, what the backward needs
+ * A workgroup owns 16 rows x 16 hidden units across all four gates: the product runs on the fp32 MFMA, the cell in the same launch.
+ * H % 4 == 0, 4 <= H <= 4096; w_hh and h_prev 16-byte aligned.                                                                   */
+#define JH_LSTM_MAX_SEGS 4
+typedef struct {
+  int32_t rows, ld_x;
+  const float *xproj, *w_hh, *h_prev, *c_prev;
+  float *h_out, *c_out, *gates_out;
+} jh_lstm_seg;
+int jh_lstm_step(jh_ctx* ctx, int32_t H, int32_t n_segs, const jh_lstm_seg* segs, jh_stream stream);
+/* One step of backpropagation through time, t descending, one launch per trained step:
+ *   dh_t = d_dh_ext (gradient reaching h_t from the layers above; NULL: 0) + d_dgates_next W_hh (d_dgates_next [R][4H] = this function's
+ *          d_dgates of step t + 1; NULL at the last step)
+ *   dc_t = d_dc_in (this function's d_dc_prev of step t + 1; NULL: 0) + dh_t o (1 - tanh(c_t)^2)
+ *   d_dgates [R][4H] = the gradient of the PRE-activation gates of step t; d_dc_prev [R][H] = dc_t f
+ * with d_gates [R][4H] the activated gates of step t, d_c_prev = c_{t-1}, d_c = c_t [R][H].  The recurrent product sits in the launch
+ * that consumes it, so that a workgroup needs the saved activations of its own 16 units only.  dW_hh, dW_ih, the bias gradients and dx
+ * are products over ALL trained steps' d_dgates at once (the tile engine), not this function's.                                  */
+int jh_lstm_step_backward(jh_ctx* ctx, int32_t R, int32_t H, const float* d_dgates_next, const float* d_w_hh, const float* d_dh_ext,
+                          const float* d_dc_in, const float* d_gates, const float* d_c_prev, const float* d_c, float* d_dgates,
+                          float* d_dc_prev, jh_stream stream);
+/* R2D2.learn() between the three sequence passes and the backward (r2d2.py:113-159), T = seq_len - n_burn_in trained steps:
+ * d_q / d_next_q / d_next_target_q float32 [T][B][A] (time-major) = online over state[:, :seq_len], online and target over
+ * state[:, n_step:]; d_action / d_reward / d_done float32 [B][seq_len + n_step - 1] as the replay row holds them (actions clamped into
+ * [0, A)); d_weights float32 [B].  Per row b and step t: a* = first maximum of next_q, y = h(fold(h^-1(next_target_q[a*]))) with the
+ * n-step fold over reward / done [i + n_burn_in + t], i = n_step - 1 .. 0, and the value rescale h(x) = sign(x)(sqrt(|x| + 1) - 1) +
+ * eps x (r2d2.py:304-313); td = |y - q[action]|.  Outputs: d_prio float64 [B] = (eta max_t td + (1 - eta) mean_t td)^alpha;
+ * d_grad_q [T][B][A], every entry written, non-zero only at the LAST step's taken action: 2 w_b (q - y) / B, the gradient of
+ * loss = mean_b w_b td[b, T - 1]^2; d_td [B][T] (NULL ok); d_stats float32[8] = {loss, max_Q over all taken q, 0, 0, 0, mark, 0, mark}, the
+ * payload fenced before the arrival marks as jh_qr_loss leaves them.  Per-row terms in double, rounded once.  A departure on purpose:
+ * sqrt(1 + y) - 1 inside h^-1 (and sqrt(|x| + 1) - 1 inside h) is formed without its cancellation; the float32 expression as written is
+ * off by up to 2e-4 of the largest target at |Q| = 0.05.  One workgroup, no atomics: the same bits every run.
+ * JH_ERR_ARG, nothing launched: B < 1 or > 1024, T < 1, seq_len > 128, A < 2 or > 64, n_step < 1.                                  */
+int jh_r2d2_loss(jh_ctx* ctx, int32_t B, int32_t T, int32_t A, int32_t n_burn_in, int32_t n_step, const float* d_q, const float* d_next_q,
+                 const float* d_next_target_q, const float* d_action, const float* d_reward, const float* d_done, const float* d_weights,
+                 float gamma, float eta, float alpha, float eps, float* d_grad_q, double* d_prio, float* d_td, float* d_stats,
+                 jh_stream stream);
+
+/* The recurrent dueling network of R2D2 (core/network/r2d2.py:8-53) with an MLP head over caller-owned flat fp32 buckets (online and target
+ * parameters, gradients, exp_avg, exp_avg_sq) of jh_r2d2net_param_count_for floats (needs no GPU; -1 for bad sizes), every segment 16-byte
+ * aligned, in the library's own order (jh_r2d2net_segment_count / _segment):
+ *   head.l.weight [H][S], head.l.bias [H], lstm.weight_ih_l0 [4H][H + A], lstm.weight_hh_l0 [4H][H], lstm.bias_ih_l0 [4H], lstm.bias_hh_l0 [4H],
+ *   l.weight [H][H], l.bias [H], l1_a.weight, l1_v.weight [H][H], l1_a.bias, l1_v.bias [H], l2_a.weight [A][H], l2_a.bias [A], l2_v.weight [1][H],
+ *   l2_v.bias [1]     (l1_a | l1_v next to each other: one [2H][H] layer to the kernels)
+ * H % 4 == 0, 2 <= A <= 64, max_batch <= 1024, 2 <= seq_len <= 128, 1 <= n_burn_in < seq_len, n_step >= 1.  Every buffer is allocated at
+ * create; nothing is allocated afterwards, so learn_forward / backward / optim_step may be captured into a graph.                     */
+typedef struct jh_r2d2net jh_r2d2net;
+int64_t jh_r2d2net_param_count_for(int32_t S, int32_t H, int32_t A);
+int jh_r2d2net_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t A, int32_t max_batch, int32_t seq_len, int32_t n_burn_in, int32_t n_step,
+                      float* d_params, float* d_target, float* d_grads, float* d_m, float* d_v, jh_r2d2net** out);
+void jh_r2d2net_destroy(jh_r2d2net* n);
+int32_t jh_r2d2net_segment_count(void);
+int jh_r2d2net_segment(const jh_r2d2net* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols);
+int jh_r2d2net_set_hyper(jh_r2d2net* n, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream);
+int jh_r2d2net_set_lr(jh_r2d2net* n, double lr, jh_stream stream);
+int jh_r2d2net_sync_target(jh_r2d2net* n, jh_stream stream);
+/* The three sequence passes of R2D2.learn() (r2d2.py:117-129 through get_q, r2d2.py:289-302), seq_len steps each, run in lockstep: the
+ * online network over steps [0, seq_len) from (d_hidden_h, d_hidden_c), the online and the target network over steps [n_step, n_step +
+ * seq_len) from (d_next_hidden_h, d_next_hidden_c).  d_state [B][seq_len + n_step][S], d_onehot [B][seq_len + n_step][A] (the previous
+ * action's one-hot), the stored states [B][H].  The head and the input projection run once per network over all stored steps (the
+ * second online pass is the first one's input n_step steps on), then one jh_lstm_step launch of three row segments per time step, then
+ * the layers above the LSTM over the seq_len - n_burn_in trained steps of all three passes.
+ * -> d_q [3][seq_len - n_burn_in][B][A], time-major: what jh_r2d2_loss takes.  seq_len + 7 launches.                                  */
+int jh_r2d2net_learn_forward(jh_r2d2net* n, const float* d_state, const float* d_onehot, const float* d_hidden_h, const float* d_hidden_c,
+                             const float* d_next_hidden_h, const float* d_next_hidden_c, int32_t B, float* d_q, jh_stream stream);
+/* Backward of d_q[0] of the last jh_r2d2net_learn_forward: d_g [seq_len - n_burn_in][B][A] -> the gradient bucket, every segment written.
+ * One jh_lstm_step_backward launch per trained step, t descending; the burn-in steps take no gradient (r2d2.py:290-295).  dW_hh, dW_ih, the
+ * bias gradients (bias_hh_l0's is a copy of bias_ih_l0's) and the head's are products over all trained steps at once.                 */
+int jh_r2d2net_backward(jh_r2d2net* n, const float* d_g, jh_stream stream);
+/* [clip_grad_norm_(max_norm) over the bucket (0: none),] torch.optim.Adam's step, the step counter advanced on the device.            */
+int jh_r2d2net_optim_step(jh_r2d2net* n, float max_norm, jh_stream stream);
+/* R2D2.act's network call (r2d2.py:62-66) for N <= max_batch actor rows, one time step: d_x [N][S], d_prev_onehot [N][A] (zeros at an episode
+ * start), the carried state d_h_in / d_c_in [N][H] (16-byte aligned) -> d_q [N][A], d_h_out / d_c_out [N][H]; all on the device.  Its
+ * buffers are its own: it may run between a learn_forward and its backward.                                                          */
+int jh_r2d2net_act_step(jh_r2d2net* n, const float* d_x, const float* d_prev_onehot, const float* d_h_in, const float* d_c_in, int32_t N, float* d_q,
+                        float* d_h_out, float* d_c_out, jh_stream stream);
+
 /* ------------------------------------------------------------------ ICM-PPO's curiosity module
  * core/network/icm.py:153-218 (ICM_MLP) with its helpers icm.py:8-34 (the feature trunk: fc1 -> bn1 -> ELU -> fc2 -> bn2 -> ELU on s; the
  * SAME fc1 and fc2 on s' with bn1_next after fc1 and no batch norm after fc2), icm.py:99-142 (forward and inverse model), icm.py:145-150

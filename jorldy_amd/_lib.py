@@ -23,6 +23,12 @@ class ColDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("elems", C.c_int64)]
 
 
+class LstmSeg(C.Structure):
+    """jh_lstm_seg: one row group of a jh_lstm_step launch."""
+    _fields_ = [("rows", C.c_int32), ("ld_x", C.c_int32), ("xproj", C.c_void_p), ("w_hh", C.c_void_p), ("h_prev", C.c_void_p), ("c_prev", C.c_void_p),
+                ("h_out", C.c_void_p), ("c_out", C.c_void_p), ("gates_out", C.c_void_p)]
+
+
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _pp = C.POINTER(C.c_void_p)
 
@@ -145,6 +151,21 @@ _PROTOS = {
     "jh_vmpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_vmpo_loss_continuous": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_mpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 12 + [_f32, _i32, _vp, _vp, _vp, _vp]),
+    "jh_lstm_step": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "jh_lstm_step_backward": (C.c_int, [_vp, _i32, _i32] + [_vp] * 10),
+    "jh_r2d2_loss": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32] + [_vp] * 7 + [_f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "jh_r2d2net_param_count_for": (_i64, [_i32, _i32, _i32]),
+    "jh_r2d2net_create": (C.c_int, [_vp] + [_i32] * 7 + [_vp] * 5 + [_pp]),
+    "jh_r2d2net_destroy": (None, [_vp]),
+    "jh_r2d2net_segment_count": (_i32, []),
+    "jh_r2d2net_segment": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
+    "jh_r2d2net_set_hyper": (C.c_int, [_vp, _f64, _f64, _f64, _f64, _i64, _vp]),
+    "jh_r2d2net_set_lr": (C.c_int, [_vp, _f64, _vp]),
+    "jh_r2d2net_sync_target": (C.c_int, [_vp, _vp]),
+    "jh_r2d2net_learn_forward": (C.c_int, [_vp] * 7 + [_i32, _vp, _vp]),
+    "jh_r2d2net_backward": (C.c_int, [_vp, _vp, _vp]),
+    "jh_r2d2net_optim_step": (C.c_int, [_vp, _f32, _vp]),
+    "jh_r2d2net_act_step": (C.c_int, [_vp] * 5 + [_i32] + [_vp] * 4),
     "jh_icmnet_param_count_for": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "jh_icmnet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _pp]),
     "jh_icmnet_destroy": (None, [_vp]),

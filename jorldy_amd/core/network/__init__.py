@@ -16,6 +16,7 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   continuous_policy            core/network/policy.py:38-55
   discrete_policy              core/network/policy.py:23-35
   icm_mlp                      core/network/icm.py:153-188 (+ utils.py:6-24 reward filter, running moments)
+  r2d2                         core/network/r2d2.py:8-26
 """
 import torch
 
@@ -110,6 +111,24 @@ class Dueling(BaseNetwork):
         super().__init__(D_in, D_hidden, head)
         self.l1_a = torch.nn.Linear(self.head.D_head_out, D_hidden)
         self.l1_v = torch.nn.Linear(self.head.D_head_out, D_hidden)
+        self.l2_a = torch.nn.Linear(D_hidden, D_out)
+        self.l2_v = torch.nn.Linear(D_hidden, 1)
+        orthogonal_init([self.l1_a, self.l1_v])
+        orthogonal_init([self.l2_a, self.l2_v], "linear")
+
+
+class R2D2(BaseNetwork):
+    """Recurrent dueling network (r2d2.py:8-26): head -> cat[x, prev_action_onehot] -> LSTM(D_head_out + D_out -> D_hidden) -> relu(l) ->
+    dueling streams.  torch.nn.LSTM is held for its four parameters (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0; gate order i, f,
+    g, o) and their default initialisation; orthogonal_init runs on the four stream layers only, as in the reference."""
+
+    def __init__(self, D_in, D_out, D_hidden=512, head="mlp"):
+        super().__init__(D_in, D_hidden, head)
+        self.D_hidden = D_hidden
+        self.lstm = torch.nn.LSTM(input_size=self.head.D_head_out + D_out, hidden_size=D_hidden, batch_first=True)
+        self.l = torch.nn.Linear(D_hidden, D_hidden)
+        self.l1_a = torch.nn.Linear(D_hidden, D_hidden)
+        self.l1_v = torch.nn.Linear(D_hidden, D_hidden)
         self.l2_a = torch.nn.Linear(D_hidden, D_out)
         self.l2_v = torch.nn.Linear(D_hidden, 1)
         orthogonal_init([self.l1_a, self.l1_v])
@@ -295,6 +314,7 @@ network_dict = {
     "continuous_policy": ContinuousPolicy,
     "discrete_policy": DiscretePolicy,
     "icm_mlp": ICM_MLP,
+    "r2d2": R2D2,
 }
 
 

@@ -658,6 +658,65 @@ def mpo_loss_discrete(la, la_next, la_old, q, qt, qt_next, action, reward, done,
     return g_la, g_q, stats
 
 
+# ============================================================================= R2D2
+def lstm_step(groups, want_gates=False):
+    """jh_lstm_step: one time step of torch.nn.LSTM for up to four row groups in ONE launch.  groups: a list of
+    (xproj [R, 4H] -- rows may be strided --, w_hh [4H, H], h_prev [R, H], c_prev [R, H]); a group with R = 0 is skipped.
+    -> a list of (h [R, H], c [R, H], gates [R, 4H] | None), the gates activated in the order i, f, g, o."""
+    assert 1 <= len(groups) <= 4
+    H = int(groups[0][1].shape[1])
+    segs, outs = (L.LstmSeg * len(groups))(), []
+    for s, (xp, w, h0, c0) in enumerate(groups):
+        R = int(xp.shape[0])
+        w, h0, c0 = _f32(w), _f32(h0), _f32(c0)
+        assert xp.dtype == torch.float32 and xp.is_cuda and xp.shape[1] == 4 * H and xp.stride(1) == 1
+        assert tuple(w.shape) == (4 * H, H) and tuple(h0.shape) == (R, H) and tuple(c0.shape) == (R, H)
+        h, c = torch.empty_like(h0), torch.empty_like(c0)
+        gates = torch.empty(R, 4 * H, dtype=torch.float32, device=h0.device) if want_gates else None
+        segs[s] = L.LstmSeg(R, int(xp.stride(0)) if R > 1 else 4 * H, xp.data_ptr(), w.data_ptr(), h0.data_ptr(), c0.data_ptr(), h.data_ptr(), c.data_ptr(),
+                            gates.data_ptr() if want_gates else None)
+        outs.append((h, c, gates, (xp, w, h0, c0)))
+    L.check(L.load().jh_lstm_step(L.ctx(_dev(groups[0][1])), H, len(groups), C.cast(segs, C.c_void_p), L.stream_ptr()))
+    return [o[:3] for o in outs]
+
+
+def lstm_step_backward(w_hh, gates, c_prev, c, dh_ext=None, dc_in=None, dgates_next=None):
+    """jh_lstm_step_backward: dh_t = dh_ext + dgates_next @ w_hh, then the gradient of step t's pre-activation gates and dc_{t-1}.
+    gates [R, 4H] activated (lstm_step's), c_prev / c [R, H]; dh_ext / dc_in [R, H] and dgates_next [R, 4H] may be None (zero).
+    -> (dgates [R, 4H], dc_prev [R, H])."""
+    w, g, c0, c1 = _f32(w_hh), _f32(gates), _f32(c_prev), _f32(c)
+    R, H = (int(v) for v in c1.shape)
+    assert tuple(w.shape) == (4 * H, H) and tuple(g.shape) == (R, 4 * H) and tuple(c0.shape) == (R, H)
+    opt = [None if v is None else _f32(v) for v in (dgates_next, dh_ext, dc_in)]
+    assert all(v is None or tuple(v.shape) == s for v, s in zip(opt, ((R, 4 * H), (R, H), (R, H))))
+    dg, dc = torch.empty_like(g), torch.empty_like(c1)
+    L.check(L.load().jh_lstm_step_backward(L.ctx(_dev(w)), R, H, L.ptr(opt[0]), L.ptr(w), L.ptr(opt[1]), L.ptr(opt[2]), L.ptr(g), L.ptr(c0), L.ptr(c1), L.ptr(dg),
+                                           L.ptr(dc), L.stream_ptr()))
+    return dg, dc
+
+
+def r2d2_loss(q, next_q, next_target_q, action, reward, done, weights, n_burn_in, n_step, gamma, eta, alpha, eps=1e-3, stats=None, want_td=False):
+    """jh_r2d2_loss (r2d2.py:113-159): q / next_q / next_target_q [T, B, A] time-major over the T = seq_len - n_burn_in trained steps;
+    action / reward / done [B, seq_len + n_step - 1] (or [.., 1]) as the replay row holds them; weights [B].
+    -> (grad_q [T, B, A], priority float64 [B], stats f32[8] = {loss, max_Q, 0, 0, 0, mark, 0, mark}, td [B, T] | None)."""
+    t = [_f32(v) for v in (q, next_q, next_target_q)]
+    T, B, A = (int(v) for v in t[0].shape)
+    assert all(tuple(v.shape) == (T, B, A) for v in t)
+    cols = [_f32(v).reshape(B, -1) for v in (action, reward, done)]
+    assert all(v.shape[1] == T + int(n_burn_in) + int(n_step) - 1 for v in cols)
+    w = _f32(weights).reshape(-1)
+    assert w.numel() == B
+    g = torch.empty_like(t[0])
+    prio = torch.empty(B, dtype=torch.float64, device=g.device)
+    td = torch.empty(B, T, dtype=torch.float32, device=g.device) if want_td else None
+    if stats is None:
+        stats = torch.empty(8, dtype=torch.float32, device=g.device)
+    assert stats.dtype == torch.float32 and stats.numel() >= 8 and stats.is_contiguous()
+    L.check(L.load().jh_r2d2_loss(L.ctx(_dev(g)), B, T, A, int(n_burn_in), int(n_step), *(L.ptr(v) for v in t), *(L.ptr(v) for v in cols), L.ptr(w), float(gamma),
+                                  float(eta), float(alpha), float(eps), L.ptr(g), L.ptr(prio), L.ptr(td), L.ptr(stats), L.stream_ptr()))
+    return g, prio, stats, td
+
+
 # ============================================================================= native policy-value MLP
 class _PinnedBlock:
     """One jh_pinned_alloc allocation, freed when the last reference goes: a PinnedBuffer and the holder of its device alias
@@ -1621,6 +1680,94 @@ class IQNNet(_NetObject):
         if optimizer != "adam":
             raise ValueError(f"IQNNet has Adam only (every config.iqn.* uses it), got {optimizer!r}")
         L.check(self._fn("optim_step")(self.h, float(max_norm or 0.0), L.stream_ptr()))
+
+
+class R2D2Net(_NetObject):
+    """jh_r2d2net_*: R2D2's recurrent dueling network (core/network/r2d2.py) with an MLP head -- the three sequence passes of learn() in
+    lockstep (one LSTM step launch per time step for all three), backpropagation through time over the trained steps, clip + Adam over the
+    flat bucket, and the one-step acting forward.  Buckets, export / import under the reference's 16 state_dict keys, set_hyper / set_lr /
+    sync_target / optim_step as the other network objects have them."""
+
+    # the library's segment order (l1_a | l1_v and their biases sit next to each other); state_dict order is the reference's
+    _SEG = ("head.l.weight", "head.l.bias", "lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0", "lstm.bias_hh_l0", "l.weight", "l.bias",
+            "l1_a.weight", "l1_v.weight", "l1_a.bias", "l1_v.bias", "l2_a.weight", "l2_a.bias", "l2_v.weight", "l2_v.bias")
+    _KEYS = ("head.l.weight", "head.l.bias", "lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0", "lstm.bias_hh_l0", "l.weight", "l.bias",
+             "l1_a.weight", "l1_a.bias", "l1_v.weight", "l1_v.bias", "l2_a.weight", "l2_a.bias", "l2_v.weight", "l2_v.bias")
+    _SYM = "jh_r2d2net_"
+    kind, cnn, noise_len = "r2d2", False, 0
+
+    def __init__(self, state_size, action_size, hidden, max_batch, seq_len, n_burn_in, n_step, device):
+        self._open(device)
+        self.S, self.A, self.H, self.maxB = int(state_size), int(action_size), int(hidden), int(max_batch)
+        self.seq_len, self.n_burn_in, self.n_step = int(seq_len), int(n_burn_in), int(n_step)
+        n = int(self._fn("param_count_for")(self.S, self.H, self.A))
+        if n <= 0:
+            L.check(-2)
+        self.n_params = n
+        self.params, self.target, self.grads, self.m, self.v = self._zeros(n)
+        self.h = C.c_void_p()
+        L.check(self._fn("create")(self.ctx, self.S, self.H, self.A, self.maxB, self.seq_len, self.n_burn_in, self.n_step, L.ptr(self.params), L.ptr(self.target),
+                                   L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), C.byref(self.h)))
+        assert int(self._fn("segment_count")()) == len(self._SEG)
+        self.seg = self._segments(self._SEG)
+
+    def _pairs(self, bucket):
+        """[(reference key, view of the bucket shaped like the reference tensor)] in the order of the reference module's state_dict."""
+        out = []
+        for k in self._KEYS:
+            off, rows, cols = self.seg[k]
+            v = bucket[off : off + rows * cols]
+            out.append((k, v.view(rows, cols) if ".weight" in k else v))  # (lstm.weight_ih_l0 does not END in .weight)
+        return out
+
+    def export_state(self, bucket=None):
+        return _export_pairs(self._pairs(self.params if bucket is None else bucket))
+
+    def import_state(self, sd, bucket=None):
+        _import_pairs(self._pairs(self.params if bucket is None else bucket), sd, self.device)
+
+    def set_hyper(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0, centered=False):
+        L.check(self._fn("set_hyper")(self.h, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
+
+    def set_lr(self, lr):
+        L.check(self._fn("set_lr")(self.h, float(lr), L.stream_ptr()))
+
+    def sync_target(self):
+        L.check(self._fn("sync_target")(self.h, L.stream_ptr()))
+
+    def learn_forward(self, state, onehot, hidden_h, hidden_c, next_hidden_h, next_hidden_c, out=None):
+        """state [B, seq_len + n_step, S], onehot [B, seq_len + n_step, A], the four stored states [B, H] (or [B, 1, H])
+        -> out [3, seq_len - n_burn_in, B, A] time-major = online over state[:, :seq_len], online and target over state[:, n_step:]."""
+        t = [_f32(v) for v in (state, onehot, hidden_h, hidden_c, next_hidden_h, next_hidden_c)]
+        B, Ls = int(t[0].shape[0]), self.seq_len + self.n_step
+        assert tuple(t[0].shape) == (B, Ls, self.S) and tuple(t[1].shape) == (B, Ls, self.A) and all(v.numel() == B * self.H for v in t[2:])
+        Tt = self.seq_len - self.n_burn_in
+        if out is None:
+            out = torch.empty(3, Tt, B, self.A, dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == 3 * Tt * B * self.A
+        L.check(self._fn("learn_forward")(self.h, *(L.ptr(v) for v in t), B, L.ptr(out), L.stream_ptr()))
+        return out
+
+    def backward(self, g, defer=False):
+        """g = d(loss)/d(out[0]) [seq_len - n_burn_in, B, A]."""
+        assert g.is_contiguous() and g.dtype == torch.float32
+        L.check(self._fn("backward")(self.h, L.ptr(g), L.stream_ptr()))
+
+    def optim_step(self, optimizer="adam", max_norm=None):
+        """[clip_grad_norm_(max_norm)] + Adam's step."""
+        if optimizer != "adam":
+            raise ValueError(f"R2D2Net has Adam only (every config.r2d2.* uses it), got {optimizer!r}")
+        L.check(self._fn("optim_step")(self.h, float(max_norm or 0.0), L.stream_ptr()))
+
+    def act_step(self, x, prev_onehot, h, c, out=None):
+        """One time step of the online network: x [N, S], prev_onehot [N, A], carried state h / c [N, H] -> (q [N, A], h', c'); out = the
+        three tensors to write into."""
+        x, p, h, c = _f32(x), _f32(prev_onehot), _f32(h), _f32(c)
+        N = int(x.shape[0])
+        assert tuple(x.shape) == (N, self.S) and tuple(p.shape) == (N, self.A) and tuple(h.shape) == (N, self.H) and tuple(c.shape) == (N, self.H)
+        q, h1, c1 = out if out is not None else (torch.empty(N, self.A, dtype=torch.float32, device=self.device), torch.empty_like(h), torch.empty_like(c))
+        L.check(self._fn("act_step")(self.h, L.ptr(x), L.ptr(p), L.ptr(h), L.ptr(c), N, L.ptr(q), L.ptr(h1), L.ptr(c1), L.stream_ptr()))
+        return q, h1, c1
 
 
 def td3_next_action(z, eps=None, noise_std=0.0, noise_clip=0.0, out=None):
