@@ -193,8 +193,6 @@ class BaseAgent(ABC):
                 self.memory.load_state_dict(extra["memory"])
             if "target_network" in extra:
                 self.target_network.load_state_dict(extra["target_network"])
-        if getattr(self, "_net", None) is not None:
-            self._import_optim_state()
 
     @staticmethod
     def _require_gpu(device):

@@ -6,7 +6,7 @@ import torch
 from ... import ops
 from ..network import Network
 from ..optimizer import Optimizer
-from .ppo import MAX_HEAD_OUTPUTS, PPO
+from .ppo import MAX_HEAD_OUTPUTS, PPO, export_views, import_views
 
 MAX_MINIBATCH = ops.ICMNet.MAX_BATCH  # jh_icmnet_*: rows of one call
 ICM_ELIGIBLE = ("ICM-PPO runs on libjorldy_hip only: network in {discrete_policy_value, continuous_policy_value}, head='mlp', int state_size, "
@@ -186,24 +186,13 @@ class ICM_PPO(PPO):
 
     def _export_optim_state(self):
         super()._export_optim_state()
-        for p, m, v in self._icm_views:  # the first seven parameters never get a gradient: no state, as in torch's own optimizer
-            self.icm_optimizer.state[p] = {"step": torch.tensor(float(self._icm_steps)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+        export_views(self.icm_optimizer, self._icm_views, self._icm_steps)  # the first seven parameters never get a gradient: no views, no state
 
     def _import_optim_state(self):
         super()._import_optim_state()
         if self._icm_net is None:
             return
-        steps = 0
-        for p, m, v in self._icm_views:
-            stt = self.icm_optimizer.state.get(p)
-            if stt:
-                m.copy_(stt["exp_avg"])
-                v.copy_(stt["exp_avg_sq"])
-                steps = int(float(stt["step"]))
-            else:
-                m.zero_()
-                v.zero_()
-        self._icm_steps = steps
+        self._icm_steps = steps = import_views(self.icm_optimizer, self._icm_views)
         d = self.icm_optimizer.defaults
         self._icm_net.set_hyper(self.icm_optimizer.param_groups[0]["lr"], d["betas"][0], d["betas"][1], d["eps"], step=steps)
 

@@ -9,8 +9,9 @@ from ..buffer import ReplayBuffer
 from ..buffer.base import h2d_small
 from ..network import Network
 from ..optimizer import Optimizer
+from . import optim_state
 from .base import BaseAgent
-from .native_net import NativeNet
+from .native_net import NativeNet, load_moments, moments_of, shadow_of
 
 MAX_ROWS = 1024  # jh_mpo_loss_discrete: one workgroup, one row of the batch_size x n_step trajectories per thread
 MAX_ACTIONS = 64  # logits per row the loss kernel loops over
@@ -19,7 +20,6 @@ MPO_ELIGIBLE = ("MPO runs on libjorldy_hip only: actor 'discrete_policy' with cr
                 f"2 <= action_size <= {MAX_ACTIONS} and batch_size * n_step <= {MAX_ROWS} (n_step counts as 1 with '1step_TD'): the Retrace scan and every "
                 "mean of a learn() run inside one workgroup (config.mpo.cartpole / mountaincar / pong_mlagent and their shapes); 'continuous_policy', "
                 "the cnn head and data-parallel learners (grad_sync) are not available for this agent")
-MULTIPLIERS = ("eta", "alpha_mu", "alpha_sigma")
 
 
 class MPO(BaseAgent):
@@ -78,7 +78,7 @@ class MPO(BaseAgent):
             net.import_state(init.state_dict())
             net.sync_target()
         self._critic.reserve_target_rows(2 * R)  # target(s) and target(s') share the target slot; allocated here, not inside a captured learn()
-        self._net = self._actor  # BaseAgent.load_full's marker of a native agent
+        self._net = self._actor  # the marker of a native agent
         self.actor, self.target_actor = NativeNet(self._actor, 0), NativeNet(self._actor, 1)
         self.critic, self.target_critic = NativeNet(self._critic, 0), NativeNet(self._critic, 1)
         self.num_learn, self.time_t = 0, 0
@@ -215,33 +215,21 @@ class MPO(BaseAgent):
     def sync_out(self, device="cpu"):
         return {"weights": {k: v.to(device) for k, v in self.actor.state_dict().items()}}
 
-    def _shadow_optimizers(self):
-        """The configured torch optimizers over copies of the parameters: the actor's also holds the three multipliers (mpo.py:142-149)."""
-        out = []
-        for net, extra in ((self._actor, True), (self._critic, False)):
-            sd = net.export_state()
-            params = [torch.nn.Parameter(v) for v in sd.values()]
-            mult = [torch.nn.Parameter(torch.tensor(float(v), device=self.device)) for v in self._mult[:3].tolist()] if extra else []
-            opt = Optimizer(**self._optim_config, params=params + mult)
-            for grp in opt.param_groups:
-                grp["lr"] = self._lr_now
-            out.append((net, opt, params, list(sd.keys()), mult))
-        return out
+    def _shadows(self):
+        """(ckpt key, net, shadow_of(net)) of both optimizers: the actor's also holds the three multipliers (mpo.py:142-149)."""
+        mult = [torch.tensor(float(v), device=self.device) for v in self._mult[:3].tolist()]
+        return [(key, net, shadow_of(net, self._optim_config, self._lr_now, extra))
+                for key, net, extra in (("actor_optimizer", self._actor, mult), ("critic_optimizer", self._critic, ()))]
 
     def save(self, path):
         print(f"...Save model to {path}...")
         ck = {"actor": self.actor.state_dict(), "critic": self.critic.state_dict()}
-        blk = self.multipliers()
-        t = lambda v: torch.tensor(float(v), dtype=torch.float32, device=self.device)
-        for (net, opt, params, keys, mult), name in zip(self._shadow_optimizers(), ("actor_optimizer", "critic_optimizer")):
+        mult_m, mult_v = ops.vmpo_block_moments(self._mult)  # alpha_sigma never takes a step: no entry, as in torch's own optimizer
+        for key, net, (opt, params, keys) in self._shadows():
             if self._adam_steps > 0:
-                m, v = net.export_state(net.m), net.export_state(net.v)
-                for p, k in zip(params, keys):
-                    opt.state[p] = {"step": torch.tensor(float(self._adam_steps)), "exp_avg": m[k], "exp_avg_sq": v[k]}
-                for p, n in zip(mult, MULTIPLIERS):
-                    if blk[n]["has_state"]:  # alpha_sigma never takes a step: no entry, as in torch's own optimizer
-                        opt.state[p] = {"step": torch.tensor(float(self._adam_steps)), "exp_avg": t(blk[n]["m"]), "exp_avg_sq": t(blk[n]["v"])}
-            ck[name] = opt.state_dict()
+                m, v = moments_of(net)
+                optim_state.fill(opt, params, self._adam_steps, m + mult_m, v + mult_v)  # (zip: the critic's ends at its own parameters)
+            ck[key] = opt.state_dict()
         torch.save(ck, os.path.join(path, "ckpt"))
 
     def load(self, path):
@@ -251,34 +239,19 @@ class MPO(BaseAgent):
             view.load_state_dict(ck[key])
             target.load_state_dict(ck[key])
         steps, g0 = 0, None
-        h = self._mult.detach().cpu().numpy().copy()
-        for (net, opt, params, keys, mult), name in zip(self._shadow_optimizers(), ("actor_optimizer", "critic_optimizer")):
-            opt.load_state_dict(ck[name])
-            net.m.zero_()
-            net.v.zero_()
-            if opt.state.get(params[0]):
-                net.import_state({k: opt.state[p]["exp_avg"] for p, k in zip(params, keys)}, net.m)
-                net.import_state({k: opt.state[p]["exp_avg_sq"] for p, k in zip(params, keys)}, net.v)
-                steps = int(float(opt.state[params[0]]["step"]))
-            for j, p in enumerate(mult):  # the moments go into the block; the VALUES are not in the reference's checkpoint and stay
-                stt = opt.state.get(p)
-                h[3 + j], h[6 + j], h[15 + j] = (float(stt["exp_avg"]), float(stt["exp_avg_sq"]), 1.0) if stt else (0.0, 0.0, 0.0)
+        for key, net, (opt, params, keys) in self._shadows():
+            opt.load_state_dict(ck[key])
+            steps = load_moments(net, keys, opt, params) or steps
+            if len(params) > len(keys):  # the multipliers' moments go into the block; their VALUES are not in the reference's checkpoint and stay
+                _, m, v = optim_state.read(opt, params[len(keys):])
+                ops.vmpo_block_set_moments(self._mult, m, v)
             g0 = g0 or opt.param_groups[0]
-        torch.cuda.current_stream().synchronize()
-        self._mult.copy_(torch.from_numpy(h))
         self._adam_steps, self._lr_now = steps, float(g0["lr"])
-        d = dict(g0)
-        d["lr"] = self._lr_now
-        self._set_hyper(d, steps)
+        self._set_hyper(g0, steps)
 
     def _resume_extra_attrs(self):
-        return {"mpo_block": [float(v).hex() for v in self._mult.detach().cpu().numpy().astype(np.float64)]}  # hex: exact, and a NaN survives JSON
+        return {"mpo_block": ops.vmpo_block_hex(self._mult)}
 
     def _resume_load_extra_attrs(self, d):
         if "mpo_block" in d:
-            h = np.asarray([float.fromhex(v) for v in d["mpo_block"]], dtype=np.float32)
-            torch.cuda.current_stream().synchronize()
-            self._mult.copy_(torch.from_numpy(h))
-
-    def _import_optim_state(self):  # BaseAgent.load_full(): load() already imported the moments
-        pass
+            ops.vmpo_block_from_hex(self._mult, d["mpo_block"])

@@ -9,6 +9,7 @@ import torch
 
 from ... import ops
 from ..optimizer import Optimizer
+from . import optim_state
 
 _KIND_OF = {"rainbow": "rainbow", "dueling": "dueling", "discrete_q_network": "q"}
 
@@ -40,6 +41,25 @@ def require_native(backend, network, head, state_size, hidden_size, optim_config
     if not native_supported(network, head, state_size, hidden_size, optim_config, noise_type):
         raise ValueError(f"{NATIVE_ELIGIBLE}; got network={network!r}, head={head!r}, state_size={state_size!r}, hidden_size={hidden_size}, "
                          f"noise_type={noise_type!r}, optim_config={optim_config!r}")
+
+
+def shadow_of(net, optim_config, lr, extra=()):
+    """-> (opt, params, keys): optim_state.shadow over copies of net's parameters in the reference's state_dict order [+ the tensors `extra`]."""
+    sd = net.export_state()
+    return (*optim_state.shadow(optim_config, list(sd.values()) + list(extra), lr), list(sd))
+
+
+def moments_of(net):
+    """-> (m, v) of net's moment buckets as lists in state_dict order."""
+    return [list(net.export_state(bucket).values()) for bucket in (net.m, net.v)]
+
+
+def load_moments(net, keys, opt, params):
+    """The loaded optimizer's moments of net's parameters (the first len(keys) of `params`) -> net's moment buckets; -> the step count."""
+    steps, m, v = optim_state.read(opt, params)
+    for bucket, moments in ((net.m, m), (net.v, v)):
+        net.import_state(dict(zip(keys, optim_state.dense(moments, params))), bucket)
+    return steps
 
 
 class NativeNet:
@@ -173,10 +193,8 @@ class NativeValueNetMixin:
         ops.value_act(logits, float(getattr(self, "v_min", 0.0)), float(getattr(self, "v_max", 0.0)), out=out)
 
     def _set_native_hyper(self, d, steps):
-        if self._opt_name == "adam":
-            self._net.set_hyper(d["lr"], d["betas"][0], d["betas"][1], d["eps"], steps)
-        else:
-            self._net.set_hyper(d["lr"], d["alpha"], 0.0, d["eps"], steps, centered=d["centered"])
+        lr, b1, b2, eps, centered = optim_state.hyper(d)
+        self._net.set_hyper(lr, b1, b2, eps, steps, centered=centered)
 
     def _as_float(self):
         # frames stay uint8 until the first convolution's operand fetch; everything else fp32 (as_tensor)
@@ -199,30 +217,12 @@ class NativeValueNetMixin:
         self._lr_now = self._lr0 * float(self._lr_weight(step, mode))
         self._net.set_lr(self._lr_now)  # a device scalar: the captured graph reads it
 
-    def _shadow_optimizer(self):
-        """The configured torch optimizer over copies of the parameters carrying the native moments: the
-        reference's ckpt format ({"network", "optimizer"}, dqn.py:184-199) both ways."""
-        sd = self._net.export_state()
-        params = [torch.nn.Parameter(v) for v in sd.values()]
-        opt = Optimizer(**self._optim_config, params=params)
-        for grp in opt.param_groups:
-            grp["lr"] = self._lr_now
-        return opt, params, list(sd.keys())
-
     def _native_save(self, path):
+        """The reference's ckpt format ({"network", "optimizer"}, dqn.py:184-199)."""
         print(f"...Save model to {path}...")
-        opt, params, keys = self._shadow_optimizer()
+        opt, params, _ = shadow_of(self._net, self._optim_config, self._lr_now)
         if self._adam_steps > 0:
-            m, v = self._net.export_state(self._net.m), self._net.export_state(self._net.v)
-            for p, k in zip(params, keys):
-                stt = {"step": torch.tensor(float(self._adam_steps))}
-                if self._opt_name == "adam":
-                    stt.update(exp_avg=m[k], exp_avg_sq=v[k])
-                else:
-                    stt["square_avg"] = v[k]
-                    if opt.defaults["centered"]:
-                        stt["grad_avg"] = m[k]
-                opt.state[p] = stt
+            optim_state.fill(opt, params, self._adam_steps, *moments_of(self._net))
         torch.save({"network": self.network.state_dict(), "optimizer": opt.state_dict()}, os.path.join(path, "ckpt"))
 
     def _native_load(self, path):
@@ -230,25 +230,11 @@ class NativeValueNetMixin:
         checkpoint = torch.load(os.path.join(path, "ckpt"), map_location=self.device, weights_only=False)
         self.network.load_state_dict(checkpoint["network"])
         self.target_network.load_state_dict(checkpoint["network"])
-        opt, params, keys = self._shadow_optimizer()
+        opt, params, keys = shadow_of(self._net, self._optim_config, self._lr_now)
         opt.load_state_dict(checkpoint["optimizer"])
-        steps = 0
-        self._net.m.zero_()
-        self._net.v.zero_()
-        if opt.state:
-            km, kv = ("exp_avg", "exp_avg_sq") if self._opt_name == "adam" else ("grad_avg", "square_avg")
-            if km in opt.state[params[0]]:
-                self._net.import_state({k: opt.state[p][km] for p, k in zip(params, keys)}, self._net.m)
-            self._net.import_state({k: opt.state[p][kv] for p, k in zip(params, keys)}, self._net.v)
-            steps = int(float(opt.state[params[0]]["step"]))
-        g0 = opt.param_groups[0]
-        self._adam_steps, self._lr_now = steps, float(g0["lr"])
-        d = dict(g0)
-        d["lr"] = self._lr_now
-        self._set_native_hyper(d, steps)
-
-    def _import_optim_state(self):  # BaseAgent.load_full(): load() already imported the moments
-        pass
+        self._adam_steps = load_moments(self._net, keys, opt, params)
+        self._lr_now = float(opt.param_groups[0]["lr"])
+        self._set_native_hyper(opt.param_groups[0], self._adam_steps)
 
 
 class NoiseDrawMixin:

@@ -7,6 +7,7 @@ from ... import np_rng, ops
 from ..buffer import RolloutBuffer
 from ..network import Network
 from ..optimizer import Optimizer
+from . import optim_state
 from .base import BaseAgent
 
 
@@ -16,6 +17,21 @@ NATIVE_ELIGIBLE = ("PPO runs on libjorldy_hip only: network in {discrete_policy_
                    f"2 * action_size + 1 (continuous) <= {MAX_HEAD_OUTPUTS} head outputs (config.ppo.cartpole, config.ppo.mujoco on all its envs; up to 8 outputs "
                    "-- CartPole, Hopper -- on the four-launch minibatch update and the persistent acting kernel, beyond that on the separate calls / the tiled engine); "
                    "head='cnn' with a (C, H, W) state_size and network 'discrete_policy_value' runs on the convolutional engine (core/agent/ppo_cnn.py: config.ppo.atari, ppo.procgen)")
+
+
+def export_views(opt, views, steps):
+    """Native moments -> the state of the persistent torch optimizer `opt`; views = [(Parameter, its m view, its v view)]."""
+    optim_state.fill(opt, [p for p, _, _ in views], steps, [m.clone() for _, m, _ in views], [v.clone() for _, _, v in views])
+
+
+def import_views(opt, views):
+    """The loaded state of `opt` -> the native moments; -> the step count."""
+    params = [p for p, _, _ in views]
+    steps, m, v = optim_state.read(opt, params)
+    for (_, dst_m, dst_v), src_m, src_v in zip(views, optim_state.dense(m, params), optim_state.dense(v, params)):
+        dst_m.copy_(src_m)
+        dst_v.copy_(src_v)
+    return steps
 
 
 class PPO(BaseAgent):
@@ -548,22 +564,13 @@ class PPO(BaseAgent):
     def _export_optim_state(self):
         """Native Adam moments -> torch.optim.Adam state, so `ckpt` keeps the reference's format
         ({"network": state_dict, "optimizer": state_dict}, reinforce.py:128-136)."""
-        if self._net is None:
-            return
-        for p, m, v in self._views:
-            self.optimizer.state[p] = {"step": torch.tensor(float(self._adam_steps)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+        if self._net is not None:
+            export_views(self.optimizer, self._views, self._adam_steps)
 
     def _import_optim_state(self):
         if self._net is None:
             return
-        steps = 0
-        for p, m, v in self._views:
-            stt = self.optimizer.state.get(p)
-            if stt:
-                m.copy_(stt["exp_avg"])
-                v.copy_(stt["exp_avg_sq"])
-                steps = int(float(stt["step"]))
-        self._adam_steps = steps
+        self._adam_steps = steps = import_views(self.optimizer, self._views)
         d = self.optimizer.defaults
         if self._ride_wait.pop("lr", None) and self._ride is not None:  # a learning rate still riding with the next commit launch would overwrite this one
             self._ride.ride_along(1, 0, 0, 0)

@@ -4,7 +4,7 @@ import numpy as np
 import torch
 
 from ... import ops
-from ..optimizer import Optimizer
+from . import optim_state
 from .base import BaseAgent
 from .td3 import ActorCriticView, DeterministicActorCritic
 
@@ -133,22 +133,19 @@ class SAC(DeterministicActorCritic):
         return result
 
     # ------------------------------------------------------------------------------------------ checkpoints
-    def _alpha_optimizer(self, blk):
-        p = torch.nn.Parameter(torch.tensor([blk["log_alpha"]], dtype=torch.float32, device=self.device))
-        opt = Optimizer("adam", [p], lr=self.alpha_lr, betas=(blk["beta1"], blk["beta2"]), eps=blk["eps"])
-        for grp in opt.param_groups:
-            grp["lr"] = blk["lr"]
-        if blk["step"] > 0:
-            t = lambda v: torch.tensor([v], dtype=torch.float32, device=self.device)
-            opt.state[p] = {"step": torch.tensor(float(blk["step"])), "exp_avg": t(blk["m"]), "exp_avg_sq": t(blk["v"])}
-        return p, opt
+    def _one(self, v):
+        """The temperature's scalars as the one-element tensors of the reference's log_alpha."""
+        return torch.tensor([v], dtype=torch.float32, device=self.device)
 
     def _ckpt(self):
         """The reference's keys (sac.py:312-326): TD3's six, plus log_alpha and alpha_optimizer when the temperature is dynamic."""
         out = super()._ckpt()
         if self.use_dynamic_alpha:
-            p, opt = self._alpha_optimizer(self._net.get_alpha())
-            out["log_alpha"], out["alpha_optimizer"] = p.detach(), opt.state_dict()
+            blk = self._net.get_alpha()
+            opt, params = optim_state.shadow({"name": "adam", "betas": (blk["beta1"], blk["beta2"]), "eps": blk["eps"]}, [self._one(blk["log_alpha"])], blk["lr"])
+            if blk["step"] > 0:
+                optim_state.fill(opt, params, blk["step"], [self._one(blk["m"])], [self._one(blk["v"])])
+            out["log_alpha"], out["alpha_optimizer"] = params[0].detach(), opt.state_dict()
         return out
 
     def load(self, path):
@@ -161,12 +158,12 @@ class SAC(DeterministicActorCritic):
         self._load_ckpt(ckpt)
         if self.use_dynamic_alpha and "log_alpha" in ckpt:
             la = float(torch.as_tensor(ckpt["log_alpha"]).reshape(-1)[0])
-            p = torch.nn.Parameter(torch.tensor([la], dtype=torch.float32, device=self.device))
-            opt = Optimizer("adam", [p], lr=self.alpha_lr)
+            opt, params = optim_state.shadow({"name": "adam"}, [self._one(la)], self.alpha_lr)
             opt.load_state_dict(ckpt["alpha_optimizer"])
-            g0, st = opt.param_groups[0], opt.state.get(p) or {}
-            self._net.set_alpha(la, lr=float(g0["lr"]), beta1=g0["betas"][0], beta2=g0["betas"][1], eps=g0["eps"], step=int(float(st.get("step", 0))),
-                                m=float(st["exp_avg"]) if st else 0.0, v=float(st["exp_avg_sq"]) if st else 0.0, dynamic=True)
+            steps, m, v = optim_state.read(opt, params)
+            lr, beta1, beta2, eps, _ = optim_state.hyper(opt.param_groups[0])
+            self._net.set_alpha(la, lr=lr, beta1=beta1, beta2=beta2, eps=eps, step=steps, m=float(optim_state.dense(m, params)[0]),
+                                v=float(optim_state.dense(v, params)[0]), dynamic=True)
 
     def save_full(self, path, version=None):
         """BaseAgent's format version 2 only.  Beside the replay buffer, the counters and the generators it carries the two target critics and

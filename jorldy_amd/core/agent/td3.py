@@ -6,7 +6,7 @@ import torch
 from ... import ops
 from ..buffer import ReplayBuffer
 from ..network import Network
-from ..optimizer import Optimizer
+from . import optim_state
 from .base import BaseAgent
 
 _ELIGIBLE = ("{name} runs on libjorldy_hip only: actor 'deterministic_policy', critic 'continuous_q_network', head 'mlp' with a scalar state_size, "
@@ -206,41 +206,18 @@ class DeterministicActorCritic(BaseAgent):
     def _critic_names(self):
         return self._net.nets()[1:]
 
-    def _optimizer_state(self, net, steps, lr):
-        sd = self._net.export_state(net)
-        params = [torch.nn.Parameter(v) for v in sd.values()]
-        opt = Optimizer("adam", params, lr=self._lr0["actor" if net == "actor" else "critic"])
-        for grp in opt.param_groups:
-            grp["lr"] = lr
-        if steps > 0:
-            m, v = self._net.export_state(net, "m"), self._net.export_state(net, "v")
-            for p, k in zip(params, sd.keys()):
-                opt.state[p] = {"step": torch.tensor(float(steps)), "exp_avg": m[k], "exp_avg_sq": v[k]}
-        return opt.state_dict()
-
-    def _load_optimizer_state(self, net, osd):
-        sd = self._net.export_state(net)
-        params = [torch.nn.Parameter(v) for v in sd.values()]
-        opt = Optimizer("adam", params, lr=self._lr0["actor" if net == "actor" else "critic"])
-        opt.load_state_dict(osd)
-        steps = 0
-        self._net.flat(net, "m").zero_()
-        self._net.flat(net, "v").zero_()
-        if opt.state:
-            self._net.import_state({k: opt.state[p]["exp_avg"] for p, k in zip(params, sd.keys())}, net, "m")
-            self._net.import_state({k: opt.state[p]["exp_avg_sq"] for p, k in zip(params, sd.keys())}, net, "v")
-            steps = int(float(opt.state[params[0]]["step"]))
-        g0 = opt.param_groups[0]
-        return steps, float(g0["lr"]), g0["betas"], g0["eps"]
-
     def _ckpt(self):
         out = {}
         for key, net, what in self.CKPT_KEYS:
-            which = "actor" if net == "actor" else "critic"
+            sd = self._net.export_state(net)
             if what == "net":
-                out[key] = self._net.export_state(net)
-            else:
-                out[key] = self._optimizer_state(net, self._adam_steps_actor if net == "actor" else self._adam_steps_critic, self._lr_now[which])
+                out[key] = sd
+                continue
+            steps, lr = (self._adam_steps_actor, self._lr_now["actor"]) if net == "actor" else (self._adam_steps_critic, self._lr_now["critic"])
+            opt, params = optim_state.shadow({"name": "adam"}, sd.values(), lr)
+            if steps > 0:
+                optim_state.fill(opt, params, steps, *(list(self._net.export_state(net, kind).values()) for kind in "mv"))
+            out[key] = opt.state_dict()
         return out
 
     def save(self, path):
@@ -259,13 +236,19 @@ class DeterministicActorCritic(BaseAgent):
             if what == "net":
                 self._net.import_state(ckpt[key], net)
                 continue
-            steps, lr, betas, eps = self._load_optimizer_state(net, ckpt[key])
+            sd = self._net.export_state(net)
+            opt, params = optim_state.shadow({"name": "adam"}, sd.values(), 0.0)
+            opt.load_state_dict(ckpt[key])
+            steps, m, v = optim_state.read(opt, params)
+            for kind, moments in (("m", m), ("v", v)):
+                self._net.import_state(dict(zip(sd, optim_state.dense(moments, params))), net, kind)
+            lr, beta1, beta2, eps, _ = optim_state.hyper(opt.param_groups[0])
             if net == "actor":
                 self._adam_steps_actor, self._lr_now["actor"] = steps, lr
-                self._net.set_hyper("actor", lr, betas[0], betas[1], eps, steps)
+                self._net.set_hyper("actor", lr, beta1, beta2, eps, steps)
             elif net == "critic1":
                 self._adam_steps_critic, self._lr_now["critic"] = steps, lr
-                self._net.set_hyper("critic", lr, betas[0], betas[1], eps, steps)
+                self._net.set_hyper("critic", lr, beta1, beta2, eps, steps)
         self._net.sync_target()
 
     # ---- complete checkpoints: BaseAgent.save_full / load_full + the targets and the exploration state
@@ -284,9 +267,6 @@ class DeterministicActorCritic(BaseAgent):
         if os.path.exists(f):
             for net, sd in torch.load(f, map_location=self.device, weights_only=False).items():
                 self._net.import_state(sd, net, "target")
-
-    def _import_optim_state(self):  # BaseAgent.load_full(): load() already imported the moments
-        pass
 
 
 class TD3(DeterministicActorCritic):

@@ -5,6 +5,7 @@ import torch
 
 from ... import ops
 from ..optimizer import Optimizer
+from . import optim_state
 from .ppo import MAX_HEAD_OUTPUTS, PPO
 
 MAX_MINIBATCH = 1024  # jh_vmpo_loss_*: one workgroup, one row per thread
@@ -13,7 +14,6 @@ VMPO_ELIGIBLE = ("V-MPO runs on libjorldy_hip only: network in {discrete_policy_
                  f"(continuous) <= {MAX_HEAD_OUTPUTS} head outputs, and batch_size <= {MAX_MINIBATCH}: the top half of a minibatch is selected inside one "
                  "workgroup (config.vmpo.cartpole, config.vmpo.mujoco on all its envs); the cnn head, data-parallel learners and the native "
                  "collector's acting-time capture are not available for this agent")
-MULTIPLIERS = ("eta", "alpha_mu", "alpha_sigma")
 
 
 class VMPO(PPO):
@@ -137,38 +137,26 @@ class VMPO(PPO):
     # ---------------------------------------------------------------------------------- checkpoint
     def _resume_extra_attrs(self):
         d = super()._resume_extra_attrs()
-        d["vmpo_block"] = [float(v).hex() for v in self._mult.detach().cpu().numpy().astype(np.float64)]  # hex: exact, and a NaN survives JSON
+        d["vmpo_block"] = ops.vmpo_block_hex(self._mult)
         return d
 
     def _resume_load_extra_attrs(self, d):
         super()._resume_load_extra_attrs(d)
         if "vmpo_block" in d:
-            h = np.asarray([float.fromhex(v) for v in d["vmpo_block"]], dtype=np.float32)
-            torch.cuda.current_stream().synchronize()
-            self._mult.copy_(torch.from_numpy(h))
+            ops.vmpo_block_from_hex(self._mult, d["vmpo_block"])
 
     def _export_optim_state(self):
         """The network's moments as PPO exports them; the multipliers that have taken a step carry theirs, the others (alpha_sigma of a discrete
         policy) have no entry, as in torch's own optimizer."""
         super()._export_optim_state()
-        blk = self.multipliers()
-        for p, name in zip(self._mult_params, MULTIPLIERS):
-            b = blk[name]
-            with torch.no_grad():
-                p.fill_(b["value"])
-            if b["has_state"]:
-                t = lambda v: torch.tensor(float(v), dtype=torch.float32, device=self.device)
-                self.optimizer.state[p] = {"step": torch.tensor(float(self._adam_steps)), "exp_avg": t(b["m"]), "exp_avg_sq": t(b["v"])}
-            else:
-                self.optimizer.state.pop(p, None)
+        with torch.no_grad():
+            for p, value in zip(self._mult_params, self._mult[:3].tolist()):
+                p.fill_(value)
+        optim_state.fill(self.optimizer, self._mult_params, self._adam_steps, *ops.vmpo_block_moments(self._mult))
 
     def _import_optim_state(self):
         """The loaded optimizer's moments of the multipliers go into the device block; their VALUES are not in the reference's checkpoint and stay
         what they are (on a freshly constructed agent: the constructor's)."""
         super()._import_optim_state()
-        h = self._mult.detach().cpu().numpy().copy()
-        for j, p in enumerate(self._mult_params):
-            stt = self.optimizer.state.get(p)
-            h[3 + j], h[6 + j], h[15 + j] = (float(stt["exp_avg"]), float(stt["exp_avg_sq"]), 1.0) if stt else (0.0, 0.0, 0.0)
-        torch.cuda.current_stream().synchronize()
-        self._mult.copy_(torch.from_numpy(h))
+        _, m, v = optim_state.read(self.optimizer, self._mult_params)
+        ops.vmpo_block_set_moments(self._mult, m, v)

@@ -577,6 +577,35 @@ def vmpo_block_read(block):
                 "has_state": bool(h[15 + j]), "grad": float(h[18 + j])} for j, k in enumerate(_VMPO_NAMES)}
 
 
+def vmpo_block_moments(block):
+    """-> (m, v) of the three multipliers as an optimizer holds them: 0-dim float32 tensors on the block's device, None where the has-state
+    flag is off (alpha_sigma of a discrete policy never takes a step).  Synchronises."""
+    h = block.detach().cpu()
+    return tuple([h[o + j].clone().to(block.device) if h[15 + j] else None for j in range(3)] for o in (3, 6))
+
+
+def _vmpo_block_write(block, h):
+    torch.cuda.current_stream().synchronize()
+    block.copy_(torch.from_numpy(np.asarray(h, np.float32)))
+
+
+def vmpo_block_set_moments(block, m, v):
+    """The inverse, in place: m / v [3] of one-element tensors, None = no optimizer state (moments 0, flag off).  The values stay."""
+    h = block.detach().cpu().numpy().copy()
+    for j in range(3):
+        h[3 + j], h[6 + j], h[15 + j] = (0.0, 0.0, 0.0) if v[j] is None else (float(m[j]), float(v[j]), 1.0)
+    _vmpo_block_write(block, h)
+
+
+def vmpo_block_hex(block):
+    """The whole block as the list of strings the resume manifest stores: exact, and a NaN survives JSON."""
+    return [float(x).hex() for x in block.detach().cpu().numpy().astype(np.float64)]
+
+
+def vmpo_block_from_hex(block, hexes):
+    _vmpo_block_write(block, [float.fromhex(x) for x in hexes])
+
+
 def vmpo_hyper(lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0, device="cuda"):
     """A hand-made optimizer block in the layout of jh_pponet_hyper_ptr (16 floats: lr, betas, eps, step, ..., the betas as doubles at
     [10:14]) for calling the V-MPO loss kernels without a network.  `step` = Adam steps taken BEFORE the coming one."""

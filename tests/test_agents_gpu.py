@@ -534,6 +534,36 @@ def test_ppo_native_checkpoint_roundtrip(tmp_path):
     torch.testing.assert_close(a1._net.m, a2._net.m, rtol=0, atol=0)
 
 
+def test_ppo_load_of_a_fresh_checkpoint_zeroes_the_native_moments(tmp_path):
+    """A checkpoint saved before the first update, loaded into an agent that has learned twice: native m and v are all zero and the step count
+    is 0 -- for the agent's own fresh checkpoint, and for the reference's, whose optimizer holds no entry at all before its first step (the case
+    in which m and v used to keep their old contents under a step count of 0)."""
+    from jorldy_amd.core.agent import Agent
+
+    z = load("ppo_disc_small")
+    S, A, H, W, T, B, E, cont = [int(x) for x in z["cfg"]]
+    mk = lambda: Agent("ppo", state_size=S, action_size=A, hidden_size=H, optim_config={"name": "adam", "lr": 1e-3}, batch_size=B, n_step=T, n_epoch=E, run_step=1000, device="cuda", backend="native", use_graph=False)
+    cols = {k: z[f"in_{k}"] for k in ["state", "next_state", "reward", "done", "action"]}
+    own, ref = tmp_path / "own", tmp_path / "ref"
+    own.mkdir()
+    ref.mkdir()
+    mk().save(str(own))
+    ck = torch.load(str(own / "ckpt"), weights_only=False)
+    ck["optimizer"]["state"] = {}
+    torch.save(ck, str(ref / "ckpt"))
+    a2 = mk()
+    a2.memory.first_store = False
+    for d in (own, ref):
+        for k in (1, 2):
+            np.random.seed(k)
+            a2.process(cols, a2.time_t + T)
+        torch.cuda.synchronize()
+        assert a2._adam_steps > 0 and bool(a2._net.m.any()) and bool(a2._net.v.any())
+        a2.load(str(d))
+        torch.cuda.synchronize()
+        assert a2._adam_steps == 0 and not bool(a2._net.m.any()) and not bool(a2._net.v.any()), d.name
+
+
 def test_native_act_discrete_distribution():
     """On-device multinomial acting: empirical action frequencies match softmax(logits)."""
     from jorldy_amd.core.agent import Agent
