@@ -906,6 +906,9 @@ int jh_collector_stats(jh_collector* c, double* act_us_per_step, double* env_us_
 /* out6 = {first step's action wait per run (acting kernel start-up), value-only query per run, commit launch per run,
  * steady-state action wait per timestep (both excluded), runs, timesteps}, microseconds; call before a resetting jh_collector_stats. */
 int jh_collector_stats_detail(jh_collector* c, double* out6);
+/* out4 = {1 if a persistent acting kernel exists else 0, lookahead (1|2), split (0|1),
+ *         runs since creation that were finished by per-step launches after the kernel gave up} */
+int jh_collector_mode(const jh_collector* c, int64_t* out4);
 
 /* N(0,1) draws on the device for NoisyNet layers (core/network/utils.py:58-60 draws torch.randn per forward):
  * counter-based (element i of call c = Box-Muller on splitmix64(seed, c, i)); d_state uint64[4] = {seed, call counter,

@@ -107,6 +107,7 @@ struct jh_collector {
   double t_first = 0, t_extra = 0, t_commit = 0;  // of t_act: the rollout's first step (kernel start-up) and the value-only query; the commit launch
   int64_t runs = 0;
   int64_t steps = 0;
+  int64_t handed_over = 0;  // runs the persistent form left to one launch per step because the kernel gave up (jh_collector_mode)
 };
 
 struct RunState;
@@ -505,6 +506,7 @@ static int kernel_gave_up(jh_collector* c, const RunState& r, int t, hipStream_t
                                  "no observations for ~0.2 s; use jh_collector_run for environments that may stall", t);
   JH_HIP(hipStreamSynchronize(st));
   *t_done = t;
+  c->handed_over += 1;
   return JH_OK;
 }
 
@@ -935,6 +937,18 @@ JH_EXPORT int jh_collector_loop(jh_collector* c, int32_t training, jh_stream str
   c->runs += 1;
   r.active = false;
   return rc;
+}
+
+// Which path produces this collector's numbers: out4 = {1 if a persistent acting kernel exists (0: every run is one launch per step), timesteps per
+// exchange (lookahead: 1 | 2), two independent halves (split: 0 | 1), runs since creation that one launch per step finished after the kernel gave up}.
+// Both fallbacks are silent by design (the rollout is the same rollout); a caller that must know which kernel it measured or checked asks here.
+JH_EXPORT int jh_collector_mode(const jh_collector* c, int64_t* out4) {
+  JH_ARG(c && out4);
+  out4[0] = c->persist ? 1 : 0;
+  out4[1] = c->lookahead;
+  out4[2] = c->split ? 1 : 0;
+  out4[3] = c->handed_over;
+  return JH_OK;
 }
 
 // More of the same: out[0..5] = per RUN microseconds {first step's action wait (kernel start-up), value-only query, commit launch},

@@ -309,6 +309,15 @@ class NativeCollector:
         return {"act_us_per_step": a.value, "env_us_per_step": e.value, "first_step_us_per_run": d[0], "value_query_us_per_run": d[1],
                 "commit_us_per_run": d[2], "act_steady_us_per_step": d[3]}
 
+    def mode(self):
+        """jh_collector_mode: which acting path this collector runs on (it exists after the first run / begin).  persistent: 1 when the
+        persistent acting kernel exists, 0 when every run is one launch per step; lookahead: timesteps per exchange (1 | 2); split: the rows
+        go as two independent halves; handed_over: runs that one launch per step finished after the kernel gave up."""
+        assert self.h is not None, "the C collector is created by the first run()"
+        m = (C.c_int64 * 4)()
+        L.check(self.lib.jh_collector_mode(self.h, m))
+        return {"persistent": int(m[0]), "lookahead": int(m[1]), "split": int(m[2]), "handed_over": int(m[3])}
+
     def sync(self, sync_item=None, init=False):
         return None
 
