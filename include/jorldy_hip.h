@@ -589,6 +589,32 @@ int jh_mpo_loss_discrete(jh_ctx* ctx, int32_t R, int32_t T, int32_t A, const flo
                          const float* d_done, const float* d_prob_b, float* d_block, const float* d_hyper, float gamma, int32_t retrace,
                          float* d_grad_la, float* d_grad_q, float* d_stats, jh_stream stream);
 
+/* ------------------------------------------------------------------ REINFORCE: the return scan and the policy-gradient losses
+ * core/agent/reinforce.py:83-113 between the network's forward and its backward, over the T rows of ONE episode (T differs from learn to
+ * learn; 1 <= T <= 65536).  The number of launches of each entry does not depend on T.
+ * jh_reinforce_returns: d_ret[t] = d_reward[t] + gamma d_ret[t + 1] over ALL T rows (no reset at a done and no done column: the reference
+ * scans whatever its buffer holds, reinforce.py:90-92); standardize != 0: then (ret - mean) / (std + 1e-7) with the population standard
+ * deviation, numpy's ret.std() (reinforce.py:93-94).  Scan, mean and variance in double (gamma is a double: numpy multiplies by the Python
+ * float), rounded once into float32 d_ret [T].  ONE workgroup: a chunked scan, per-thread local scans whose carries are combined with
+ * gamma^len by shuffles and through LDS; no float atomics, the same bits every run.  T = 1 with standardize gives exactly 0.
+ * jh_reinforce_loss_discrete: d_logits [T][A], d_action [T] as float (clamped into [0, A)), d_ret [T]:
+ *   loss = -mean_t(logp[t][a_t] ret[t]), logp a log-softmax (the reference takes log(softmax): finite where its float32 pi underflows)
+ *   d_grad_logits[t][k] = ret[t] (pi[t][k] - [k == a_t]) / T                                                     2 <= A <= 64
+ * jh_reinforce_loss_continuous: d_head [T][2A] = [mu_raw | log_std_raw], d_action [T][A], d_ret [T]:
+ *   mu = clamp(mu_raw, -5, 5), std = exp(tanh(log_std_raw)) (network/policy.py:49-55), z = atanh(clamp(action, -1 + 1e-7, 1 - 1e-7)) with the
+ *   bounds as float32 values, loss = -mean over T * A of (Normal(mu, std).log_prob(z) ret[t])
+ *   d_grad_head [T][2A] with respect to the raw head: zero where mu_raw is clamped, through tanh and exp for the std half  1 <= A <= 32
+ * Both losses: per-row terms in double; the mean is a two-stage sum in a fixed order (workgroup partials in the context's scratch, then one
+ * thread over them in index order); d_stats float32[JH_REINFORCE_STATS_FLOATS] = {loss, T} is written by the second stage, so nothing is
+ * read back by the call.  JH_ERR_ARG, nothing launched: T < 1 or T > 65536, A outside its range, a null pointer.                      */
+#define JH_REINFORCE_STATS_FLOATS 2
+#define JH_REINFORCE_MAX_ROWS 65536
+int jh_reinforce_returns(jh_ctx* ctx, int32_t T, const float* d_reward, double gamma, int32_t standardize, float* d_ret, jh_stream stream);
+int jh_reinforce_loss_discrete(jh_ctx* ctx, int32_t T, int32_t A, const float* d_logits, const float* d_action, const float* d_ret,
+                               float* d_grad_logits, float* d_stats, jh_stream stream);
+int jh_reinforce_loss_continuous(jh_ctx* ctx, int32_t T, int32_t A, const float* d_head, const float* d_action, const float* d_ret,
+                                 float* d_grad_head, float* d_stats, jh_stream stream);
+
 /* ------------------------------------------------------------------ R2D2: the LSTM recurrence and the sequence loss
  * torch.nn.LSTM(H + A -> H, one layer) as core/network/r2d2.py:13-15, 38 runs it, one time step per launch.  Gate order i, f, g, o.
  * jh_lstm_step, for every segment s < n_segs (up to JH_LSTM_MAX_SEGS row groups in ONE launch, each with weights and buffers of its own:

@@ -151,6 +151,9 @@ _PROTOS = {
     "jh_vmpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_vmpo_loss_continuous": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_mpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 12 + [_f32, _i32, _vp, _vp, _vp, _vp]),
+    "jh_reinforce_returns": (C.c_int, [_vp, _i32, _vp, _f64, _i32, _vp, _vp]),
+    "jh_reinforce_loss_discrete": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_reinforce_loss_continuous": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_lstm_step": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "jh_lstm_step_backward": (C.c_int, [_vp, _i32, _i32] + [_vp] * 10),
     "jh_r2d2_loss": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32] + [_vp] * 7 + [_f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),

@@ -687,6 +687,52 @@ def mpo_loss_discrete(la, la_next, la_old, q, qt, qt_next, action, reward, done,
     return g_la, g_q, stats
 
 
+# ============================================================================= REINFORCE
+REINFORCE_MAX_ROWS = 65536  # JH_REINFORCE_MAX_ROWS: the rows of one episode that one learn() takes
+REINFORCE_STATS = ("loss", "rows")
+
+
+def reinforce_returns(reward, gamma, standardize=True, out=None, T=None):
+    """jh_reinforce_returns: reward [T] -> ret [T] float32, ret[t] = reward[t] + gamma ret[t + 1] over all T rows, then (standardize) the
+    population standardisation, both in double on the device.  T: the row count handed to the library (default: reward's)."""
+    r = _f32(reward).reshape(-1)
+    T = int(r.numel()) if T is None else int(T)
+    if out is None:
+        out = torch.empty(max(T, 1), dtype=torch.float32, device=r.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= min(T, r.numel())
+    L.check(L.load().jh_reinforce_returns(L.ctx(_dev(r)), T, L.ptr(r), float(gamma), int(bool(standardize)), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def _reinforce_loss(entry, head, A, action, ret, stats, out, T):
+    h = _f32(head)
+    T = int(h.shape[0]) if T is None else int(T)
+    a, r = _f32(action).reshape(-1), _f32(ret).reshape(-1)
+    grad = out if out is not None else torch.empty_like(h)
+    assert grad.is_contiguous() and grad.dtype == torch.float32 and grad.numel() >= h.numel()
+    if stats is None:
+        stats = torch.zeros(len(REINFORCE_STATS), dtype=torch.float32, device=h.device)
+    assert stats.dtype == torch.float32 and stats.numel() >= len(REINFORCE_STATS) and stats.is_contiguous()
+    L.check(getattr(L.load(), entry)(L.ctx(_dev(h)), T, int(A), L.ptr(h), L.ptr(a), L.ptr(r), L.ptr(grad), L.ptr(stats), L.stream_ptr()))
+    return grad, stats
+
+
+def reinforce_loss_discrete(logits, action, ret, stats=None, out=None, T=None):
+    """jh_reinforce_loss_discrete: logits [T, A], action [T] (any dtype, taken as float), ret [T] -> (d(loss)/d(logits) [T, A], stats f32[2] =
+    {loss, T}) with loss = -mean_t(log_softmax(logits)[t, a_t] ret[t]).  Nothing is read back."""
+    h = _f32(logits)
+    assert h.dim() == 2 and (T is not None or (action.numel() == h.shape[0] and ret.numel() == h.shape[0]))
+    return _reinforce_loss("jh_reinforce_loss_discrete", h, h.shape[1], action, ret, stats, out, T)
+
+
+def reinforce_loss_continuous(head, action, ret, stats=None, out=None, T=None):
+    """jh_reinforce_loss_continuous: head [T, 2A] = [mu_raw | log_std_raw], action [T, A], ret [T] -> (d(loss)/d(head) [T, 2A], stats f32[2] =
+    {loss, T}) with loss = -mean over T * A of Normal(clamp(mu_raw, -5, 5), exp(tanh(log_std_raw))).log_prob(atanh(clamp(action))) ret[t]."""
+    h = _f32(head)
+    assert h.dim() == 2 and h.shape[1] % 2 == 0 and (T is not None or (action.numel() * 2 == h.numel() and ret.numel() == h.shape[0]))
+    return _reinforce_loss("jh_reinforce_loss_continuous", h, h.shape[1] // 2, action, ret, stats, out, T)
+
+
 # ============================================================================= R2D2
 def lstm_step(groups, want_gates=False):
     """jh_lstm_step: one time step of torch.nn.LSTM for up to four row groups in ONE launch.  groups: a list of
@@ -1362,7 +1408,7 @@ class RainbowNet(_NetObject):
     _SEG = ("w1", "b1", "w2", "b2", "w3", "b3", "wl", "bl", "mu_av1", "sig_av1", "mub_av1", "sigb_av1", "mu_a2", "sig_a2", "mub_a2", "sigb_a2",
             "mu_v2", "sig_v2", "mub_v2", "sigb_v2")
     _SYM = "jh_rbnet_"
-    _KIND = {"rainbow": 0, "dueling": 1, "q": 2, "pv": 2, "pi": 2, "noisy": 4}  # "noisy": network/noisy.py (head -> noisy -> noisy; 5 with independent noise); "pv": the discrete policy-value net (policy_value.py:8-22) = head -> l -> (pi | v) stacked into ONE last layer of A + 1 rows
+    _KIND = {"rainbow": 0, "dueling": 1, "q": 2, "pv": 2, "pi": 2, "gauss": 2, "noisy": 4}  # "noisy": network/noisy.py (head -> noisy -> noisy; 5 with independent noise); "pv": the discrete policy-value net (policy_value.py:8-22) = head -> l -> (pi | v) stacked into ONE last layer of A + 1 rows; "gauss": the Gaussian policy (policy.py:38-55) = head -> l -> (mu | log_std), raw, stacked into ONE last layer of 2A rows
 
     def __init__(self, state_size, action_size, num_support, hidden, head, max_batch, device, kind="rainbow", noise_type="factorized"):
         self._open(device)
@@ -1375,6 +1421,8 @@ class RainbowNet(_NetObject):
         self.H, self.A, self.K, self.maxB = int(hidden), int(action_size), int(num_support), int(max_batch)
         if kind == "pv":
             self.n_actions, self.A = self.A, self.A + 1  # the library sees a q-network with one more output row: the value head
+        if kind == "gauss":
+            self.n_actions, self.A = self.A, 2 * self.A  # the Gaussian policy (policy.py:38-55) = a q-network with 2A output rows: mu | log_std, raw
         kid = self._KIND[kind]
         self.noise_type = noise_type
         if kind in ("rainbow", "noisy") and noise_type == "independent":
@@ -1448,6 +1496,11 @@ class RainbowNet(_NetObject):
             out += head
             out += [("l.weight", self._feat_cols(self._v(bucket, "wl"))), ("l.bias", self._v(bucket, "bl").view(-1)),
                     ("pi.weight", w[:n]), ("pi.bias", b[:n]), ("v.weight", w[n:]), ("v.bias", b[n:])]
+        elif self.kind == "gauss":
+            w, b, n = self._v(bucket, "mu_a2"), self._v(bucket, "mub_a2").view(-1), self.n_actions
+            out += head
+            out += [("l.weight", self._feat_cols(self._v(bucket, "wl"))), ("l.bias", self._v(bucket, "bl").view(-1)),
+                    ("mu.weight", w[:n]), ("mu.bias", b[:n]), ("log_std.weight", w[n:]), ("log_std.bias", b[n:])]
         else:
             last = "pi" if self.kind == "pi" else "q"  # "pi": the discrete policy (policy.py:23-35) = a q-network whose last layer is named pi
             out += head
