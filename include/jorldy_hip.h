@@ -447,6 +447,26 @@ int jh_acnet_critic_update(jh_acnet* n, const float* d_x, const float* d_action,
  * input into the actor, the actor's Adam step.  Critic 1's parameters, gradient bucket and moments are not written.
  * -> d_action_pred [B][A] (optional), d_stats as jh_td3_actor_seed.  16 launches.                                   */
 int jh_acnet_actor_update(jh_acnet* n, const float* d_x, int32_t B, float* d_action_pred, float* d_stats, jh_stream stream);
+/* Critic 0 over SAMPLED actions (continuous MPO, mpo.py:219-231, 261-263; objects with n_critics = 1 for the last two entries).  The
+ * reference repeats every state N times in front of the critic; here head.l(s) runs once per state row, on R rows, its outputs are copied
+ * into the rows of that state's N samples, and only e(a), l and q run over the N * R rows, on the tile engine.
+ *   jh_acnet_reserve_sampled         room for rows = N * R sampled rows in each of two slots; allocates, so: once, outside any stream capture
+ *   jh_acnet_critic_forward_sampled  critic 0 (which 0 online / 1 target) of d_x [R][S] over d_actions [N][R][A] -> d_q [N][R].  5 launches.
+ *   jh_acnet_mpo_forward             every critic forward of one learn(): d_x = [state; next_state] (2R rows), d_action [R][A] the stored
+ *                                    action, d_a_next / d_a_add [N][R][A] -> d_q = online(s, a), d_qt_a = target(s, a) [R], d_qt_next =
+ *                                    target(s', a_next), d_qt_add = target(s, a_add) [N][R]; one grouped launch per layer for the four, the
+ *                                    target's head.l(s) shared by target(s, a) and the samples of a_add.  5 launches (a group of a heavy and
+ *                                    a light problem may go as two).  The online activations stay for jh_acnet_critic_fit.
+ *   jh_acnet_critic_fit              d_dq [R] = d(loss)/d(online q) of the last jh_acnet_mpo_forward -> the critic's backward,
+ *                                    clip_grad_norm_(max_norm; <= 0: none) and Adam on the critic's own optimizer block.  The actor's
+ *                                    buckets are not touched.
+ * JH_ERR_ARG: R > max_batch, N * R over the reserved rows, N < 1.                                                                     */
+int jh_acnet_reserve_sampled(jh_acnet* n, int32_t rows);
+int jh_acnet_critic_forward_sampled(jh_acnet* n, int32_t which, const float* d_x, const float* d_actions, int32_t R, int32_t N, float* d_q,
+                                    jh_stream stream);
+int jh_acnet_mpo_forward(jh_acnet* n, const float* d_x, const float* d_action, const float* d_a_next, const float* d_a_add, int32_t R, int32_t N,
+                         float* d_q, float* d_qt_a, float* d_qt_next, float* d_qt_add, jh_stream stream);
+int jh_acnet_critic_fit(jh_acnet* n, const float* d_x, const float* d_action, const float* d_dq, int32_t R, float max_norm, jh_stream stream);
 
 /* ------------------------------------------------------------------ soft actor-critic, continuous actions (SAC)
  * The elementwise steps of sac.py:161-269 on the Gaussian policy of policy.py:38-55 (float32, fixed summation order, capturable, no
@@ -588,6 +608,44 @@ int jh_mpo_loss_discrete(jh_ctx* ctx, int32_t R, int32_t T, int32_t A, const flo
                          const float* d_q, const float* d_qt, const float* d_qt_next, const float* d_action, const float* d_reward,
                          const float* d_done, const float* d_prob_b, float* d_block, const float* d_hyper, float gamma, int32_t retrace,
                          float* d_grad_la, float* d_grad_q, float* d_stats, jh_stream stream);
+
+/* ------------------------------------------------------------------ MPO, continuous policy
+ * core/agent/mpo.py:199-309.  R and T as above, N = num_sample, A = action_size.  A Gaussian policy's RAW head is a float32 row [mu | log_std]
+ * of 2A floats (jh_rbnet kind "gauss"); mu = clamp(raw, -5, 5), std = exp(tanh(raw)) (network/policy.py:53-55).  Both entries take
+ * 1 <= R <= 1024, 1 <= N, N * R <= 8192 and 1 <= A <= 8; anything else is JH_ERR_ARG with nothing launched.
+ *
+ * jh_mpo_sample: ONE elementwise launch.  d_head_next = online(s'), d_head_old = target(s), each [R][2A]; d_eps [2][N][R][A] standard normals.
+ *   d_zn = mu' + std' eps[0], d_a_next = tanh(d_zn)               (mpo.py:221-226)
+ *   d_zt_add = mu_old + std_old eps[1], d_a_add = tanh(d_zt_add)  (mpo.py:255-258)          each [N][R][A], float32 arithmetic
+ *
+ * jh_mpo_loss_continuous: between the forwards and the two backwards, ONE launch of ONE workgroup, one row per thread.  d_head = online(s)
+ * and d_head_old = target(s) [R][2A]; d_q = online critic(s, a), d_qt_a = target critic(s, a) [R]; d_qt_next = target critic(s', a_next),
+ * d_qt_add = target critic(s, a_add) [N][R]; d_zt_add [N][R][A]; d_action [R][A] the stored (tanh-squashed) action; d_reward, d_done,
+ * d_prob_b [R].
+ *   z        = atanh(clamp(a, -(1 - 1e-7), 1 - 1e-7)), the bound as float32 rounds it; log_prob = sum_A log N(z; mu, std)
+ *   c        = min(exp(log_prob) / (prob_b + 1e-6), 1)             the ONLINE policy, as the reference (mpo.py:203-206, 233)
+ *   Qret     = reward + gamma mean_n qt_next (1 - done), then the Retrace scan of jh_mpo_loss_discrete with qt_a  (mpo.py:235-253)
+ *   critic   mean_r (q - Qret)^2; d_grad_q[r] = 2 (q - Qret) / R
+ *   At = qt_add - mean_n qt_add, w = softmax_n(At / eta) taken as a constant; actor = -mean_r sum_n w log N(zt_add[n]; mu, std)
+ *   eta_loss = eta eps_eta + eta mean_r log mean_n exp(At / eta), the log-mean formed around the row's largest At / eta: the reference's
+ *            formula (mpo.py:276-278) wherever its float32 exp is finite, and finite beyond
+ *   KLD_mu = 1/2 sum_A (mu - mu_old)^2 std_old^2; KLD_sigma = 1/2 (sum_A std^2 / std_old^2 - A + log(prod ss / prod ss_old)), ss = 1 / std^2,
+ *            the log of the product ratio formed as the sum of the logs (finite at any A, equal elsewhere); alpha_loss = mean[alpha_mu
+ *            (eps_alpha_mu - KLD_mu) + alpha_mu KLD_mu] + mean[alpha_sigma (eps_alpha_sigma - KLD_sigma) + alpha_sigma KLD_sigma]  (mpo.py:280-309)
+ *   d_grad_head [R][2A]: d(actor + alpha_mu KLD_mu + alpha_sigma KLD_sigma)/d(raw head of online(s)), the multipliers as constants: zero in mu
+ *            where the raw value lies outside [-5, 5], through 1 - tanh^2 for log_std
+ *   d eta = eps_eta + mean L_r - (1 / eta) mean_r sum_n w At; d alpha_mu = eps_alpha_mu - mean KLD_mu; d alpha_sigma = eps_alpha_sigma - mean KLD_sigma
+ * d_block and d_hyper as jh_mpo_loss_discrete; ALL THREE multipliers take their Adam step and then their floors.
+ * d_stats optional float32[11] as jh_mpo_loss_discrete; min / max q over d_q [R], min / max At over all [N][R] entries.  Per-row terms in
+ * double, every mean a double sum in a fixed order, no atomics: the same bits every run.  The [N][R] tables are read from global memory
+ * (one reader per element, consecutive across a wavefront); LDS holds the scan's per-row state.
+ * JH_ERR_ARG besides the shape rule above: T < 1, R % T != 0.                                                                       */
+int jh_mpo_sample(jh_ctx* ctx, int32_t R, int32_t N, int32_t A, const float* d_head_next, const float* d_head_old, const float* d_eps, float* d_zn,
+                  float* d_zt_add, float* d_a_next, float* d_a_add, jh_stream stream);
+int jh_mpo_loss_continuous(jh_ctx* ctx, int32_t R, int32_t T, int32_t N, int32_t A, const float* d_head, const float* d_head_old, const float* d_q,
+                           const float* d_qt_a, const float* d_qt_next, const float* d_qt_add, const float* d_zt_add, const float* d_action,
+                           const float* d_reward, const float* d_done, const float* d_prob_b, float* d_block, const float* d_hyper, float gamma,
+                           int32_t retrace, float* d_grad_head, float* d_grad_q, float* d_stats, jh_stream stream);
 
 /* ------------------------------------------------------------------ REINFORCE: the return scan and the policy-gradient losses
  * core/agent/reinforce.py:83-113 between the network's forward and its backward, over the T rows of ONE episode (T differs from learn to

@@ -129,6 +129,10 @@ _PROTOS = {
     "jh_acnet_critic_forward": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "jh_acnet_critic_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "jh_acnet_actor_update": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "jh_acnet_reserve_sampled": (C.c_int, [_vp, _i32]),
+    "jh_acnet_critic_forward_sampled": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "jh_acnet_mpo_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "jh_acnet_critic_fit": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f32, _vp]),
     "jh_sac_sample": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_sac_critic_loss": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "jh_sac_actor_seed": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -151,6 +155,8 @@ _PROTOS = {
     "jh_vmpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_vmpo_loss_continuous": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_mpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 12 + [_f32, _i32, _vp, _vp, _vp, _vp]),
+    "jh_mpo_sample": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 8),
+    "jh_mpo_loss_continuous": (C.c_int, [_vp, _i32, _i32, _i32, _i32] + [_vp] * 13 + [_f32, _i32, _vp, _vp, _vp, _vp]),
     "jh_reinforce_returns": (C.c_int, [_vp, _i32, _vp, _f64, _i32, _vp, _vp]),
     "jh_reinforce_loss_discrete": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_reinforce_loss_continuous": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

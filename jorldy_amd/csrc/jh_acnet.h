@@ -22,6 +22,10 @@ struct jh_acnet {
   float *c_cat[2] = {nullptr, nullptr}, *c_h[2] = {nullptr, nullptr}, *c_q[2] = {nullptr, nullptr};
   // backward: dq [nc][maxB], dh [nc][maxB][H], dcat [nc][maxB][2H], da [maxB][A], dz [maxB][head], d(actor h) / d(actor feat) [maxB][H]
   float *dq = nullptr, *dh = nullptr, *dcat = nullptr, *da = nullptr, *dz = nullptr, *dah = nullptr, *dafeat = nullptr;
+  // critic 0 over sampled actions (MPO, jh_acnet_reserve_sampled): two slots of smax = N * R rows, cat [2][smax][2H] and h [2][smax][H], and
+  // head.l(s) of the slot-0 states [maxB][H], computed on R rows and copied into its samples' rows
+  int smax = 0;
+  float *s_cat = nullptr, *s_h = nullptr, *s_feat = nullptr;
 };
 
 constexpr int kMaxLossRows = 1 << 20;

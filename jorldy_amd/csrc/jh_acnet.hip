@@ -328,3 +328,131 @@ int ac_actor_backward(jh_acnet* n, const float* d_x, int B, hipStream_t st) {
   if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 1, st))) return rc;
   return jh_flat_adam_step(n->nA, n->ap, n->ag, n->am, n->av, n->opt_a.hyper, n->opt_a.ticket, n->core.norm_partial, 0.f, st);
 }
+
+// ---------------------------------------------------------------------------------- critic 0 over sampled actions (MPO, mpo.py:219-231, 261-263)
+// The reference repeats every state N times in front of the critic.  Here head.l(s) runs ONCE per state row, on R rows; its H outputs are
+// then copied into the [head(s) | relu(e(a))] rows of that state's N samples, and only e(a), l and q run over the N * R rows.  A job is one
+// critic forward: the R-row ones (online / target of (s, a), in the object's own activation sets, head.l(s) already in place) and the
+// sampled ones ride the same grouped launch per layer.
+namespace {
+
+struct AcJob {
+  const float* P;     // parameter bucket of the critic
+  const float* act;   // [rows][A]
+  int rows;
+  float *cat, *h;     // [rows][2H], [rows][H]
+  float* q;           // [rows]
+  const float* feat;  // sampled: head.l(s) [R][ldfeat] to copy into cat[:, :H] of every sample's rows; nullptr: already in cat
+  int ldfeat;
+};
+
+// dst[(n * R + r) * 2H + j] = src[r * ld + j] for j < H, 16 bytes per thread; blockIdx.y picks one of up to two copies
+__global__ void __launch_bounds__(256) jh_ac_spread_head_kernel(int rows, int R, int H4, const float* __restrict__ src0, int ld0, float* __restrict__ dst0,
+                                                                const float* __restrict__ src1, int ld1, float* __restrict__ dst1) {
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= rows * H4) return;
+  const int row = i / H4, j = (i - row * H4) * 4, r = row % R;
+  const float* src = blockIdx.y ? src1 : src0;
+  const int ld = blockIdx.y ? ld1 : ld0;
+  float* dst = blockIdx.y ? dst1 : dst0;
+  *reinterpret_cast<float4*>(dst + (size_t)row * 8 * H4 + j) = *reinterpret_cast<const float4*>(src + (size_t)r * ld + j);
+}
+
+// levels 2-5 of `nj` jobs whose head.l(s) the caller has launched: e(a); the copy of head.l(s) into the samples' rows; l; q.  4 launches.
+int ac_jobs_run(jh_acnet* n, const AcJob* j, int nj, int R, hipStream_t st) {
+  const int H = n->H, A = n->A;
+  TGemm g[kMaxGroup];
+  int rc;
+  const AcJob* s[2] = {nullptr, nullptr};  // the sampled jobs; checked before anything is launched
+  int ns = 0;
+  for (int i = 0; i < nj; ++i)
+    if (j[i].feat) {
+      if (ns == 2 || (ns == 1 && j[i].rows != s[0]->rows)) return jh_fail(JH_ERR_ARG, "jh_acnet: at most two sampled jobs of one size");
+      s[ns++] = &j[i];
+    }
+  for (int i = 0; i < nj; ++i)
+    g[i] = mk_gemm(j[i].rows, H, A, op_dense(OP_KCONT, j[i].act, A), op_dense(OP_KCONT, j[i].P + n->seg_off[AC_C_WE], A), j[i].cat + H, 2 * H, TEPI_BIAS_RELU,
+                   j[i].P + n->seg_off[AC_C_BE]);
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, nj, st))) return rc;
+  if (ns) {
+    const AcJob* s1 = s[ns - 1];
+    const int total = s[0]->rows * (H / 4);
+    JH_LAUNCH(jh_ac_spread_head_kernel, dim3((unsigned)((total + 255) / 256), ns), dim3(256), 0, st, s[0]->rows, R, H / 4, s[0]->feat, s[0]->ldfeat, s[0]->cat,
+              s1->feat, s1->ldfeat, s1->cat);
+    JH_LAUNCH_CHECK();
+  }
+  for (int i = 0; i < nj; ++i)
+    g[i] = mk_gemm(j[i].rows, H, 2 * H, op_dense(OP_KCONT, j[i].cat, 2 * H), op_dense(OP_KCONT, j[i].P + n->seg_off[AC_C_WL], 2 * H), j[i].h, H, TEPI_BIAS_RELU,
+                   j[i].P + n->seg_off[AC_C_BL]);
+  if ((rc = core_tgemm(&n->core, "jh_tgemm_dense", g, nj, st))) return rc;
+  for (int i = 0; i < nj; ++i)
+    g[i] = mk_gemm(j[i].rows, 1, H, op_dense(OP_KCONT, j[i].h, H), op_dense(OP_KCONT, j[i].P + n->seg_off[AC_C_WQ], H), j[i].q, 1, TEPI_BIAS, j[i].P + n->seg_off[AC_C_BQ]);
+  return core_tgemm(&n->core, "jh_tgemm_dense", g, nj, st);
+}
+
+inline float* ac_scat(const jh_acnet* n, int slot) { return n->s_cat + (size_t)slot * n->smax * 2 * n->H; }
+inline float* ac_sh(const jh_acnet* n, int slot) { return n->s_h + (size_t)slot * n->smax * n->H; }
+
+}  // namespace
+
+// Room for `rows` = N * R sampled rows in each of the two slots.  Allocates: once, outside any stream capture.
+JH_EXPORT int jh_acnet_reserve_sampled(jh_acnet* n, int32_t rows) {
+  JH_ARG(n && rows > 0 && (int64_t)rows * 2 * n->H < ((int64_t)1 << 31));  // the tile engine indexes in 32 bits
+  if (rows <= n->smax) return JH_OK;
+  if (n->smax) return jh_fail(JH_ERR_STATE, "jh_acnet_reserve_sampled: already reserved %d rows", n->smax);
+  JH_HIP(hipSetDevice(n->core.ctx->device));
+  int rc = core_alloc(&n->core, "jh_acnet", (void**)&n->s_cat, (size_t)2 * rows * 2 * n->H * sizeof(float), true);
+  if (!rc) rc = core_alloc(&n->core, "jh_acnet", (void**)&n->s_h, (size_t)2 * rows * n->H * sizeof(float), true);
+  if (!rc) rc = core_alloc(&n->core, "jh_acnet", (void**)&n->s_feat, (size_t)n->maxB * n->H * sizeof(float), true);
+  if (rc) return rc;
+  n->smax = rows;
+  return core_drain();
+}
+
+// critic 0 (which 0 online / 1 target) of d_x [R][S] over d_actions [N][R][A] -> d_q [N][R]: head.l(s) on R rows, then ac_jobs_run.  5 launches.
+JH_EXPORT int jh_acnet_critic_forward_sampled(jh_acnet* n, int32_t which, const float* d_x, const float* d_actions, int32_t R, int32_t N, float* d_q,
+                                              jh_stream stream) {
+  JH_ARG(n && d_x && d_actions && d_q);
+  JH_ARG(R > 0 && R <= n->maxB && N > 0 && (int64_t)N * R <= n->smax && (which == 0 || which == 1));
+  hipStream_t st = jh_s(stream);
+  const float* P = which == 0 ? n->cp : n->ct;
+  TGemm g[1] = {ac_head(n, P, AC_C_W1, AC_C_B1, d_x, R, n->s_feat, n->H)};
+  int rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 1, st);
+  if (rc) return rc;
+  const AcJob j{P, d_actions, N * R, ac_scat(n, 0), ac_sh(n, 0), d_q, n->s_feat, n->H};
+  return ac_jobs_run(n, &j, 1, R, st);
+}
+
+// Every critic forward of one MPO learn() (mpo.py:201, 219, 228-231, 261-263) in 5 grouped launches.  d_x = [state; next_state] (2R rows),
+// d_action [R][A] the stored action, d_a_next / d_a_add [N][R][A] the sampled ones -> d_q = online(s, a) and d_qt_a = target(s, a) [R],
+// d_qt_next = target(s', a_next) and d_qt_add = target(s, a_add) [N][R].  The target's head.l(s) serves both target(s, a) and the N samples
+// of a_add.  The online activations stay in set 0 for jh_acnet_critic_fit.
+JH_EXPORT int jh_acnet_mpo_forward(jh_acnet* n, const float* d_x, const float* d_action, const float* d_a_next, const float* d_a_add, int32_t R, int32_t N,
+                                   float* d_q, float* d_qt_a, float* d_qt_next, float* d_qt_add, jh_stream stream) {
+  JH_ARG(n && d_x && d_action && d_a_next && d_a_add && d_q && d_qt_a && d_qt_next && d_qt_add);
+  JH_ARG(n->nc == 1 && R > 0 && R <= n->maxB && N > 0 && (int64_t)N * R <= n->smax);
+  hipStream_t st = jh_s(stream);
+  const float* xs = d_x;
+  const float* xn = d_x + (size_t)R * n->S;
+  TGemm g[3] = {ac_c_head(n, n->cp, 0, 0, xs, R), ac_c_head(n, n->ct, 1, 0, xs, R), ac_head(n, n->ct, AC_C_W1, AC_C_B1, xn, R, n->s_feat, n->H)};
+  int rc = core_tgemm(&n->core, "jh_tgemm_dense", g, 3, st);
+  if (rc) return rc;
+  const AcJob j[4] = {{n->cp, d_action, R, ac_cat(n, 0, 0), ac_ch(n, 0, 0), d_q, nullptr, 0},
+                      {n->ct, d_action, R, ac_cat(n, 1, 0), ac_ch(n, 1, 0), d_qt_a, nullptr, 0},
+                      {n->ct, d_a_next, N * R, ac_scat(n, 0), ac_sh(n, 0), d_qt_next, n->s_feat, n->H},
+                      {n->ct, d_a_add, N * R, ac_scat(n, 1), ac_sh(n, 1), d_qt_add, ac_cat(n, 1, 0), 2 * n->H}};
+  return ac_jobs_run(n, j, 4, R, st);
+}
+
+// The critic's step from a gradient the caller supplies (MPO's loss kernel writes it): d_dq [R] = d(loss)/d(q) of the online(s, a) that the
+// last jh_acnet_mpo_forward left in set 0 -> the critic's backward, clip_grad_norm_(max_norm; <= 0: none) and Adam on the critic's own
+// optimizer block.  1 copy + 3 grouped launches + the optimizer's.
+JH_EXPORT int jh_acnet_critic_fit(jh_acnet* n, const float* d_x, const float* d_action, const float* d_dq, int32_t R, float max_norm, jh_stream stream) {
+  JH_ARG(n && d_x && d_action && d_dq);
+  JH_ARG(n->nc == 1 && R > 0 && R <= n->maxB);
+  hipStream_t st = jh_s(stream);
+  JH_HIP(hipMemcpyAsync(n->dq, d_dq, sizeof(float) * (size_t)R, hipMemcpyDeviceToDevice, st));
+  int rc = ac_critic_backward(n, R, d_x, d_action, true, 0, 1, st);
+  if (rc) return rc;
+  return jh_flat_adam_step(n->nC, n->cp, n->cg, n->cm, n->cv, n->opt_c.hyper, n->opt_c.ticket, n->core.norm_partial, max_norm > 0.f ? max_norm : 0.f, st);
+}

@@ -182,3 +182,251 @@ JH_EXPORT int jh_mpo_loss_discrete(jh_ctx* ctx, int32_t R, int32_t T, int32_t A,
   JH_LAUNCH_CHECK();
   return JH_OK;
 }
+
+// MPO, continuous policy (core/agent/mpo.py:199-309): the Gaussian policy's raw heads are [mu | log_std] rows of 2A floats with
+// mu = clamp(raw, -5, 5) and std = exp(tanh(raw)) (network/policy.py:53-55); N = num_sample actions per row come from two policies.
+//   jh_mpo_sample            one elementwise launch: zn = mu' + std' eps[0] from online(s'), zt_add = mut + stdt eps[1] from target(s), and their
+//                            tanh, each [N][R][A]                                                                    (mpo.py:221-226, 255-258)
+//   jh_mpo_loss_continuous   the discrete kernel's sibling, ONE launch of ONE workgroup, one row per thread:
+//     importance   z = atanh(clamp(a, -(1 - 1e-7), 1 - 1e-7)) of the stored action, c = min(exp(sum_A log N(z; mu, std)) / (prob_b + 1e-6), 1)
+//                  from the ONLINE policy                                                                            (mpo.py:203-206, 233)
+//     target       Qret = reward + gamma mean_n qt_next (1 - done) -> LDS, then the Retrace scan of the discrete kernel   (mpo.py:235-253)
+//     E-step       At = qt_add - mean_n qt_add, w = softmax_n(At / eta) (a constant), actor = -mean_r sum_n w log N(zt_add[n]; mu, std);
+//                  eta_loss = eta eps_eta + eta mean_r log mean_n exp(At / eta)                                      (mpo.py:265-278)
+//     trust region KLD_mu = 1/2 sum_A (mu - mu_old)^2 std_old^2, KLD_sigma = 1/2 (sum_A std^2 / std_old^2 - A + log(prod ss / prod ss_old)),
+//                  ss = 1 / std^2, each with its own multiplier and threshold                                        (mpo.py:280-309)
+//     gradients    with respect to the RAW heads of online(s) (zero in mu where the raw value lies outside [-5, 5], through 1 - tanh^2 for
+//                  log_std) and to q
+//     multipliers  eta, alpha_mu AND alpha_sigma step here (all three have a gradient), then the floors.
+// The [N][R] tables qt_next / qt_add and zt_add [N][R][A] stay in global memory: thread r reads element (n, r), so a wavefront's loads
+// are consecutive floats for every n, every element has exactly one reader and there is nothing for LDS to share; the second pass over
+// qt_add (at most 8192 floats in all) comes out of L2.  LDS holds the scan's per-row state only, as in the discrete kernel.
+// Departures on purpose: the log-mean of eta_loss is formed around the row's largest At / eta (finite where float32 exp overflows), and
+// the log of the product ratio in KLD_sigma is the sum of the logs, 2 sum_A (tanh_old - tanh): finite at any A, equal elsewhere.
+namespace {
+
+constexpr int kMaxSampled = 8192;    // N * R rows of the sampled tables
+constexpr int kMaxContActions = 8;   // A: the row's thread keeps two accumulators per action dimension in registers
+constexpr float kAtanhLo = -0.99999988f, kAtanhHi = 0.99999988f;  // (float)(1 - 1e-7): the reference clamps the float32 action tensor
+constexpr double kHalfLog2Pi = 0.91893853320467274178;
+
+// i over [N][R][A]; blockIdx.y 0: online(s') and eps[0] -> zn, a_next; 1: target(s) and eps[1] -> zt_add, a_add
+__global__ void __launch_bounds__(256) jh_mpo_sample_kernel(int n, int R, int A, const float* __restrict__ head_next, const float* __restrict__ head_old,
+                                                            const float* __restrict__ eps, float* __restrict__ zn, float* __restrict__ zt_add,
+                                                            float* __restrict__ a_next, float* __restrict__ a_add) {
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= n) return;
+  const int which = (int)blockIdx.y;
+  const int k = i % A, r = (i / A) % R;
+  const float* head = (which ? head_old : head_next) + (size_t)r * 2 * A;
+  const float mu = fminf(fmaxf(head[k], -5.f), 5.f);
+  const float sd = expf(tanhf(head[A + k]));
+  const float z = mu + sd * eps[(size_t)which * n + i];
+  (which ? zt_add : zn)[i] = z;
+  (which ? a_add : a_next)[i] = tanhf(z);
+}
+
+struct MpoContArgs {
+  int R, T, N, A, retrace;
+  const float *head, *head_old;      // [R][2A]
+  const float *q, *qt_a;             // [R]
+  const float *qt_next, *qt_add;     // [N][R]
+  const float* zt_add;               // [N][R][A]
+  const float* action;               // [R][A]
+  const float *reward, *done, *prob_b;  // [R]
+  float* blk;
+  const float* hyper;
+  float gamma;
+  float *g_head, *g_q;  // [R][2A], [R]
+  float* stats;
+};
+
+__global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_cont_kernel(MpoContArgs a) {
+  __shared__ double s_qret[kMaxRows];
+  __shared__ float s_c[kMaxRows], s_qta[kMaxRows], s_done[kMaxRows];
+  __shared__ double s_red[kMaxWaves][8];
+  __shared__ float s_ext[kMaxWaves][4];
+  const int i = threadIdx.x, R = a.R, T = a.T, N = a.N, A = a.A;
+  const bool on = i < R;
+  const float eta = a.blk[VB_VAL + 0], alpha_mu = a.blk[VB_VAL + 1], alpha_sigma = a.blk[VB_VAL + 2];
+  const float eps_eta = a.blk[VB_EPS + 0], eps_mu = a.blk[VB_EPS + 1], eps_sigma = a.blk[VB_EPS + 2];
+  const size_t o = (size_t)i * 2 * A;  // only dereferenced when `on`
+
+  // ---- per row: log pi(a) of the stored action, c, the one-step target
+  if (on) {
+    double logp = 0.0;
+    for (int k = 0; k < A; ++k) {
+      const double mu = fmin(fmax((double)a.head[o + k], -5.0), 5.0);
+      const double th = tanh((double)a.head[o + A + k]);
+      const float ac = fminf(fmaxf(a.action[(size_t)i * A + k], kAtanhLo), kAtanhHi);
+      const double dm = atanh((double)ac) - mu;
+      logp += -(dm * dm) / (2.0 * exp(2.0 * th)) - th - kHalfLog2Pi;  // Normal.log_prob, log(std) = tanh(log_std_raw)
+    }
+    const double ratio = exp(logp) / ((double)a.prob_b[i] + 1e-6);
+    double qn = 0.0;
+    for (int n = 0; n < N; ++n) qn += (double)a.qt_next[(size_t)n * R + i];
+    const float dn = a.done[i];
+    s_qret[i] = (double)a.reward[i] + (double)a.gamma * (qn / (double)N) * (1.0 - (double)dn);
+    s_c[i] = (float)(ratio < 1.0 ? ratio : 1.0);  // a NaN ratio stays out of the `<` and gives 1; torch.clip would keep it: the inputs are finite
+    s_qta[i] = a.qt_a[i];
+    s_done[i] = dn;
+  }
+  __syncthreads();
+
+  // ---- Retrace: one lane per trajectory, T - 1 dependent steps out of LDS (i < R / T: every index below stays under R)
+  if (a.retrace && T > 1 && i < R / T) {
+    const int base = i * T;
+    double nxt = s_qret[base + T - 1];
+    for (int t = T - 2; t >= 0; --t) {
+      const double cur = s_qret[base + t] + (double)a.gamma * (double)s_c[base + t + 1] * (nxt - (double)s_qta[base + t + 1]) * (1.0 - (double)s_done[base + t]);
+      s_qret[base + t] = cur;
+      nxt = cur;
+    }
+  }
+  __syncthreads();
+
+  // ---- per row: critic, advantage over the samples, E-step weights, actor, temperature and trust-region terms, head gradients
+  double crit = 0.0, act = 0.0, Lr = 0.0, wAt = 0.0, kl0 = 0.0, kl1 = 0.0;
+  float q_lo = INFINITY, q_hi = -INFINITY, at_lo = INFINITY, at_hi = -INFINITY;
+  if (on) {
+    const double inv_R = 1.0 / (double)R, d_eta = (double)eta;
+    const float qf = a.q[i];
+    const double dq = (double)qf - s_qret[i];
+    crit = dq * dq;
+    a.g_q[i] = (float)(2.0 * dq * inv_R);
+    q_lo = qf; q_hi = qf;
+    double V = 0.0;
+    for (int n = 0; n < N; ++n) V += (double)a.qt_add[(size_t)n * R + i];
+    V /= (double)N;
+    double xm = -INFINITY;
+    for (int n = 0; n < N; ++n) {
+      const double At = (double)a.qt_add[(size_t)n * R + i] - V;
+      xm = fmax(xm, At / d_eta);
+      const float Atf = (float)At;
+      at_lo = fminf(at_lo, Atf); at_hi = fmaxf(at_hi, Atf);
+    }
+    // sums over the samples of e = exp(At / eta - xm): e, e At, and per action dimension e dm and e dm^2 with dm = zt_add - mu
+    double sw = 0.0, s1[kMaxContActions], s2[kMaxContActions], mu[kMaxContActions];
+#pragma unroll
+    for (int k = 0; k < kMaxContActions; ++k) {
+      s1[k] = 0.0; s2[k] = 0.0;
+      mu[k] = k < A ? fmin(fmax((double)a.head[o + k], -5.0), 5.0) : 0.0;
+    }
+    for (int n = 0; n < N; ++n) {
+      const double At = (double)a.qt_add[(size_t)n * R + i] - V;
+      const double e = exp(At / d_eta - xm);
+      sw += e;
+      wAt += e * At;
+      const float* zt = a.zt_add + ((size_t)n * R + i) * A;
+#pragma unroll
+      for (int k = 0; k < kMaxContActions; ++k) {
+        if (k < A) {
+          const double dm = (double)zt[k] - mu[k];
+          s1[k] += e * dm;
+          s2[k] += e * dm * dm;
+        }
+      }
+    }
+    Lr = xm + log(sw / (double)N);
+    wAt /= sw;
+    const double c_mu = (double)alpha_mu * inv_R, c_sg = (double)alpha_sigma * inv_R;
+    double kls = 0.0;
+#pragma unroll
+    for (int k = 0; k < kMaxContActions; ++k) {
+      if (k < A) {
+        const float mr = a.head[o + k];
+        const double th = tanh((double)a.head[o + A + k]), var = exp(2.0 * th);
+        const double mu_o = fmin(fmax((double)a.head_old[o + k], -5.0), 5.0);
+        const double th_o = tanh((double)a.head_old[o + A + k]), var_o = exp(2.0 * th_o);
+        const double w1 = s1[k] / sw, w2 = s2[k] / sw;  // sum_n w dm, sum_n w dm^2
+        act += -w2 / (2.0 * var) - th - kHalfLog2Pi;    // sum_n w log N(zt_add[n]; mu, std) of this dimension (sum_n w = 1)
+        const double d = mu[k] - mu_o, ratio = var / var_o;
+        kl0 += d * d * var_o;                           // mpo.py:289-290: times the OLD variance, as written there
+        kls += ratio + 2.0 * (th_o - th);               // std^2 / std_old^2 + log(ss / ss_old) of this dimension, ss = exp(-2 th)
+        // d(-sum_n w logp): -w1 / var to mu, -(w2 / var - 1) to tanh; std' = std (1 - th^2) through exp(tanh(.))
+        const double g_mu = (-w1 / var) * inv_R + c_mu * d * var_o;
+        const double g_th = -(w2 / var - 1.0) * inv_R + c_sg * (ratio - 1.0);
+        a.g_head[o + k] = (mr >= -5.f && mr <= 5.f) ? (float)g_mu : 0.f;  // the clamp passes the gradient on its bounds
+        a.g_head[o + A + k] = (float)(g_th * (1.0 - th * th));
+      }
+    }
+    kl0 *= 0.5;
+    kl1 = 0.5 * (kls - (double)A);
+  }
+  // alpha_loss as written (mpo.py:291-309): mean of alpha (eps - KLD) + alpha KLD, for mu and for sigma
+  const double al = on ? ((double)alpha_mu * ((double)eps_mu - kl0) + (double)alpha_mu * kl0) +
+                             ((double)alpha_sigma * ((double)eps_sigma - kl1) + (double)alpha_sigma * kl1)
+                       : 0.0;
+  q_lo = jh_wave_min(q_lo); q_hi = jh_wave_max(q_hi); at_lo = jh_wave_min(at_lo); at_hi = jh_wave_max(at_hi);
+  if ((i & 63) == 0) {
+    s_ext[i >> 6][0] = q_lo; s_ext[i >> 6][1] = q_hi; s_ext[i >> 6][2] = at_lo; s_ext[i >> 6][3] = at_hi;
+  }
+  double s7[7] = {crit, act, Lr, wAt, kl0, kl1, al};
+  block_sums<7>(s7, s_red);  // its barriers publish s_ext too
+  if (i != 0) return;
+
+  // ---- one thread: the scalar losses, the three multipliers' gradients and steps, the statistics
+  const double n = (double)R, d_eta = (double)eta;
+  const double mean_L = s7[2] / n;
+  const double eta_loss = d_eta * (double)eps_eta + d_eta * mean_L;                    // mpo.py:276-278
+  const float g_eta = (float)((double)eps_eta + mean_L - (s7[3] / n) / d_eta);
+  const float g_mu = (float)((double)eps_mu - s7[4] / n);
+  const float g_sg = (float)((double)eps_sigma - s7[5] / n);
+  const float t = a.hyper[JH_HY_STEP] + 1.f;  // the step the actor's Adam takes for this learn (its optimizer pass advances it later)
+  const float eta_n = multiplier_step(a.blk, 0, g_eta, a.hyper, t);
+  const float mu_n = multiplier_step(a.blk, 1, g_mu, a.hyper, t);
+  const float sg_n = multiplier_step(a.blk, 2, g_sg, a.hyper, t);
+  if (a.stats) {
+    const int nw = ((int)blockDim.x + 63) >> 6;
+    for (int w = 1; w < nw; ++w) {
+      q_lo = fminf(q_lo, s_ext[w][0]); q_hi = fmaxf(q_hi, s_ext[w][1]); at_lo = fminf(at_lo, s_ext[w][2]); at_hi = fmaxf(at_hi, s_ext[w][3]);
+    }
+    a.stats[0] = (float)(-s7[1] / n);
+    a.stats[1] = (float)(s7[0] / n);
+    a.stats[2] = (float)eta_loss;
+    a.stats[3] = (float)(s7[6] / n);
+    a.stats[4] = eta_n;
+    a.stats[5] = mu_n;
+    a.stats[6] = sg_n;
+    a.stats[7] = q_lo;
+    a.stats[8] = q_hi;
+    a.stats[9] = at_lo;
+    a.stats[10] = at_hi;
+  }
+}
+
+inline bool mpo_cont_shape_ok(int R, int N, int A) {
+  return R >= 1 && R <= kMaxRows && N >= 1 && (int64_t)N * R <= kMaxSampled && A >= 1 && A <= kMaxContActions;
+}
+
+}  // namespace
+
+JH_EXPORT int jh_mpo_sample(jh_ctx* ctx, int32_t R, int32_t N, int32_t A, const float* d_head_next, const float* d_head_old, const float* d_eps, float* d_zn,
+                            float* d_zt_add, float* d_a_next, float* d_a_add, jh_stream stream) {
+  JH_ARG(ctx && d_head_next && d_head_old && d_eps && d_zn && d_zt_add && d_a_next && d_a_add);
+  JH_ARG(mpo_cont_shape_ok(R, N, A));
+  const int n = N * R * A;  // <= 8192 * 8
+  JH_LAUNCH(jh_mpo_sample_kernel, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, jh_s(stream), n, R, A, d_head_next, d_head_old, d_eps, d_zn, d_zt_add,
+            d_a_next, d_a_add);
+  JH_LAUNCH_CHECK();
+  return JH_OK;
+}
+
+JH_EXPORT int jh_mpo_loss_continuous(jh_ctx* ctx, int32_t R, int32_t T, int32_t N, int32_t A, const float* d_head, const float* d_head_old, const float* d_q,
+                                     const float* d_qt_a, const float* d_qt_next, const float* d_qt_add, const float* d_zt_add, const float* d_action,
+                                     const float* d_reward, const float* d_done, const float* d_prob_b, float* d_block, const float* d_hyper, float gamma,
+                                     int32_t retrace, float* d_grad_head, float* d_grad_q, float* d_stats, jh_stream stream) {
+  JH_ARG(ctx && d_head && d_head_old && d_q && d_qt_a && d_qt_next && d_qt_add && d_zt_add && d_action && d_reward && d_done && d_prob_b && d_block && d_hyper);
+  JH_ARG(d_grad_head && d_grad_q);
+  JH_ARG(mpo_cont_shape_ok(R, N, A) && T >= 1 && R % T == 0);
+  JH_ARG(retrace == 0 || retrace == 1);
+  JH_ARG(((uintptr_t)d_hyper & 7) == 0);
+  MpoContArgs a{};
+  a.R = R; a.T = T; a.N = N; a.A = A; a.retrace = retrace; a.head = d_head; a.head_old = d_head_old; a.q = d_q; a.qt_a = d_qt_a; a.qt_next = d_qt_next;
+  a.qt_add = d_qt_add; a.zt_add = d_zt_add; a.action = d_action; a.reward = d_reward; a.done = d_done; a.prob_b = d_prob_b; a.blk = d_block; a.hyper = d_hyper;
+  a.gamma = gamma; a.g_head = d_grad_head; a.g_q = d_grad_q; a.stats = d_stats;
+  const int threads = ((R + 63) / 64) * 64;
+  JH_LAUNCH(jh_mpo_loss_cont_kernel, dim3(1), dim3(threads), 0, jh_s(stream), a);
+  JH_LAUNCH_CHECK();
+  return JH_OK;
+}

@@ -687,6 +687,51 @@ def mpo_loss_discrete(la, la_next, la_old, q, qt, qt_next, action, reward, done,
     return g_la, g_q, stats
 
 
+MPO_MAX_ROWS, MPO_MAX_SAMPLED, MPO_MAX_CONT_ACTIONS = 1024, 8192, 8  # the caps of jh_mpo_sample / jh_mpo_loss_continuous: R, N * R, A
+
+
+def mpo_sample(head_next, head_old, eps, out=None):
+    """jh_mpo_sample: the raw Gaussian heads [mu | log_std] of online(s') and target(s), each [R, 2A], and standard normals eps [2, N, R, A].
+    out = (z [2, N, R, A], a [2, N, R, A]) to write into.  -> (zn, zt_add, a_next, a_add), each [N, R, A]: views of the two."""
+    hn, ho, eps = _f32(head_next), _f32(head_old), _f32(eps)
+    two, N, R, A = eps.shape
+    assert two == 2 and tuple(hn.shape) == tuple(ho.shape) == (R, 2 * A)
+    z, a = out if out is not None else (torch.empty_like(eps), torch.empty_like(eps))
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (2, N, R, A) for t in (z, a))
+    L.check(L.load().jh_mpo_sample(L.ctx(_dev(eps)), R, N, A, L.ptr(hn), L.ptr(ho), L.ptr(eps), L.ptr(z[0]), L.ptr(z[1]), L.ptr(a[0]), L.ptr(a[1]), L.stream_ptr()))
+    return z[0], z[1], a[0], a[1]
+
+
+def mpo_loss_continuous(head, head_old, q, qt_a, qt_next, qt_add, zt_add, action, reward, done, prob_b, T, block, hyper, gamma, retrace=True, stats=None, out=None):
+    """jh_mpo_loss_continuous: the raw heads [R, 2A] of online(s) and target(s), the critic's online q and target qt_a [R], the target critic over
+    the sampled actions qt_next / qt_add [N, R], zt_add [N, R, A], the stored action [R, A] and the replayed columns [R]; `block` and `hyper` as
+    mpo_loss_discrete (all three multipliers are advanced).  out = (grad_head, grad_q) to write into.
+    -> (grad_head [R, 2A], grad_q [R], stats f32[11] in the order of MPO_STATS)."""
+    h, ho, zt, act = _f32(head), _f32(head_old), _f32(zt_add), _f32(action)
+    N, R, A = zt.shape
+    assert tuple(h.shape) == tuple(ho.shape) == (R, 2 * A) and act.numel() == R * A
+    qn, qa = _f32(qt_next).reshape(N, -1), _f32(qt_add).reshape(N, -1)
+    assert tuple(qn.shape) == tuple(qa.shape) == (N, R)
+    cols = [_f32(v).reshape(-1) for v in (reward, done, prob_b)]
+    q, qt_a = _f32(q).reshape(-1), _f32(qt_a).reshape(-1)
+    assert all(v.numel() == R for v in cols + [q, qt_a])
+    assert block.dtype == torch.float32 and block.numel() == VMPO_BLOCK_FLOATS and block.is_contiguous()
+    if torch.is_tensor(hyper):
+        assert hyper.dtype == torch.float32 and hyper.numel() >= 16 and hyper.is_contiguous() and hyper.device == h.device
+        hyper_ptr = C.c_void_p(hyper.data_ptr())
+    else:
+        hyper_ptr = C.c_void_p(int(hyper))
+    g_h, g_q = out if out is not None else (torch.empty_like(h), torch.empty_like(q))
+    assert g_h.is_contiguous() and g_q.is_contiguous() and g_h.numel() == R * 2 * A and g_q.numel() == R and g_h.dtype == g_q.dtype == torch.float32
+    if stats is None:
+        stats = torch.zeros(len(MPO_STATS), dtype=torch.float32, device=h.device)
+    assert stats.dtype == torch.float32 and stats.numel() >= len(MPO_STATS) and stats.is_contiguous()
+    L.check(L.load().jh_mpo_loss_continuous(L.ctx(_dev(h)), R, int(T), N, A, L.ptr(h), L.ptr(ho), L.ptr(q), L.ptr(qt_a), L.ptr(qn), L.ptr(qa), L.ptr(zt), L.ptr(act),
+                                            *(L.ptr(v) for v in cols), L.ptr(block), hyper_ptr, float(gamma), int(bool(retrace)), L.ptr(g_h), L.ptr(g_q),
+                                            L.ptr(stats), L.stream_ptr()))
+    return g_h, g_q, stats
+
+
 # ============================================================================= REINFORCE
 REINFORCE_MAX_ROWS = 65536  # JH_REINFORCE_MAX_ROWS: the rows of one episode that one learn() takes
 REINFORCE_STATS = ("loss", "rows")
@@ -2015,6 +2060,45 @@ class ACNet(_ActorCriticBuckets):
         B = int(x.shape[0])
         assert x.is_contiguous() and x.dtype == torch.float32 and x.shape[1] == self.S and (action_pred is None or action_pred.numel() == B * self.A)
         L.check(self.lib.jh_acnet_actor_update(self.h, L.ptr(x), B, L.ptr(action_pred), L.ptr(stats), L.stream_ptr()))
+
+    # ---- critic 0 over sampled actions (continuous MPO)
+    def reserve_sampled(self, rows):
+        """Room for rows = N * R sampled rows (two slots); allocates: once, outside any capture."""
+        L.check(self.lib.jh_acnet_reserve_sampled(self.h, int(rows)))
+
+    def critic_forward_sampled(self, x, actions, which=0, out=None):
+        """critic 0 of x [R, S] over actions [N, R, A] -> [N, R]; head.l(s) runs once per state row."""
+        N, R, A = (int(v) for v in actions.shape)
+        for t in (x, actions):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device
+        assert tuple(x.shape) == (R, self.S) and A == self.A
+        out = torch.empty(N, R, dtype=torch.float32, device=self.device) if out is None else out
+        assert out.is_contiguous() and out.numel() == N * R and out.dtype == torch.float32
+        L.check(self.lib.jh_acnet_critic_forward_sampled(self.h, int(which), L.ptr(x), L.ptr(actions), R, N, L.ptr(out), L.stream_ptr()))
+        return out
+
+    def mpo_forward(self, x_all, action, a_next, a_add, out=None):
+        """x_all = [state; next_state] (2R rows), action [R, A], a_next / a_add [N, R, A].  out = (q [R], qt_a [R], qt_next [N, R], qt_add [N, R])
+        to write into -> the four: online(s, a), target(s, a), target(s', a_next), target(s, a_add)."""
+        N, R, A = (int(v) for v in a_next.shape)
+        for t in (x_all, action, a_next, a_add):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device
+        assert tuple(x_all.shape) == (2 * R, self.S) and action.numel() == R * self.A and A == self.A and tuple(a_add.shape) == (N, R, A)
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
+        q, qt_a, qt_next, qt_add = out if out is not None else (f(R), f(R), f(N, R), f(N, R))
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (q, qt_a, qt_next, qt_add))
+        assert q.numel() == qt_a.numel() == R and qt_next.numel() == qt_add.numel() == N * R
+        L.check(self.lib.jh_acnet_mpo_forward(self.h, L.ptr(x_all), L.ptr(action), L.ptr(a_next), L.ptr(a_add), R, N, L.ptr(q), L.ptr(qt_a), L.ptr(qt_next),
+                                              L.ptr(qt_add), L.stream_ptr()))
+        return q, qt_a, qt_next, qt_add
+
+    def critic_fit(self, x, action, dq, max_norm=0.0):
+        """The critic's backward from dq [R] (of the online q the last mpo_forward produced), clip_grad_norm_(max_norm) and its Adam step."""
+        R = int(dq.numel())
+        for t in (x, action, dq):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device
+        assert tuple(x.shape) == (R, self.S) and action.numel() == R * self.A
+        L.check(self.lib.jh_acnet_critic_fit(self.h, L.ptr(x), L.ptr(action), L.ptr(dq), R, float(max_norm or 0.0), L.stream_ptr()))
 
 
 SAC_ALPHA_FLOATS = 16

@@ -9,7 +9,15 @@ own per-kernel timers over one eager learn), and single-mode env steps/s: act() 
 per env step, as MPO.process does.  In the same process, alternating with it, Agent("dqn") at the same observation and hidden size with
 B 64: ONE network, three forwards and one learn per env step, next to MPO's two networks, six forwards and n_epoch learns.  One JSON line.
 
-    python tools/bench_mpo.py [--updates 300] [--steps 60] [--rounds 3] [--shapes cartpole,default]
+    python tools/bench_mpo.py [--updates 300] [--steps 60] [--rounds 3] [--shapes cartpole,default] [--continuous [--curve]]
+
+--continuous adds, on the same JSON line, the continuous agent (actor continuous_policy, critic continuous_q_network, num_sample 30) at
+
+  pendulum        config.mpo.pendulum: S 3, A 1, hidden 512, B 64 trajectories of T 4 (256 rows, 7680 sampled rows), Retrace
+  hopper_mlagent  config.mpo.hopper_mlagent: S 76, A 3, hidden 512, B 32, 1step_TD (32 rows, 960 sampled rows)
+
+alternating in the same process with the discrete agent at `cartpole`: learn() in ms and the launches of one learn.  --curve adds three seeds of it
+on the control env (tests/mpo_cont_truth.py's CURVE_CONFIG) next to the reference's curves of tests/golden/curves_reference_mpo_continuous.json.
 """
 import argparse
 import json
@@ -27,6 +35,46 @@ SHAPES = {
     "default": dict(batch_size=64, n_step=8, n_epoch=64),
 }
 S, A, FILL = 4, 2, 2048
+CONTINUOUS = {
+    "pendulum": dict(state_size=3, action_size=1, batch_size=64, n_step=4, n_epoch=64, critic_loss_type="retrace"),
+    "hopper_mlagent": dict(state_size=76, action_size=3, batch_size=32, n_step=1, n_epoch=64, critic_loss_type="1step_TD"),
+}
+
+
+def make_continuous(shape):
+    from jorldy_amd.core.agent import Agent
+
+    rng = np.random.RandomState(1)
+    kw = dict(CONTINUOUS[shape], hidden_size=512, head="mlp", actor="continuous_policy", critic="continuous_q_network", optim_config={"name": "adam", "lr": 2.5e-4},
+              gamma=0.99, buffer_size=4096, start_train_step=0, run_step=1_000_000, num_sample=30, device="cuda")
+    agent = Agent("mpo", **kw)
+    T, s, a = agent.n_step, kw["state_size"], kw["action_size"]
+    agent.memory.first_store = False
+    agent.memory.store_soa({"state": rng.randn(FILL, T, s).astype(np.float32), "action": np.tanh(rng.randn(FILL, T, a)).astype(np.float32),
+                            "reward": rng.choice([0.1, -1.0], size=(FILL, T, 1)).astype(np.float32), "next_state": rng.randn(FILL, T, s).astype(np.float32),
+                            "done": rng.rand(FILL, T, 1) < 0.02, "prob": rng.uniform(0.05, 0.7, size=(FILL, T, 1)).astype(np.float32)})
+    return agent
+
+
+def continuous_leg(args):
+    """learn() of the continuous agent at the reference's two continuous shapes, the discrete agent at `cartpole` next to it in the same process."""
+    res = {}
+    discrete, _ = make_agent("mpo", "cartpole")
+    time_learn(discrete, args.warmup)
+    for shape in CONTINUOUS:
+        agent = make_continuous(shape)
+        time_learn(agent, args.warmup)
+        learn = {"continuous": [], "discrete_cartpole": []}
+        for _ in range(args.rounds):
+            learn["continuous"].append(time_learn(agent, args.updates))
+            learn["discrete_cartpole"].append(time_learn(discrete, args.updates))
+        per, total = launches(agent)
+        res[shape] = {"learn_ms": round(float(np.median(learn["continuous"])) * 1e3, 4), "rows": agent.batch_size * agent.n_step,
+                      "sampled_rows": agent.num_sample * agent.batch_size * agent.n_step, "launches_per_learn": total, "launches_of_one_learn": per,
+                      "learn_in_hipgraph": agent._graph is not None, "learn_ms_rounds": [round(v * 1e3, 4) for v in learn["continuous"]],
+                      "discrete_cartpole_learn_ms": round(float(np.median(learn["discrete_cartpole"])) * 1e3, 4)}
+        del agent
+    return res
 
 
 def make_agent(name, shape):
@@ -86,6 +134,35 @@ def launches(agent):
     return per, sum(per.values())
 
 
+def continuous_curve():
+    """The continuous agent in MPO's single-mode loop on the control env (ops.ControlVec, the oracle's dynamics) at tests/mpo_cont_truth.py's
+    CURVE_CONFIG, one curve per seed, next to the unmodified reference's curves of tests/golden/curves_reference_mpo_continuous.json
+    (tools/gen_golden_mpo_continuous.py --only curves): first and last tenth of each."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mpo_cont_truth as D
+
+    from jorldy_amd import ops
+    from jorldy_amd.core.agent import Agent
+
+    c = D.CURVE_CONFIG
+    hip = []
+    for seed in c["seeds"]:
+        np.random.seed(seed)
+        torch.manual_seed(seed)
+        agent = Agent("mpo", run_step=c["run_step"], device="cuda", **c["agent"])
+        agent.memory.first_store = False
+        hip.append([round(v, 4) for v in D.control_curve(agent, ops.ControlVec(1, c["S"], c["A"], seed=1000 + seed), c["steps"], c["bin"])])
+    out = {"config": json.loads(json.dumps(c)), "hip": hip, "hip_first_last_tenth": [D.curve_tenths(v) for v in hip]}
+    path = os.path.join(D.GOLDEN, "curves_reference_mpo_continuous.json")
+    if os.path.exists(path):
+        with open(path) as f:
+            fx = json.load(f)
+        ref = fx["mpo_control"]["reference"]
+        out["reference_config_matches"] = fx["config"] == out["config"]
+        out["reference_first_last_tenth"] = [D.curve_tenths(v) for v in ref]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--updates", type=int, default=300)
@@ -93,6 +170,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3, help="alternations mpo / dqn; the median is reported")
     ap.add_argument("--shapes", default="cartpole,default")
+    ap.add_argument("--continuous", action="store_true", help="add the continuous agent at config.mpo.pendulum's and config.mpo.hopper_mlagent's shapes")
+    ap.add_argument("--curve", action="store_true", help="with --continuous: three seeds of the continuous agent on the control env next to the reference's curves")
     args = ap.parse_args()
     out = {"tool": "tools/bench_mpo.py", "updates": args.updates, "steps": args.steps, "rounds": args.rounds, "shapes": {}}
     if torch.cuda.is_available():
@@ -125,6 +204,10 @@ def main():
             res["mpo_over_dqn_learn"] = round(res["mpo"]["learn_ms"] / res["dqn"]["learn_ms"], 3)
             out["shapes"][shape] = res
             del agents
+        if args.continuous:
+            out["continuous"] = continuous_leg(args)
+            if args.curve:
+                out["continuous_curve"] = continuous_curve()
     else:
         out["device"] = None
     line = json.dumps(out)
