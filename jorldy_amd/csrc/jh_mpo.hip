@@ -20,6 +20,7 @@
 // exp(At / eta) is finite, and stays finite where that overflows.
 #include "jh_common.h"
 #include "jh_mult.h"
+#include "jh_policy_head.h"  // the categorical row, the squashed-Gaussian head element, its trust region, alpha_loss_row
 
 namespace {
 
@@ -38,13 +39,59 @@ struct MpoArgs {
   float* stats;       // [11] or null
 };
 
-// log-softmax pieces of one row: -> the row's log-sum-exp
-__device__ __forceinline__ double row_lse(const float* z, int A) {
-  float zm = z[0];
-  for (int k = 1; k < A; ++k) zm = fmaxf(zm, z[k]);
-  double se = 0.0;
-  for (int k = 0; k < A; ++k) se += exp((double)z[k] - (double)zm);
-  return (double)zm + log(se);
+// ---- shared by the two loss kernels.  The multipliers and their thresholds as the launch finds them:
+struct Mult { float eta, alpha_mu, alpha_sigma, eps_eta, eps_mu, eps_sigma; };
+__device__ __forceinline__ Mult mult_load(const float* b) { return Mult{b[VB_VAL], b[VB_VAL + 1], b[VB_VAL + 2], b[VB_EPS], b[VB_EPS + 1], b[VB_EPS + 2]}; }
+
+// Retrace (mpo.py:347-355, 245-253): one lane per trajectory, T - 1 dependent steps out of LDS (i < R / T: every index below stays under R).
+// The caller's barriers stand before and after it.
+__device__ __forceinline__ void retrace_scan(double* s_qret, const float* s_c, const float* s_qta, const float* s_done, int retrace, int R, int T, float gamma) {
+  const int i = threadIdx.x;
+  if (retrace && T > 1 && i < R / T) {
+    const int base = i * T;
+    double nxt = s_qret[base + T - 1];
+    for (int t = T - 2; t >= 0; --t) {
+      const double cur = s_qret[base + t] + (double)gamma * (double)s_c[base + t + 1] * (nxt - (double)s_qta[base + t + 1]) * (1.0 - (double)s_done[base + t]);
+      s_qret[base + t] = cur;
+      nxt = cur;
+    }
+  }
+}
+
+// the exact extrema of q and At: a row's own, then its wave's (published through s_ext), then thread 0's fold over the waves
+struct Extrema { float q_lo = INFINITY, q_hi = -INFINITY, at_lo = INFINITY, at_hi = -INFINITY; };
+__device__ __forceinline__ void extrema_publish(Extrema& x, float (*s_ext)[4]) {
+  const int i = threadIdx.x;
+  x.q_lo = jh_wave_min(x.q_lo); x.q_hi = jh_wave_max(x.q_hi); x.at_lo = jh_wave_min(x.at_lo); x.at_hi = jh_wave_max(x.at_hi);
+  if ((i & 63) == 0) {
+    s_ext[i >> 6][0] = x.q_lo; s_ext[i >> 6][1] = x.q_hi; s_ext[i >> 6][2] = x.at_lo; s_ext[i >> 6][3] = x.at_hi;
+  }
+}
+
+// Thread 0, after block_sums: the scalar losses, the multipliers' gradients and steps, the statistics in MPO_STATS order.  alpha_sigma
+// steps only where it has a gradient (`step_sigma`: the continuous policy); the discrete kernel reports the block's value.  `a`: either
+// kernel's arguments (R, blk, hyper, stats); s: the workgroup's sums of the rows' terms.
+struct MpoSums { double crit, act, L, wAt, kl_mu, kl_sigma, al; };
+template <typename Args>
+__device__ __forceinline__ void mpo_finish(const Args& a, const Mult& m, const MpoSums& s, bool step_sigma, Extrema x, const float (*s_ext)[4]) {
+  const double n = (double)a.R, d_eta = (double)m.eta;
+  const double mean_L = s.L / n;
+  const double eta_loss = d_eta * (double)m.eps_eta + d_eta * mean_L;  // mpo.py:276-278, 370-372
+  const float g_eta = (float)((double)m.eps_eta + mean_L - (s.wAt / n) / d_eta);
+  const float g_mu = (float)((double)m.eps_mu - s.kl_mu / n);
+  const float g_sg = (float)((double)m.eps_sigma - s.kl_sigma / n);
+  const float t = a.hyper[JH_HY_STEP] + 1.f;  // the step the actor's Adam takes for this learn (its optimizer pass advances it later)
+  const float eta_n = multiplier_step(a.blk, 0, g_eta, a.hyper, t);
+  const float mu_n = multiplier_step(a.blk, 1, g_mu, a.hyper, t);
+  const float sg_n = step_sigma ? multiplier_step(a.blk, 2, g_sg, a.hyper, t) : m.alpha_sigma;
+  if (float* stats = a.stats) {
+    const int nw = ((int)blockDim.x + 63) >> 6;
+    for (int w = 1; w < nw; ++w) {
+      x.q_lo = fminf(x.q_lo, s_ext[w][0]); x.q_hi = fmaxf(x.q_hi, s_ext[w][1]); x.at_lo = fminf(x.at_lo, s_ext[w][2]); x.at_hi = fmaxf(x.at_hi, s_ext[w][3]);
+    }
+    const float out[11] = {(float)(-s.act / n), (float)(s.crit / n), (float)eta_loss, (float)(s.al / n), eta_n, mu_n, sg_n, x.q_lo, x.q_hi, x.at_lo, x.at_hi};
+    for (int j = 0; j < 11; ++j) stats[j] = out[j];
+  }
 }
 
 __global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_kernel(MpoArgs a) {
@@ -54,8 +101,7 @@ __global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_kernel(MpoArgs a) {
   __shared__ float s_ext[kMaxWaves][4];
   const int i = threadIdx.x, R = a.R, T = a.T, A = a.A;
   const bool on = i < R;
-  const float eta = a.blk[VB_VAL + 0], alpha_mu = a.blk[VB_VAL + 1], alpha_sigma = a.blk[VB_VAL + 2];
-  const float eps_eta = a.blk[VB_EPS + 0], eps_mu = a.blk[VB_EPS + 1];
+  const Mult m = mult_load(a.blk);
   const size_t o = (size_t)i * A;  // only dereferenced when `on`
 
   // ---- per row: the policies' log-sums, c, the one-step target
@@ -65,8 +111,7 @@ __global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_kernel(MpoArgs a) {
     lse = row_lse(a.la + o, A);
     lse_old = row_lse(a.la_old + o, A);
     const double lse_next = row_lse(a.la_next + o, A);
-    ak = (int)a.action[i];
-    ak = ak < 0 ? 0 : (ak >= A ? A - 1 : ak);
+    ak = action_index(a.action[i], A);
     const double pa = exp((double)a.la[o + ak] - lse);
     const double ratio = pa / ((double)a.prob_b[i] + 1e-6);
     double ev = 0.0;
@@ -79,23 +124,14 @@ __global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_kernel(MpoArgs a) {
   }
   __syncthreads();
 
-  // ---- Retrace: one lane per trajectory, T - 1 dependent steps out of LDS (i < R / T: every index below stays under R)
-  if (a.retrace && T > 1 && i < R / T) {
-    const int base = i * T;
-    double nxt = s_qret[base + T - 1];
-    for (int t = T - 2; t >= 0; --t) {
-      const double cur = s_qret[base + t] + (double)a.gamma * (double)s_c[base + t + 1] * (nxt - (double)s_qta[base + t + 1]) * (1.0 - (double)s_done[base + t]);
-      s_qret[base + t] = cur;
-      nxt = cur;
-    }
-  }
+  retrace_scan(s_qret, s_c, s_qta, s_done, a.retrace, R, T, a.gamma);
   __syncthreads();
 
   // ---- per row: critic, advantage, E-step weights, actor, temperature and trust-region terms, head gradients
   double crit = 0.0, act = 0.0, Lr = 0.0, uAt = 0.0, kld = 0.0;
-  float q_lo = INFINITY, q_hi = -INFINITY, at_lo = INFINITY, at_hi = -INFINITY;
+  Extrema x;
   if (on) {
-    const double inv_R = 1.0 / (double)R, d_eta = (double)eta;
+    const double inv_R = 1.0 / (double)R, d_eta = (double)m.eta;
     const double dq = (double)a.q[o + ak] - s_qret[i];
     crit = dq * dq;
     double V = 0.0;
@@ -118,48 +154,19 @@ __global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_kernel(MpoArgs a) {
       act += w * lp;
       uAt += (po * e / su) * At;
       kld += po * (lpo - lp);
-      a.g_la[o + k] = (float)(((pk - w) + (double)alpha_mu * (pk - po)) * inv_R);
+      a.g_la[o + k] = (float)(((pk - w) + (double)m.alpha_mu * (pk - po)) * inv_R);
       a.g_q[o + k] = k == ak ? (float)(2.0 * dq * inv_R) : 0.f;
-      q_lo = fminf(q_lo, qk); q_hi = fmaxf(q_hi, qk);
+      x.q_lo = fminf(x.q_lo, qk); x.q_hi = fmaxf(x.q_hi, qk);
       const float Atf = (float)At;
-      at_lo = fminf(at_lo, Atf); at_hi = fmaxf(at_hi, Atf);
+      x.at_lo = fminf(x.at_lo, Atf); x.at_hi = fmaxf(x.at_hi, Atf);
     }
   }
-  const double al = on ? ((double)alpha_mu * ((double)eps_mu - kld) + (double)alpha_mu * kld) : 0.0;  // mpo.py:381-384 as written
-  q_lo = jh_wave_min(q_lo); q_hi = jh_wave_max(q_hi); at_lo = jh_wave_min(at_lo); at_hi = jh_wave_max(at_hi);
-  if ((i & 63) == 0) {
-    s_ext[i >> 6][0] = q_lo; s_ext[i >> 6][1] = q_hi; s_ext[i >> 6][2] = at_lo; s_ext[i >> 6][3] = at_hi;
-  }
+  const double al = on ? alpha_loss_row(m.alpha_mu, m.eps_mu, kld) : 0.0;
+  extrema_publish(x, s_ext);
   double s6[6] = {crit, act, Lr, uAt, kld, al};
   block_sums<6>(s6, s_red);  // its barriers publish s_ext too
   if (i != 0) return;
-
-  // ---- one thread: the scalar losses, the multipliers' gradients and steps, the statistics
-  const double n = (double)R, d_eta = (double)eta;
-  const double mean_L = s6[2] / n;
-  const double eta_loss = d_eta * (double)eps_eta + d_eta * mean_L;                    // mpo.py:370-372
-  const float g_eta = (float)((double)eps_eta + mean_L - (s6[3] / n) / d_eta);
-  const float g_mu = (float)((double)eps_mu - s6[4] / n);
-  const float t = a.hyper[JH_HY_STEP] + 1.f;  // the step the actor's Adam takes for this learn (its optimizer pass advances it later)
-  const float eta_n = multiplier_step(a.blk, 0, g_eta, a.hyper, t);
-  const float mu_n = multiplier_step(a.blk, 1, g_mu, a.hyper, t);
-  if (a.stats) {
-    const int nw = ((int)blockDim.x + 63) >> 6;
-    for (int w = 1; w < nw; ++w) {
-      q_lo = fminf(q_lo, s_ext[w][0]); q_hi = fmaxf(q_hi, s_ext[w][1]); at_lo = fminf(at_lo, s_ext[w][2]); at_hi = fmaxf(at_hi, s_ext[w][3]);
-    }
-    a.stats[0] = (float)(-s6[1] / n);
-    a.stats[1] = (float)(s6[0] / n);
-    a.stats[2] = (float)eta_loss;
-    a.stats[3] = (float)(s6[5] / n);
-    a.stats[4] = eta_n;
-    a.stats[5] = mu_n;
-    a.stats[6] = alpha_sigma;
-    a.stats[7] = q_lo;
-    a.stats[8] = q_hi;
-    a.stats[9] = at_lo;
-    a.stats[10] = at_hi;
-  }
+  mpo_finish(a, m, MpoSums{s6[0], s6[1], s6[2], s6[3], s6[4], 0.0, s6[5]}, false, x, s_ext);
 }
 
 }  // namespace
@@ -188,7 +195,7 @@ JH_EXPORT int jh_mpo_loss_discrete(jh_ctx* ctx, int32_t R, int32_t T, int32_t A,
 //   jh_mpo_sample            one elementwise launch: zn = mu' + std' eps[0] from online(s'), zt_add = mut + stdt eps[1] from target(s), and their
 //                            tanh, each [N][R][A]                                                                    (mpo.py:221-226, 255-258)
 //   jh_mpo_loss_continuous   the discrete kernel's sibling, ONE launch of ONE workgroup, one row per thread:
-//     importance   z = atanh(clamp(a, -(1 - 1e-7), 1 - 1e-7)) of the stored action, c = min(exp(sum_A log N(z; mu, std)) / (prob_b + 1e-6), 1)
+//     importance   z = the pre-tanh value of the stored action (jh_policy_head.h's gauss_z), c = min(exp(sum_A log N(z; mu, std)) / (prob_b + 1e-6), 1)
 //                  from the ONLINE policy                                                                            (mpo.py:203-206, 233)
 //     target       Qret = reward + gamma mean_n qt_next (1 - done) -> LDS, then the Retrace scan of the discrete kernel   (mpo.py:235-253)
 //     E-step       At = qt_add - mean_n qt_add, w = softmax_n(At / eta) (a constant), actor = -mean_r sum_n w log N(zt_add[n]; mu, std);
@@ -207,8 +214,6 @@ namespace {
 
 constexpr int kMaxSampled = 8192;    // N * R rows of the sampled tables
 constexpr int kMaxContActions = 8;   // A: the row's thread keeps two accumulators per action dimension in registers
-constexpr float kAtanhLo = -0.99999988f, kAtanhHi = 0.99999988f;  // (float)(1 - 1e-7): the reference clamps the float32 action tensor
-constexpr double kHalfLog2Pi = 0.91893853320467274178;
 
 // i over [N][R][A]; blockIdx.y 0: online(s') and eps[0] -> zn, a_next; 1: target(s) and eps[1] -> zt_add, a_add
 __global__ void __launch_bounds__(256) jh_mpo_sample_kernel(int n, int R, int A, const float* __restrict__ head_next, const float* __restrict__ head_old,
@@ -248,19 +253,15 @@ __global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_cont_kernel(MpoContArgs 
   __shared__ float s_ext[kMaxWaves][4];
   const int i = threadIdx.x, R = a.R, T = a.T, N = a.N, A = a.A;
   const bool on = i < R;
-  const float eta = a.blk[VB_VAL + 0], alpha_mu = a.blk[VB_VAL + 1], alpha_sigma = a.blk[VB_VAL + 2];
-  const float eps_eta = a.blk[VB_EPS + 0], eps_mu = a.blk[VB_EPS + 1], eps_sigma = a.blk[VB_EPS + 2];
+  const Mult m = mult_load(a.blk);
   const size_t o = (size_t)i * 2 * A;  // only dereferenced when `on`
 
   // ---- per row: log pi(a) of the stored action, c, the one-step target
   if (on) {
     double logp = 0.0;
     for (int k = 0; k < A; ++k) {
-      const double mu = fmin(fmax((double)a.head[o + k], -5.0), 5.0);
-      const double th = tanh((double)a.head[o + A + k]);
-      const float ac = fminf(fmaxf(a.action[(size_t)i * A + k], kAtanhLo), kAtanhHi);
-      const double dm = atanh((double)ac) - mu;
-      logp += -(dm * dm) / (2.0 * exp(2.0 * th)) - th - kHalfLog2Pi;  // Normal.log_prob, log(std) = tanh(log_std_raw)
+      const GaussElem e = gauss_elem(a.head[o + k], a.head[o + A + k]);
+      logp += gauss_log_prob(gauss_z(a.action[(size_t)i * A + k]) - e.mu, e.th, e.var);
     }
     const double ratio = exp(logp) / ((double)a.prob_b[i] + 1e-6);
     double qn = 0.0;
@@ -273,28 +274,19 @@ __global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_cont_kernel(MpoContArgs 
   }
   __syncthreads();
 
-  // ---- Retrace: one lane per trajectory, T - 1 dependent steps out of LDS (i < R / T: every index below stays under R)
-  if (a.retrace && T > 1 && i < R / T) {
-    const int base = i * T;
-    double nxt = s_qret[base + T - 1];
-    for (int t = T - 2; t >= 0; --t) {
-      const double cur = s_qret[base + t] + (double)a.gamma * (double)s_c[base + t + 1] * (nxt - (double)s_qta[base + t + 1]) * (1.0 - (double)s_done[base + t]);
-      s_qret[base + t] = cur;
-      nxt = cur;
-    }
-  }
+  retrace_scan(s_qret, s_c, s_qta, s_done, a.retrace, R, T, a.gamma);
   __syncthreads();
 
   // ---- per row: critic, advantage over the samples, E-step weights, actor, temperature and trust-region terms, head gradients
   double crit = 0.0, act = 0.0, Lr = 0.0, wAt = 0.0, kl0 = 0.0, kl1 = 0.0;
-  float q_lo = INFINITY, q_hi = -INFINITY, at_lo = INFINITY, at_hi = -INFINITY;
+  Extrema x;
   if (on) {
-    const double inv_R = 1.0 / (double)R, d_eta = (double)eta;
+    const double inv_R = 1.0 / (double)R, d_eta = (double)m.eta;
     const float qf = a.q[i];
     const double dq = (double)qf - s_qret[i];
     crit = dq * dq;
     a.g_q[i] = (float)(2.0 * dq * inv_R);
-    q_lo = qf; q_hi = qf;
+    x.q_lo = qf; x.q_hi = qf;
     double V = 0.0;
     for (int n = 0; n < N; ++n) V += (double)a.qt_add[(size_t)n * R + i];
     V /= (double)N;
@@ -303,14 +295,14 @@ __global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_cont_kernel(MpoContArgs 
       const double At = (double)a.qt_add[(size_t)n * R + i] - V;
       xm = fmax(xm, At / d_eta);
       const float Atf = (float)At;
-      at_lo = fminf(at_lo, Atf); at_hi = fmaxf(at_hi, Atf);
+      x.at_lo = fminf(x.at_lo, Atf); x.at_hi = fmaxf(x.at_hi, Atf);
     }
     // sums over the samples of e = exp(At / eta - xm): e, e At, and per action dimension e dm and e dm^2 with dm = zt_add - mu
     double sw = 0.0, s1[kMaxContActions], s2[kMaxContActions], mu[kMaxContActions];
 #pragma unroll
     for (int k = 0; k < kMaxContActions; ++k) {
       s1[k] = 0.0; s2[k] = 0.0;
-      mu[k] = k < A ? fmin(fmax((double)a.head[o + k], -5.0), 5.0) : 0.0;
+      mu[k] = k < A ? gauss_mu(a.head[o + k]) : 0.0;
     }
     for (int n = 0; n < N; ++n) {
       const double At = (double)a.qt_add[(size_t)n * R + i] - V;
@@ -329,70 +321,33 @@ __global__ void __launch_bounds__(kMaxRows) jh_mpo_loss_cont_kernel(MpoContArgs 
     }
     Lr = xm + log(sw / (double)N);
     wAt /= sw;
-    const double c_mu = (double)alpha_mu * inv_R, c_sg = (double)alpha_sigma * inv_R;
+    const double c_mu = (double)m.alpha_mu * inv_R, c_sg = (double)m.alpha_sigma * inv_R;
     double kls = 0.0;
 #pragma unroll
     for (int k = 0; k < kMaxContActions; ++k) {
       if (k < A) {
-        const float mr = a.head[o + k];
-        const double th = tanh((double)a.head[o + A + k]), var = exp(2.0 * th);
-        const double mu_o = fmin(fmax((double)a.head_old[o + k], -5.0), 5.0);
-        const double th_o = tanh((double)a.head_old[o + A + k]), var_o = exp(2.0 * th_o);
+        GaussElem e = gauss_elem(a.head[o + k], a.head[o + A + k]);
+        e.mu = mu[k];  // the same value, already in a register: the clamp is not evaluated a second time
+        const GaussTrust tr = gauss_trust(e, gauss_elem(a.head_old[o + k], a.head_old[o + A + k]));
         const double w1 = s1[k] / sw, w2 = s2[k] / sw;  // sum_n w dm, sum_n w dm^2
-        act += -w2 / (2.0 * var) - th - kHalfLog2Pi;    // sum_n w log N(zt_add[n]; mu, std) of this dimension (sum_n w = 1)
-        const double d = mu[k] - mu_o, ratio = var / var_o;
-        kl0 += d * d * var_o;                           // mpo.py:289-290: times the OLD variance, as written there
-        kls += ratio + 2.0 * (th_o - th);               // std^2 / std_old^2 + log(ss / ss_old) of this dimension, ss = exp(-2 th)
-        // d(-sum_n w logp): -w1 / var to mu, -(w2 / var - 1) to tanh; std' = std (1 - th^2) through exp(tanh(.))
-        const double g_mu = (-w1 / var) * inv_R + c_mu * d * var_o;
-        const double g_th = -(w2 / var - 1.0) * inv_R + c_sg * (ratio - 1.0);
-        a.g_head[o + k] = (mr >= -5.f && mr <= 5.f) ? (float)g_mu : 0.f;  // the clamp passes the gradient on its bounds
-        a.g_head[o + A + k] = (float)(g_th * (1.0 - th * th));
+        act += gauss_log_prob_sq(w2, e.th, e.var);      // sum_n w log N(zt_add[n]; mu, std) of this dimension (sum_n w = 1)
+        kl0 += tr.kl0;
+        kls += tr.kls;
+        // d(-sum_n w logp): -w1 / var to mu, -(w2 / var - 1) to th
+        const double g_mu = (-w1 / e.var) * inv_R + gauss_trust_grad_mu(tr, c_mu);
+        const double g_th = -(w2 / e.var - 1.0) * inv_R + gauss_trust_grad_th(tr, c_sg);
+        a.g_head[o + k] = gauss_grad_mu_raw(e, g_mu);
+        a.g_head[o + A + k] = gauss_grad_log_std_raw(e, g_th);
       }
     }
-    kl0 *= 0.5;
-    kl1 = 0.5 * (kls - (double)A);
+    gauss_trust_finish(kl0, kl1, kls, A);
   }
-  // alpha_loss as written (mpo.py:291-309): mean of alpha (eps - KLD) + alpha KLD, for mu and for sigma
-  const double al = on ? ((double)alpha_mu * ((double)eps_mu - kl0) + (double)alpha_mu * kl0) +
-                             ((double)alpha_sigma * ((double)eps_sigma - kl1) + (double)alpha_sigma * kl1)
-                       : 0.0;
-  q_lo = jh_wave_min(q_lo); q_hi = jh_wave_max(q_hi); at_lo = jh_wave_min(at_lo); at_hi = jh_wave_max(at_hi);
-  if ((i & 63) == 0) {
-    s_ext[i >> 6][0] = q_lo; s_ext[i >> 6][1] = q_hi; s_ext[i >> 6][2] = at_lo; s_ext[i >> 6][3] = at_hi;
-  }
+  const double al = on ? alpha_loss_row(m.alpha_mu, m.eps_mu, kl0) + alpha_loss_row(m.alpha_sigma, m.eps_sigma, kl1) : 0.0;
+  extrema_publish(x, s_ext);
   double s7[7] = {crit, act, Lr, wAt, kl0, kl1, al};
   block_sums<7>(s7, s_red);  // its barriers publish s_ext too
   if (i != 0) return;
-
-  // ---- one thread: the scalar losses, the three multipliers' gradients and steps, the statistics
-  const double n = (double)R, d_eta = (double)eta;
-  const double mean_L = s7[2] / n;
-  const double eta_loss = d_eta * (double)eps_eta + d_eta * mean_L;                    // mpo.py:276-278
-  const float g_eta = (float)((double)eps_eta + mean_L - (s7[3] / n) / d_eta);
-  const float g_mu = (float)((double)eps_mu - s7[4] / n);
-  const float g_sg = (float)((double)eps_sigma - s7[5] / n);
-  const float t = a.hyper[JH_HY_STEP] + 1.f;  // the step the actor's Adam takes for this learn (its optimizer pass advances it later)
-  const float eta_n = multiplier_step(a.blk, 0, g_eta, a.hyper, t);
-  const float mu_n = multiplier_step(a.blk, 1, g_mu, a.hyper, t);
-  const float sg_n = multiplier_step(a.blk, 2, g_sg, a.hyper, t);
-  if (a.stats) {
-    const int nw = ((int)blockDim.x + 63) >> 6;
-    for (int w = 1; w < nw; ++w) {
-      q_lo = fminf(q_lo, s_ext[w][0]); q_hi = fmaxf(q_hi, s_ext[w][1]); at_lo = fminf(at_lo, s_ext[w][2]); at_hi = fmaxf(at_hi, s_ext[w][3]);
-    }
-    a.stats[0] = (float)(-s7[1] / n);
-    a.stats[1] = (float)(s7[0] / n);
-    a.stats[2] = (float)eta_loss;
-    a.stats[3] = (float)(s7[6] / n);
-    a.stats[4] = eta_n;
-    a.stats[5] = mu_n;
-    a.stats[6] = sg_n;
-    a.stats[7] = q_lo;
-    a.stats[8] = q_hi;
-    a.stats[9] = at_lo;
-    a.stats[10] = at_hi;
-  }
+  mpo_finish(a, m, MpoSums{s7[0], s7[1], s7[2], s7[3], s7[4], s7[5], s7[6]}, true, x, s_ext);
 }
 
 inline bool mpo_cont_shape_ok(int R, int N, int A) {

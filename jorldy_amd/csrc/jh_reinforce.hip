@@ -2,7 +2,7 @@
 //   jh_reinforce_returns          ret[t] = r[t] + gamma ret[t + 1] over ALL T rows of the episode (no reset at a done, reinforce.py:90-92), then
 //                                 (ret - mean) / (std + 1e-7) with the population std (reinforce.py:93-94); scan, mean and variance in double
 //   jh_reinforce_loss_discrete    loss = -mean_t(log pi[t, a_t] ret[t]) with log pi a log-softmax, and d(loss)/d(logits)         (reinforce.py:104-106)
-//   jh_reinforce_loss_continuous  mu = clamp(mu_raw, -5, 5), std = exp(tanh(log_std_raw)) (network/policy.py:49-55), z = atanh(clamp(a)),
+//   jh_reinforce_loss_continuous  the squashed-Gaussian head of jh_policy_head.h (network/policy.py:49-55), z the pre-tanh value of the action,
 //                                 loss = -mean over T * A of Normal(mu, std).log_prob(z) ret[t], and d(loss)/d(raw head)          (reinforce.py:98-106)
 // T changes with every episode, so nothing here depends on it in its NUMBER of launches: the scan is one workgroup for any T <= 65536, each
 // loss is a row pass over at most kLossBlocks workgroups (grid-stride) and a one-workgroup finish.
@@ -14,14 +14,13 @@
 // tree followed by the waves' (or workgroups') partials in index order, the same bits every run.
 // Departure on purpose (as jh_mpo_loss_discrete): log pi is a log-softmax of the logits where the reference takes log(softmax).
 #include "jh_common.h"
+#include "jh_policy_head.h"  // the categorical row and the squashed-Gaussian head element, shared with jh_vmpo.hip and jh_mpo.hip
 
 namespace {
 
 constexpr int kScanThreads = 1024, kScanWaves = kScanThreads / 64, kMaxRows = 65536;
 constexpr int kLossThreads = 256, kLossBlocks = 64;
 constexpr int kMaxActionsDiscrete = 64, kMaxActionsContinuous = 32;
-constexpr float kAtanhLo = -0.99999988f, kAtanhHi = 0.99999988f;  // (float)(1 - 1e-7): the reference clamps the float32 action tensor
-constexpr double kHalfLog2Pi = 0.91893853320467274178;
 
 // the affine map x -> b + a x of a run of rows; `then(first, second)` is the map of the run `first` followed (in time) by the run `second`:
 // the return in front of `first` is first(second(x))
@@ -139,13 +138,8 @@ __global__ void __launch_bounds__(kLossThreads) jh_reinforce_loss_discrete_kerne
   for (int t = blockIdx.x * kLossThreads + threadIdx.x; t < a.T; t += gridDim.x * kLossThreads) {
     const float* z = a.head + (size_t)t * A;
     float* g = a.grad + (size_t)t * A;
-    float zm = z[0];
-    for (int k = 1; k < A; ++k) zm = fmaxf(zm, z[k]);
-    double se = 0.0;
-    for (int k = 0; k < A; ++k) se += exp((double)z[k] - (double)zm);
-    const double lse = (double)zm + log(se);
-    int ak = (int)a.action[t];
-    ak = ak < 0 ? 0 : (ak >= A ? A - 1 : ak);
+    const double lse = row_lse(z, A);
+    const int ak = action_index(a.action[t], A);
     const double r = (double)a.ret[t];
     acc += ((double)z[ak] - lse) * r;
     const double w = r * inv_T;
@@ -167,15 +161,12 @@ __global__ void __launch_bounds__(kLossThreads) jh_reinforce_loss_continuous_ker
     const double w = (double)a.ret[t] * inv_n;
     double row = 0.0;
     for (int k = 0; k < A; ++k) {
-      const float mr = h[k];
-      const bool inside = mr >= -5.f && mr <= 5.f;  // torch.clamp passes the gradient at the bounds themselves
-      const double mu = (double)fminf(fmaxf(mr, -5.f), 5.f);
-      const double ls = tanh((double)h[A + k]), var = exp(2.0 * ls);
-      const float ac = fminf(fmaxf(a.action[(size_t)t * A + k], kAtanhLo), kAtanhHi);
-      const double d = atanh((double)ac) - mu;
-      row += -0.5 * d * d / var - ls - kHalfLog2Pi;
-      g[k] = inside ? (float)(-w * d / var) : 0.f;
-      g[A + k] = (float)(-w * (d * d / var - 1.0) * (1.0 - ls * ls));
+      const float mr = h[k], lr = h[A + k], ac = a.action[(size_t)t * A + k];  // the three loads together, ahead of the arithmetic
+      const GaussElem e = gauss_elem(mr, lr);
+      const double d = gauss_z(ac) - e.mu;
+      row += gauss_log_prob(d, e.th, e.var);
+      g[k] = gauss_grad_mu_raw(e, -w * d / e.var);
+      g[A + k] = gauss_grad_log_std_raw(e, -w * (d * d / e.var - 1.0));
     }
     acc += row * (double)a.ret[t];
   }

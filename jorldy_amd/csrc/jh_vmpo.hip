@@ -16,12 +16,11 @@
 // Empty top half (b == 1, or no advantage above the median): as the reference -- no actor gradient, eta_loss = log(mean of nothing) = NaN,
 // and so is the stepped eta (x < floor ? floor : x keeps a NaN, as torch.max does).
 #include "jh_common.h"
-#include "jh_mult.h"  // the multiplier block's layout, block_sums, multiplier_step: shared with jh_mpo.hip
+#include "jh_mult.h"         // the multiplier block's layout, block_sums, multiplier_step: shared with jh_mpo.hip
+#include "jh_policy_head.h"  // the categorical row, the squashed-Gaussian head element, its trust region, alpha_loss_row
 
 namespace {
 
-constexpr float kAtanhLo = -0.99999988f, kAtanhHi = 0.99999988f;  // (float)(1 - 1e-7): the reference clamps the float32 action tensor
-constexpr double kHalfLog2Pi = 0.91893853320467274178;
 constexpr int kMaxRows = 1024, kMaxWaves = kMaxRows / 64;
 constexpr int kMaxHead = 64;  // action dimensions / logits per row, looped over by the row's thread (jh_pponet: <= 39)
 
@@ -111,13 +110,8 @@ __global__ void __launch_bounds__(kMaxRows) jh_vmpo_loss_kernel(VmpoArgs<CONT> a
       if (!CONT) {
         const float* z = a.h0 + (size_t)i * A;
         const float* zo = a.h0_old + (size_t)r * A;
-        float zm = z[0], zom = zo[0];
-        for (int k = 1; k < A; ++k) { zm = fmaxf(zm, z[k]); zom = fmaxf(zom, zo[k]); }
-        double se = 0.0, seo = 0.0;
-        for (int k = 0; k < A; ++k) { se += exp((double)z[k] - (double)zm); seo += exp((double)zo[k] - (double)zom); }
-        const double lse = (double)zm + log(se), lseo = (double)zom + log(seo);
-        int ak = (int)a.action[r];
-        ak = ak < 0 ? 0 : (ak >= A ? A - 1 : ak);
+        const double lse = row_lse(z, A), lseo = row_lse(zo, A);
+        const int ak = action_index(a.action[r], A);
         logp = (double)z[ak] - lse;
         double s_old = 0.0;
         for (int k = 0; k < A; ++k) {
@@ -134,31 +128,22 @@ __global__ void __launch_bounds__(kMaxRows) jh_vmpo_loss_kernel(VmpoArgs<CONT> a
         const double c_mu = (double)alpha_mu * inv_b, c_sg = (double)alpha_sigma * inv_b;
         double kls = 0.0;
         for (int k = 0; k < A; ++k) {
-          const float mr = a.h0[(size_t)i * A + k];
-          const double mu = fmin(fmax((double)mr, -5.0), 5.0);  // policy_value.py:54
-          const double th = tanh((double)a.h1[(size_t)i * A + k]), sd = exp(th);
-          const double mu_o = fmin(fmax((double)a.h0_old[(size_t)r * A + k], -5.0), 5.0);
-          const double th_o = tanh((double)a.h1_old[(size_t)r * A + k]), var_o = exp(2.0 * th_o);
-          const float ac = fminf(fmaxf(a.action[(size_t)r * A + k], kAtanhLo), kAtanhHi);
-          const double zt = atanh((double)ac), dm = zt - mu, var = sd * sd;
-          logp += -(dm * dm) / (2.0 * var) - th - kHalfLog2Pi;  // Normal.log_prob, log(std) = tanh(log_std_raw)
-          const double d = mu - mu_o, ratio = var / var_o;
-          kl0 += d * d * var_o;                    // vmpo.py:210-213: times the OLD variance, as written there
-          kls += ratio + 2.0 * (th_o - th);        // std^2 / std_old^2 + log(ss / ss_old) of this dimension, ss = exp(-2 th)
-          // d(-psi logp): -psi dm / var to mu, -psi (dm^2 - var) / (var std) to std; std' = std (1 - th^2) through exp(tanh(.))
-          const double g_mu = -psi * dm / var + c_mu * d * var_o;
-          const double g_th = -psi * ((dm * dm - var) / var) + c_sg * (ratio - 1.0);
-          a.g0[(size_t)i * A + k] = (mr >= -5.f && mr <= 5.f) ? (float)g_mu : 0.f;  // the clamp passes the gradient on its bounds
-          a.g1[(size_t)i * A + k] = (float)(g_th * (1.0 - th * th));
+          const GaussElem e = gauss_elem(a.h0[(size_t)i * A + k], a.h1[(size_t)i * A + k]);  // policy_value.py:54
+          const GaussTrust tr = gauss_trust(e, gauss_elem(a.h0_old[(size_t)r * A + k], a.h1_old[(size_t)r * A + k]));
+          const double dm = gauss_z(a.action[(size_t)r * A + k]) - e.mu;
+          logp += gauss_log_prob(dm, e.th, e.var);
+          kl0 += tr.kl0;
+          kls += tr.kls;
+          // d(-psi logp): -psi dm / var to mu, -psi (dm^2 - var) / (var std) to std and so -psi (dm^2 - var) / var to th = log(std)
+          const double g_mu = -psi * dm / e.var + gauss_trust_grad_mu(tr, c_mu);
+          const double g_th = -psi * ((dm * dm - e.var) / e.var) + gauss_trust_grad_th(tr, c_sg);
+          a.g0[(size_t)i * A + k] = gauss_grad_mu_raw(e, g_mu);
+          a.g1[(size_t)i * A + k] = gauss_grad_log_std_raw(e, g_th);
         }
-        kl0 *= 0.5;
-        kl1 = 0.5 * (kls - (double)A);  // vmpo.py:220-229
+        gauss_trust_finish(kl0, kl1, kls, A);  // vmpo.py:220-229
       }
     }
-    // alpha_loss as written (vmpo.py:214-217, 230-233, 239-242): mean of alpha (eps - KL) + alpha KL
-    const double al = on ? ((double)alpha_mu * ((double)eps_mu - kl0) + (double)alpha_mu * kl0) +
-                               (CONT ? ((double)alpha_sigma * ((double)eps_sigma - kl1) + (double)alpha_sigma * kl1) : 0.0)
-                         : 0.0;
+    const double al = on ? alpha_loss_row(alpha_mu, eps_mu, kl0) + (CONT ? alpha_loss_row(alpha_sigma, eps_sigma, kl1) : 0.0) : 0.0;
     double s5[5] = {psi * logp, crit, kl0, kl1, al};
     block_sums<5>(s5, s_red);
     if (i != 0) return;

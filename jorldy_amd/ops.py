@@ -616,20 +616,38 @@ def vmpo_hyper(lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0, device="cuda"):
     return torch.from_numpy(h).to(device)
 
 
+def _mult_args(block, hyper, device):
+    """The multiplier block of a loss call of the MPO family, checked, and `hyper` (a vmpo_hyper tensor or a net's hyper_ptr()) as a c_void_p."""
+    assert block.dtype == torch.float32 and block.numel() == VMPO_BLOCK_FLOATS and block.is_contiguous()
+    if not torch.is_tensor(hyper):
+        return C.c_void_p(int(hyper))
+    assert hyper.dtype == torch.float32 and hyper.numel() >= 16 and hyper.is_contiguous() and hyper.device == device
+    return C.c_void_p(hyper.data_ptr())
+
+
+def _stats_arg(stats, n, device):
+    """stats: made (zeros) where None, checked to hold n floats where given."""
+    if stats is None:
+        return torch.zeros(n, dtype=torch.float32, device=device)
+    assert stats.dtype == torch.float32 and stats.numel() >= n and stats.is_contiguous()
+    return stats
+
+
+def _out_arg(out, like, at_least=False):
+    """out: a tensor a loss call writes a gradient into, made like `like` where None, checked to hold its floats (exactly, or at least) where given."""
+    if out is None:
+        return torch.empty_like(like)
+    assert out.is_contiguous() and out.dtype == torch.float32 and (out.numel() >= like.numel() if at_least else out.numel() == like.numel())
+    return out
+
+
 def _vmpo_common(head, value_pred, idx, block, hyper, stats, mask):
     B, A = head.shape
     assert idx is None or (idx.dtype == torch.int64 and idx.numel() == B and idx.is_contiguous())
-    assert block.dtype == torch.float32 and block.numel() == VMPO_BLOCK_FLOATS and block.is_contiguous()
-    if torch.is_tensor(hyper):
-        assert hyper.dtype == torch.float32 and hyper.numel() >= 16 and hyper.is_contiguous() and hyper.device == head.device
-        hyper_ptr = C.c_void_p(hyper.data_ptr())
-    else:
-        hyper_ptr = C.c_void_p(int(hyper))
+    hyper_ptr = _mult_args(block, hyper, head.device)
     g_v = torch.empty(B, dtype=torch.float32, device=head.device)
-    if stats is None:
-        stats = torch.zeros(8, dtype=torch.float32, device=head.device)
     assert mask is None or (mask.dtype == torch.float32 and mask.numel() >= B and mask.is_contiguous())
-    return B, A, hyper_ptr, g_v, stats
+    return B, A, hyper_ptr, g_v, _stats_arg(stats, 8, head.device)
 
 
 def vmpo_loss_discrete(logits, value_pred, idx, action, adv, value_old, logits_old, block, hyper, stats=None, mask=None):
@@ -671,17 +689,10 @@ def mpo_loss_discrete(la, la_next, la_old, q, qt, qt_next, action, reward, done,
     assert all(tuple(v.shape) == (R, A) for v in t)
     cols = [_f32(v).reshape(-1) for v in (action, reward, done, prob_b)]
     assert all(v.numel() == R for v in cols)
-    assert block.dtype == torch.float32 and block.numel() == VMPO_BLOCK_FLOATS and block.is_contiguous()
-    if torch.is_tensor(hyper):
-        assert hyper.dtype == torch.float32 and hyper.numel() >= 16 and hyper.is_contiguous() and hyper.device == t[0].device
-        hyper_ptr = C.c_void_p(hyper.data_ptr())
-    else:
-        hyper_ptr = C.c_void_p(int(hyper))
-    g_la, g_q = out if out is not None else (torch.empty_like(t[0]), torch.empty_like(t[3]))
-    assert g_la.is_contiguous() and g_q.is_contiguous() and g_la.numel() == R * A and g_q.numel() == R * A and g_la.dtype == g_q.dtype == torch.float32
-    if stats is None:
-        stats = torch.zeros(len(MPO_STATS), dtype=torch.float32, device=t[0].device)
-    assert stats.dtype == torch.float32 and stats.numel() >= len(MPO_STATS) and stats.is_contiguous()
+    hyper_ptr = _mult_args(block, hyper, t[0].device)
+    g_la, g_q = out if out is not None else (None, None)
+    g_la, g_q = _out_arg(g_la, t[0]), _out_arg(g_q, t[3])
+    stats = _stats_arg(stats, len(MPO_STATS), t[0].device)
     L.check(L.load().jh_mpo_loss_discrete(L.ctx(_dev(t[0])), R, int(T), A, *(L.ptr(v) for v in t), *(L.ptr(v) for v in cols), L.ptr(block), hyper_ptr, float(gamma),
                                           int(bool(retrace)), L.ptr(g_la), L.ptr(g_q), L.ptr(stats), L.stream_ptr()))
     return g_la, g_q, stats
@@ -715,17 +726,10 @@ def mpo_loss_continuous(head, head_old, q, qt_a, qt_next, qt_add, zt_add, action
     cols = [_f32(v).reshape(-1) for v in (reward, done, prob_b)]
     q, qt_a = _f32(q).reshape(-1), _f32(qt_a).reshape(-1)
     assert all(v.numel() == R for v in cols + [q, qt_a])
-    assert block.dtype == torch.float32 and block.numel() == VMPO_BLOCK_FLOATS and block.is_contiguous()
-    if torch.is_tensor(hyper):
-        assert hyper.dtype == torch.float32 and hyper.numel() >= 16 and hyper.is_contiguous() and hyper.device == h.device
-        hyper_ptr = C.c_void_p(hyper.data_ptr())
-    else:
-        hyper_ptr = C.c_void_p(int(hyper))
-    g_h, g_q = out if out is not None else (torch.empty_like(h), torch.empty_like(q))
-    assert g_h.is_contiguous() and g_q.is_contiguous() and g_h.numel() == R * 2 * A and g_q.numel() == R and g_h.dtype == g_q.dtype == torch.float32
-    if stats is None:
-        stats = torch.zeros(len(MPO_STATS), dtype=torch.float32, device=h.device)
-    assert stats.dtype == torch.float32 and stats.numel() >= len(MPO_STATS) and stats.is_contiguous()
+    hyper_ptr = _mult_args(block, hyper, h.device)
+    g_h, g_q = out if out is not None else (None, None)
+    g_h, g_q = _out_arg(g_h, h), _out_arg(g_q, q)
+    stats = _stats_arg(stats, len(MPO_STATS), h.device)
     L.check(L.load().jh_mpo_loss_continuous(L.ctx(_dev(h)), R, int(T), N, A, L.ptr(h), L.ptr(ho), L.ptr(q), L.ptr(qt_a), L.ptr(qn), L.ptr(qa), L.ptr(zt), L.ptr(act),
                                             *(L.ptr(v) for v in cols), L.ptr(block), hyper_ptr, float(gamma), int(bool(retrace)), L.ptr(g_h), L.ptr(g_q),
                                             L.ptr(stats), L.stream_ptr()))
@@ -753,11 +757,8 @@ def _reinforce_loss(entry, head, A, action, ret, stats, out, T):
     h = _f32(head)
     T = int(h.shape[0]) if T is None else int(T)
     a, r = _f32(action).reshape(-1), _f32(ret).reshape(-1)
-    grad = out if out is not None else torch.empty_like(h)
-    assert grad.is_contiguous() and grad.dtype == torch.float32 and grad.numel() >= h.numel()
-    if stats is None:
-        stats = torch.zeros(len(REINFORCE_STATS), dtype=torch.float32, device=h.device)
-    assert stats.dtype == torch.float32 and stats.numel() >= len(REINFORCE_STATS) and stats.is_contiguous()
+    grad = _out_arg(out, h, at_least=True)
+    stats = _stats_arg(stats, len(REINFORCE_STATS), h.device)
     L.check(getattr(L.load(), entry)(L.ctx(_dev(h)), T, int(A), L.ptr(h), L.ptr(a), L.ptr(r), L.ptr(grad), L.ptr(stats), L.stream_ptr()))
     return grad, stats
 
