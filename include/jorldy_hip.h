@@ -393,6 +393,51 @@ int jh_miqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_lo
 int jh_iqn_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,
                const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, float* d_q_all, jh_stream stream);
 
+/* ------------------------------------------------------------------ Rainbow-IQN: the noisy dueling tail on the implicit quantile trunk
+ * core/network/rainbow_iqn.py:9-113 on jh_iqnnet's object: the trunk above up to relu(l2) at the CALLER's width (rainbow_iqn.py:85-94
+ * passes hidden_size; IQN's agent does not), then Rainbow's four NoisyNet layers (network/utils.py:55-107) with one support over the
+ * rows x N sampled rows:  x_a = relu(noisy a1), x_v = relu(noisy v1) (H -> H each, stacked as one [2H][H] operand as jh_rbnet keeps
+ * them), noisy a2 (H -> A), noisy v2 (H -> 1), out = x_a - mean_a x_a + x_v -> [rows][N][A]        (rainbow_iqn.py:54-104)
+ * jh_riqnnet_create gives a jh_iqnnet whose segment table (jh_iqnnet_segment, jh_riqnnet_segment_count entries) is the trunk's ten
+ * segments, q's two left empty, then -- [out][in], the reference keeps noisy weights [in][out] --
+ *   12 mu a1|v1 [2H][H]  13 sig  14 mu_b [2H]  15 sig_b   16 mu a2 [A][H]  17 sig  18 mu_b  19 sig_b   20 mu v2 [1][H]  21 sig  22 mu_b  23 sig_b
+ * One noise set (jh_riqnnet_noise_len floats of N(0, 1), the draw order of a forward: a1, v1, a2, v2; utils.py:58-60, 75-76):
+ *   factorized   [ei_a1 H][ej_a1 H][ei_v1 H][ej_v1 H][ei_a2 H][ej_a2 A][ei_v2 H][ej_v2 1]  eps_w = outer(f(ei), f(ej)), eps_b = f(ej)
+ *   independent  [eps_w a1 H x H (in, out)][eps_b a1 H][eps_w v1][eps_b v1][eps_w a2 H x A][eps_b a2 A][eps_w v2 H][eps_b v2 1]
+ * state_size % 4 == 0, H % 4 == 0, 1 <= N <= 256, 3 * max_batch * N * 2H < 2^31.  jh_iqnnet_destroy / _segment / _set_hyper / _set_lr /
+ * _sync_target / _backward / _optim_step serve this object as they serve IQN's; jh_iqnnet_forward / _learn_forward / _learn_forward_m
+ * refuse it, as the entries below refuse IQN's.                                                                                   */
+int64_t jh_riqnnet_param_count_for(int32_t state_size, int32_t hidden, int32_t embedding_dim, int32_t num_sample, int32_t action_size);
+int jh_riqnnet_create(jh_ctx* ctx, int32_t state_size, int32_t hidden, int32_t embedding_dim, int32_t num_sample, int32_t action_size,
+                      int32_t independent_noise, int32_t max_batch, float* d_params, float* d_target, float* d_grads, float* d_m, float* d_v,
+                      jh_iqnnet** out);
+int32_t jh_riqnnet_segment_count(void);
+int64_t jh_riqnnet_noise_len(const jh_iqnnet* n);
+/* network(x, is_train) with the draws d_tau [rows][N] (rainbow_iqn.py:42-104): d_noise one noise set, or NULL for is_train False
+ * (W = mu); which 0 online / 1 target (its own sigmas) -> d_logits [rows][N][A]                                                    */
+int jh_riqnnet_forward(jh_iqnnet* n, int32_t which, const float* d_x, int32_t rows, const float* d_tau, const float* d_noise, float* d_logits,
+                       jh_stream stream);
+/* The three forwards of RainbowIQN.learn() (agent/rainbow_iqn.py:172, 182, 185): d_x = [state; next_state] (2B rows), d_tau [3][B][N],
+ * d_noise [3][noise_len] -> d_logits [3][B][N][A] = online(state), online(next_state), target(next_state), forward i under draw i of
+ * both.  The trunk runs as jh_iqnnet_learn_forward's two jobs; the tail as three: one effective-weight launch for the three
+ * (parameter set, draw) pairs, grouped GEMMs, one dueling launch.  jh_iqnnet_backward then differentiates online(state): dueling
+ * backward, a2 / v2, a1 | v1 (d(mu) in place, both streams' data gradients into the trunk as one GEMM), the trunk,
+ * d(sig) = d(mu) * eps under draw 0 (rainbow_iqn.py:221-223).  No floating-point atomics; a replay gives the eager call's bits.      */
+int jh_riqnnet_learn_forward(jh_iqnnet* n, const float* d_x, int32_t B, const float* d_tau, const float* d_noise, float* d_logits,
+                             jh_stream stream);
+/* jh_iqn_loss under Rainbow's return and replay (agent/rainbow_iqn.py:158-224): d_reward / d_done float32 [B][n_step] (n_step 0: [B],
+ * as jh_c51_loss takes it), T[j] = target_logit[b][j][a*] folded as T = reward[b][i] + (1 - done[b][i]) * gamma * T for
+ * i = n_step - 1 .. 0 in torch's order of operations (rainbow_iqn.py:192-195); d_weights float32 [B], the importance weights.
+ * With loss_b = 1 / N * sum_j sum_i (e < 0 ? 1 - tau[b][i] : tau[b][i]) * smooth_l1(e):  d_prio[b] = powf(loss_b, alpha)
+ * (rainbow_iqn.py:212).  The reference multiplies weights [B, 1] with loss [B] (rainbow_iqn.py:217-219): the mean of that [B, B]
+ * product is loss = mean(w) * mean_b(loss_b) -- the broadcast jh_c51_loss keeps under JH_C51_PER -- so with w = mean(w), summed in a
+ * fixed order:  d_grad_logit[b][i][action[b]] = -w * sum_j (...) clip(e, -1, 1) / (B N), zeros elsewhere, and
+ * d_stats float32[8] in jh_iqn_loss's slots with d_stats[0] = w * mean_b(loss_b).  With n_step <= 1 and unit
+ * weights the gradient and the statistics are jh_iqn_loss's bits.  1 <= N <= 256, n_step >= 0.  Two launches, no atomics.           */
+int jh_riqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, int32_t n_step, const float* d_logit, const float* d_next_logit_online,
+                 const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done, const float* d_weights,
+                 const float* d_tau, float gamma, float alpha, float* d_grad_logit, float* d_prio, float* d_stats, jh_stream stream);
+
 /* ------------------------------------------------------------------ deterministic actor-critic (TD3, DDPG)
  * The elementwise steps of td3.py:146-209 / ddpg.py:117-163 (float32, fixed summation order, capturable, no host sync):
  *   jh_td3_next_action    a = clamp(tanh(z) + clamp(noise_std * eps, -noise_clip, noise_clip), -1, 1) on [B][A] (td3.py:159-162);

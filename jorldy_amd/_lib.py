@@ -105,6 +105,13 @@ _PROTOS = {
     "jh_iqnnet_learn_forward_m": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "jh_iqnnet_backward": (C.c_int, [_vp, _vp, _vp]),
     "jh_iqnnet_optim_step": (C.c_int, [_vp, _f32, _vp]),
+    "jh_riqnnet_param_count_for": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "jh_riqnnet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _pp]),
+    "jh_riqnnet_segment_count": (_i32, []),
+    "jh_riqnnet_noise_len": (_i64, [_vp]),
+    "jh_riqnnet_forward": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "jh_riqnnet_learn_forward": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "jh_riqn_loss": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp]),
     "jh_iqn_cos_features": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "jh_iqn_hadamard": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "jh_iqn_hadamard_backward": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -14,6 +14,7 @@ from .ppo import PPO
 from .qrdqn import QRDQN
 from .r2d2 import R2D2
 from .rainbow import C51, Rainbow
+from .rainbow_iqn import RainbowIQN
 from .reinforce import REINFORCE
 from .sac import SAC
 from .td3 import TD3
@@ -21,7 +22,7 @@ from .vmpo import VMPO
 
 agent_dict = {"dqn": DQN, "double": Double, "multistep": Multistep, "per": PER, "ape_x": ApeX, "c51": C51, "rainbow": Rainbow, "ppo": PPO, "qrdqn": QRDQN, "m_dqn": MDQN, "iqn": IQN,
               "m_iqn": MIQN, "td3": TD3, "ddpg": DDPG, "sac": SAC, "vmpo": VMPO,
-              "mpo": MPO, "noisy": Noisy, "dueling": Dueling, "icm_ppo": ICM_PPO, "r2d2": R2D2, "reinforce": REINFORCE}
+              "mpo": MPO, "noisy": Noisy, "dueling": Dueling, "icm_ppo": ICM_PPO, "r2d2": R2D2, "reinforce": REINFORCE, "rainbow_iqn": RainbowIQN}
 
 
 def Agent(name, *args, **kwargs):

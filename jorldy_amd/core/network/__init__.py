@@ -11,6 +11,7 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   rainbow                      core/network/rainbow.py:8-94 (+ utils.py:55-107 noisy linear)
   noisy                        core/network/noisy.py:8-50 (+ utils.py:89-107 init_weights)
   iqn                          core/network/iqn.py:9-47
+  rainbow_iqn                  core/network/rainbow_iqn.py:9-40
   deterministic_policy         core/network/policy.py:8-20
   continuous_q_network         core/network/q_network.py:23-39
   continuous_policy            core/network/policy.py:38-55
@@ -205,6 +206,25 @@ class IQN(BaseNetwork):
         orthogonal_init(self.q, "linear")
 
 
+class RainbowIQN(BaseNetwork):
+    """IQN's trunk under Rainbow's noisy dueling tail with one support (rainbow_iqn.py:9-40).  D_hidden is the caller's here; as in IQN the
+    orthogonal_init call names sample_embed twice and state_embed never (rainbow_iqn.py:40).  Own parameters (the 16 noisy tensors) come
+    first in state_dict(), the submodules after."""
+
+    def __init__(self, D_in, D_out, D_em, N_sample, noise_type, D_hidden=512, head="mlp"):
+        super().__init__(D_in, D_hidden, head)
+        self.D_out, self.noise_type, self.N_sample, self.D_em = D_out, noise_type, N_sample, D_em
+        self.state_embed = torch.nn.Linear(self.head.D_head_out, D_hidden)
+        self.sample_embed = torch.nn.Linear(D_em, D_hidden)
+        self.l1 = torch.nn.Linear(D_hidden, D_hidden)
+        self.l2 = torch.nn.Linear(D_hidden, D_hidden)
+        self.mu_w_a1, self.sig_w_a1, self.mu_b_a1, self.sig_b_a1 = _init_weights((D_hidden, D_hidden), noise_type)
+        self.mu_w_v1, self.sig_w_v1, self.mu_b_v1, self.sig_b_v1 = _init_weights((D_hidden, D_hidden), noise_type)
+        self.mu_w_a2, self.sig_w_a2, self.mu_b_a2, self.sig_b_a2 = _init_weights((D_hidden, D_out), noise_type)
+        self.mu_w_v2, self.sig_w_v2, self.mu_b_v2, self.sig_b_v2 = _init_weights((D_hidden, 1), noise_type)
+        orthogonal_init([self.sample_embed, self.sample_embed, self.l1, self.l2])
+
+
 class DeterministicPolicy(BaseNetwork):
     """The actor of TD3 / DDPG (policy.py:8-20): head -> relu(l) -> tanh(pi)."""
 
@@ -309,6 +329,7 @@ network_dict = {
     "rainbow": Rainbow,
     "noisy": Noisy,
     "iqn": IQN,
+    "rainbow_iqn": RainbowIQN,
     "deterministic_policy": DeterministicPolicy,
     "continuous_q_network": ContinuousQ_Network,
     "continuous_policy": ContinuousPolicy,

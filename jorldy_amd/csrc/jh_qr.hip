@@ -6,6 +6,8 @@
 //   jh_iqn_loss      the same on [B][N][A] with tau [B][N], the draw of each sample   (iqn.py:89-121)
 //   jh_miqn_loss     jh_iqn_loss's pairwise phase under the Munchausen target: log-policy bonus of the online net's second draw at s,
 //                    soft bootstrap over the target net's policy at s'                (m_iqn.py:29-95)
+//   jh_riqn_loss     jh_iqn_loss under Rainbow's return and replay: the greedy target folded over an n-step window of rewards and
+//                    dones, an importance weight per sample, priorities loss_b ^ alpha  (rainbow_iqn.py:158-224)
 //   jh_quantile_act  epsilon-greedy acting on the mean of the N quantiles, [R][A][N]  (qrdqn.py:33-47, 112-115)
 //   jh_iqn_act       the same on [R][N][A]                                            (iqn.py:60-76, 142-146)
 // No floating-point atomics: every sum has a fixed order, so two runs (and a graph replay) give the same bits.
@@ -32,12 +34,25 @@ enum QTarget {
                     // bonus; the target net's own means at s' are the policy of the soft bootstrap             (m_iqn.py:50-79)
 };
 
+// What a sample brings beside its transition -- and with it the shape of reward / done and what leaves the kernel beside the gradient.
+enum QReturn {
+  Q_RET_1STEP,     // reward, done [B]; every sample weighs 1
+  Q_RET_NSTEP_PER  // reward, done [B][n_step], folded from the last step to the first; prio[b] = loss_b ^ alpha; the IS weights enter as their
+                   // mean: rainbow_iqn.py:217-219 multiplies weights [B, 1] with loss [B], a [B, B] product whose mean is mean(w) * mean(loss_b)
+                   // (the broadcast jh_c51_loss keeps for Rainbow under JH_C51_PER)
+};
+
 struct QrArgs {
   int B, A, N;
   const float *logit, *next_logit, *target_logit, *action, *reward, *done, *tau;
   float gamma;
   float alpha, tau_e, l_0;  // Munchausen: scale of the bonus, entropy temperature (the agent's self.tau), lower clip of the log-policy
   float *grad, *stats, *partial;  // partial [B][4] = {sum_j sum_i w * huber, max Q, max logit, min logit} of a sample
+  // Q_RET_NSTEP_PER
+  int n_step;
+  const float* weights;  // [B]
+  float prio_alpha;
+  float* prio;           // [B]
 };
 
 // Mean of the N quantiles of action a of row block b of z on one wave (torch.mean(_logits, dim=-1), qrdqn.py:114; logits2Q,
@@ -100,7 +115,7 @@ __device__ __forceinline__ void qr_munchausen_target(const QrArgs& a, int b, int
 // LDS: [N] Bellman image of the target quantiles, [A] selector means, [4][3] per-wave statistics, [16] reduction; Munchausen: + [3][A]
 // (the target net's means at s', pi, logpi).
 // Every thread stays to the end: the work of threads i >= N is predicated, not skipped (block reduction at the end).
-template <QLayout L, QTarget T>
+template <QLayout L, QTarget T, QReturn R>
 __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -112,7 +127,15 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
   float* s_nxt = s_red + 16;   // [A], then s_pi [A], s_lpi [A]   (Munchausen only)
   int act = (int)a.action[b];
   act = act < 0 ? 0 : (act >= A ? A - 1 : act);
-  const float r = a.reward[b], dn = a.done[b];
+  // n-step: the window's rewards and dones are read where the target is folded
+  const float r = R == Q_RET_1STEP ? a.reward[b] : 0.f, dn = R == Q_RET_1STEP ? a.done[b] : 0.f;
+  // wb: mean of the batch's importance weights, summed in the same fixed order by every workgroup (unit weights: exactly 1)
+  float wb = 1.f;
+  if constexpr (R == Q_RET_NSTEP_PER) {
+    float ws = 0.f;
+    for (int k = tid; k < a.B; k += 256) ws += a.weights[k];
+    wb = jh_block_reduce(ws, s_red, JhAdd(), 0.f) / (float)a.B;
+  }
   // what phase 3 keeps in registers, requested ahead of the reductions of phase 1
   const bool own = tid < N;
   const int ti = own ? tid : N - 1;
@@ -160,7 +183,16 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
       if (q > bq) { bq = q; best = aa; }
     }
     // ---- phase 2: theta_target = reward + (1 - done) * gamma * target(s')[a*]  (qrdqn.py:79-81, iqn.py:109-111, in torch's order of operations)
-    if (own) s_T[tid] = r + ((1.f - dn) * a.gamma) * a.target_logit[q_at<L>(b, A, N, best, tid)];
+    if constexpr (R == Q_RET_1STEP) {
+      if (own) s_T[tid] = r + ((1.f - dn) * a.gamma) * a.target_logit[q_at<L>(b, A, N, best, tid)];
+    } else if (own) {
+      // rainbow_iqn.py:192-195: for i in reversed(range(n_step)): T = reward[:, i] + (1 - done[:, i]) * gamma * T, in torch's order of operations
+      float t = a.target_logit[q_at<L>(b, A, N, best, tid)];
+      const float* rw = a.reward + (size_t)b * a.n_step;
+      const float* dw = a.done + (size_t)b * a.n_step;
+      for (int i = a.n_step - 1; i >= 0; --i) t = rw[i] + ((1.f - dw[i]) * a.gamma) * t;
+      s_T[tid] = t;
+    }
   } else {
     // ---- phase 2: theta_target = reward + Munchausen bonus + (1 - done) * gamma * soft value of target(s')   (m_iqn.py:53-79)
     qr_munchausen_target<L>(a, b, act, r, dn, s_qsel, s_nxt, s_nxt + A, s_nxt + 2 * A, s_T, tid, own);
@@ -176,7 +208,8 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
     ls += w * hub;
     gs += w * fminf(fmaxf(e, -1.f), 1.f);
   }
-  if (own) a.grad[q_at<L>(b, A, N, act, tid)] = -gs / ((float)a.B * (float)N);
+  // rainbow_iqn.py:219: loss = mean(w) * mean_b(loss_b); unit weights leave the 1-step entries' bits
+  if (own) a.grad[q_at<L>(b, A, N, act, tid)] = R == Q_RET_1STEP ? -gs / ((float)a.B * (float)N) : -(wb * gs) / ((float)a.B * (float)N);
   // ---- phase 4: the sample's loss, wave shuffle tree then the waves in order
   const float tot = jh_block_reduce(own ? ls : 0.f, s_red, JhAdd(), 0.f);
   if (tid == 0) {
@@ -188,7 +221,8 @@ __global__ void __launch_bounds__(256) jh_qr_block_kernel(QrArgs a) {
       nl = fminf(nl, s_stat[w * 3 + 2]);
     }
     float* p = a.partial + 4 * (size_t)b;
-    p[0] = tot; p[1] = mq; p[2] = ml; p[3] = nl;
+    p[0] = R == Q_RET_1STEP ? tot : wb * tot; p[1] = mq; p[2] = ml; p[3] = nl;
+    if constexpr (R == Q_RET_NSTEP_PER) a.prio[b] = powf(tot / (float)N, a.prio_alpha);  // rainbow_iqn.py:205, 212: (mean_j sum_i) ^ alpha
   }
 }
 
@@ -254,15 +288,22 @@ __global__ void __launch_bounds__(256) jh_quantile_act_kernel(int R, int A, int 
 struct QMunchausen {
   float alpha, tau_e, l_0;
 };
+struct QPer {
+  int n_step;  // columns of reward / done
+  const float* weights;
+  float alpha;
+  float* prio;
+};
 
 // The launches keep the names the profile report and DESIGN.md's kernel table know them by, one set per entry point.
-template <QLayout L, QTarget T>
+template <QLayout L, QTarget T, QReturn R = Q_RET_1STEP>
 int qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, const float* d_next_logit_online, const float* d_target_logit,
             const float* d_action, const float* d_reward, const float* d_done, const float* d_tau, float gamma, float* d_grad_logit, float* d_stats,
-            jh_stream stream, QMunchausen mu = {0.f, 1.f, 0.f}) {
+            jh_stream stream, QMunchausen mu = {0.f, 1.f, 0.f}, QPer per = {1, nullptr, 0.f, nullptr}) {
   JH_ARG(ctx && d_logit && d_next_logit_online && d_target_logit && d_action && d_reward && d_done && d_tau && d_grad_logit);
   JH_ARG(B >= 1 && A >= 1 && N >= 1 && N <= 256);
   JH_ARG(mu.tau_e > 0.f && mu.l_0 <= 0.f);
+  if (R == Q_RET_NSTEP_PER) JH_ARG(per.n_step >= 1 && per.weights && per.prio);
   hipStream_t st = jh_s(stream);
   void* scratch = nullptr;
   int rc = jh_ctx_scratch(ctx, sizeof(float) * 4 * (size_t)B, &scratch);
@@ -272,14 +313,16 @@ int qr_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const float* d_logit, 
   a.logit = d_logit; a.next_logit = d_next_logit_online; a.target_logit = d_target_logit; a.action = d_action;
   a.reward = d_reward; a.done = d_done; a.tau = d_tau; a.gamma = gamma; a.grad = d_grad_logit; a.stats = d_stats;
   a.alpha = mu.alpha; a.tau_e = mu.tau_e; a.l_0 = mu.l_0;
+  a.n_step = per.n_step; a.weights = per.weights; a.prio_alpha = per.alpha; a.prio = per.prio;
   a.partial = (float*)scratch;
   const size_t lds = sizeof(float) * ((size_t)N + (size_t)A * (T == Q_TGT_MUNCHAUSEN ? 4 : 1) + 12 + 16);
   JH_ARG(lds <= 64 * 1024);
-  const bool m = T == Q_TGT_MUNCHAUSEN;
-  JH_LAUNCH_NAMED(m ? "jh_miqn_block_kernel" : L == Q_ACTION_MAJOR ? "jh_qr_block_kernel" : "jh_iqn_block_kernel", (jh_qr_block_kernel<L, T>), dim3(B), dim3(256), lds,
-                  st, a);
+  const bool m = T == Q_TGT_MUNCHAUSEN, p = R == Q_RET_NSTEP_PER;
+  JH_LAUNCH_NAMED(p ? "jh_riqn_block_kernel" : m ? "jh_miqn_block_kernel" : L == Q_ACTION_MAJOR ? "jh_qr_block_kernel" : "jh_iqn_block_kernel", (jh_qr_block_kernel<L, T, R>),
+                  dim3(B), dim3(256), lds, st, a);
   JH_LAUNCH_CHECK();
-  JH_LAUNCH_NAMED(m ? "jh_miqn_finish_kernel" : L == Q_ACTION_MAJOR ? "jh_qr_finish_kernel" : "jh_iqn_finish_kernel", jh_qr_finish_kernel, dim3(1), dim3(256), 0, st, a);
+  JH_LAUNCH_NAMED(p ? "jh_riqn_finish_kernel" : m ? "jh_miqn_finish_kernel" : L == Q_ACTION_MAJOR ? "jh_qr_finish_kernel" : "jh_iqn_finish_kernel", jh_qr_finish_kernel,
+                  dim3(1), dim3(256), 0, st, a);
   JH_LAUNCH_CHECK();
   return JH_OK;
 }
@@ -317,6 +360,15 @@ JH_EXPORT int jh_miqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, const f
                            float l_0, float* d_grad_logit, float* d_stats, jh_stream stream) {
   return qr_loss<Q_SAMPLE_MAJOR, Q_TGT_MUNCHAUSEN>(ctx, B, A, N, d_logit, d_logit_again, d_target_logit, d_action, d_reward, d_done, d_tau, gamma, d_grad_logit,
                                                    d_stats, stream, QMunchausen{alpha, tau_e, l_0});
+}
+
+// n_step as jh_c51_loss takes it: 0 (plain [B] reward / done) or the number of columns of the window
+JH_EXPORT int jh_riqn_loss(jh_ctx* ctx, int32_t B, int32_t A, int32_t N, int32_t n_step, const float* d_logit, const float* d_next_logit_online,
+                           const float* d_target_logit, const float* d_action, const float* d_reward, const float* d_done, const float* d_weights,
+                           const float* d_tau, float gamma, float alpha, float* d_grad_logit, float* d_prio, float* d_stats, jh_stream stream) {
+  JH_ARG(n_step >= 0 && d_weights && d_prio);
+  return qr_loss<Q_SAMPLE_MAJOR, Q_TGT_GREEDY, Q_RET_NSTEP_PER>(ctx, B, A, N, d_logit, d_next_logit_online, d_target_logit, d_action, d_reward, d_done, d_tau, gamma,
+                                                                d_grad_logit, d_stats, stream, QMunchausen{0.f, 1.f, 0.f}, QPer{n_step > 0 ? n_step : 1, d_weights, alpha, d_prio});
 }
 
 JH_EXPORT int jh_quantile_act(jh_ctx* ctx, int32_t R, int32_t A, int32_t N, const float* d_logits, const float* h_eps, const double* h_u,

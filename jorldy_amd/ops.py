@@ -1275,6 +1275,26 @@ def miqn_loss(logit, logit_again, target_logit, action, reward, done, tau, gamma
     return _quantile_loss(entry, B, A, N, z, logit_again, target_logit, action, reward, done, t, gamma, stats)
 
 
+def riqn_loss(logit, next_logit_online, target_logit, action, reward, done, weights, tau, gamma, alpha, n_step, stats=None):
+    """jh_riqn_loss (rainbow_iqn.py:158-224): iqn_loss's arguments with reward / done [B, n_step] (the stored window, folded from its last
+    step to its first), the importance weights [B] and the priority exponent.  Returns (grad_logit [B, N, A], prio [B] = loss_b ^ alpha,
+    stats f32[8] as iqn_loss with stats[0] = mean(w) * mean_b(loss_b), the reference's [B, 1] x [B] broadcast)."""
+    z, t = _f32(logit), _f32(tau)
+    B, N, A = (int(v) for v in z.shape)
+    zn, zt = _f32(next_logit_online), _f32(target_logit)
+    assert t.numel() == B * N and zn.shape == z.shape and zt.shape == z.shape and t.device == z.device
+    a, w = _f32(action).reshape(-1), _f32(weights).reshape(-1)
+    r, d = _f32(reward).reshape(B, -1), _f32(done).reshape(B, -1)
+    assert a.numel() == B and w.numel() == B and r.shape[1] == max(int(n_step), 1) and d.shape == r.shape
+    g = torch.empty_like(z)
+    prio = torch.empty(B, dtype=torch.float32, device=z.device)
+    if stats is None:
+        stats = torch.empty(8, dtype=torch.float32, device=z.device)
+    L.check(L.load().jh_riqn_loss(L.ctx(_dev(z)), B, A, N, int(n_step), L.ptr(z), L.ptr(zn), L.ptr(zt), L.ptr(a), L.ptr(r), L.ptr(d), L.ptr(w), L.ptr(t), float(gamma),
+                                  float(alpha), L.ptr(g), L.ptr(prio), L.ptr(stats), L.stream_ptr()))
+    return g, prio, stats
+
+
 def iqn_act(logits, eps=None, u=None, rand_action=None, out=None, want_q_all=False):
     """jh_iqn_act: network outputs [R, N, A] (N samples per row, Q = their mean) -> (action int64 [R], q_taken float32 [R], q_all | None)
     on the device.  eps / u / rand_action as in value_act."""
@@ -1808,6 +1828,83 @@ class IQNNet(_NetObject):
         if optimizer != "adam":
             raise ValueError(f"IQNNet has Adam only (every config.iqn.* uses it), got {optimizer!r}")
         L.check(self._fn("optim_step")(self.h, float(max_norm or 0.0), L.stream_ptr()))
+
+
+class RainbowIQNNet(IQNNet):
+    """jh_riqnnet_* on jh_iqnnet's object: IQN's trunk at the caller's width, then Rainbow's noisy dueling tail with one support over the
+    rows x N sampled rows (network/rainbow_iqn.py:9-113).  IQNNet's surface with a noise draw beside tau: `forward(x, which, tau, noise)`
+    (noise None = is_train False: W = mu), `learn_forward(x_all, B, tau, noise, out)` with tau [3, B, N] and noise [3, noise_len].  One noise
+    set is RainbowNet's with K = 1: [ei_a1 H][ej_a1 H][ei_v1 H][ej_v1 H][ei_a2 H][ej_a2 A][ei_v2 H][ej_v2 1] (factorized), or eps_w [in, out]
+    then eps_b per layer a1, v1, a2, v2 (independent)."""
+
+    _SEG = IQNNet._SEG + ("mu_av1", "sig_av1", "mub_av1", "sigb_av1", "mu_a2", "sig_a2", "mub_a2", "sigb_a2", "mu_v2", "sig_v2", "mub_v2", "sigb_v2")
+    kind = "rainbow_iqn"
+
+    def __init__(self, state_size, action_size, embedding_dim, num_sample, hidden, max_batch, device, noise_type="factorized"):
+        self._open(device)
+        self.S, self.A, self.E, self.N, self.H, self.maxB = int(state_size), int(action_size), int(embedding_dim), int(num_sample), int(hidden), int(max_batch)
+        self.K = self.N
+        self.noise_type = noise_type
+        self.tau_range, self.tau_inject = (0.0, 1.0), None
+        self.act_noise = None  # the draw of a forward() that is given none (the agent's act() in training mode sets it around its call)
+        n = int(self.lib.jh_riqnnet_param_count_for(self.S, self.H, self.E, self.N, self.A))
+        if n <= 0:
+            L.check(-2)
+        self.n_params = n
+        self.params, self.target, self.grads, self.m, self.v = self._zeros(n)
+        self.h = C.c_void_p()
+        L.check(self.lib.jh_riqnnet_create(self.ctx, self.S, self.H, self.E, self.N, self.A, int(noise_type == "independent"), self.maxB, L.ptr(self.params),
+                                           L.ptr(self.target), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), C.byref(self.h)))
+        assert int(self.lib.jh_riqnnet_segment_count()) == len(self._SEG)
+        self.seg = self._segments(self._SEG)
+        self.noise_len = int(self.lib.jh_riqnnet_noise_len(self.h))
+
+    def _v(self, bucket, name):
+        off, rows, cols = self.seg[name]
+        return bucket[off : off + rows * cols].view(rows, cols)
+
+    def _pairs(self, bucket):
+        """The reference module's state_dict order: its own 16 noisy tensors (a1, v1, a2, v2: mu_w, sig_w, mu_b, sig_b, each weight [in, out]),
+        then the submodules head.l, state_embed, sample_embed, l1, l2 (network/rainbow_iqn.py:13-38)."""
+        H = self.H
+        out = []
+        av1 = {k: self._v(bucket, f"{k}_av1") for k in ("mu", "sig")}
+        bav1 = {k: self._v(bucket, f"{k}b_av1").view(-1) for k in ("mu", "sig")}
+        for tag, sl in (("a1", slice(0, H)), ("v1", slice(H, 2 * H))):
+            out += [(f"mu_w_{tag}", av1["mu"][sl].t()), (f"sig_w_{tag}", av1["sig"][sl].t()), (f"mu_b_{tag}", bav1["mu"][sl]), (f"sig_b_{tag}", bav1["sig"][sl])]
+        for tag in ("a2", "v2"):
+            out += [(f"mu_w_{tag}", self._v(bucket, f"mu_{tag}").t()), (f"sig_w_{tag}", self._v(bucket, f"sig_{tag}").t()),
+                    (f"mu_b_{tag}", self._v(bucket, f"mub_{tag}").view(-1)), (f"sig_b_{tag}", self._v(bucket, f"sigb_{tag}").view(-1))]
+        trunk = {k: v for k, v in self.seg.items() if "." in k and not k.startswith("q.")}
+        return out + _seg_pairs(bucket, trunk)
+
+    def forward(self, x, which=0, tau=None, noise=None, out=None):
+        """network(x, is_train = noise is not None) -> logits [rows, N, A]; rows <= max_batch.  tau [rows, N] or None (see draw_tau);
+        noise None: `act_noise`, else W = mu."""
+        assert x.is_contiguous() and x.device == self.device and x.dtype == torch.float32
+        rows = int(x.shape[0])
+        tau = self.draw_tau(rows) if tau is None else tau
+        noise = self.act_noise if noise is None else noise
+        assert tau.is_contiguous() and tau.dtype == torch.float32 and tau.numel() == rows * self.N and tau.device == self.device
+        assert noise is None or (noise.is_contiguous() and noise.dtype == torch.float32 and noise.numel() == self.noise_len and noise.device == self.device)
+        if out is None:
+            out = torch.empty(rows, self.N, self.A, dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.numel() == rows * self.N * self.A
+        L.check(self.lib.jh_riqnnet_forward(self.h, int(which), L.ptr(x), rows, L.ptr(tau), L.ptr(noise), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def learn_forward(self, x_all, B, tau, noise, out):
+        """x_all = [state; next_state] (2B rows), tau [3, B, N], noise [3, noise_len] -> out [3, B, N, A] = online(state), online(next_state),
+        target(next_state), forward i under tau draw i and noise draw i."""
+        assert x_all.is_contiguous() and x_all.dtype == torch.float32 and int(x_all.shape[0]) == 2 * B
+        assert tau.is_contiguous() and tau.dtype == torch.float32 and tau.numel() == 3 * B * self.N
+        assert noise.is_contiguous() and noise.dtype == torch.float32 and noise.numel() == 3 * self.noise_len
+        assert out.is_contiguous() and out.numel() == 3 * B * self.N * self.A
+        L.check(self.lib.jh_riqnnet_learn_forward(self.h, L.ptr(x_all), int(B), L.ptr(tau), L.ptr(noise), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def learn_forward_m(self, *a, **k):
+        raise NotImplementedError("RainbowIQNNet has Rainbow-IQN's arrangement of forwards only")
 
 
 class R2D2Net(_NetObject):
