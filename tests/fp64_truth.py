@@ -47,6 +47,33 @@ def vs_exact(ours, exact, ref32, tol, what):
     return e_ours, e_ref
 
 
+def step_allowance(w, w_before, lr):
+    """What one optimizer step's weights may differ by from the float64 step of the same gradient, per element: one rounding of w + the update's
+    own rounding + a floor (the criterion in the module docstring).  w, w_before: float64 tensors after / before the float64 step."""
+    return 2.0 ** -22 * w.abs() + 1e-4 * (w - w_before).abs() + 1e-6 * lr
+
+
+def check_flat_step(ours_w, w, w_before, lr, what, versus, moments=(), moment_tag="{key}", allowed=None):
+    """THE criterion of an optimizer step checked as arithmetic, on one tensor of any shape (a parameter, or a whole flat bucket):
+        |ours_w - w|_i <= 2^-22 |w_i| + 1e-4 |w_i - w_before_i| + 1e-6 lr      per ELEMENT (`allowed`, when given, replaces the right-hand side:
+                                                                                  an un-forced trajectory passes its running sum)
+        |ours - exact| <= 1e-5 max |exact|                                       per tensor, for every (key, ours, exact) of `moments`
+    w / w_before / exact: the float64 step's tensors.  Every comparison lands in the margin ledger.  -> worst weight ratio achieved / allowed."""
+    w, w_before = w.detach().double().cpu(), w_before.detach().double().cpu()
+    if allowed is None:
+        allowed = step_allowance(w, w_before, lr)
+    err = (torch.as_tensor(ours_w).detach().double().cpu().reshape(w.shape) - w).abs()
+    ratio = (err / allowed).reshape(-1)
+    j = int(torch.argmax(ratio))
+    margins.leq(float(err.reshape(-1)[j]), float(allowed.reshape(-1)[j]), f"{what}[{j}] {versus} (max err {float(err.max()):.2e})")
+    for key, ours, exact in moments:
+        exact = exact.detach().double().cpu()
+        scale = float(exact.abs().max()) + 1e-30
+        e = float((torch.as_tensor(ours).detach().double().cpu().reshape(exact.shape) - exact).abs().max()) / scale
+        margins.leq(e, 1e-5, f"{moment_tag.format(key=key)} {versus}, / max |{key}|")
+    return float(ratio[j])
+
+
 class OptimTruth:
     """One optimizer configuration run three ways: float64 truth (torch.optim on the CPU), torch-CPU float32, and whatever `native`
     callbacks drive.  `named64` / `named32`: OrderedDict name -> parameter (same names as the native state_dict)."""
@@ -102,20 +129,10 @@ class OptimTruth:
             o_.step()
         worst = 0.0
         for i, (name, p) in enumerate(mod.named_parameters()):
-            w = p.detach()
-            allowed = 2.0 ** -22 * w.abs() + 1e-4 * (w - w_before[i]).abs() + 1e-6 * self.lr
-            err = (ours_params[name].detach().double().cpu().reshape(w.shape) - w).abs()
-            ratio = (err / allowed).reshape(-1)
-            j = int(torch.argmax(ratio))
-            margins.leq(float(err.reshape(-1)[j]), float(allowed.reshape(-1)[j]), f"{tag} weight {name}[{j}] vs float64 step of OUR gradient (max err {float(err.max()):.2e})")
-            worst = max(worst, float(ratio[j]))
             st = opt.state[p]
-            for key, ours in ((self.state_keys[0], ours_m), (self.state_keys[1], ours_v)):
-                if key is not None and ours is not None:
-                    exact = st[key].detach()
-                    scale = float(exact.abs().max()) + 1e-30
-                    e = float((ours[name].detach().double().cpu().reshape(exact.shape) - exact).abs().max()) / scale
-                    margins.leq(e, 1e-5, f"{tag} {key} {name} vs float64 step of OUR gradient, / max |{key}|")
+            moments = [(key, ours[name], st[key]) for key, ours in ((self.state_keys[0], ours_m), (self.state_keys[1], ours_v)) if key is not None and ours is not None]
+            worst = max(worst, check_flat_step(ours_params[name], p, w_before[i], self.lr, f"{tag} weight {name}", "vs float64 step of OUR gradient",
+                                               moments=moments, moment_tag=f"{tag} {{key}} {name}"))
         return worst
 
 
@@ -131,16 +148,7 @@ def check_first_step_from_our_gradient(w0, g_clipped, w1, make_opt, lr, tag):
     for k, p in params.items():
         p.grad = t64(g_clipped[k]).reshape(p.shape).clone()
     opt.step()
-    worst = 0.0
-    for k, p in params.items():
-        w = p.detach()
-        allowed = 2.0 ** -22 * w.abs() + 1e-4 * (w - before[k]).abs() + 1e-6 * lr
-        err = (t64(w1[k]).reshape(w.shape) - w).abs()
-        ratio = (err / allowed).reshape(-1)
-        j = int(torch.argmax(ratio))
-        margins.leq(float(err.reshape(-1)[j]), float(allowed.reshape(-1)[j]), f"{tag} weight {k}[{j}] vs float64 step of OUR gradient from the fixture's w0 (max err {float(err.max()):.2e})")
-        worst = max(worst, float(ratio[j]))
-    return worst
+    return max(check_flat_step(w1[k], p, before[k], lr, f"{tag} weight {k}", "vs float64 step of OUR gradient from the fixture's w0") for k, p in params.items())
 
 
 def ppo_head_grads_float64(cont, heads, action, adv, ret, v_old, lp_old, eps, vf, ent):
