@@ -853,6 +853,61 @@ int jh_icmnet_reward(jh_icmnet* n, const float* d_state, const float* d_next_sta
 int jh_icmnet_update(jh_icmnet* n, const float* d_state, const float* d_next_state, const float* d_action, const int64_t* d_idx, int32_t b,
                      int64_t n_rows, double beta, float max_norm, float* d_stats, jh_stream stream);
 
+/* ------------------------------------------------------------------ RND-PPO's distillation module and its PPO kernels
+ * core/network/rnd.py:173-225 (RND_MLP) with rnd.py:9-52 (normalize_obs; predictor and frozen target, each fc1 [H][S] -> bn1 -> ReLU ->
+ * fc2 [256][H] -> bn2 -> ReLU), rnd.py:159-164 (the reward filter) and utils.py:6-52, as rnd_ppo.py:119-120 and rnd_ppo.py:251-266 use
+ * them.  All four batch norms use BATCH statistics and advance their running statistics on every forward, the target's included (the
+ * module is never put into eval mode).  Caller-owned flat fp32 buckets of jh_rndnet_param_count_for floats (needs no GPU; -1 for bad
+ * sizes) in 16 segments, every offset a multiple of 4 floats: fc1_predict [H][S], [H], fc2_predict [256][H], [256], bn1_predict [H], [H],
+ * bn2_predict [256], [256], then the same eight of the target; without JH_RND_BATCH_NORM the batch norms' segments have 0 rows.  Only
+ * the first jh_rndnet_trainable_floats floats (the predictor's eight) get gradients, moments and Adam steps, and clip_grad_norm_ runs
+ * over exactly those.  H % 4 == 0; max_batch <= 8192 rows per call.  The statistics block (device, jh_rndnet_stats_floats floats):
+ *   rms_obs mean [S], var [S], count | rms_ri mean, var, count | rff.rewems [W] | running mean, var of bn1_predict [H], bn2_predict
+ *   [256], bn1_target [H], bn2_target [256]                                                                                            */
+typedef struct jh_rndnet jh_rndnet;
+#define JH_RND_OBS_NORMALIZE 1
+#define JH_RND_RI_NORMALIZE 2
+#define JH_RND_BATCH_NORM 4
+int64_t jh_rndnet_param_count_for(int32_t S, int32_t H, int32_t batch_norm);
+int jh_rndnet_create(jh_ctx* ctx, int32_t S, int32_t H, int32_t num_workers, int32_t max_batch, int32_t flags, double gamma_i, float* d_params,
+                     float* d_grads, float* d_m, float* d_v, jh_rndnet** out);
+void jh_rndnet_destroy(jh_rndnet* n);
+int32_t jh_rndnet_segment_count(const jh_rndnet* n);
+int jh_rndnet_segment(const jh_rndnet* n, int32_t i, int64_t* offset, int32_t* rows, int32_t* cols);
+int64_t jh_rndnet_trainable_floats(const jh_rndnet* n);
+/* the module's own Adam (rnd_ppo.py:83); learning_rate_decay never reaches it (base.py:103-104)                     */
+int jh_rndnet_set_hyper(jh_rndnet* n, double lr, double beta1, double beta2, double eps, int64_t step, jh_stream stream);
+int jh_rndnet_set_lr(jh_rndnet* n, double lr, jh_stream stream);
+int64_t jh_rndnet_stats_floats(const jh_rndnet* n);
+int jh_rndnet_stats_get(jh_rndnet* n, float* h_out, jh_stream stream);
+int jh_rndnet_stats_set(jh_rndnet* n, const float* h_in, jh_stream stream);
+/* rnd.update_rms_obs(next_state) (rnd_ppo.py:119), as jh_icmnet_obs_update.  JH_ERR_ARG, nothing launched: rows < 2, rows > max_batch. */
+int jh_rndnet_obs_update(jh_rndnet* n, const float* d_next_state, int32_t rows, jh_stream stream);
+/* r_i = rnd(next_state, update_ri=True) (rnd_ppo.py:120) over a whole rollout of rows = W T rows, no gradient: r_i = mean_f (p - t)^2,
+ * the reward filter and rms_ri exactly as jh_icmnet_reward documents them (T copies of the FINAL rewems), then with JH_RND_RI_NORMALIZE
+ * r_i /= sqrt(rms_ri.var) + 1e-7.  Writes d_ri [rows]; optional d_ri_mean [1] = mean(r_i), d_ri_raw [rows] = r_i before the
+ * normalisation.  JH_ERR_ARG, nothing launched: rows < 2, rows > max_batch, rows % num_workers != 0.  7 launches.      */
+int jh_rndnet_reward(jh_rndnet* n, const float* d_next_state, int32_t rows, float* d_ri, float* d_ri_mean, float* d_ri_raw, jh_stream stream);
+/* One minibatch (rnd_ppo.py:251-252, 261-266) on rows d_idx[0 .. b) of the n_rows-row next_state array (NULL: rows 0 .. b - 1; an index
+ * is clamped into the rollout): forward of both networks, loss = mean of the normalised r_i, backward through the predictor,
+ * clip_grad_norm_(max_norm) over the predictor's tensors (0: none), Adam.  d_stats optional float32[4] = {r_i mean, 0, 0, arrival mark
+ * 0}, the mark written last behind a system-scope fence.  JH_ERR_ARG, nothing launched: b < 1, b < 2 under batch norm, b > max_batch.
+ * 12 launches.                                                                                                                       */
+int jh_rndnet_update(jh_rndnet* n, const float* d_next_state, const int64_t* d_idx, int32_t b, int64_t n_rows, float max_norm, float* d_stats,
+                     jh_stream stream);
+/* rnd_ppo.py:153-166 behind two jh_gae calls with standardize off: d_adv [W T] = extrinsic_coeff d_adv_e + intrinsic_coeff d_adv_i, with
+ * standardize (adv - mean) / (std + 1e-7) per row of T = n_step entries (UNBIASED std); d_means[0] = mean(d_ret), [1] = mean(d_ret_i).   */
+int jh_rnd_adv_mix(jh_ctx* ctx, int32_t W, int32_t T, float extrinsic_coeff, float intrinsic_coeff, int32_t standardize, const float* d_adv_e,
+                   const float* d_adv_i, const float* d_ret, const float* d_ret_i, float* d_adv, float* d_means, jh_stream stream);
+/* jh_ppo_loss_packed with the second critic (rnd_ppo.py:201-249): d_heads [B][ld] = (head0 [A] | head1 [A] (continuous) | v | v_i |
+ * padding), the gradient of actor + vf_coef (critic_e + critic_i) + ent_coef entropy goes back in the same layout (padding columns are not
+ * written); each critic is the max of the MEANS of its plain and its clipped squared error.  d_stats optional float32[8] = {0, actor,
+ * critic_e, critic_i, entropy, max ratio, min prob, 0}.  Discrete 2 <= A <= 64, continuous 1 <= A <= 32.  One launch.                 */
+int jh_rnd_ppo_loss_packed(jh_ctx* ctx, int32_t continuous, int32_t B, int32_t A, const float* d_heads, int32_t ld, const int64_t* d_idx,
+                           const float* d_action, const float* d_adv, const float* d_ret, const float* d_ret_i, const float* d_value_old,
+                           const float* d_vi_old, const float* d_logp_old, float eps_clip, float vf_coef, float ent_coef, float* d_grad_heads,
+                           float* d_stats, jh_stream stream);
+
 /* ------------------------------------------------------------------ native policy-value MLP
  * The encoder of the PPO configs (core/network/head.py:6-18 MLP head + policy_value.py:8-57):
  * S -> H relu -> H relu -> {A logits | A mu, A log_std} + value, as hand-written kernels

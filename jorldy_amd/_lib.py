@@ -195,6 +195,22 @@ _PROTOS = {
     "jh_icmnet_obs_update": (C.c_int, [_vp, _vp, _i32, _vp]),
     "jh_icmnet_reward": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "jh_icmnet_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _f64, _f32, _vp, _vp]),
+    "jh_rndnet_param_count_for": (_i64, [_i32, _i32, _i32]),
+    "jh_rndnet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _pp]),
+    "jh_rndnet_destroy": (None, [_vp]),
+    "jh_rndnet_segment_count": (_i32, [_vp]),
+    "jh_rndnet_segment": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
+    "jh_rndnet_trainable_floats": (_i64, [_vp]),
+    "jh_rndnet_set_hyper": (C.c_int, [_vp, _f64, _f64, _f64, _f64, _i64, _vp]),
+    "jh_rndnet_set_lr": (C.c_int, [_vp, _f64, _vp]),
+    "jh_rndnet_stats_floats": (_i64, [_vp]),
+    "jh_rndnet_stats_get": (C.c_int, [_vp, _vp, _vp]),
+    "jh_rndnet_stats_set": (C.c_int, [_vp, _vp, _vp]),
+    "jh_rndnet_obs_update": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "jh_rndnet_reward": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "jh_rndnet_update": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _f32, _vp, _vp]),
+    "jh_rnd_adv_mix": (C.c_int, [_vp, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jh_rnd_ppo_loss_packed": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp]),
     "jh_pponet_param_count": (_i64, [_i32, _i32, _i32, _i32]),
     "jh_pponet_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_uint64, _pp]),
     "jh_pponet_destroy": (None, [_vp]),

@@ -5,6 +5,7 @@ from .ddpg import DDPG
 from .dqn import DQN, ApeX, Double, Multistep, PER
 from .dueling import Dueling
 from .icm_ppo import ICM_PPO
+from .rnd_ppo import RND_PPO
 from .iqn import IQN
 from .mdqn import MDQN
 from .miqn import MIQN
@@ -22,7 +23,7 @@ from .vmpo import VMPO
 
 agent_dict = {"dqn": DQN, "double": Double, "multistep": Multistep, "per": PER, "ape_x": ApeX, "c51": C51, "rainbow": Rainbow, "ppo": PPO, "qrdqn": QRDQN, "m_dqn": MDQN, "iqn": IQN,
               "m_iqn": MIQN, "td3": TD3, "ddpg": DDPG, "sac": SAC, "vmpo": VMPO,
-              "mpo": MPO, "noisy": Noisy, "dueling": Dueling, "icm_ppo": ICM_PPO, "r2d2": R2D2, "reinforce": REINFORCE, "rainbow_iqn": RainbowIQN}
+              "mpo": MPO, "noisy": Noisy, "dueling": Dueling, "icm_ppo": ICM_PPO, "rnd_ppo": RND_PPO, "r2d2": R2D2, "reinforce": REINFORCE, "rainbow_iqn": RainbowIQN}
 
 
 def Agent(name, *args, **kwargs):

@@ -30,7 +30,97 @@ class PolicyValueNet(NativeNet):
         return torch.softmax(out[:, :n], dim=-1), out[:, n:].clone()
 
 
-class PPOConv(NativeValueNetMixin, PPO):
+class PackedHeadsPPO(NativeValueNetMixin, PPO):
+    """What the PPO agents on the value-network engine share (PPOConv below, RND-PPO in rnd_ppo.py): a network whose last layer stacks the
+    heads (ops.RainbowNet), learn() as `_enqueue_pre` / `_enqueue_main` through ops.LearnGraphs with the epochs' shuffles drawn by
+    np_rng.epoch_shuffles and ONE statistics read-back, process(), the cosine decay of the native learning rate.  A subclass provides
+    __init__, act(), `_alloc_static`, `_enqueue_pre`, `_enqueue_main` and, when its result has other keys, `_result`."""
+
+    def _init_packed(self, what, seed):
+        """The fields learn() and process() below read that PPO.__init__ would have set."""
+        self.time_t = self.learn_stamp = 0
+        self.memory = RolloutBuffer(device=self.device)
+        self.grad_sync = None
+        self.dp_exact_critic = os.environ.get("JH_DP_EXACT_CRITIC", "1") == "1"
+        self.backend = "native"
+        self.graph_with_collective = os.environ.get("JH_GRAPH_DP", "1") == "1"
+        self._learn_graphs, self._static, self._stats = ops.LearnGraphs(what), None, None
+        self._seed, self._act_ctr = int(seed), 0
+        self._ride, self._ride_wait = None, {}  # (PPO._upload_idx: nothing rides on a collector's commit launch here)
+
+    def _init_optimizer(self, optim_config):
+        self._optim_config = dict(optim_config)
+        self._opt_name = "adam"
+        d = Optimizer(**optim_config, params=[torch.nn.Parameter(torch.zeros(1))]).defaults
+        self._lr0, self._lr_now, self._adam_steps = float(d["lr"]), float(d["lr"]), 0
+        self._set_native_hyper(d, 0)
+        self.optimizer = None
+
+    def _stat_tensors(self, st):
+        """The device tensors learn() reads back, st["stats"] first."""
+        return (st["stats"],)
+
+    def learn(self):
+        M, E = self.memory.size, self.n_epoch
+        if self._static is None or self._static["M"] != M:
+            self._static = self._alloc_static(M)
+            self.reset_graphs()
+        st = self._static
+        if st.get("store") is not self.memory._store:  # the rollout store was replaced (it grows by doubling): a captured graph holds the old one's addresses
+            st["store"] = self.memory._store
+            self.reset_graphs()
+        graphable = (self.use_graph and not ops._PROF["on"]
+                     and (self.grad_sync is None or (self.graph_with_collective and getattr(self.grad_sync, "capturable", True))))
+        # the reference's global-RNG shuffles (ppo.py:118) of all epochs, drawn before the launches (nothing else touches np.random inside learn())
+        self._upload_idx(st, lambda out: np_rng.epoch_shuffles(M, E, out))
+        self._learn_graphs.run("learn", lambda: self._enqueue_learn(st), graphable)
+        self.memory._store.clear()
+        self._adam_steps += st["n_upd"]
+        read = self._read_stats(*self._stat_tensors(st))  # the only host sync of learn()
+        return self._result(*(a.astype(np.float64) for a in read), st["n_upd"])
+
+    def _drop_rides(self):
+        pass
+
+    def learning_rate_decay(self, step, optimizers=None, mode="cosine"):
+        self._native_lr_decay(step, mode)
+
+    def process(self, transitions, step):
+        """ppo.py:187-202."""
+        result = {}
+        if transitions is None:
+            pass
+        elif isinstance(transitions, dict):
+            self.memory.store_soa(transitions)
+        else:
+            self.memory.store(transitions)
+        delta_t = step - self.time_t
+        self.time_t = step
+        self.learn_stamp += delta_t
+        if self.learn_stamp >= self.n_step:
+            result = self.learn()
+            if self.lr_decay:
+                self.learning_rate_decay(step)
+            self.learn_stamp = 0
+        return result
+
+    def process_begin(self, step):
+        raise NotImplementedError("the split process() is the MLP policy's (NativeCollector); PPO on the value-network engine takes process()")
+
+    process_end = process_begin
+
+    def early_ready(self):
+        return False
+
+    def _resume_extra_attrs(self):
+        return {"act_seed": str(self._seed), "act_ctr": str(self._act_ctr)}
+
+    def _resume_load_extra_attrs(self, d):
+        if "act_seed" in d:
+            self._seed, self._act_ctr = int(d["act_seed"]), int(d["act_ctr"])
+
+
+class PPOConv(PackedHeadsPPO):
     """core/agent/ppo.py:10-202 for `head="cnn"` (config/ppo/atari.py, config/ppo/procgen.py; network/head.py:21-61 under policy_value.py:8-22).
 
     The network is conv 8x8/4 -> conv 4x4/2 -> conv 3x3/1 -> Linear(F, hidden) -> (pi | v): the q-network of the DQN family with one more row in its
@@ -64,26 +154,14 @@ class PPOConv(NativeValueNetMixin, PPO):
         self.gamma, self.use_standardization, self.run_step, self.lr_decay = gamma, use_standardization, run_step, lr_decay
         self.batch_size, self.n_step, self.n_epoch, self._lambda = batch_size, n_step, n_epoch, _lambda
         self.epsilon_clip, self.vf_coef, self.ent_coef, self.clip_grad_norm, self.num_workers = epsilon_clip, vf_coef, ent_coef, clip_grad_norm, num_workers
-        self.time_t = self.learn_stamp = 0
-        self.memory = RolloutBuffer(device=self.device)
-        self.grad_sync = None
-        self.dp_exact_critic = os.environ.get("JH_DP_EXACT_CRITIC", "1") == "1"
-        self.backend, self.use_graph = "native", use_graph
-        self.graph_with_collective = os.environ.get("JH_GRAPH_DP", "1") == "1"
-        self._learn_graphs, self._static, self._stats = ops.LearnGraphs("PPO(cnn).learn()"), None, None
-        self._seed, self._act_ctr = int(seed), 0
-        self._ride, self._ride_wait = None, {}  # (PPO._upload_idx: nothing rides on a collector's commit launch here)
+        self.use_graph = use_graph
+        self._init_packed("PPO(cnn).learn()", seed)
         # the reference's initialisation (orthogonal, utils.py:110-124) drawn by the reference's module on the host, then moved into the library's bucket
         torch_net = Network(network, self.state_size, self.action_size, D_hidden=hidden_size, head=head)
         self._net = ops.RainbowNet(self.state_size, self.action_size, 1, hidden_size, "cnn", max(int(batch_size), int(forward_rows)), self.device, kind="pv")
         self._net.import_state(torch_net.state_dict())
         self.network = PolicyValueNet(self._net, 0)
-        self._optim_config = dict(optim_config)
-        self._opt_name = "adam"
-        d = Optimizer(**optim_config, params=[torch.nn.Parameter(torch.zeros(1))]).defaults
-        self._lr0, self._lr_now, self._adam_steps = float(d["lr"]), float(d["lr"]), 0
-        self._set_native_hyper(d, 0)
-        self.optimizer = None
+        self._init_optimizer(optim_config)
 
     # ---------------------------------------------------------------------------------- act
     @torch.no_grad()
@@ -162,66 +240,7 @@ class PPOConv(NativeValueNetMixin, PPO):
                 net.optim_step("adam", max_norm=self.clip_grad_norm)
                 k += 1
 
-    def learn(self):
-        M, E = self.memory.size, self.n_epoch
-        if self._static is None or self._static["M"] != M:
-            self._static = self._alloc_static(M)
-            self.reset_graphs()
-        st = self._static
-        if st.get("store") is not self.memory._store:  # the rollout store was replaced (it grows by doubling): a captured graph holds the old one's addresses
-            st["store"] = self.memory._store
-            self.reset_graphs()
-        graphable = (self.use_graph and not ops._PROF["on"]
-                     and (self.grad_sync is None or (self.graph_with_collective and getattr(self.grad_sync, "capturable", True))))
-        # the reference's global-RNG shuffles (ppo.py:118) of all epochs, drawn before the launches (nothing else touches np.random inside learn())
-        self._upload_idx(st, lambda out: np_rng.epoch_shuffles(M, E, out))
-        self._learn_graphs.run("learn", lambda: self._enqueue_learn(st), graphable)
-        self.memory._store.clear()
-        self._adam_steps += st["n_upd"]
-        s = self._read_stats(st["stats"])[0].astype(np.float64)  # the only host sync of learn()
-        return self._result(s, st["n_upd"])
-
-    def _drop_rides(self):
-        pass
-
-    def learning_rate_decay(self, step, optimizers=None, mode="cosine"):
-        self._native_lr_decay(step, mode)
-
-    def process(self, transitions, step):
-        """ppo.py:187-202."""
-        result = {}
-        if transitions is None:
-            pass
-        elif isinstance(transitions, dict):
-            self.memory.store_soa(transitions)
-        else:
-            self.memory.store(transitions)
-        delta_t = step - self.time_t
-        self.time_t = step
-        self.learn_stamp += delta_t
-        if self.learn_stamp >= self.n_step:
-            result = self.learn()
-            if self.lr_decay:
-                self.learning_rate_decay(step)
-            self.learn_stamp = 0
-        return result
-
-    def process_begin(self, step):
-        raise NotImplementedError("the split process() is the MLP policy's (NativeCollector); PPO on the CNN head takes process()")
-
-    process_end = process_begin
-
-    def early_ready(self):
-        return False
-
     # ---------------------------------------------------------------------------------- checkpoint
-    def _resume_extra_attrs(self):
-        return {"act_seed": str(self._seed), "act_ctr": str(self._act_ctr)}
-
-    def _resume_load_extra_attrs(self, d):
-        if "act_seed" in d:
-            self._seed, self._act_ctr = int(d["act_seed"]), int(d["act_ctr"])
-
     def save(self, path):
         self._native_save(path)
 

@@ -7,6 +7,7 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   discrete_q_network           core/network/q_network.py:8-20
   discrete_policy_value        core/network/policy_value.py:8-22
   continuous_policy_value      core/network/policy_value.py:38-57
+  discrete_policy_separate_value / continuous_policy_separate_value   core/network/policy_value.py:25-35, 60-70 (a second value head v_i)
   dueling                      core/network/dueling.py:8-35
   rainbow                      core/network/rainbow.py:8-94 (+ utils.py:55-107 noisy linear)
   noisy                        core/network/noisy.py:8-50 (+ utils.py:89-107 init_weights)
@@ -17,6 +18,7 @@ checkpoint format need.  (The forward-capable restatement that the parity tests 
   continuous_policy            core/network/policy.py:38-55
   discrete_policy              core/network/policy.py:23-35
   icm_mlp                      core/network/icm.py:153-188 (+ utils.py:6-24 reward filter, running moments)
+  rnd_mlp                      core/network/rnd.py:13-35, 167-203 (predictor and frozen target)
   r2d2                         core/network/r2d2.py:8-26
 """
 import torch
@@ -105,6 +107,25 @@ class ContinuousPolicyValue(BaseNetwork):
         orthogonal_init(self.mu, "linear")
         orthogonal_init(self.log_std, "tanh")
         orthogonal_init(self.v, "linear")
+
+
+class DiscretePolicySeparateValue(DiscretePolicyValue):
+    """RND-PPO's discrete net (policy_value.py:25-35): one more value head v_i for the intrinsic return; v and v_i are re-drawn with gain 0.01
+    after the parent's initialisation, in this order, so one torch.manual_seed gives the reference's weights."""
+
+    def __init__(self, D_in, D_out, D_hidden=512, head="mlp"):
+        super().__init__(D_in, D_out, D_hidden, head)
+        self.v_i = torch.nn.Linear(D_hidden, 1)
+        orthogonal_init([self.v, self.v_i], 0.01)
+
+
+class ContinuousPolicySeparateValue(ContinuousPolicyValue):
+    """RND-PPO's continuous net (policy_value.py:60-70), as DiscretePolicySeparateValue."""
+
+    def __init__(self, D_in, D_out, D_hidden=512, head="mlp"):
+        super().__init__(D_in, D_out, D_hidden, head)
+        self.v_i = torch.nn.Linear(D_hidden, 1)
+        orthogonal_init([self.v, self.v_i], 0.01)
 
 
 class Dueling(BaseNetwork):
@@ -321,10 +342,41 @@ class ICM_MLP(_Container):
             self.bn1_next = torch.nn.BatchNorm1d(D_hidden)
 
 
+class RND_MLP(_Container):
+    """RND-PPO's distillation module (rnd.py:173-203): module names, registration order and initialisation (orthogonal with the ReLU gain on
+    the four linear layers, predictor first) as the reference's, so its state_dict has the reference's 35 keys (15 without batch norm) and,
+    after the same torch.manual_seed, the reference's weights.  Every parameter whose name contains "target" is frozen -- the target's batch
+    norm affine parameters too.  The feature size is 256 whatever D_hidden says (rnd.py:196)."""
+
+    def __init__(self, D_in, D_out, num_workers, gamma_i, ri_normalize=True, obs_normalize=True, batch_norm=True, D_hidden=256):
+        super().__init__()
+        self.D_in, self.D_out, self.num_workers = D_in, D_out, num_workers
+        self.rms_obs = RunningMeanStd(D_in)
+        self.rms_ri = RunningMeanStd(1)
+        self.rff = RewardForwardFilter(gamma_i, num_workers)
+        self.obs_normalize, self.ri_normalize, self.batch_norm = obs_normalize, ri_normalize, batch_norm
+        feature_size = 256
+        self.fc1_predict_mlp = torch.nn.Linear(D_in, D_hidden)
+        self.fc2_predict_mlp = torch.nn.Linear(D_hidden, feature_size)
+        self.fc1_target_mlp = torch.nn.Linear(D_in, D_hidden)
+        self.fc2_target_mlp = torch.nn.Linear(D_hidden, feature_size)
+        orthogonal_init([self.fc1_predict_mlp, self.fc2_predict_mlp, self.fc1_target_mlp, self.fc2_target_mlp])
+        if batch_norm:
+            self.bn1_predict_mlp = torch.nn.BatchNorm1d(D_hidden)
+            self.bn2_predict_mlp = torch.nn.BatchNorm1d(feature_size)
+            self.bn1_target_mlp = torch.nn.BatchNorm1d(D_hidden)
+            self.bn2_target_mlp = torch.nn.BatchNorm1d(feature_size)
+        for name, param in self.named_parameters():
+            if "target" in name:
+                param.requires_grad = False
+
+
 network_dict = {
     "discrete_q_network": DiscreteQ_Network,
     "discrete_policy_value": DiscretePolicyValue,
     "continuous_policy_value": ContinuousPolicyValue,
+    "discrete_policy_separate_value": DiscretePolicySeparateValue,
+    "continuous_policy_separate_value": ContinuousPolicySeparateValue,
     "dueling": Dueling,
     "rainbow": Rainbow,
     "noisy": Noisy,
@@ -335,6 +387,7 @@ network_dict = {
     "continuous_policy": ContinuousPolicy,
     "discrete_policy": DiscretePolicy,
     "icm_mlp": ICM_MLP,
+    "rnd_mlp": RND_MLP,
     "r2d2": R2D2,
 }
 

@@ -5,19 +5,16 @@
 //                the running moments of the observations and of the intrinsic reward, the discounted reward filter, the no-grad reward pass
 //                over a whole rollout, and one minibatch update (forward, both losses, backward, global-norm clip, Adam).
 // Every dense contraction runs on the tile engine (jh_tgemm.hip) under the call-site name "dense", independent layers sharing a grouped
-// launch.  The kernels of this file are everything else: gather + normalise + clip, batch norm under BATCH statistics fused with ELU (the
-// module is never put into eval mode; the running statistics are advanced by the same kernel), the two-headed loss, the backward of batch
-// norm fused with ELU's, the observation moments and the reward kernels.
-// A column's statistics are taken by ONE workgroup over all rows (16 columns x 16 row lanes: shuffles inside a wave, then LDS across the four
-// waves), the variance about the mean in a second pass, in double.  No atomics and no spinning: every sum has a fixed order, so two runs (and
-// a graph replay) give the same bits.
-#include "jh_netcore.h"
+// launch.  Gather + normalise + clip, batch norm under BATCH statistics fused with the activation (the module is never put into eval mode;
+// the running statistics are advanced by the same kernel) and its backward, the observation moments and the reward filter are
+// jh_curiosity.h's, shared with RND-PPO's module (jh_rnd.hip) and instantiated here with ELU; the kernels of this file are the two-headed
+// loss and the raw intrinsic reward.  No atomics and no spinning: every sum has a fixed order, so two runs (and a graph replay) give the
+// same bits.
+#include "jh_curiosity.h"
 
 namespace {
 
-constexpr int kF = 256;          // feature size, whatever hidden_size says (icm.py:181)
-constexpr int kMaxBatch = 8192;  // rows of one call: the tile engine indexes in 32 bits, the loss kernel is one workgroup
-constexpr float kBnEps = 1e-5f, kBnMomentum = 0.1f;
+constexpr int kF = kCurF, kMaxBatch = kCurMaxBatch;
 
 enum { IC_FC1_W, IC_FC1_B, IC_FC2_W, IC_FC2_B, IC_FF1_W, IC_FF1_B, IC_FF2_W, IC_FF2_B, IC_IF1_W, IC_IF1_B, IC_IF2_W, IC_IF2_B,
        IC_BN1_W, IC_BN1_B, IC_BN2_W, IC_BN2_B, IC_BN1N_W, IC_BN1N_B, IC_SEG_MAX };
@@ -68,223 +65,6 @@ int icm_layout(jh_icmnet* n, int32_t S, int32_t H, int32_t A, int32_t cont, int3
   n->nseg = n->bn ? IC_SEG_MAX : kSegPlain;
   n->n_params = seg_pack(n->seg_rows, n->seg_cols, 0, n->nseg, n->seg_off);
   return JH_OK;
-}
-
-__device__ __forceinline__ float icm_elu(float u) { return u > 0.f ? u : expm1f(u); }
-
-// sum over the 16 row lanes of a column: lanes c, c + 16, c + 32, c + 48 of each wave by shuffles, then the four waves through LDS in wave order
-__device__ __forceinline__ double icm_col_sum(double v, double (*red)[16]) {
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();  // protect `red` from a previous use
-  if (lane < 16) red[w][lane] = v;
-  __syncthreads();
-  const int c = threadIdx.x & 15;
-  return ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-}
-
-// RunningMeanStd.update_from_moments (utils.py:31-52) in float32, operation for operation
-__device__ __forceinline__ void icm_rms_merge(float& mean, float& var, float count, float bm, float bv, float bc) {
-  const float delta = bm - mean;
-  const float tot = count + bc;
-  const float new_mean = mean + delta * bc / tot;
-  const float m_a = var * count;
-  const float m_b = bv * bc;
-  const float M2 = m_a + m_b + delta * delta * count * bc / (count + bc);
-  var = M2 / (count + bc);
-  mean = new_mean;
-}
-
-// ---------------------------------------------------------------------------------- observation moments and their merge
-// icm.update_rms_obs(next_state) (icm_ppo.py:98, utils.py:26-29): per-feature mean and UNBIASED variance over the rows, merged into the
-// running mean / var / count.  One workgroup: the count is one word that every feature's merge reads and the last step writes.
-__global__ void __launch_bounds__(256) jh_icm_obs_update_kernel(int rows, int S, const float* __restrict__ x, float* mean, float* var, float* count) {
-  __shared__ double s_red[4][16];
-  const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
-  const float cnt = *count;
-  for (int c0 = 0; c0 < S; c0 += 16) {
-    const int c = c0 + cl;
-    const bool on = c < S;
-    double s = 0.0;
-    if (on)
-      for (int r = rl; r < rows; r += 16) s += (double)x[(size_t)r * S + c];
-    s = icm_col_sum(s, s_red);
-    const double mu = s / (double)rows;
-    double q = 0.0;
-    if (on)
-      for (int r = rl; r < rows; r += 16) {
-        const double d = (double)x[(size_t)r * S + c] - mu;
-        q += d * d;
-      }
-    q = icm_col_sum(q, s_red);
-    if (on && rl == 0) {
-      float mn = mean[c], vr = var[c];
-      icm_rms_merge(mn, vr, cnt, (float)mu, (float)(q / (double)(rows - 1)), (float)rows);
-      mean[c] = mn;
-      var[c] = vr;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) *count = (float)rows + cnt;
-}
-
-// ---------------------------------------------------------------------------------- gather, normalise, clip
-// x = [state[idx]; next_state[idx]] (2b rows), normalize_obs (rnd.py:9-10) when mean != nullptr; the action columns of [phi | a] and [fh | a]
-struct PrepArgs {
-  int b, S, ac, H, ldf, ldf2;
-  int64_t n_rows;
-  const float *state, *next_state, *action;
-  const int64_t* idx;
-  const float *mean, *var;
-  float *x, *fin, *fin2;
-};
-__device__ __forceinline__ int64_t icm_row(const PrepArgs& a, int r) {
-  int64_t s = a.idx ? a.idx[r] : (int64_t)r;
-  return s < 0 ? 0 : (s >= a.n_rows ? a.n_rows - 1 : s);  // a bad index must not read outside the rollout
-}
-__global__ void __launch_bounds__(256) jh_icm_prep_kernel(PrepArgs a) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t nx = (int64_t)2 * a.b * a.S;
-  if (i < nx) {
-    const int c = (int)(i % a.S);
-    const int rr = (int)(i / a.S);
-    const int half = rr >= a.b, r = rr - half * a.b;
-    float v = (half ? a.next_state : a.state)[icm_row(a, r) * a.S + c];
-    if (a.mean) {
-      v = (v - a.mean[c]) / (sqrtf(a.var[c]) + 1e-7f);
-      v = fminf(fmaxf(v, -5.f), 5.f);
-    }
-    a.x[i] = v;
-  } else if (i < nx + (int64_t)a.b * a.ac) {
-    const int64_t j = i - nx;
-    const int k = (int)(j % a.ac), r = (int)(j / a.ac);
-    const float v = a.action[icm_row(a, r) * a.ac + k];
-    a.fin[(size_t)r * a.ldf + kF + k] = v;
-    a.fin2[(size_t)r * a.ldf2 + a.H + k] = v;
-  }
-}
-
-// ---------------------------------------------------------------------------------- batch norm (batch statistics) + ELU
-// z [2b][C]: half h = rows [h b, h b + b) with its own batch norm (gamma == nullptr: none, ELU only).  y = elu((z - mean) / sqrt(var + eps)
-// * gamma + beta) with the BIASED batch variance; running_mean / running_var advance with momentum 0.1 and the UNBIASED variance (icm.py:20-34).
-struct BnHalf {
-  const float *gamma, *beta;
-  float *rmean, *rvar, *smean, *sinv;
-  float* out0;
-  int ld0;
-  float* out1;  // optional second copy of the output
-  int ld1;
-};
-struct BnFwdArgs {
-  const float* z;
-  int b, C;
-  BnHalf h[2];
-};
-__global__ void __launch_bounds__(256) jh_icm_bn_elu_kernel(BnFwdArgs a) {
-  __shared__ double s_red[4][16];
-  const BnHalf& h = a.h[blockIdx.y];
-  const int c = blockIdx.x * 16 + (threadIdx.x & 15), rl = threadIdx.x >> 4;
-  const int b = a.b, C = a.C;
-  const bool on = c < C;
-  const float* z = a.z + (size_t)blockIdx.y * b * C;
-  float mean = 0.f, inv = 1.f, ga = 1.f, be = 0.f;
-  if (h.gamma) {  // uniform over the workgroup
-    double s = 0.0;
-    if (on)
-      for (int r = rl; r < b; r += 16) s += (double)z[(size_t)r * C + c];
-    s = icm_col_sum(s, s_red);
-    const double mu = s / (double)b;
-    double q = 0.0;
-    if (on)
-      for (int r = rl; r < b; r += 16) {
-        const double d = (double)z[(size_t)r * C + c] - mu;
-        q += d * d;
-      }
-    q = icm_col_sum(q, s_red);
-    const double var = q / (double)b;
-    mean = (float)mu;
-    inv = (float)(1.0 / sqrt(var + (double)kBnEps));
-    if (on) {
-      ga = h.gamma[c];
-      be = h.beta[c];
-      if (rl == 0) {
-        h.smean[c] = mean;
-        h.sinv[c] = inv;
-        const float unb = (float)(q / (double)(b - 1));
-        h.rmean[c] = kBnMomentum * mean + (1.f - kBnMomentum) * h.rmean[c];
-        h.rvar[c] = kBnMomentum * unb + (1.f - kBnMomentum) * h.rvar[c];
-      }
-    }
-  }
-  if (!on) return;
-  for (int r = rl; r < b; r += 16) {
-    const float u = (z[(size_t)r * C + c] - mean) * inv * ga + be;
-    const float y = icm_elu(u);
-    h.out0[(size_t)r * h.ld0 + c] = y;
-    if (h.out1) h.out1[(size_t)r * h.ld1 + c] = y;
-  }
-}
-
-// backward of the above: g = (dy0 + dy1) * elu'(u) with elu'(u) = 1 (y > 0) | y + 1 = exp(u); through the batch statistics
-// dz = gamma inv (g - mean_r g - xhat mean_r (g xhat)), d(gamma) = sum_r g xhat, d(beta) = sum_r g; without batch norm dz = g
-struct BnBwdHalf {
-  const float* dy0;
-  int ldd0;
-  const float* dy1;  // optional second source of the gradient
-  int ldd1;
-  const float* y;
-  int ldy;
-  const float *gamma, *smean, *sinv;
-  float *dgamma, *dbeta;
-};
-struct BnBwdArgs {
-  const float* z;
-  float* dz;
-  int b, C;
-  BnBwdHalf h[2];
-};
-__device__ __forceinline__ float icm_bn_g(const BnBwdHalf& h, int r, int c) {
-  float d = h.dy0[(size_t)r * h.ldd0 + c];
-  if (h.dy1) d += h.dy1[(size_t)r * h.ldd1 + c];
-  const float y = h.y[(size_t)r * h.ldy + c];
-  return y > 0.f ? d : d * (y + 1.f);
-}
-__global__ void __launch_bounds__(256) jh_icm_bn_elu_bwd_kernel(BnBwdArgs a) {
-  __shared__ double s_red[4][16];
-  const BnBwdHalf& h = a.h[blockIdx.y];
-  const int c = blockIdx.x * 16 + (threadIdx.x & 15), rl = threadIdx.x >> 4;
-  const int b = a.b, C = a.C;
-  const bool on = c < C;
-  const float* z = a.z + (size_t)blockIdx.y * b * C;
-  float* dz = a.dz + (size_t)blockIdx.y * b * C;
-  if (!h.gamma) {
-    if (on)
-      for (int r = rl; r < b; r += 16) dz[(size_t)r * C + c] = icm_bn_g(h, r, c);
-    return;
-  }
-  const float mean = on ? h.smean[c] : 0.f, inv = on ? h.sinv[c] : 1.f, ga = on ? h.gamma[c] : 1.f;
-  double sg = 0.0, sgx = 0.0;
-  if (on)
-    for (int r = rl; r < b; r += 16) {
-      const float g = icm_bn_g(h, r, c);
-      const float xh = (z[(size_t)r * C + c] - mean) * inv;
-      sg += (double)g;
-      sgx += (double)g * (double)xh;
-    }
-  sg = icm_col_sum(sg, s_red);
-  sgx = icm_col_sum(sgx, s_red);
-  if (!on) return;
-  if (rl == 0) {
-    h.dgamma[c] = (float)sgx;
-    h.dbeta[c] = (float)sg;
-  }
-  const float mg = (float)(sg / (double)b), mgx = (float)(sgx / (double)b);
-  for (int r = rl; r < b; r += 16) {
-    const float g = icm_bn_g(h, r, c);
-    const float xh = (z[(size_t)r * C + c] - mean) * inv;
-    dz[(size_t)r * C + c] = ga * inv * (g - mg - xh * mgx);
-  }
 }
 
 // ---------------------------------------------------------------------------------- the loss with two heads
@@ -357,77 +137,19 @@ __global__ void __launch_bounds__(256) jh_icm_ri_kernel(int rows, const float* _
   if (lane == 0) ri[r] = half_eta * s;
 }
 
-// ri_update (icm.py:145-150) as the reference really behaves, the normalisation and the mix (icm.py:215-216, icm_ppo.py:100-102).  One workgroup.
-//   filter     worker w's rows are w T .. w T + T - 1 (r_i.view(num_workers, -1)): rewems_w <- rewems_w * gamma + r_i[w, t] for t = 0 .. T - 1
-//   rms_ri     RewardForwardFilter.update returns the Parameter ITSELF, so the reference's stack is T copies of the FINAL rewems: batch count
-//              T W, batch mean mean_w rewems_w, unbiased batch variance T sum_w (rewems_w - mean)^2 / (T W - 1)
-//   r_i        /= sqrt(rms_ri.var) + 1e-7 (the var AFTER this update), reward <- ext * reward + int * r_i, *ri_mean = mean(r_i)
-struct RewardArgs {
-  int rows, W, T, ri_norm;
-  const float* ri_raw;
-  float *ri_blk, *rewems;  // {mean, var, count}, [W]
-  float gamma, ext, intr;
-  float *reward, *ri_out, *ri_mean;
-};
-__global__ void __launch_bounds__(256) jh_icm_reward_kernel(RewardArgs a) {
-  __shared__ double s_red[16];
-  __shared__ float s_den;
-  const int W = a.W, T = a.T;
-  for (int w = threadIdx.x; w < W; w += 256) {
-    float rew = a.rewems[w];
-    for (int t = 0; t < T; ++t) rew = rew * a.gamma + a.ri_raw[(size_t)w * T + t];
-    a.rewems[w] = rew;
-  }
-  __syncthreads();
-  double s = 0.0;
-  for (int w = threadIdx.x; w < W; w += 256) s += (double)a.rewems[w];
-  s = jh_block_reduce(s, s_red, JhAdd(), 0.0);
-  const double mu = s / (double)W;
-  double q = 0.0;
-  for (int w = threadIdx.x; w < W; w += 256) {
-    const double d = (double)a.rewems[w] - mu;
-    q += d * d;
-  }
-  q = jh_block_reduce(q, s_red, JhAdd(), 0.0);
-  if (threadIdx.x == 0) {
-    const double n = (double)T * (double)W;
-    float mn = a.ri_blk[0], vr = a.ri_blk[1];
-    const float cnt = a.ri_blk[2];
-    icm_rms_merge(mn, vr, cnt, (float)mu, (float)((double)T * q / (n - 1.0)), (float)n);
-    a.ri_blk[0] = mn;
-    a.ri_blk[1] = vr;
-    a.ri_blk[2] = (float)n + cnt;
-    s_den = a.ri_norm ? sqrtf(vr) + 1e-7f : 1.f;
-  }
-  __syncthreads();
-  const float den = s_den;
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < a.rows; i += 256) {
-    float r = a.ri_raw[i];
-    if (a.ri_norm) r = r / den;
-    if (a.ri_out) a.ri_out[i] = r;
-    const float e = a.ext * a.reward[i];
-    const float f = a.intr * r;
-    a.reward[i] = e + f;
-    acc += (double)r;
-  }
-  acc = jh_block_reduce(acc, s_red, JhAdd(), 0.0);
-  if (threadIdx.x == 0 && a.ri_mean) *a.ri_mean = (float)(acc / (double)a.rows);
-}
-
 // ---------------------------------------------------------------------------------- host side
 inline const float* P(const jh_icmnet* n, int s) { return n->p + n->seg_off[s]; }
 inline float* G(const jh_icmnet* n, int s) { return n->g + n->seg_off[s]; }
 
 int icm_prep(jh_icmnet* n, const float* state, const float* next_state, const float* action, const int64_t* idx, int b, int64_t n_rows, hipStream_t st) {
   PrepArgs a{};
-  a.b = b; a.S = n->S; a.ac = n->ac; a.H = n->H; a.ldf = n->ldf; a.ldf2 = n->ldf2; a.n_rows = n_rows;
-  a.state = state; a.next_state = next_state; a.action = action; a.idx = idx;
+  a.b = b; a.S = n->S; a.ac = n->ac; a.halves = 2; a.fcol = kF; a.fcol2 = n->H; a.ldf = n->ldf; a.ldf2 = n->ldf2; a.n_rows = n_rows;
+  a.src[0] = state; a.src[1] = next_state; a.action = action; a.idx = idx;
   a.mean = n->obs_norm ? n->blk + n->o_obs_mean : nullptr;
   a.var = n->blk + n->o_obs_var;
   a.x = n->x; a.fin = n->fin; a.fin2 = n->fin2;
-  const int64_t total = (int64_t)2 * b * n->S + (int64_t)b * n->ac;
-  JH_LAUNCH(jh_icm_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
+  const int64_t total = cur_prep_threads(a);
+  JH_LAUNCH_NAMED("jh_icm_prep_kernel", jh_cur_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
   JH_LAUNCH_CHECK();
   return JH_OK;
 }
@@ -455,7 +177,7 @@ int icm_forward(jh_icmnet* n, int b, hipStream_t st) {
     a.z = n->z1; a.b = b; a.C = H;
     a.h[0] = icm_bn_half(n, IC_BN1_W, n->o_bn1, H, n->save, n->a1, H, nullptr, 0);
     a.h[1] = icm_bn_half(n, IC_BN1N_W, n->o_bn1n, H, n->save + 2 * H + 2 * kF, n->a1 + (size_t)b * H, H, nullptr, 0);
-    JH_LAUNCH(jh_icm_bn_elu_kernel, dim3((unsigned)((H + 15) / 16), 2), dim3(256), 0, st, a);
+    JH_LAUNCH_NAMED("jh_icm_bn_elu_kernel", jh_cur_bn_act_kernel<CUR_ELU>, dim3((unsigned)((H + 15) / 16), 2), dim3(256), 0, st, a);
     JH_LAUNCH_CHECK();
   }
   g[0] = mk_gemm(2 * b, kF, H, op_dense(OP_KCONT, n->a1, H), op_dense(OP_KCONT, P(n, IC_FC2_W), H), n->z2, kF, TEPI_BIAS, P(n, IC_FC2_B));
@@ -465,7 +187,7 @@ int icm_forward(jh_icmnet* n, int b, hipStream_t st) {
     a.z = n->z2; a.b = b; a.C = kF;
     a.h[0] = icm_bn_half(n, IC_BN2_W, n->o_bn2, kF, n->save + 2 * H, n->cat, 2 * kF, n->fin, n->ldf);
     a.h[1] = icm_bn_half(n, -1, 0, kF, nullptr, n->cat + kF, 2 * kF, nullptr, 0);  // no batch norm after fc2 on s' (icm.py:32)
-    JH_LAUNCH(jh_icm_bn_elu_kernel, dim3(kF / 16, 2), dim3(256), 0, st, a);
+    JH_LAUNCH_NAMED("jh_icm_bn_elu_kernel", jh_cur_bn_act_kernel<CUR_ELU>, dim3(kF / 16, 2), dim3(256), 0, st, a);
     JH_LAUNCH_CHECK();
   }
   g[0] = mk_gemm(b, H, kF + ac, op_dense(OP_KCONT, n->fin, n->ldf), op_dense(OP_KCONT, P(n, IC_FF1_W), kF + ac), n->fin2, n->ldf2, TEPI_BIAS_RELU, P(n, IC_FF1_B));
@@ -499,7 +221,7 @@ int icm_backward(jh_icmnet* n, int b, hipStream_t st) {
     if (n->bn) { h0.gamma = P(n, IC_BN2_W); h0.smean = n->save + 2 * H; h0.sinv = n->save + 2 * H + kF; h0.dgamma = G(n, IC_BN2_W); h0.dbeta = G(n, IC_BN2_B); }
     BnBwdHalf& h1 = a.h[1];
     h1.dy0 = n->dcat + kF; h1.ldd0 = 2 * kF; h1.y = n->cat + kF; h1.ldy = 2 * kF;
-    JH_LAUNCH(jh_icm_bn_elu_bwd_kernel, dim3(kF / 16, 2), dim3(256), 0, st, a);
+    JH_LAUNCH_NAMED("jh_icm_bn_elu_bwd_kernel", jh_cur_bn_act_bwd_kernel<CUR_ELU>, dim3(kF / 16, 2), dim3(256), 0, st, a);
     JH_LAUNCH_CHECK();
   }
   g[0] = mk_gemm(kF, H, 2 * b, op_dense(OP_XCONT, n->dz2, kF), op_dense(OP_XCONT, n->a1, H), G(n, IC_FC2_W), H, TEPI_NONE, nullptr, nullptr, 0, G(n, IC_FC2_B));
@@ -517,7 +239,7 @@ int icm_backward(jh_icmnet* n, int b, hipStream_t st) {
         h.gamma = P(n, w); h.smean = save; h.sinv = save + H; h.dgamma = G(n, w); h.dbeta = G(n, w + 1);
       }
     }
-    JH_LAUNCH(jh_icm_bn_elu_bwd_kernel, dim3((unsigned)((H + 15) / 16), 2), dim3(256), 0, st, a);
+    JH_LAUNCH_NAMED("jh_icm_bn_elu_bwd_kernel", jh_cur_bn_act_bwd_kernel<CUR_ELU>, dim3((unsigned)((H + 15) / 16), 2), dim3(256), 0, st, a);
     JH_LAUNCH_CHECK();
   }
   g[0] = mk_gemm(H, S, 2 * b, op_dense(OP_XCONT, n->dz1, H), op_dense(OP_XCONT, n->x, S), G(n, IC_FC1_W), S, TEPI_NONE, nullptr, nullptr, 0, G(n, IC_FC1_B));
@@ -636,7 +358,7 @@ JH_EXPORT int jh_icmnet_stats_set(jh_icmnet* n, const float* h_in, jh_stream str
 JH_EXPORT int jh_icmnet_obs_update(jh_icmnet* n, const float* d_next_state, int32_t rows, jh_stream stream) {
   JH_ARG(n && d_next_state);
   JH_ARG(rows >= 2 && rows <= n->maxB);  // x.std of one row is NaN
-  JH_LAUNCH(jh_icm_obs_update_kernel, dim3(1), dim3(256), 0, jh_s(stream), rows, n->S, d_next_state, n->blk + n->o_obs_mean, n->blk + n->o_obs_var, n->blk + n->o_obs_cnt);
+  JH_LAUNCH_NAMED("jh_icm_obs_update_kernel", jh_cur_obs_update_kernel, dim3(1), dim3(256), 0, jh_s(stream), rows, n->S, d_next_state, n->blk + n->o_obs_mean, n->blk + n->o_obs_var, n->blk + n->o_obs_cnt);
   JH_LAUNCH_CHECK();
   return JH_OK;
 }
@@ -657,7 +379,7 @@ JH_EXPORT int jh_icmnet_reward(jh_icmnet* n, const float* d_state, const float* 
   RewardArgs a{};
   a.rows = rows; a.W = n->W; a.T = rows / n->W; a.ri_norm = n->ri_norm; a.ri_raw = raw; a.ri_blk = n->blk + n->o_ri; a.rewems = n->blk + n->o_rew;
   a.gamma = n->gamma; a.ext = extrinsic_coeff; a.intr = intrinsic_coeff; a.reward = d_reward; a.ri_out = d_ri; a.ri_mean = d_ri_mean;
-  JH_LAUNCH(jh_icm_reward_kernel, dim3(1), dim3(256), 0, st, a);
+  JH_LAUNCH_NAMED("jh_icm_reward_kernel", jh_cur_reward_kernel, dim3(1), dim3(256), 0, st, a);
   JH_LAUNCH_CHECK();
   return JH_OK;
 }

@@ -544,6 +544,36 @@ def heads_unpack(packed, A, h0, h1, value):
     L.check(L.load().jh_heads_unpack(L.ctx(_dev(packed)), int(packed.shape[0]), int(A), L.ptr(packed), int(packed.shape[1]), L.ptr(h0), L.ptr(h1), L.ptr(value), L.stream_ptr()))
 
 
+def rnd_adv_mix(adv_e, adv_i, ret, ret_i, n_step, extrinsic_coeff, intrinsic_coeff, standardize, out, means):
+    """rnd_ppo.py:153-166 behind two gae(..., standardize=False) calls: out [M] = ext * adv_e + int * adv_i, standardised per row of n_step
+    entries (unbiased std, + 1e-7) when asked; means [2] = mean(ret), mean(ret_i)."""
+    a_e, a_i, r_e, r_i, o = (_f32(t).reshape(-1) for t in (adv_e, adv_i, ret, ret_i, out))
+    M = int(a_e.numel())
+    assert M % int(n_step) == 0 and all(int(t.numel()) == M for t in (a_i, r_e, r_i, o)) and means.numel() >= 2 and means.is_contiguous()
+    L.check(L.load().jh_rnd_adv_mix(L.ctx(_dev(a_e)), M // int(n_step), int(n_step), float(extrinsic_coeff), float(intrinsic_coeff), int(bool(standardize)), L.ptr(a_e),
+                                    L.ptr(a_i), L.ptr(r_e), L.ptr(r_i), L.ptr(o), L.ptr(means), L.stream_ptr()))
+    return out
+
+
+def rnd_ppo_loss_packed(heads, A, idx, action, adv, ret, ret_i, value_old, vi_old, logp_old, eps_clip, vf_coef, ent_coef, grad_out, stats, continuous=False):
+    """RND-PPO's losses (rnd_ppo.py:201-249) on heads float32 [B, ld] = (head0 [A] | head1 [A] (continuous) | v | v_i | padding); grad_out the same
+    shape, padding columns untouched.  idx None: the per-row inputs are already the minibatch's rows.  stats [8] = 0, actor, critic_e, critic_i,
+    entropy, max ratio, min prob, 0."""
+    assert heads.dtype == torch.float32 and heads.is_contiguous() and grad_out.is_contiguous() and grad_out.shape == heads.shape
+    assert stats is None or (stats.numel() >= 8 and stats.is_contiguous())
+    B, ld = int(heads.shape[0]), int(heads.shape[1])
+    act = _f32(action) if continuous else _f32(action).reshape(-1)
+    lpo = _f32(logp_old) if continuous else _f32(logp_old).reshape(-1)
+    per_row = [_f32(t).reshape(-1) for t in (adv, ret, ret_i, value_old, vi_old)]
+    rows = int(per_row[0].numel())
+    assert all(int(t.numel()) == rows for t in per_row) and int(act.numel()) == rows * (A if continuous else 1) and int(lpo.numel()) == int(act.numel())
+    assert idx is not None or rows >= B
+    L.check(L.load().jh_rnd_ppo_loss_packed(L.ctx(_dev(heads)), int(bool(continuous)), B, int(A), L.ptr(heads), ld, L.ptr(idx), L.ptr(act), *(L.ptr(t) for t in per_row[:3]),
+                                            L.ptr(per_row[3]), L.ptr(per_row[4]), L.ptr(lpo), float(eps_clip), float(vf_coef), float(ent_coef), L.ptr(grad_out),
+                                            L.ptr(stats), L.stream_ptr()))
+    return grad_out
+
+
 def policy_act_discrete(heads, A, seed, counter, training, out):
     """ppo.py:63-69 on device-resident heads [W, ld]: out int64 [W] (device / device-mapped) <- sampled (training) or greedy actions."""
     assert heads.is_contiguous() and out.dtype == torch.int64
@@ -1474,7 +1504,7 @@ class RainbowNet(_NetObject):
     _SEG = ("w1", "b1", "w2", "b2", "w3", "b3", "wl", "bl", "mu_av1", "sig_av1", "mub_av1", "sigb_av1", "mu_a2", "sig_a2", "mub_a2", "sigb_a2",
             "mu_v2", "sig_v2", "mub_v2", "sigb_v2")
     _SYM = "jh_rbnet_"
-    _KIND = {"rainbow": 0, "dueling": 1, "q": 2, "pv": 2, "pi": 2, "gauss": 2, "noisy": 4}  # "noisy": network/noisy.py (head -> noisy -> noisy; 5 with independent noise); "pv": the discrete policy-value net (policy_value.py:8-22) = head -> l -> (pi | v) stacked into ONE last layer of A + 1 rows; "gauss": the Gaussian policy (policy.py:38-55) = head -> l -> (mu | log_std), raw, stacked into ONE last layer of 2A rows
+    _KIND = {"rainbow": 0, "dueling": 1, "q": 2, "pv": 2, "pi": 2, "gauss": 2, "pv2": 2, "gauss2": 2, "noisy": 4}  # "noisy": network/noisy.py (head -> noisy -> noisy; 5 with independent noise); "pv": the discrete policy-value net (policy_value.py:8-22) = head -> l -> (pi | v) stacked into ONE last layer of A + 1 rows; "gauss": the Gaussian policy (policy.py:38-55) = head -> l -> (mu | log_std), raw, stacked into ONE last layer of 2A rows
 
     def __init__(self, state_size, action_size, num_support, hidden, head, max_batch, device, kind="rainbow", noise_type="factorized"):
         self._open(device)
@@ -1489,6 +1519,10 @@ class RainbowNet(_NetObject):
             self.n_actions, self.A = self.A, self.A + 1  # the library sees a q-network with one more output row: the value head
         if kind == "gauss":
             self.n_actions, self.A = self.A, 2 * self.A  # the Gaussian policy (policy.py:38-55) = a q-network with 2A output rows: mu | log_std, raw
+        if kind in ("pv2", "gauss2"):
+            # the policy-value nets with two value heads (policy_value.py:25-35, 60-70) = a q-network whose last layer stacks (pi | v | v_i) in
+            # A + 2 rows or (mu | log_std | v | v_i), raw, in 2A + 2 rows
+            self.n_actions, self.A = self.A, (self.A if kind == "pv2" else 2 * self.A) + 2
         kid = self._KIND[kind]
         self.noise_type = noise_type
         if kind in ("rainbow", "noisy") and noise_type == "independent":
@@ -1567,6 +1601,15 @@ class RainbowNet(_NetObject):
             out += head
             out += [("l.weight", self._feat_cols(self._v(bucket, "wl"))), ("l.bias", self._v(bucket, "bl").view(-1)),
                     ("mu.weight", w[:n]), ("mu.bias", b[:n]), ("log_std.weight", w[n:]), ("log_std.bias", b[n:])]
+        elif self.kind in ("pv2", "gauss2"):
+            w, b, n = self._v(bucket, "mu_a2"), self._v(bucket, "mub_a2").view(-1), self.n_actions
+            out += head
+            out += [("l.weight", self._feat_cols(self._v(bucket, "wl"))), ("l.bias", self._v(bucket, "bl").view(-1))]
+            names = ("pi",) if self.kind == "pv2" else ("mu", "log_std")
+            for i, name in enumerate(names):
+                out += [(f"{name}.weight", w[i * n : (i + 1) * n]), (f"{name}.bias", b[i * n : (i + 1) * n])]
+            nv = len(names) * n
+            out += [("v.weight", w[nv : nv + 1]), ("v.bias", b[nv : nv + 1]), ("v_i.weight", w[nv + 1 :]), ("v_i.bias", b[nv + 1 :])]
         else:
             last = "pi" if self.kind == "pi" else "q"  # "pi": the discrete policy (policy.py:23-35) = a q-network whose last layer is named pi
             out += head
@@ -2460,6 +2503,98 @@ class ICMNet(_NetObject):
         assert stats is None or stats.numel() >= 4
         L.check(self._fn("update")(self.h, L.ptr(state), L.ptr(next_state), L.ptr(action), L.ptr(idx), b, int(state.shape[0]), float(beta),
                                    float(max_norm if max_norm else 0.0), L.ptr(stats), L.stream_ptr()))
+
+
+class RNDNet(_NetObject):
+    """jh_rndnet_*: RND-PPO's distillation module (network/rnd.py:173-225) -- predictor and frozen target, each fc1 -> bn1 -> ReLU -> fc2 -> bn2
+    -> ReLU under batch statistics, the running moments of observations and intrinsic reward, the reward filter -- with the no-grad reward
+    pass over a rollout (`obs_update`, `reward`) and one minibatch update of the predictor (`update`) as tile-engine launches plus the kernels
+    of jh_rnd.hip / jh_curiosity.h.  The 16 tensors live in flat buckets, the predictor's eight first (`_SEG`; only they get gradients, moments
+    and Adam steps); `_pairs` lists them in the reference's registration order (`_ORDER`).  Everything that is a buffer-like Parameter in the
+    reference (rms_obs, rms_ri, rff, the batch norms' running statistics) lives in the device statistics block (`stats()` / `set_stats()`)."""
+
+    _SEG = tuple(f"{layer}_{net}_mlp.{t}" for net in ("predict", "target") for layer in ("fc1", "fc2", "bn1", "bn2") for t in ("weight", "bias"))
+    _ORDER = tuple(f"{kind}{i}_{net}_mlp.{t}" for kind in ("fc", "bn") for net in ("predict", "target") for i in (1, 2) for t in ("weight", "bias"))
+    _SYM = "jh_rndnet_"
+    F = 256            # feature size (rnd.py:196)
+    MAX_BATCH = 8192   # rows of one call (jh_curiosity.h: kCurMaxBatch)
+
+    def __init__(self, state_size, hidden, num_workers, max_batch, device, gamma_i=0.99, obs_normalize=True, ri_normalize=True, batch_norm=True, buckets=None):
+        self._open(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.S, self.H, self.W, self.maxB = int(state_size), int(hidden), int(num_workers), int(max_batch)
+        self.gamma_i = float(gamma_i)
+        self.obs_normalize, self.ri_normalize, self.batch_norm = bool(obs_normalize), bool(ri_normalize), bool(batch_norm)
+        n = int(self._fn("param_count_for")(self.S, self.H, int(self.batch_norm)))
+        if n <= 0:
+            L.check(-2)
+        self.n_params = n
+        self.params, self.grads, self.m, self.v = self._zeros(n, 4) if buckets is None else buckets
+        assert all(t.numel() == n and t.is_contiguous() and t.dtype == torch.float32 for t in (self.params, self.grads, self.m, self.v))
+        flags = int(self.obs_normalize) | (int(self.ri_normalize) << 1) | (int(self.batch_norm) << 2)
+        self.h = C.c_void_p()
+        L.check(self._fn("create")(self.ctx, self.S, self.H, self.W, self.maxB, flags, self.gamma_i, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v),
+                                   C.byref(self.h)))
+        assert int(self._fn("segment_count")(self.h)) == len(self._SEG)
+        self.seg = {k: v for k, v in self._segments(self._SEG).items() if v[1] * v[2] > 0}  # without batch norm its segments are empty
+        self.n_train = int(self._fn("trainable_floats")(self.h))
+        self.stats_floats = int(self._fn("stats_floats")(self.h))
+
+    def _pairs(self, bucket, trainable_only=False):
+        """[(reference key, view of the bucket shaped like the reference tensor)] in the reference's registration order."""
+        out = []
+        for name in self._ORDER:
+            if name not in self.seg or (trainable_only and "target" in name):
+                continue
+            off, rows, cols = self.seg[name]
+            v = bucket[off : off + rows * cols]
+            out.append((name, v.view(rows, cols) if name.endswith(".weight") and not name.startswith("bn") else v))
+        return out
+
+    def export_state(self, bucket=None):
+        return _export_pairs(self._pairs(self.params if bucket is None else bucket))
+
+    def import_state(self, sd, bucket=None):
+        _import_pairs(self._pairs(self.params if bucket is None else bucket), sd, self.device)
+
+    def set_hyper(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
+        L.check(self._fn("set_hyper")(self.h, float(lr), float(beta1), float(beta2), float(eps), int(step), L.stream_ptr()))
+
+    def set_lr(self, lr):
+        L.check(self._fn("set_lr")(self.h, float(lr), L.stream_ptr()))
+
+    def _stats_layout(self):
+        S, H, W, F = self.S, self.H, self.W, self.F
+        return (("rms_obs.mean", S), ("rms_obs.var", S), ("rms_obs.count", 0), ("rms_ri.mean", 1), ("rms_ri.var", 1), ("rms_ri.count", 0), ("rff.rewems", W),
+                ("bn1_predict_mlp.running_mean", H), ("bn1_predict_mlp.running_var", H), ("bn2_predict_mlp.running_mean", F), ("bn2_predict_mlp.running_var", F),
+                ("bn1_target_mlp.running_mean", H), ("bn1_target_mlp.running_var", H), ("bn2_target_mlp.running_mean", F), ("bn2_target_mlp.running_var", F))
+
+    stats, set_stats = ICMNet.stats, ICMNet.set_stats  # the block's codec is the same: {reference state_dict key: float32 array} by `_stats_layout`
+
+    def _check_rows(self, next_state):
+        assert next_state.is_contiguous() and next_state.dtype == torch.float32 and next_state.device == self.device and next_state.dim() == 2 and next_state.shape[1] == self.S
+
+    def obs_update(self, next_state):
+        """rnd.update_rms_obs(next_state) (rnd_ppo.py:119)."""
+        self._check_rows(next_state)
+        L.check(self._fn("obs_update")(self.h, L.ptr(next_state), int(next_state.shape[0]), L.stream_ptr()))
+
+    def reward(self, next_state, ri, ri_mean=None, ri_raw=None):
+        """The no-grad pass of rnd_ppo.py:120 over the whole rollout: ri [M] = the (normalised) intrinsic reward; optional ri_mean [1], ri_raw [M]."""
+        self._check_rows(next_state)
+        M = int(next_state.shape[0])
+        assert ri.is_contiguous() and ri.dtype == torch.float32 and ri.numel() == M
+        assert (ri_raw is None or ri_raw.numel() == M) and (ri_mean is None or ri_mean.numel() >= 1)
+        L.check(self._fn("reward")(self.h, L.ptr(next_state), M, L.ptr(ri), L.ptr(ri_mean), L.ptr(ri_raw), L.stream_ptr()))
+
+    def update(self, next_state, idx, max_norm, stats=None, b=None):
+        """One minibatch (rnd_ppo.py:251-252, 261-266) on rows idx (int64) of next_state, or on rows 0 .. b - 1.  stats [4] = r_i mean, 0, 0, mark."""
+        self._check_rows(next_state)
+        b = int(idx.numel()) if idx is not None else (int(next_state.shape[0]) if b is None else int(b))
+        assert idx is None or (idx.is_contiguous() and idx.dtype == torch.int64 and idx.device == self.device)
+        assert stats is None or stats.numel() >= 4
+        L.check(self._fn("update")(self.h, L.ptr(next_state), L.ptr(idx), b, int(next_state.shape[0]), float(max_norm if max_norm else 0.0), L.ptr(stats), L.stream_ptr()))
 
 
 class StagingRing:

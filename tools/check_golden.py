@@ -22,7 +22,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOLS = ("qrdqn", "mdqn", "iqn", "miqn", "riqn", "noisy", "td3", "sac", "vmpo", "mpo", "mpo_continuous", "icm", "r2d2", "reinforce")
+TOOLS = ("qrdqn", "mdqn", "iqn", "miqn", "riqn", "noisy", "td3", "sac", "vmpo", "mpo", "mpo_continuous", "icm", "r2d2", "reinforce", "rnd")
 
 
 def npz_differences(new, old):
