@@ -7,7 +7,8 @@
   val_rescale / inv_val_rescale   r2d2.py:304-313 AS WRITTEN (in float64 their cancellation costs 1e-13)
   loss            jh_r2d2_loss's contract in numpy float64, from the three time-major Q tensors on
   learn           the whole of R2D2.learn() (r2d2.py:99-163) up to the raw gradients, in the dtype of the networks
-and the tables of the kernel tests: STEP_SHAPES, NET_SHAPES, SWEEP with its case builder; the reader of the fixtures of
+and the tables of the kernel tests: STEP_SHAPES, NET_SHAPES, SWEEP with its case builder; beside them the tables at the kernels' own dispatch
+limits (EDGE_STEP_SHAPES, EDGE_NET_SHAPE, EDGE_LOSS_CASES) with their builders and the targeted variants of one multi-wave loss case; the reader of the fixtures of
 tools/gen_golden_r2d2.py (Fixture) with the generator's fill loop for any agent (fill_loop)."""
 import itertools
 import os
@@ -127,6 +128,132 @@ def sweep_case(B, T, A, n_step, scale, seed=0):
 
 def sweep_truth(c, eta):
     return loss(c["q"], c["next_q"], c["next_target_q"], c["action"], c["reward"], c["done"], c["weights"], c["burn"], c["n_step"], GAMMA, eta, ALPHA, EPS)
+
+
+# ---------------------------------------------------------------------------------------------- the kernels' own dispatch edges
+# (rows, H, A) of tests/test_r2d2_edges_gpu.py.  jh_lstm_step splits ceil(H / 16) k chunks over four waves and owns 16 rows x 16 units per
+# workgroup: H 8 half a unit tile; 16 one tile, one chunk; 20 two chunks, the second with 4 live k, the second unit tile with 4 units; 48 three
+# chunks (wave 3 idle); 52 four, the last partial; 68 five (wave 0 takes two, the others one); 100 seven (three waves take two); 1024 sixteen
+# per wave.  Every H meets one of the rows 15 / 16 / 17, rows 1 and 33 (three row tiles) a few of them.
+EDGE_STEP_SHAPES = ((15, 8, 2), (16, 16, 3), (1, 16, 2), (17, 20, 5), (1, 20, 2), (15, 48, 2), (16, 52, 3), (17, 68, 2), (33, 68, 3), (15, 100, 4), (1, 100, 2),
+                    (17, 1024, 2))
+# the network object beside NET_SHAPES (seq_len, n_burn_in, n_step, B, H, S, A): two row tiles with one row in the second, a partial unit tile
+# and a partial k chunk at every one of its three-segment step launches
+EDGE_NET_SHAPE = (5, 2, 2, 17, 20, 3, 4)
+# (B, T', A, n_step, seed) at SWEEP_BURN burn-in steps, both |Q| scales, eta 0.9: every wave count edge of the one-workgroup loss kernel
+# (B <= 1024 = 16 waves), the widest A, T' + burn-in = 128, n_step > T' and n_step at its cap.  The seed is the first one at which
+# test_r2d2_cpu's two conditions on these cases hold: off every discontinuity, and a loss that a lost wave would miss by ten times the
+# tolerance (both decided by the float64 truth alone).
+EDGE_LOSS_CASES = ((65, 1, 2, 1, 1), (128, 3, 5, 3, 0), (255, 3, 64, 5, 0), (256, 1, 18, 5, 0), (257, 3, 2, 3, 0), (1023, 1, 5, 1, 0), (1024, 1, 64, 3, 0),
+                   (1024, 3, 18, 1, 1), (64, 40, 64, 3, 0), (256, 40, 5, 3, 1), (2, 126, 5, 3, 0), (65, 126, 2, 1, 0), (7, 1, 2, 128, 0))
+EDGE_SCALES = (0.05, 50.0)
+EDGE_ETA = 0.9
+EDGE_MULTI = (1024, 3, 18, 1, 1)  # the multi-wave case of the targeted variants; it also runs at eta 0 and 1
+
+
+def step_case(rows, H, A, seed):
+    """One row group of a jh_lstm_step launch in float64, rounded to float32 values (test_r2d2_gpu._step_case's construction): xproj = x W_ih^T +
+    b_ih + b_hh from an input row of H + A entries, W_hh in torch.nn.LSTM's initial range."""
+    g = torch.Generator().manual_seed(1000 * seed + 7 * rows + H + A)
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    k = 1.0 / np.sqrt(H)
+    w_ih, w_hh, b = k * r(4 * H, H + A), k * r(4 * H, H), k * r(4 * H)
+    xproj = (r(rows, H + A) @ w_ih.t() + b).float().double()
+    return dict(xproj=xproj, w_hh=w_hh.float().double(), h=(0.5 * r(rows, H)).float().double(), c=r(rows, H).float().double())
+
+
+def edge_step_groups(rows, H, A):
+    """The four row groups of one launch, each with weights of its own: rows, none (the empty segment in the middle), rows + 3, one."""
+    return [step_case(n, H, A, 11 + s) for s, n in enumerate((rows, 0, rows + 3, 1))]
+
+
+def _copy(c):
+    return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c.items()}
+
+
+def taken(c):
+    """[B, T'] the action of every trained step as the kernel reads it (clamped into [0, A))."""
+    return np.clip(c["action"][:, c["burn"]:c["burn"] + c["T"]].astype(np.int64), 0, c["A"] - 1)
+
+
+def with_max_q_at(c, row, t=0):
+    """The taken-action q of (row, step t) raised above every other entry -> (case, that float32 value): max_Q must be exactly it."""
+    c = _copy(c)
+    v = np.float32(4.0 * np.abs(c["q"]).max())
+    c["q"][t, row, taken(c)[row, t]] = v
+    return c, v
+
+
+def with_one_weight(c, wave):
+    """Every importance weight zero but one of wave `wave` (rows 64 wave ..): the row of that wave whose last-step |td| is largest in the float64
+    truth, at weight 1 -> (case, row).  The loss is then one term that only the cross-wave sum can deliver to thread 0."""
+    c = _copy(c)
+    t = sweep_truth(c, EDGE_ETA)
+    lo, hi = 64 * wave, min(c["B"], 64 * wave + 64)
+    row = lo + int(np.argmax(t["td"][lo:hi, -1]))
+    c["weights"][:] = 0.0
+    c["weights"][row] = 1.0
+    return c, row
+
+
+def variant_rows(B):
+    """Six rows away from row 0 (the episode end) and row B - 1 (the padded one); beyond one wave three of them sit in the last wave."""
+    return (1, 2, 3, B - 4, B - 3, B - 2) if B > 64 else (1, 2, 3, 4, 5, 6)
+
+
+def with_bad_actions(c):
+    """Stored actions out of range over the whole trained window of six rows: -1, A, A + 3, -1, A, A + 3 -> (case, {row: the column the
+    kernel's documented clamp lands on}).  r2d2_truth.loss clips the same way."""
+    c = _copy(c)
+    want = {}
+    for i, row in enumerate(variant_rows(c["B"])):
+        v = (-1.0, float(c["A"]), float(c["A"] + 3))[i % 3]
+        c["action"][row, c["burn"]:c["burn"] + c["T"]] = v
+        want[row] = 0 if v < 0 else c["A"] - 1
+    return c, want
+
+
+def with_exact_ties(c):
+    """In six rows, at every trained step, the second-best next_q entry set to the best one's float32 value, and next_target_q at those two
+    actions set to + and - max |next_target_q| (the lower index gets the +): `first maximum` decides the target by twice that -> (case, rows)."""
+    c = _copy(c)
+    rows = variant_rows(c["B"])
+    scale = np.float32(np.abs(c["next_target_q"]).max())
+    for row in rows:
+        for t in range(c["T"]):
+            k2, k1 = np.argsort(c["next_q"][t, row], kind="stable")[-2:]
+            c["next_q"][t, row, k2] = c["next_q"][t, row, k1]
+            lo, hi = min(k1, k2), max(k1, k2)
+            c["next_target_q"][t, row, lo], c["next_target_q"][t, row, hi] = scale, -scale
+    return c, rows
+
+
+def with_all_done(c, row):
+    """done = 1 at every column of `row`: its targets are the rescaled rewards alone."""
+    c = _copy(c)
+    c["done"][row, :] = 1.0
+    return c
+
+
+def edge_multi_variants(scale):
+    """The targeted variants of EDGE_MULTI at one |Q| scale -> [(name, case, what the variant pins down)]: the global max_Q in the last wave's
+    last row, in the first row of a middle wave and in row 0; all of the loss in one row of the last and of a middle wave; actions out of
+    range; exact next_q ties; a row that is done at every column."""
+    B, T, A, n_step, seed = EDGE_MULTI
+    c = sweep_case(B, T, A, n_step, scale, seed)
+    out = []
+    for row in (B - 1, 64 * 7, 0):
+        cc, v = with_max_q_at(c, row)
+        out.append((f"max_Q in row {row}", cc, dict(max_q=v, row=row)))
+    for wave in (15, 9):
+        cc, row = with_one_weight(c, wave)
+        out.append((f"the only weight in wave {wave}", cc, dict(only_row=row)))
+    cc, want = with_bad_actions(c)
+    out.append(("actions out of range", cc, dict(columns=want)))
+    cc, rows = with_exact_ties(c)
+    out.append(("exact ties", cc, dict(tie_rows=rows)))
+    out.append(("a row done at every column", with_all_done(c, 5), dict(done_row=5)))
+    return out
 
 
 def batch(rs, B, seq_len, n_step, S, A, H, pad_rows=(), done_rows=()):

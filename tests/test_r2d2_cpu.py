@@ -101,6 +101,124 @@ def test_no_sweep_case_sits_on_a_discontinuity():
     assert sorted({v[0] for v in D.SWEEP_VARIANTS}) == [1, 3] and sorted({v[1] for v in D.SWEEP_VARIANTS}) == [0.05, 50.0] and sorted({v[2] for v in D.SWEEP_VARIANTS}) == [0.0, 0.9, 1.0]
 
 
+TOL = 1e-5  # the GPU tests' tolerance: the sensitivity conditions below are stated against it
+
+
+def _off_every_discontinuity(c, t, what, tie_rows=()):
+    """test_no_sweep_case_sits_on_a_discontinuity's conditions on one case; `tie_rows` hold an exact tie instead of a gap (an exact tie is not
+    decided by rounding: the kernel documents the first maximum).  -> the scale the GPU criteria divide by."""
+    B, tie = c["B"], list(tie_rows)
+    big = max(np.abs(t["target_q"]).max(), np.abs(t["q_taken"]).max())
+    free = np.ones(B, bool)
+    free[tie] = False
+    assert (t["gap"][free] > 2.0 ** -20 * np.abs(c["next_q"]).max()).all(), what
+    assert (t["gap"][tie] == 0.0).all(), what
+    assert (t["td"][:, -1] > 2e-5 * big).all(), what
+    assert c["done"][0, c["burn"]:].any(), what
+    if B > 1:
+        assert c["pad"] > c["burn"] and not c["action"][B - 1, :c["pad"]].any() and not c["reward"][B - 1, :c["pad"]].any() and not c["done"][B - 1, :c["pad"]].any(), what
+    return big
+
+
+def test_no_edge_loss_case_sits_on_a_discontinuity():
+    """EDGE_LOSS_CASES at both |Q| scales, and every targeted variant of EDGE_MULTI, under the conditions of the sweep; the table's coverage:
+    every wave-count edge up to the cap of 1024 rows, A up to 64, T' + burn-in = 128, n_step > T' and n_step = 128."""
+    cases = D.EDGE_LOSS_CASES
+    for B, T, A, n_step, seed in cases:
+        assert D.SWEEP_BURN + T <= 128 and B <= 1024 and A <= 64 and n_step <= 128
+        for scale in D.EDGE_SCALES:
+            c = D.sweep_case(B, T, A, n_step, scale, seed)
+            _off_every_discontinuity(c, D.sweep_truth(c, D.EDGE_ETA), (B, T, A, n_step, scale))
+    assert sorted({c[0] for c in cases}) == [2, 7, 64, 65, 128, 255, 256, 257, 1023, 1024]
+    assert {c[0] for c in cases if c[1] <= 3} >= {65, 128, 255, 256, 257, 1023, 1024}
+    assert sorted({c[2] for c in cases}) == [2, 5, 18, 64] and sorted({c[1] for c in cases}) == [1, 3, 40, 126] and sorted({c[3] for c in cases}) == [1, 3, 5, 128]
+    shapes = {c[:3] for c in cases}
+    assert {(1024, 1, 64), (255, 3, 64), (64, 40, 64), (256, 40, 5)} <= shapes
+    assert {c[0] for c in cases if c[1] + D.SWEEP_BURN == 128} == {2, 65}
+    assert {c[1] for c in cases if c[3] == 5} == {1, 3} and (7, 1, 2, 128) in {c[:4] for c in cases}
+    assert D.EDGE_MULTI in cases and D.EDGE_MULTI[0] == 1024 and D.EDGE_SCALES == (0.05, 50.0) and D.EDGE_ETA == 0.9
+    for scale in D.EDGE_SCALES:
+        names = []
+        for name, c, info in D.edge_multi_variants(scale):
+            t = D.sweep_truth(c, D.EDGE_ETA)
+            big = _off_every_discontinuity(c, t, (name, scale), info.get("tie_rows", ()))
+            names.append(name)
+            if "columns" in info:  # out-of-range actions over the whole trained window, both sides of the range
+                window = c["action"][list(info["columns"]), c["burn"]:c["burn"] + c["T"]]
+                assert ((window < 0) | (window >= c["A"])).all() and set(info["columns"].values()) == {0, c["A"] - 1}
+            if "tie_rows" in info:  # the other maximum would move every tied row's |td| by far more than the tolerance
+                other = D._copy(c)
+                for row in info["tie_rows"]:
+                    for s in range(c["T"]):
+                        lo, hi = np.flatnonzero(c["next_q"][s, row] == c["next_q"][s, row].max())
+                        other["next_target_q"][s, row, [lo, hi]] = c["next_target_q"][s, row, [hi, lo]]
+                moved = np.abs(D.sweep_truth(other, D.EDGE_ETA)["td"] - t["td"]).max(1)
+                assert (moved[list(info["tie_rows"])] > 100 * TOL * big).all() and set(info["tie_rows"]) & {64 * 15 + k for k in range(64)}
+            if "done_row" in info:  # the target is the rescaled reward of the step itself
+                r = c["reward"][info["done_row"], c["burn"]:c["burn"] + c["T"]].astype(np.float64)
+                assert np.abs(t["target_q"][info["done_row"]] - D.val_rescale(r, float(np.float32(D.EPS)))).max() <= 1e-12
+        assert len(names) == len(set(names)) == 8
+
+
+def test_edge_loss_cases_would_expose_a_kernel_that_loses_waves():
+    """Conditions on the inputs, from the float64 truth alone.  A sum over the first wave's rows only (what thread 0 holds before the cross-wave
+    half of the block sum) misses every multi-wave case's loss by more than the loss criterion allows; in the one-weight variants it is zero;
+    in the max_Q variants the maximum over every wave but the doctored row's own misses max_Q outright."""
+    n = 0
+    for B, T, A, n_step, seed in D.EDGE_LOSS_CASES:
+        if B <= 64:
+            continue
+        for scale in D.EDGE_SCALES:
+            c = D.sweep_case(B, T, A, n_step, scale, seed)
+            t = D.sweep_truth(c, D.EDGE_ETA)
+            big = max(np.abs(t["target_q"]).max(), np.abs(t["q_taken"]).max())
+            first_wave = float((c["weights"].astype(np.float64) * t["td"][:, -1] ** 2)[:64].sum()) / B
+            assert abs(first_wave - t["loss"]) > 10 * TOL * big * big, (B, T, A, n_step, scale)
+            n += 1
+    assert n == 2 * 10
+    for scale in D.EDGE_SCALES:
+        for name, c, info in D.edge_multi_variants(scale):
+            t = D.sweep_truth(c, D.EDGE_ETA)
+            big = max(np.abs(t["target_q"]).max(), np.abs(t["q_taken"]).max())
+            if "only_row" in info:
+                assert info["only_row"] >= 64 and t["loss"] > 10 * TOL * big * big, (name, scale)
+                assert np.count_nonzero(t["grad_q"]) == 1
+            if "max_q" in info:
+                others = np.ones(c["B"], bool)
+                others[info["row"] // 64 * 64:info["row"] // 64 * 64 + 64] = False
+                assert t["max_Q"] == float(info["max_q"]) and t["q_taken"][others].max() < t["max_Q"], (name, scale)
+
+
+def test_edge_step_shapes_would_expose_a_lost_k_chunk_or_unit_tile():
+    """EDGE_STEP_SHAPES covers the rows and the H values of the kernel's dispatch edges, and its inputs are sensitive to them: where the last
+    16-deep k chunk is partial, or the chunk count is no multiple of the four waves, a float64 cell without that chunk's share of h W_hh^T is
+    further than TOL max|h'| from the truth, in every non-empty group; the same with the recurrent term of the last unit tile zeroed."""
+    shapes = D.EDGE_STEP_SHAPES
+    assert {s[0] for s in shapes} == {1, 15, 16, 17, 33} and sorted({s[1] for s in shapes}) == [8, 16, 20, 48, 52, 68, 100, 1024]
+    for H in {s[1] for s in shapes}:
+        assert {s[0] for s in shapes if s[1] == H} & {15, 16, 17}, H
+    assert (17, 1024, 2) in shapes and any(s[0] == 33 and 48 <= s[1] <= 100 for s in shapes)
+    assert sorted({-(-s[1] // 16) for s in shapes}) == [1, 2, 3, 4, 5, 7, 64]
+    n = 0
+    for rows, H, A in shapes:
+        chunks = -(-H // 16)
+        if H % 16 == 0 and chunks % 4 == 0:
+            continue
+        n += 1
+        k0 = u0 = 16 * (chunks - 1)
+        for s, g in enumerate(D.edge_step_groups(rows, H, A)):
+            if not g["h"].shape[0]:
+                continue
+            exact = D.lstm_cell(g["xproj"], g["h"], g["c"], g["w_hh"])[0]
+            h_cut = g["h"].clone()
+            h_cut[:, k0:] = 0.0
+            w_cut = g["w_hh"].clone()
+            w_cut.view(4, H, H)[:, u0:, :] = 0.0
+            for what, other in (("k chunk", D.lstm_cell(g["xproj"], h_cut, g["c"], g["w_hh"])[0]), ("unit tile", D.lstm_cell(g["xproj"], g["h"], g["c"], w_cut)[0])):
+                assert float((other - exact).abs().max()) > 10 * TOL * float(exact.abs().max()), (rows, H, s, what)
+    assert n == len(shapes) - 1  # all but H = 1024
+
+
 def test_stable_inverse_rescale_is_the_written_one_in_float64_and_float32_as_written_is_not():
     """The departure of jh_r2d2_loss: y / (sqrt(1 + y) + 1) for sqrt(1 + y) - 1.  In float64 both forms agree to 1e-12; the reference's float32
     expression is off by more than 1e-5 of the value at |Q| = 0.05 -- which is why the kernel is held to float64 and not to float32 torch."""
