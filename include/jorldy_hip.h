@@ -1310,6 +1310,42 @@ int64_t jh_feed_state_bytes(const jh_feed* f);
 int jh_feed_save(jh_feed* f, void* h_out, int64_t bytes, jh_stream stream);
 int jh_feed_load(jh_feed* f, const void* h_in, int64_t bytes, jh_stream stream);
 
+/* ------------------------------------------------------------------ batched recurrent actors (R2D2)
+ * N lockstep actors of one acting copy of the R2D2 network (csrc/jh_r2d2_actors.hip).  Replaces, per tick, the four device-to-host copies
+ * of R2D2.act (core/agent/r2d2.py:47-90: q, hidden_h, hidden_c, the action) and the host numpy of interact_callback (r2d2.py:179-287:
+ * a deque(maxlen = n_step + seq_len) per actor, the stacked row every store_period steps and at once after an episode start, front
+ * zero-padding, the actor-side priority).  The carried (h, c), the previous action's one-hot, the windows and the priorities stay in HBM.
+ *   create    limits (JH_ERR_ARG with a message): n_actors 1..1024, action_size 2..64, seq_len + n_step <= 160; H % 4 == 0, H <= 4096.
+ *   carried   the buffers of the tick that is about to act: jh_r2d2net_act_step reads *h_in / *c_in [N][H] and *onehot [N][A] and writes
+ *             *h_out / *c_out (the two slots swap every tick, so carrying the state is no copy).
+ *   act       after the step: d_q float [N][A], d_obs float [N][S], d_h_in / d_c_in = what the step read (16-byte aligned).  Per actor the
+ *             first-maximum argmax, epsilon-greedy with the host's draws (jh_value_act's convention; all three NULL: greedy), the record
+ *             of the tick into the actor's window ring, the next tick's one-hot.  d_action int64 [N] / d_q_taken float [N] may be
+ *             device-mapped host memory: q is written and fenced before the action, whose low word is the arrival mark.
+ *   emit      the env's answer h_reward / h_done float [N] (host) closes the tick: the state machine of interact_callback for every actor,
+ *             the rows of the actors that emit compacted in ascending actor order behind the rows already in `out` (restart != 0: from row
+ *             0), never beyond `capacity` rows (capacity >= n_actors).  Row r: state float [L][S], prev_action_onehot float [L][A], action / reward / done float
+ *             [L - 1], the four LSTM states float [H], priority double; L = seq_len + n_step.  *d_count (int64, may be device-mapped host
+ *             memory) <- the number of rows now in `out`; a value over `capacity` says that the rows beyond it were dropped.  Everything is
+ *             enqueued on `stream`.  One host thread drives an object.
+ *   state_bytes / save / load   the checkpoint of the actors' own state, as jh_feed_save.                                            */
+typedef struct jh_r2d2_actors jh_r2d2_actors;
+typedef struct {
+  float *state, *prev_action_onehot, *action, *reward, *done, *hidden_h, *hidden_c, *next_hidden_h, *next_hidden_c;
+  double* priority;
+} jh_r2d2_rows;
+int jh_r2d2_actors_create(jh_ctx* ctx, int32_t n_actors, int32_t S, int32_t A, int32_t H, int32_t seq_len, int32_t n_burn_in, int32_t n_step,
+                          int32_t store_period, int32_t zero_padding, double gamma, double eta, jh_r2d2_actors** out);
+void jh_r2d2_actors_destroy(jh_r2d2_actors* f);
+int jh_r2d2_actors_carried(jh_r2d2_actors* f, float** h_in, float** c_in, float** h_out, float** c_out, float** onehot);
+int jh_r2d2_actors_act(jh_r2d2_actors* f, const float* d_q, const float* d_obs, const float* d_h_in, const float* d_c_in, const float* h_eps,
+                       const double* h_u, const int64_t* h_rand_action, int64_t* d_action, float* d_q_taken, jh_stream stream);
+int jh_r2d2_actors_emit(jh_r2d2_actors* f, const float* h_reward, const float* h_done, const jh_r2d2_rows* out, int64_t capacity,
+                        int32_t restart, int64_t* d_count, jh_stream stream);
+int64_t jh_r2d2_actors_state_bytes(const jh_r2d2_actors* f);
+int jh_r2d2_actors_save(jh_r2d2_actors* f, void* h_out, int64_t bytes, jh_stream stream);
+int jh_r2d2_actors_load(jh_r2d2_actors* f, const void* h_in, int64_t bytes, jh_stream stream);
+
 /* ------------------------------------------------------------------ data-parallel learners: the collective
  * The reference has ONE learner and no collective (its "distributed" mode is Ray actors feeding that learner,
  * manager/distributed_manager.py, process.py); BASELINE.json's north star re-expresses Ape-X's many-actor / one-learner

@@ -29,6 +29,12 @@ class LstmSeg(C.Structure):
                 ("h_out", C.c_void_p), ("c_out", C.c_void_p), ("gates_out", C.c_void_p)]
 
 
+class R2D2Rows(C.Structure):
+    """jh_r2d2_rows: the output columns of jh_r2d2_actors_emit."""
+    NAMES = ("state", "prev_action_onehot", "action", "reward", "done", "hidden_h", "hidden_c", "next_hidden_h", "next_hidden_c", "priority")
+    _fields_ = [(k, C.c_void_p) for k in NAMES]
+
+
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _pp = C.POINTER(C.c_void_p)
 
@@ -291,6 +297,14 @@ _PROTOS = {
     "jh_feed_state_bytes": (_i64, [_vp]),
     "jh_feed_save": (C.c_int, [_vp, _vp, _i64, _vp]),
     "jh_feed_load": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "jh_r2d2_actors_create": (C.c_int, [_vp] + [_i32] * 9 + [_f64, _f64, _pp]),
+    "jh_r2d2_actors_destroy": (None, [_vp]),
+    "jh_r2d2_actors_carried": (C.c_int, [_vp] + [_pp] * 5),
+    "jh_r2d2_actors_act": (C.c_int, [_vp] * 11),
+    "jh_r2d2_actors_emit": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "jh_r2d2_actors_state_bytes": (_i64, [_vp]),
+    "jh_r2d2_actors_save": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "jh_r2d2_actors_load": (C.c_int, [_vp, _vp, _i64, _vp]),
     "jh_collector_stats": (C.c_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), _i32]),
     "jh_collector_run": (C.c_int, [_vp, _i32, _i32, _vp]),
     "jh_collector_stats_detail": (C.c_int, [_vp, C.POINTER(_f64)]),

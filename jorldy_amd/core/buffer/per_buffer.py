@@ -34,8 +34,12 @@ class PERBuffer(ReplayBuffer):
         return n
 
     def store_device(self, cols, example=None, priorities=None):
+        """+ the rows' leaves; `priorities`: host values, or a float64 CUDA tensor [n] (actor-side priorities computed on the device)."""
         n = super().store_device(cols, example)
-        self._tree.push(n, None if priorities is None else np.asarray(priorities, dtype=np.float64).reshape(-1))
+        if torch.is_tensor(priorities):
+            self._tree.push_device(n, priorities)
+        else:
+            self._tree.push(n, None if priorities is None else np.asarray(priorities, dtype=np.float64).reshape(-1))
         return n
 
     def store_feed_rows(self, cols, n, priorities=None):

@@ -67,13 +67,15 @@ class ReplayBuffer(BaseBuffer):
         """Rows that are already in HBM (a device-side producer, synthetic prefills): `cols` maps the agent-side keys
         to CUDA tensors [n, ...] in the STORED dtype (uint8 frames, float32, int64 actions, uint8 done flags);
         device-to-device ring append, same bookkeeping as store().  `example`: one host SoA batch that fixes the
-        column layout when nothing has been stored yet."""
+        column layout when nothing has been stored yet.  A column in another dtype than the stored one is converted on
+        the device (a producer that does not know whether the first stored batch made `action` int64 or float32)."""
         assert not self.frame_dedup, "frame_dedup recognises frames on the host"
         if self._store is None:
             assert example is not None, "the buffer has no layout yet: pass an example batch"
             self._make_store(example, self.buffer_size)
         self.flush()
-        flat = self._flat_cols(cols)
+        stored = {name: ops._TORCH_OF[dt] for name, dt, _, _ in self._store.columns}
+        flat = {name: v.to(stored[name]) for name, v in self._flat_cols(cols).items()}
         n = int(next(iter(flat.values())).shape[0])
         self._store.push_device(flat, n)
         self.buffer_index = (self.buffer_index + n) % self.buffer_size

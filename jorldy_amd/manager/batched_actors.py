@@ -103,6 +103,151 @@ class BatchedValueActors:
         return {"action": am.np.reshape(N, 1).copy(), "q": qm.np.reshape(N, 1).copy()}
 
 
+class BatchedRecurrentActors:
+    """R2D2's actors, batched: act() for n_actors lockstep environments on an acting copy of `agent`'s ops.R2D2Net, push() for the envs'
+    answer, drain_into() for the learner.  One launch chain per tick (upload -> jh_r2d2net_act_step -> jh_r2d2_actors_act); the carried
+    (h, c), the previous action's one-hot, the seq_len + n_step windows and the actor-side priorities of interact_callback
+    (core/agent/r2d2.py:179-287) stay in HBM (ops.R2D2ActorFeed).  Down come the N actions and one row count, up go N rewards and done flags.
+
+        actors = BatchedRecurrentActors(agent, n_envs)
+        out = actors.act(obs)                 # {"action": int64 [N, 1]}
+        actors.drain_into(agent.memory)       # the rows emitted so far + priorities -> the PER buffer, device to device
+        ... obs, reward, done = envs.step(out["action"]) ...
+        actors.push(reward, done)             # interact_callback of every actor, enqueued
+
+    The row count of a push() comes down with the next act()'s actions: a drain_into() between act() and push() knows it already and
+    waits for nothing, one right after push() waits for that count first (a second host wait in the tick).
+
+    agent: an R2D2 agent (head 'mlp').  epsilons: per-actor exploration rates (default: Ape-X's schedule eps^(1 + i/(N-1) * alpha),
+    ape_x.py:166-172).  capacity: rows one drain can take (default 8 N; every tick may emit up to N); push() refuses when the next
+    tick might not fit."""
+
+    MAX_ACTORS, MAX_WINDOW = 1024, 160  # jh_r2d2_actors_create's limits
+
+    def __init__(self, agent, n_actors, epsilons=None, stream=None, capacity=None):
+        from ..core.agent.r2d2 import R2D2
+
+        if not isinstance(agent, R2D2):
+            raise ValueError(f"BatchedRecurrentActors serves R2D2 agents (a network with a carried state), got {type(agent).__name__}; "
+                             "the feed-forward value agents go to BatchedValueActors")
+        N = int(n_actors)
+        if not 1 <= N <= self.MAX_ACTORS:
+            raise ValueError(f"n_actors = {N} is outside 1..{self.MAX_ACTORS}")
+        if agent.seq_len + agent.n_step > self.MAX_WINDOW:
+            raise ValueError(f"seq_len + n_step = {agent.seq_len} + {agent.n_step} is over {self.MAX_WINDOW}")
+        src = agent._net
+        self.agent, self.N, self.device = agent, N, agent.device
+        self.net = ops.R2D2Net(src.S, src.A, src.H, N, src.seq_len, src.n_burn_in, src.n_step, self.device)
+        self.feed = ops.R2D2ActorFeed(N, src.S, src.A, src.H, agent.seq_len, agent.n_burn_in, agent.n_step, agent.store_period, agent.zero_padding,
+                                      agent.gamma, agent.eta, self.device)
+        self.stream = stream or torch.cuda.Stream(device=self.device)
+        if epsilons is None:
+            epsilons = [agent.epsilon ** (1 + (i / (N - 1)) * agent.epsilon_alpha) for i in range(N)] if N > 1 else [agent.epsilon]
+        self.eps = np.ascontiguousarray(epsilons, dtype=np.float32)
+        assert self.eps.size == N
+        self._x_pin = torch.empty((N, src.S), dtype=torch.float32, pin_memory=True)
+        self._x_dev = torch.empty((N, src.S), dtype=torch.float32, device=self.device)
+        self._q = torch.empty((N, src.A), dtype=torch.float32, device=self.device)
+        # actions / q of a tick and the row count in device-mapped pinned memory: the kernels write them across PCIe, act() waits for the
+        # actions' arrival; the count of tick t's emit is written before tick t + 1's actions, so it is there when they are
+        self._maps = [(ops.PinnedBuffer((N,), np.int64, self.device), ops.PinnedBuffer((N,), np.float32, self.device)) for _ in range(2)]
+        self._count = ops.PinnedBuffer((1,), np.int64, self.device)
+        # two sets of output rows: one fills while the learner copies the other out
+        self.capacity = int(capacity) if capacity is not None else 8 * N
+        assert self.capacity >= N, "one tick can emit a row per actor"
+        self._rows = [self.feed.rows(self.capacity) for _ in range(2)]
+        self._ready = [torch.cuda.Event() for _ in range(2)]  # set s: every emit so far has run (acting stream)
+        self._taken = [None, None]                            # set s: the learner's copies out of it have run (learner stream)
+        self._set, self._filled, self._restart, self._in_flight = 0, 0, True, False
+        self.ticks = self.stored_rows = 0
+        self.sync()
+
+    @property
+    def obs_slab(self):
+        """numpy view [N, S] of the pinned staging slab: vectorised envs can write their observations in place."""
+        return self._x_pin.numpy()
+
+    def sync(self):
+        """The learner's weights for all actors: one D2D copy of the flat parameter bucket on the acting stream (BatchedValueActors.sync)."""
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            self.net.params.copy_(self.agent._net.params, non_blocking=True)
+
+    def _read_count(self):
+        if self._in_flight:
+            self._count.wait(what="BatchedRecurrentActors: the row count", stream=self.stream, timeout_s=ops.ACT_WAIT_S)
+            self._filled, self._in_flight = int(self._count.np[0]), False
+            if self._filled > self.capacity:  # push() keeps room for a full tick, so: the counters of this object were bypassed
+                raise RuntimeError(f"BatchedRecurrentActors: {self._filled} rows emitted into {self.capacity}: the rows beyond the capacity are lost")
+
+    @torch.no_grad()
+    def act(self, obs=None, training=True):
+        """obs: numpy float32 [N, S], or None when the envs wrote into `obs_slab` -> {"action": int64 [N, 1]} (blocking: the envs need the
+        actions).  training=False: greedy for every actor."""
+        if obs is not None:
+            np.copyto(self._x_pin.numpy(), obs, casting="same_kind")
+        N = self.N
+        eps = u = ra = None
+        if training and np.any(self.eps > 0):
+            eps = self.eps
+            u = np.random.random(N)                        # `np.random.random() < epsilon` per actor
+            ra = np.random.randint(0, self.net.A, size=N)  # `np.random.randint(0, action_size)` per actor
+        am, qm = self._maps[self.ticks & 1]
+        with torch.cuda.stream(self.stream):
+            self._x_dev.copy_(self._x_pin, non_blocking=True)
+            h_in, c_in, h_out, c_out, onehot = self.feed.carried()
+            self.net.act_step(self._x_dev, onehot, h_in, c_in, out=(self._q, h_out, c_out))
+            am.arm()
+            self.feed.act(self._q, self._x_dev, h_in, c_in, (am.dev, qm.dev), eps, u, ra)
+        am.wait(what="BatchedRecurrentActors.act(): the actions", stream=self.stream, timeout_s=ops.ACT_WAIT_S)
+        self._read_count()
+        return {"action": am.np.reshape(N, 1).copy()}
+
+    def push(self, reward, done):
+        """The envs' answer to the actions of the last act(): enqueue interact_callback of every actor.  The number of rows it emitted is
+        known when the next act() returns (or at the next drain_into)."""
+        self._read_count()
+        if self._filled + self.N > self.capacity:
+            raise RuntimeError(f"BatchedRecurrentActors.push(): {self._filled} of {self.capacity} rows wait for the learner and a tick can emit {self.N}: "
+                               "call drain_into() first (or give the actors a larger capacity)")
+        s = self._set
+        with torch.cuda.stream(self.stream):
+            if self._restart and self._taken[s] is not None:
+                self.stream.wait_event(self._taken[s])  # the learner's copies out of this set are done
+            self._count.arm()
+            self.feed.emit(reward, done, self._rows[s], self._count.dev, restart=self._restart)
+            self._ready[s].record(self.stream)
+        self._restart, self._in_flight = False, True
+        self.ticks += 1
+
+    def _example(self):
+        """One host row with the dtypes the first row of R2D2.interact_callback has: a padded first window is float64 throughout (stored as
+        float32), an unpadded one keeps int64 actions and bool done flags."""
+        pad = bool(self.agent.zero_padding)
+        ex = {k: np.zeros((1,) + tuple(v.shape[1:]), np.float32) for k, v in self._rows[0].items() if k != "priority"}
+        if not pad:
+            ex["action"], ex["done"] = ex["action"].astype(np.int64), ex["done"].astype(bool)
+        return ex
+
+    def drain_into(self, memory):
+        """Learner stream: append the emitted rows to the PER buffer (store_device: DeviceStore.push_device for the rows, SumTree.push_device
+        for their actor-side priorities); returns the number of rows taken.  Waits for the row count of a push() that no act() followed."""
+        self._read_count()
+        n, s = self._filled, self._set
+        if n == 0:
+            return 0
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(self._ready[s])
+        cols = {k: v[:n] for k, v in self._rows[s].items() if k != "priority"}
+        memory.store_device(cols, example=self._example(), priorities=self._rows[s]["priority"][:n])
+        memory.first_store = False
+        self._taken[s] = torch.cuda.Event()
+        self._taken[s].record(cur)
+        self._set, self._filled, self._restart = 1 - s, 0, True
+        self.stored_rows += n
+        return n
+
+
 class VecNStepApeX:
     """Ape-X's n-step assembler with actor-side priorities (ape_x.py:174-199) for N actors at once: the per-actor
     deque(maxlen = n + 1) of the reference becomes rolling arrays [n + 1, N, ...]; one push per tick emits N n-step

@@ -311,6 +311,86 @@ class ActorFeed:
         return int(fl.value), int(pw.value)
 
 
+class R2D2ActorFeed:
+    """jh_r2d2_actors_*: the acting epilogue and interact_callback (core/agent/r2d2.py:47-90, 179-287) of N lockstep R2D2 actors in HBM
+    (csrc/jh_r2d2_actors.hip): per-actor window rings of seq_len + n_step ticks, the carried (h, c) and the fed one-hot, the state machine
+    of the stored rows and their actor-side priorities.  A tick is act() then emit()."""
+
+    COLS = L.R2D2Rows.NAMES
+
+    def __init__(self, n_actors, state_size, action_size, hidden, seq_len, n_burn_in, n_step, store_period, zero_padding, gamma, eta, device=None):
+        self.lib = L.load()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.N, self.S, self.A, self.H, self.L = int(n_actors), int(state_size), int(action_size), int(hidden), int(seq_len) + int(n_step)
+        self.h = C.c_void_p()
+        L.check(self.lib.jh_r2d2_actors_create(L.ctx(self.device.index), self.N, self.S, self.A, self.H, int(seq_len), int(n_burn_in), int(n_step),
+                                               int(store_period), int(bool(zero_padding)), float(gamma), float(eta), C.byref(self.h)))
+        self._rew, self._done = np.empty(self.N, np.float32), np.empty(self.N, np.float32)
+        self._views = {}  # carried(): views of the library's memory, valid while this object lives
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.jh_r2d2_actors_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def carried(self):
+        """(h_in, c_in, h_out, c_out [N, H], onehot [N, A]) of the tick that is about to act: R2D2Net.act_step reads the first two and the
+        one-hot and writes the other two; the slots swap at every emit()."""
+        p = [C.c_void_p() for _ in range(5)]
+        L.check(self.lib.jh_r2d2_actors_carried(self.h, *(C.byref(v) for v in p)))
+        views = self._views.get(p[0].value)  # two sets, one per tick parity: wrapped once
+        if views is None:
+            views = self._views[p[0].value] = tuple(_wrap_device(v.value, (self.N, self.H if i < 4 else self.A), torch.float32, self.device)
+                                                    for i, v in enumerate(p))
+        return views
+
+    def rows(self, capacity):
+        """Output columns for `capacity` stored rows, named and shaped as R2D2.interact_callback's (float32; priority float64 [capacity])."""
+        n, Lw = int(capacity), self.L
+        shapes = {"state": (Lw, self.S), "prev_action_onehot": (Lw, self.A), "action": (Lw - 1, 1), "reward": (Lw - 1, 1), "done": (Lw - 1, 1)}
+        out = {k: torch.zeros((n,) + shapes.get(k, (1, self.H)), dtype=torch.float32, device=self.device) for k in self.COLS[:-1]}
+        out["priority"] = torch.zeros(n, dtype=torch.float64, device=self.device)
+        return out
+
+    def act(self, q, obs, h_in, c_in, out, eps=None, u=None, rand_action=None):
+        """q [N, A], obs [N, S] and the (h_in, c_in) the step read -> out = (action int64 [N], q_taken float32 [N]), mapped host memory or
+        not; eps / u / rand_action: the host's epsilon-greedy draws as ops.value_act takes them, or all None for greedy."""
+        q, obs, h_in, c_in = _f32(q), _f32(obs), _f32(h_in), _f32(c_in)
+        assert tuple(q.shape) == (self.N, self.A) and tuple(obs.shape) == (self.N, self.S) and h_in.numel() == self.N * self.H == c_in.numel()
+        act, qt, _, eps, u, rand_action = _act_buffers(self.N, self.A, self.device, eps, u, rand_action, out, False)
+        assert act.dtype == torch.int64 and qt.dtype == torch.float32 and act.numel() == self.N == qt.numel()
+        L.check(self.lib.jh_r2d2_actors_act(self.h, L.ptr(q), L.ptr(obs), L.ptr(h_in), L.ptr(c_in), L.ptr(eps), L.ptr(u), L.ptr(rand_action), L.ptr(act), L.ptr(qt),
+                                            L.stream_ptr()))
+        return act, qt
+
+    def emit(self, reward, done, out, count, restart=True):
+        """The env's answer closes the tick: reward / done host arrays [N]; out = rows(capacity), filled behind the rows it holds (restart:
+        from row 0), capacity >= N; count: int64 [1] device (or mapped) tensor <- the number of rows now in `out`, over the capacity when
+        rows did not fit and were dropped (the caller keeps room for N more rows before every emit)."""
+        np.copyto(self._rew, np.asarray(reward, dtype=np.float32).reshape(-1))
+        np.copyto(self._done, np.asarray(done, dtype=np.float32).reshape(-1))
+        cap = int(out["priority"].numel())
+        for k in self.COLS:
+            assert out[k].is_cuda and out[k].is_contiguous() and out[k].dtype == (torch.float64 if k == "priority" else torch.float32) and out[k].shape[0] == cap, k
+        assert count.dtype == torch.int64 and count.numel() >= 1
+        rows = L.R2D2Rows(*(out[k].data_ptr() for k in self.COLS))
+        L.check(self.lib.jh_r2d2_actors_emit(self.h, L.ptr(self._rew), L.ptr(self._done), C.byref(rows), cap, int(bool(restart)), L.ptr(count), L.stream_ptr()))
+
+    def state(self):
+        """The actors' own state (device block + tick) as bytes; synchronises the current stream."""
+        n = int(self.lib.jh_r2d2_actors_state_bytes(self.h))
+        buf = np.empty(n, np.uint8)
+        L.check(self.lib.jh_r2d2_actors_save(self.h, L.ptr(buf), n, L.stream_ptr()))
+        return buf
+
+    def load_state(self, buf):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        L.check(self.lib.jh_r2d2_actors_load(self.h, L.ptr(buf), int(buf.size), L.stream_ptr()))
+
+
 class SumTree:
     """Device float64 sum tree (jh_per_*), bit-identical to per_buffer.py's numpy tree."""
 
