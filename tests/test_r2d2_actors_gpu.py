@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import margins
+from r2d2_actors_truth import done_from_sets, host_rows, trace
 from tests.util import f32, npy
 
 pytestmark = pytest.mark.gpu
@@ -23,47 +24,6 @@ GAMMA, ETA = 0.99, 0.9
 PRIORITY_TOL = 2 * 4.96e-7
 
 
-def _host_actor(seq, burn, n, period, pad):
-    """An R2D2 that holds only what interact_callback reads: no device, no network."""
-    from collections import deque
-
-    from jorldy_amd.core.agent.r2d2 import R2D2
-
-    ag = object.__new__(R2D2)
-    ag.seq_len, ag.n_burn_in, ag.n_step, ag.store_period, ag.zero_padding, ag.gamma, ag.eta = seq, burn, n, period, pad, GAMMA, ETA
-    ag.tmp_buffer, ag.store_period_stamp, ag.store_start, ag.hidden, ag.prev_action = deque(maxlen=n + seq), 0, True, None, None
-    return ag
-
-
-def _trace(seed, S, A):
-    """The injected ticks: observations, all-action q in float64, the forced action, LSTM states, rewards, the done schedule."""
-    rs = np.random.RandomState(seed)
-    tr = dict(obs=rs.randn(TICKS, N, S).astype(np.float32), q=3.0 * rs.randn(TICKS, N, A), action=rs.randint(0, A, size=(TICKS, N)),
-              h=rs.randn(TICKS, N, H).astype(np.float32), c=rs.randn(TICKS, N, H).astype(np.float32),
-              reward=rs.choice([-1.0, 0.0, 0.5, 1.0], size=(TICKS, N)).astype(np.float32))
-    tr["done"] = np.asarray([[t in DONES[a] for a in range(N)] for t in range(TICKS)])
-    return tr
-
-
-def host_rows(case, tr, q_as=np.float64):
-    """rows[t] = [(actor, row dict)] in ascending actor order, from N interact_callbacks with float64 q / reward."""
-    seq, burn, n, period, pad, S, A = case
-    actors, prev, rows = [_host_actor(seq, burn, n, period, pad) for _ in range(N)], [None] * N, []
-    for t in range(TICKS):
-        out = []
-        for a, ag in enumerate(actors):
-            act = int(tr["action"][t, a])
-            onehot = np.zeros((1, A), np.float32) if prev[a] is None else np.eye(A, dtype=np.float32)[[prev[a]]]
-            row = ag.interact_callback({"state": tr["obs"][t, a][None], "reward": np.asarray([[tr["reward"][t, a]]], np.float64), "done": np.asarray([[tr["done"][t, a]]]),
-                                        "action": np.asarray([[act]]), "prev_action_onehot": onehot, "q": np.asarray([[tr["q"][t, a, act]]]).astype(q_as).astype(np.float64),
-                                        "hidden_h": tr["h"][t, a][None, None], "hidden_c": tr["c"][t, a][None, None]})
-            prev[a] = None if tr["done"][t, a] else act
-            if row:
-                out.append((a, row))
-        rows.append(out)
-    return rows
-
-
 @pytest.mark.parametrize("case", CASES, ids=[f"seq{c[0]}-burn{c[1]}-n{c[2]}-period{c[3]}-pad{int(c[4])}-S{c[5]}" for c in CASES])
 def test_emitted_rows_and_priorities_are_the_host_interact_callbacks(case):
     """Per tick: as many rows as the host emits, in ascending actor order, every column equal bit for bit (copies and zero fills), the float64
@@ -73,8 +33,8 @@ def test_emitted_rows_and_priorities_are_the_host_interact_callbacks(case):
 
     seq, burn, n, period, pad, S, A = case
     L = seq + n
-    tr = _trace(seq * 100 + n, S, A)
-    truth = host_rows(case, tr)
+    tr = trace(seq * 100 + n, TICKS, N, S, A, H, done_from_sets(DONES, TICKS))
+    truth = host_rows(case, tr, GAMMA, ETA)
     lens = [int((r["state"][0] != 0).any(-1).sum()) for out in truth for _, r in out]
     assert L in lens and (not pad or min(lens) < L), "the schedule yields a full window and, with padding, a short one"
     feed = ops.R2D2ActorFeed(N, S, A, H, seq, burn, n, period, pad, GAMMA, ETA, "cuda:0")
