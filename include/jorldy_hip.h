@@ -692,6 +692,40 @@ int jh_mpo_loss_continuous(jh_ctx* ctx, int32_t R, int32_t T, int32_t N, int32_t
                            const float* d_reward, const float* d_done, const float* d_prob_b, float* d_block, const float* d_hyper, float gamma,
                            int32_t retrace, float* d_grad_head, float* d_grad_q, float* d_stats, jh_stream stream);
 
+/* ------------------------------------------------------------------ SAC, discrete actions
+ * core/agent/sac.py:192-269 (the discrete branches) between the networks' forwards and backwards.  1 <= B <= 1024 rows, 2 <= A <= 64
+ * actions; anything else is JH_ERR_ARG with nothing launched.  A row is owned by a group of G lanes, G the smallest power of two >= A;
+ * a workgroup of 256 lanes takes 256 / G rows and the grid as many workgroups as the batch needs.  Every batch sum is finished by the
+ * last workgroup to arrive over per-workgroup partials in workgroup order (an integer ticket, no floating-point atomics): the same bits
+ * in every run and in a hipGraph replay.  d_work: caller-owned, 8-byte aligned, JH_SACD_WORK_FLOATS floats, ZERO before the first call
+ * (the ticket returns to zero by itself); the two entries may share one.
+ * d_block is the multiplier block of jh_vmpo_loss_* (JH_VMPO_BLOCK_FLOATS) used as the temperature block: [0] log_alpha, [3] / [6] its
+ * Adam moments, [9] its floor (-inf), [12] target_entropy, [15] 1 once it has stepped, [18] its last gradient; [1] the alpha IN USE
+ * (exp(log_alpha) as of the previous learn's refresh, sac.py:250-255).
+ * With pi = softmax(logits), log pi = the log-softmax, and Categorical's clamp, H = -sum_a pi clamp(log pi, log eps, log(1 - eps)) with
+ * float32 eps (zero derivative through the log where the clamp binds):
+ *
+ * jh_sacd_critic_loss: d_la_next = actor(s') raw logits, d_qt1_next / d_qt2_next = target critics on s', d_q1 / d_q2 = online critics
+ * on s, each [B][A]; d_action (clamped into [0, A)), d_reward, d_done [B].
+ *   next_q_i = sum_a pi' qt_i; y = r + (1 - d) gamma (min(next_q1, next_q2) + alpha H')       the minimum of the two EXPECTATIONS
+ *   d_grad_q_i[b][a] = 2 (q_i[b][a] - y) / B at the taken action, 0 elsewhere (every entry written)
+ *   d_stats[0..3) = {mean (q1[a] - y)^2, mean (q2[a] - y)^2, max_b y}.  d_block is only read.
+ *
+ * jh_sacd_actor_loss: d_la = actor(s) raw logits, d_q1 / d_q2 = the online critics on s AFTER their optimizer step (sac.py:235-237).
+ *   q_i = sum_a pi Q_i; actor_loss = -mean(alpha H + min(q1, q2)); d_grad_la = its gradient with respect to the RAW logits: through H,
+ *   through the smaller expectation (half each when q1 == q2: torch.min's backward) and through the softmax Jacobian.  The critics
+ *   receive no gradient.  alpha_loss = log_alpha mean(H - target_entropy).  Then one thread: [1] <- exp(log_alpha), and, dynamic == 1,
+ *   torch's single-tensor Adam step on log_alpha with gradient mean(H - target_entropy) and d_hyper's lr, betas (the doubles), eps and
+ *   t = step + 1 (the code jh_vmpo_loss_* step their multipliers with); d_hyper's step count becomes t.  d_hyper: the temperature's OWN
+ *   8-byte aligned optimizer block of 16 floats in the layout of jh_pponet_hyper_ptr.
+ *   d_stats[3..8) = {actor_loss, alpha_loss, mean_b min(q1, q2), the refreshed alpha, mean_b H}.                                       */
+#define JH_SACD_WORK_FLOATS 2312
+int jh_sacd_critic_loss(jh_ctx* ctx, int32_t B, int32_t A, const float* d_la_next, const float* d_qt1_next, const float* d_qt2_next, const float* d_q1,
+                        const float* d_q2, const float* d_action, const float* d_reward, const float* d_done, float gamma, const float* d_block,
+                        float* d_grad_q1, float* d_grad_q2, float* d_stats, float* d_work, jh_stream stream);
+int jh_sacd_actor_loss(jh_ctx* ctx, int32_t B, int32_t A, const float* d_la, const float* d_q1, const float* d_q2, float* d_block, float* d_hyper,
+                       int32_t dynamic, float* d_grad_la, float* d_stats, float* d_work, jh_stream stream);
+
 /* ------------------------------------------------------------------ REINFORCE: the return scan and the policy-gradient losses
  * core/agent/reinforce.py:83-113 between the network's forward and its backward, over the T rows of ONE episode (T differs from learn to
  * learn; 1 <= T <= 65536).  The number of launches of each entry does not depend on T.

@@ -170,6 +170,8 @@ _PROTOS = {
     "jh_mpo_loss_discrete": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 12 + [_f32, _i32, _vp, _vp, _vp, _vp]),
     "jh_mpo_sample": (C.c_int, [_vp, _i32, _i32, _i32] + [_vp] * 8),
     "jh_mpo_loss_continuous": (C.c_int, [_vp, _i32, _i32, _i32, _i32] + [_vp] * 13 + [_f32, _i32, _vp, _vp, _vp, _vp]),
+    "jh_sacd_critic_loss": (C.c_int, [_vp, _i32, _i32] + [_vp] * 8 + [_f32] + [_vp] * 6),
+    "jh_sacd_actor_loss": (C.c_int, [_vp, _i32, _i32] + [_vp] * 5 + [_i32] + [_vp] * 4),
     "jh_reinforce_returns": (C.c_int, [_vp, _i32, _vp, _f64, _i32, _vp, _vp]),
     "jh_reinforce_loss_discrete": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "jh_reinforce_loss_continuous": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -846,6 +846,61 @@ def mpo_loss_continuous(head, head_old, q, qt_a, qt_next, qt_add, zt_add, action
     return g_h, g_q, stats
 
 
+# ============================================================================= SAC, discrete actions
+SACD_STATS = ("critic_loss1", "critic_loss2", "max_Q", "actor_loss", "alpha_loss", "mean_Q", "alpha", "entropy")
+SACD_MAX_ROWS, SACD_MAX_ACTIONS, SACD_WORK_FLOATS = 1024, 64, 2312  # the caps of jh_sacd_*: B, A; JH_SACD_WORK_FLOATS
+
+
+def sacd_temperature(log_alpha, target_entropy, alpha=None, m=0.0, v=0.0, has_state=False, device="cuda"):
+    """The temperature of the discrete SAC as a multiplier block (vmpo_block: one layout, one Adam step for every learned scalar): slot 0 is
+    log_alpha (no floor, its threshold field holds target_entropy), slot 1's value the alpha IN USE (default exp(log_alpha) in float32)."""
+    alpha = float(np.exp(np.float32(log_alpha))) if alpha is None else alpha
+    return vmpo_block(log_alpha, alpha, 0.0, -np.inf, -np.inf, -np.inf, target_entropy, 0.0, 0.0, m=(m, 0.0, 0.0), v=(v, 0.0, 0.0),
+                      has_state=(has_state, False, False), device=device)
+
+
+def sacd_workspace(device="cuda"):
+    """The zeroed workspace both jh_sacd_* entries finish their batch sums in (per-workgroup partials and the arrival ticket)."""
+    return torch.zeros(SACD_WORK_FLOATS, dtype=torch.float32, device=device)
+
+
+def _sacd_common(heads, block, stats, work):
+    t = [_f32(v) for v in heads]
+    B, A = t[0].shape
+    assert all(tuple(v.shape) == (B, A) for v in t)
+    assert block.dtype == torch.float32 and block.numel() == VMPO_BLOCK_FLOATS and block.is_contiguous()
+    work = sacd_workspace(t[0].device) if work is None else work
+    assert work.dtype == torch.float32 and work.numel() >= SACD_WORK_FLOATS and work.is_contiguous()
+    return t, B, A, _stats_arg(stats, len(SACD_STATS), t[0].device), work
+
+
+def sacd_critic_loss(la_next, qt1_next, qt2_next, q1, q2, action, reward, done, gamma, block, stats=None, work=None, out=None):
+    """jh_sacd_critic_loss: the actor's raw logits on s', the target critics on s', the online critics on s, each [B, A], the replayed columns
+    [B] and the temperature block (sacd_temperature; only read).  out = (grad_q1, grad_q2) to write into.
+    -> (grad_q1 [B, A], grad_q2 [B, A], stats: entries 0..2 of SACD_STATS written)."""
+    t, B, A, stats, work = _sacd_common((la_next, qt1_next, qt2_next, q1, q2), block, stats, work)
+    cols = [_f32(v).reshape(-1) for v in (action, reward, done)]
+    assert all(v.numel() == B for v in cols)
+    g1, g2 = out if out is not None else (None, None)
+    g1, g2 = _out_arg(g1, t[3]), _out_arg(g2, t[4])
+    L.check(L.load().jh_sacd_critic_loss(L.ctx(_dev(t[0])), B, A, *(L.ptr(v) for v in t), *(L.ptr(v) for v in cols), float(gamma), L.ptr(block), L.ptr(g1), L.ptr(g2),
+                                         L.ptr(stats), L.ptr(work), L.stream_ptr()))
+    return g1, g2, stats
+
+
+def sacd_actor_loss(la, q1, q2, block, hyper, dynamic, stats=None, work=None, out=None):
+    """jh_sacd_actor_loss: the actor's raw logits on s and the online critics on s AFTER their step, each [B, A]; `block` (sacd_temperature) is
+    advanced in place -- the alpha in use is refreshed, and, dynamic, log_alpha takes its Adam step with the temperature's own `hyper`
+    (a vmpo_hyper tensor, whose step count advances too).  out = grad_la to write into.
+    -> (grad_la [B, A] with respect to the raw logits, stats: entries 3..7 of SACD_STATS written)."""
+    t, B, A, stats, work = _sacd_common((la, q1, q2), block, stats, work)
+    assert torch.is_tensor(hyper) and hyper.dtype == torch.float32 and hyper.numel() >= 16 and hyper.is_contiguous() and hyper.device == t[0].device
+    g = _out_arg(out, t[0])
+    L.check(L.load().jh_sacd_actor_loss(L.ctx(_dev(t[0])), B, A, *(L.ptr(v) for v in t), L.ptr(block), L.ptr(hyper), int(bool(dynamic)), L.ptr(g), L.ptr(stats),
+                                        L.ptr(work), L.stream_ptr()))
+    return g, stats
+
+
 # ============================================================================= REINFORCE
 REINFORCE_MAX_ROWS = 65536  # JH_REINFORCE_MAX_ROWS: the rows of one episode that one learn() takes
 REINFORCE_STATS = ("loss", "rows")
