@@ -1128,6 +1128,30 @@ int jh_collector_stats_detail(jh_collector* c, double* out6);
  *         runs since creation that were finished by per-step launches after the kernel gave up} */
 int jh_collector_mode(const jh_collector* c, int64_t* out4);
 
+/* ------------------------------------------------------------------ device-resident rollouts (csrc/jh_devroll.hip)
+ * The two built-in envs with their state in HBM (float64 state [W][S], int64 step count [W], the per-env splitmix64 word [W]; the
+ * arithmetic is csrc/jh_env_dyn.h, shared with the host envs).  Creation runs the host env's own seeding and reset and uploads: a
+ * device env starts bit-identical to jh_cartpole_create(W, seed) / jh_control_create(W, S, A, seed), and resets continue the same
+ * per-env stream bit for bit.  The device's sin / cos may differ from the host's in the last bits: trajectories are not promised
+ * to be bit-equal to the host env's.                                                                                          */
+typedef struct jh_devenv jh_devenv;
+enum { JH_DEVENV_CARTPOLE = 0 /* S 4, A 2, discrete */, JH_DEVENV_CONTROL = 1 /* S <= 64, A <= 16, continuous */ };
+int jh_devenv_create(jh_ctx* ctx, int32_t kind, int32_t W, int32_t S, int32_t A, uint64_t seed, jh_devenv** out);
+void jh_devenv_destroy(jh_devenv* e);
+/* Host copies of the state, any pointer NULL = skipped; blocking, ordered behind what `stream` holds. */
+int jh_devenv_get_state(jh_devenv* e, double* h_s, int64_t* h_t, uint64_t* h_rng, jh_stream stream);
+int jh_devenv_set_state(jh_devenv* e, const double* h_s, const int64_t* h_t, const uint64_t* h_rng, jh_stream stream);
+/* T timesteps of all W envs in ONE launch: per timestep the policy-value forward (fp32 MFMA), action sampling on the net's counter-based
+ * stream (the statements of the host collectors; counter + T afterwards, training == 0: argmax / tanh(mu)), the env step with
+ * auto-reset, and the transition.  The W * T rows are appended to `store` in worker-major order (row = w * T + t; cols = the store's
+ * column numbers of state f32[S], action i64[1] | f32[A], reward f32[1], next_state f32[S] -- the terminal observation where done --,
+ * done u8[1]).  d_value != NULL: the acting-time capture with the layout and meaning of jh_collector_set_capture (one value-only
+ * forward follows the last step).  Env row w's output is a function of (weights, env state, sampling seed, counter, w) only.
+ * hidden_size % 16 == 0 up to JH_DEVROLL_MAX_H (both activation tiles of a 16-row workgroup live in the 160 KB of LDS); beyond: JH_ERR_ARG. */
+#define JH_DEVROLL_MAX_H 1024
+int jh_devroll_run(jh_pponet* net, jh_devenv* env, jh_store* store, const int32_t* cols, int32_t T, int32_t training, float* d_h0, float* d_h1,
+                   float* d_value, float* d_next_value, jh_stream stream);
+
 /* N(0,1) draws on the device for NoisyNet layers (core/network/utils.py:58-60 draws torch.randn per forward):
  * counter-based (element i of call c = Box-Muller on splitmix64(seed, c, i)); d_state uint64[4] = {seed, call counter,
  * 0, 0} in DEVICE memory, advanced by the kernel itself, so a replayed hipGraph draws fresh noise every time.        */

@@ -320,6 +320,11 @@ _PROTOS = {
     "jh_cartpole_destroy": (None, [_vp]),
     "jh_cartpole_obs": (C.c_int, [_vp, _vp]),
     "jh_cartpole_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "jh_devenv_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.c_uint64, _pp]),
+    "jh_devenv_destroy": (None, [_vp]),
+    "jh_devenv_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "jh_devenv_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "jh_devroll_run": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "jh_comm_unique_id": (C.c_int, [_vp]),
     "jh_comm_create": (C.c_int, [_vp, _i32, _i32, _vp, _pp]),
     "jh_comm_destroy": (None, [_vp]),

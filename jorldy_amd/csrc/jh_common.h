@@ -197,49 +197,74 @@ struct jh_pponet {
 // ---------------------------------------------------------------- host-side action sampling (PPO.act, ppo.py:55-69)
 // Counter-based splitmix64 streams keyed by (net seed, timestep counter, env row[, dim]): the same actions
 // whichever acting path (persistent kernel / one launch per step) produced the raw heads.
-static inline uint64_t jh_mix64(uint64_t x) {
+// (JH_HD: the stream and the two samplers are ONE statement for the host collectors and for kernels that sample on the device --
+// jh_policy_act_discrete, the device rollout of jh_devroll.hip)
+#ifdef __HIPCC__
+#define JH_HD __host__ __device__
+#else
+#define JH_HD
+#endif
+JH_HD static inline uint64_t jh_mix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
 }
-static inline double jh_u01_of(uint64_t key) { return (double)(jh_mix64(key) >> 11) * (1.0 / 9007199254740992.0); }
+JH_HD static inline double jh_u01_of(uint64_t key) { return (double)(jh_mix64(key) >> 11) * (1.0 / 9007199254740992.0); }
 
 // Categorical(softmax(z)).sample() by inverse CDF (torch.multinomial(pi, 1)); argmax when !training
-static inline int64_t jh_sample_discrete(const jh_pponet* n, const float* z, int wq, int training) {
-  const int A = n->A;
+JH_HD static inline int64_t jh_sample_discrete_at(int A, uint64_t seed, uint64_t ctr, const float* z, int wq, int training) {
   int act = 0;
   float mx = z[0];
   for (int k = 1; k < A; ++k)
     if (z[k] > mx) { mx = z[k]; act = k; }
   if (!training) return act;
-  float e[40], se = 0.f;  // (jh_pponet_create: <= 40 head outputs)
-  for (int k = 0; k < A; ++k) { e[k] = expf(z[k] - mx); se += e[k]; }
-  const float u = (float)jh_u01_of(n->act_seed * 0x100000001B3ull + n->act_ctr * 0x9E3779B97F4A7C15ull + (uint64_t)wq) * se;
+  // the host keeps the exponentials of a jh_pponet's heads (<= 40 outputs) for the second pass; a kernel evaluates them again -- the same
+  // values -- because an indexed private array would live in scratch memory, and so does any caller with more than 40 actions
+#ifdef __HIP_DEVICE_COMPILE__
+  constexpr int kKeep = 0;
+  float e[1];
+#else
+  constexpr int kKeep = 40;
+  float e[kKeep];
+#endif
+  const bool keep = A <= kKeep;
+  float se = 0.f;
+  for (int k = 0; k < A; ++k) {
+    const float ek = expf(z[k] - mx);
+    if (keep) e[k] = ek;
+    se += ek;
+  }
+  const float u = (float)jh_u01_of(seed * 0x100000001B3ull + ctr * 0x9E3779B97F4A7C15ull + (uint64_t)wq) * se;
   float c = 0.f;
   act = A - 1;
   for (int k = 0; k < A; ++k) {
-    c += e[k];
+    c += keep ? e[k] : expf(z[k] - mx);
     if (u < c) { act = k; break; }
   }
   return act;
 }
+static inline int64_t jh_sample_discrete(const jh_pponet* n, const float* z, int wq, int training) {
+  return jh_sample_discrete_at(n->A, n->act_seed, n->act_ctr, z, wq, training);
+}
 
 // z = (mu_raw[A], log_std_raw[A]): mu = clamp(mu_raw, -5, 5), std = exp(tanh(log_std_raw)) (policy_value.py:54-56);
 // action = tanh(Normal(mu, std).sample()) when training (Box-Muller on two counter-based uniforms), tanh(mu) otherwise
-static inline void jh_sample_continuous(const jh_pponet* n, const float* z, int wq, int training, float* action) {
-  const int A = n->A;
+JH_HD static inline void jh_sample_continuous_at(int A, uint64_t seed, uint64_t ctr, const float* z, int wq, int training, float* action) {
   for (int k = 0; k < A; ++k) {
     const float mu = fminf(fmaxf(z[k], -5.f), 5.f);
     float v = mu;
     if (training) {
       const float sd = expf(tanhf(z[A + k]));
-      const uint64_t key = n->act_seed * 0x100000001B3ull + n->act_ctr * 0x9E3779B97F4A7C15ull + (uint64_t)wq * 64u + (uint64_t)k;
+      const uint64_t key = seed * 0x100000001B3ull + ctr * 0x9E3779B97F4A7C15ull + (uint64_t)wq * 64u + (uint64_t)k;
       const double u1 = 1.0 - jh_u01_of(key * 2 + 1), u2 = jh_u01_of(key * 2 + 2);  // u1 in (0, 1]
       v = mu + sd * (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
     }
     action[k] = tanhf(v);
   }
+}
+static inline void jh_sample_continuous(const jh_pponet* n, const float* z, int wq, int training, float* action) {
+  jh_sample_continuous_at(n->A, n->act_seed, n->act_ctr, z, wq, training, action);
 }
 
 // ---------------------------------------------------------------- optimizer hyper block (device memory, JH_HY_FLOATS floats)

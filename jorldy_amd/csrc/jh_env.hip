@@ -7,27 +7,13 @@
 #include <math.h>
 
 #include "jh_common.h"
+#include "jh_env_dyn.h"
 
 
 namespace {
-constexpr double kGrav = 9.8, kMc = 1.0, kMp = 0.1, kLen = 0.5, kFmag = 10.0, kTau = 0.02;
-constexpr double kThetaLim = 12.0 * 2.0 * 3.14159265358979323846 / 360.0;
-constexpr double kXLim = 2.4;
-constexpr int64_t kMaxSteps = 500;
+using namespace jh_env;  // jh_env_dyn.h: the constants and the step arithmetic, shared with the device-resident envs (jh_devroll.hip)
 
-inline double next_u01(uint64_t& st) {
-  st += 0x9E3779B97F4A7C15ull;
-  uint64_t x = st;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  x = x ^ (x >> 31);
-  return (double)(x >> 11) * (1.0 / 9007199254740992.0);
-}
-
-inline void reset_env(jh_cartpole* e, int w) {
-  for (int k = 0; k < 4; ++k) e->s[4 * (size_t)w + k] = -0.05 + 0.1 * next_u01(e->rng[w]);
-  e->t[w] = 0;
-}
+inline void reset_env(jh_cartpole* e, int w) { reset_row(&e->s[4 * (size_t)w], 4, e->rng[w], e->t[w]); }
 }  // namespace
 
 JH_EXPORT int jh_cartpole_create(int32_t W, uint64_t seed, jh_cartpole** out) {
@@ -38,7 +24,7 @@ JH_EXPORT int jh_cartpole_create(int32_t W, uint64_t seed, jh_cartpole** out) {
   e->t.assign(W, 0);
   e->rng.resize(W);
   for (int w = 0; w < W; ++w) {
-    e->rng[w] = seed * 0x9E3779B97F4A7C15ull + (uint64_t)(w + 1) * 0xBF58476D1CE4E5B9ull;
+    e->rng[w] = seed_word(seed, w);
     reset_env(e, w);
   }
   *out = e;
@@ -66,26 +52,13 @@ JH_EXPORT int jh_cartpole_step(jh_cartpole* e, const int64_t* h_action, float* h
 }
 
 void jh_cartpole_step_rows(jh_cartpole* e, int r0, int r1, const int64_t* h_action, float* h_next_obs, float* h_reward, uint8_t* h_done) {
-  const double total_mass = kMc + kMp, pml = kMp * kLen;
   for (int w = r0; w < r1; ++w) {
     double* s = &e->s[4 * (size_t)w];
-    double x = s[0], xd = s[1], th = s[2], thd = s[3];
-    const double force = h_action[w] == 1 ? kFmag : -kFmag;
-    const double ct = cos(th), st = sin(th);
-    const double temp = (force + pml * thd * thd * st) / total_mass;
-    const double thacc = (kGrav * st - ct * temp) / (kLen * (4.0 / 3.0 - kMp * ct * ct / total_mass));
-    const double xacc = temp - pml * thacc * ct / total_mass;
-    x = x + kTau * xd;
-    xd = xd + kTau * xacc;
-    th = th + kTau * thd;
-    thd = thd + kTau * thacc;
-    s[0] = x; s[1] = xd; s[2] = th; s[3] = thd;
-    e->t[w] += 1;
-    const bool d = x < -kXLim || x > kXLim || th < -kThetaLim || th > kThetaLim || e->t[w] >= kMaxSteps;
+    const bool d = cartpole_advance(s, e->t[w], h_action[w]);
     for (int k = 0; k < 4; ++k) h_next_obs[4 * (size_t)w + k] = (float)s[k];
     h_done[w] = d ? 1 : 0;
-    h_reward[w] = d ? -1.0f : 0.1f;  // gym_env.py:78
-    if (d) reset_env(e, w);          // distributed_manager.py:91
+    h_reward[w] = d ? kRewardDone : kRewardStep;  // gym_env.py:78
+    if (d) reset_env(e, w);                       // distributed_manager.py:91
   }
 }
 
@@ -98,21 +71,18 @@ void jh_cartpole_step_rows(jh_cartpole* e, int r0, int r1, const int64_t* h_acti
 // float32 observations, auto-reset like Actor.run (manager/distributed_manager.py:91).  The CPU oracle
 // (oracle/jorldy_oracle.py: ControlOracle) reproduces every trajectory bit for bit.
 namespace {
-inline void reset_control(jh_control* e, int w) {
-  for (int k = 0; k < e->S; ++k) e->s[(size_t)e->S * w + k] = -0.05 + 0.1 * next_u01(e->rng[w]);
-  e->t[w] = 0;
-}
+inline void reset_control(jh_control* e, int w) { reset_row(&e->s[(size_t)e->S * w], e->S, e->rng[w], e->t[w]); }
 }  // namespace
 
 JH_EXPORT int jh_control_create(int32_t W, int32_t S, int32_t A, uint64_t seed, jh_control** out) {
-  JH_ARG(out != nullptr && W > 0 && S > 0 && S <= 64 && A > 0 && A <= 16);
+  JH_ARG(out != nullptr && W > 0 && S > 0 && S <= kControlMaxS && A > 0 && A <= kControlMaxA);
   jh_control* e = new jh_control();
   e->W = W; e->S = S; e->A = A;
   e->s.assign((size_t)S * W, 0.0);
   e->t.assign(W, 0);
   e->rng.resize(W);
   for (int w = 0; w < W; ++w) {
-    e->rng[w] = seed * 0x9E3779B97F4A7C15ull + (uint64_t)(w + 1) * 0xBF58476D1CE4E5B9ull;
+    e->rng[w] = seed_word(seed, w);
     reset_control(e, w);
   }
   *out = e;
@@ -143,19 +113,14 @@ void jh_control_step_rows(jh_control* e, int r0, int r1, const float* h_action, 
   for (int w = r0; w < r1; ++w) {
     double* s = &e->s[(size_t)S * w];
     const float* a = h_action + (size_t)A * w;
-    double a2 = 0.0;
-    for (int j = 0; j < A; ++j) a2 += (double)a[j] * (double)a[j];
-    for (int i = 0; i < S; ++i) {
-      double drive = 0.0;
-      for (int j = 0; j < A; ++j) drive += 0.5 * sin(1.7 * (i + 1) + 2.3 * (j + 1)) * (double)a[j];
-      nxt[i] = 0.95 * s[i] + 0.05 * drive + 0.02 * sin(s[(i + 1) % S]);
-    }
+    const double a2 = control_action_cost(a, A);
+    for (int i = 0; i < S; ++i) nxt[i] = control_next(s, a, S, A, i, [](int i_, int j_) { return control_coupling(i_, j_); });
     for (int i = 0; i < S; ++i) s[i] = nxt[i];
     e->t[w] += 1;
-    const bool d = s[0] > 2.0 || s[0] < -2.0 || e->t[w] >= 1000;
+    const bool d = control_done(s[0], e->t[w]);
     for (int i = 0; i < S; ++i) h_next_obs[(size_t)S * w + i] = (float)s[i];
     h_done[w] = d ? 1 : 0;
-    h_reward[w] = (float)(s[0] + 0.1 - 0.001 * a2);
+    h_reward[w] = control_reward(s[0], a2);
     if (d) reset_control(e, w);
   }
 }

@@ -1243,34 +1243,11 @@ JH_EXPORT int jh_heads_unpack(jh_ctx* ctx, int64_t rows, int32_t A, const float*
 // PPO.act for a discrete policy whose heads are already on the device (ppo.py:63-69): Categorical(softmax(z)).sample() by inverse CDF on the SAME
 // counter-based stream as the host-side sampler of the MLP policy (jh_common.h: jh_sample_discrete; key = seed, timestep counter, row), argmax (first
 // maximum, torch.argmax) when !training.  One thread per row; d_action [W] int64 (device or device-mapped host memory).
-__device__ __forceinline__ static uint64_t jh_mix64_dev(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 __global__ void __launch_bounds__(64) jh_policy_act_discrete_kernel(int W, int A, const float* __restrict__ heads, int ld, uint64_t seed, uint64_t ctr, int training,
                                                                     int64_t* __restrict__ action) {
   const int w = blockIdx.x * 64 + threadIdx.x;
   if (w >= W) return;
-  const float* z = heads + (size_t)w * ld;
-  int act = 0;
-  float mx = z[0];
-  for (int k = 1; k < A; ++k)
-    if (z[k] > mx) { mx = z[k]; act = k; }
-  if (training) {
-    float se = 0.f;
-    for (int k = 0; k < A; ++k) se += expf(z[k] - mx);
-    const double u01 = (double)(jh_mix64_dev(seed * 0x100000001B3ull + ctr * 0x9E3779B97F4A7C15ull + (uint64_t)w) >> 11) * (1.0 / 9007199254740992.0);
-    const float u = (float)u01 * se;
-    float c = 0.f;
-    act = A - 1;
-    for (int k = 0; k < A; ++k) {
-      c += expf(z[k] - mx);
-      if (u < c) { act = k; break; }
-    }
-  }
-  action[w] = act;
+  action[w] = jh_sample_discrete_at(A, seed, ctr, heads + (size_t)w * ld, w, training);
 }
 JH_EXPORT int jh_policy_act_discrete(jh_ctx* ctx, int32_t W, int32_t A, const float* d_heads, int32_t ld, uint64_t seed, uint64_t counter, int32_t training,
                                      int64_t* d_action, jh_stream stream) {

@@ -1,4 +1,4 @@
 from .batched_actors import BatchedValueActors, DeviceActorFeed, VecNStepApeX
-from .collector import NativeCollector, VecCollector
+from .collector import DeviceCollector, NativeCollector, VecCollector
 
-__all__ = ["VecCollector", "NativeCollector", "BatchedValueActors", "VecNStepApeX", "DeviceActorFeed"]
+__all__ = ["VecCollector", "NativeCollector", "DeviceCollector","BatchedValueActors", "VecNStepApeX", "DeviceActorFeed"]

@@ -12,6 +12,8 @@ VecCollector     Python loop over timesteps, works with any agent (`agent.act`).
 NativeCollector  the whole T-step loop in one C call (jh_collector_run): acting kernels read the
                  observations from device-mapped pinned memory and write the actions back the same
                  way; transitions go directly into the rollout store's pinned staging slab.
+DeviceCollector  the whole T-step loop in one KERNEL (jh_devroll_run) for the built-in envs with their state on the
+                 device (ops.DeviceCartPole / ops.DeviceControl): nothing crosses PCIe between the timesteps.
 """
 import ctypes as C
 
@@ -56,6 +58,59 @@ class VecCollector:
 
     def sync(self, sync_item=None, init=False):
         """DistributedManager.sync (:55-60): nothing to do, actors read the learner's weights in HBM."""
+        return None
+
+    def terminate(self):
+        return None
+
+
+DEVICE_ELIGIBLE = ("DeviceCollector runs the PPO agent on the MLP head only (class PPO itself: not its V-MPO / ICM-PPO / RND-PPO subclasses, not PPOConv) "
+                   f"with hidden_size % 16 == 0 up to {ops.DEVROLL_MAX_H}, on a device-resident env whose action type is the policy's: ops.DeviceCartPole "
+                   "(discrete_policy_value) or ops.DeviceControl (continuous_policy_value); host and Python envs stay on NativeCollector")
+
+
+class DeviceCollector:
+    """jh_devroll_run: the whole T-step rollout in ONE kernel launch -- policy-value forward, sampling, env step with auto-reset, rows and
+    acting-time capture -- for a PPO agent on a device-resident env (ops.DeviceCartPole / ops.DeviceControl).  Nothing crosses PCIe
+    between the timesteps, so W is bounded by memory, not by the host loop.  Protocol of NativeCollector: `run(step)` appends W * step
+    transitions to the agent's rollout store and returns (None, 1.0); pass None to `agent.process`.  It does not register as
+    `agent._ride`: the agent uploads its index lists and learning rate itself."""
+
+    def __init__(self, env_vec, agent, num_workers=None, mode="sync"):
+        from ..core.agent.ppo import PPO
+        import os
+
+        got = f"; got agent {type(agent).__name__}, env {type(env_vec).__name__}"
+        if mode != "sync" or type(agent) is not PPO or not isinstance(env_vec, ops._DeviceEnv):
+            raise ValueError(DEVICE_ELIGIBLE + got)
+        if agent.action_type != env_vec.action_type or agent._net.H > ops.DEVROLL_MAX_H:
+            raise ValueError(DEVICE_ELIGIBLE + got + f" with a {agent.action_type} policy of hidden_size {agent._net.H} on a {env_vec.action_type} env")
+        if (agent._net.S, agent._net.A) != (env_vec.state_size, env_vec.action_size):
+            raise ValueError(DEVICE_ELIGIBLE + got + f": the policy is {agent._net.S} -> {agent._net.A}, the env {env_vec.state_size} -> {env_vec.action_size}")
+        assert num_workers in (None, env_vec.W)
+        self.lib = L.load()
+        self.env, self.agent = env_vec, agent
+        self.num_workers = env_vec.W
+        self.capture = os.environ.get("JH_COLLECT_CAPTURE", "1") == "1"  # as NativeCollector: the heads / values of acting replace learn()'s two no-grad passes
+
+    def run(self, step=1, training=True):
+        n_rows = self.env.W * step
+        mem, agent = self.agent.memory, self.agent
+        S, cont = self.env.state_size, self.env.action_type == "continuous"
+        # the columns NativeCollector._bind names, with the same dtypes (one example row: a new store takes only dtype and row shape from it)
+        action = np.zeros((1, self.env.action_size), np.float32) if cont else np.zeros((1, 1), np.int64)
+        mem._ensure({"state": np.zeros((1, S), np.float32), "action": action, "reward": np.zeros((1, 1), np.float32),
+                     "next_state": np.zeros((1, S), np.float32), "done": np.zeros((1, 1), np.uint8)}, n_rows)
+        cap = agent._capture_targets(n_rows) if self.capture else (None, None, None, None)  # may grow the network: before its handle is read
+        store, net = mem._store, agent._net
+        cols = (C.c_int32 * 5)(*[store.names.index(k) for k in ("state", "action", "reward", "next_state", "done")])
+        h0, h1, v, nv = cap
+        L.check(self.lib.jh_devroll_run(net.h, self.env.h, store.h, cols, int(step), int(bool(training)), L.ptr(h0), L.ptr(h1), L.ptr(v), L.ptr(nv), L.stream_ptr()))
+        if self.capture:
+            agent._captured = n_rows  # the coming learn() takes the heads / values of these rows as delivered
+        return None, 1.0
+
+    def sync(self, sync_item=None, init=False):
         return None
 
     def terminate(self):

@@ -1565,6 +1565,64 @@ class ControlVec:
         return next_obs, reward, done
 
 
+DEVROLL_MAX_H = 1024  # include/jorldy_hip.h: JH_DEVROLL_MAX_H
+
+
+class _DeviceEnv:
+    """jh_devenv_*: W built-in envs whose state lives in HBM (float64 state, step count, per-env reset stream), stepped only by the
+    device rollout kernel (jh_devroll_run, manager.DeviceCollector).  Starts bit-identical to the host env of the same seed."""
+
+    def __init__(self, kind, W, S, A, seed, device):
+        self.lib = L.load()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.W, self.state_size, self.action_size = int(W), int(S), int(A)
+        self.h = C.c_void_p()
+        L.check(self.lib.jh_devenv_create(L.ctx(self.device.index), kind, self.W, self.state_size, self.action_size, C.c_uint64(int(seed)), C.byref(self.h)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.jh_devenv_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def state(self):
+        """-> {"s": float64 [W, S], "t": int64 [W], "rng": uint64 [W]} host copies (checkpoints, tests)."""
+        out = {"s": np.empty((self.W, self.state_size), np.float64), "t": np.empty(self.W, np.int64), "rng": np.empty(self.W, np.uint64)}
+        L.check(self.lib.jh_devenv_get_state(self.h, L.ptr(out["s"]), L.ptr(out["t"]), L.ptr(out["rng"]), L.stream_ptr()))
+        return out
+
+    def set_state(self, s=None, t=None, rng=None):
+        fit = lambda a, dt, shape: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(shape)
+        s, t, rng = fit(s, np.float64, (self.W, self.state_size)), fit(t, np.int64, (self.W,)), fit(rng, np.uint64, (self.W,))
+        L.check(self.lib.jh_devenv_set_state(self.h, L.ptr(s), L.ptr(t), L.ptr(rng), L.stream_ptr()))
+
+    def obs(self, out=None):
+        """Host copy of the current observations, float32 [W, S]."""
+        o = self.state()["s"].astype(np.float32)
+        if out is None:
+            return o
+        out[...] = o
+        return out
+
+
+class DeviceCartPole(_DeviceEnv):
+    """CartPoleVec(W, seed) on the device (S 4, A 2, discrete)."""
+    action_type = "discrete"
+
+    def __init__(self, W, seed=0, device=None):
+        super().__init__(0, W, 4, 2, seed, device)
+
+
+class DeviceControl(_DeviceEnv):
+    """ControlVec(W, state_size, action_size, seed) on the device (S <= 64, A <= 16, continuous)."""
+    action_type = "continuous"
+
+    def __init__(self, W, state_size=11, action_size=3, seed=0, device=None):
+        super().__init__(1, W, state_size, action_size, seed, device)
+
+
 class _NetObject:
     """What RainbowNet, IQNNet and _ActorCriticBuckets share below their architecture: library / device / context, zeroed flat float32
     buckets, the segment table name -> (offset, rows, cols) read through the native entries `_SYM + name`, and destroy on collection."""
