@@ -1152,6 +1152,40 @@ int jh_devenv_set_state(jh_devenv* e, const double* h_s, const int64_t* h_t, con
 int jh_devroll_run(jh_pponet* net, jh_devenv* env, jh_store* store, const int32_t* cols, int32_t T, int32_t training, float* d_h0, float* d_h1,
                    float* d_value, float* d_next_value, jh_stream stream);
 
+/* ------------------------------------------------------------------ device-resident Ape-X actors (csrc/jh_devroll_q.hip)
+ * Env row i of a JH_DEVENV_CARTPOLE env is Ape-X actor i.  One launch runs T timesteps of all W actors: the Q forward of a jh_rbnet of
+ * kind q or dueling on the mlp head (fp32 MFMA), epsilon-greedy with the actor's own epsilon, the env step with auto-reset, the n-step
+ * window of ape_x.py:174-199 (never cleared, not at an episode end either) and the actor-side priority |G_n - q_{t-n}|, folded in double
+ * from the float32 q of the actions TAKEN.
+ * jh_devwin: the window carried between runs -- per env the last n_step states (an HBM ring), rewards, dones, q values and actions --
+ * with the number of timesteps seen and the exploration stream's (seed, counter).  Draws: u0, u1 = the collectors' counter-based
+ * uniforms at keys 2 key + 1 and 2 key + 2, key = seed * 0x100000001B3 + (counter + t) * 0x9E3779B97F4A7C15 + env row; u0 < epsilon_i
+ * explores with action floor(u1 * A), else the first index of the largest float32 q.  counter + T afterwards.
+ * hidden_size % 16 == 0 up to the caps below (the H tile and the second tile -- H wide for kind q, 2H for the stacked l1_a | l1_v of kind
+ * dueling -- of a 16-row workgroup live together in the 160 KB of LDS); beyond: JH_ERR_ARG.                                          */
+typedef struct jh_devwin jh_devwin;
+typedef struct jh_rbnet jh_rbnet; /* (described below) */
+#define JH_DEVROLL_Q_MAX_H 1216
+#define JH_DEVROLL_Q_MAX_H_DUELING 816
+#define JH_DEVROLL_Q_MAX_NSTEP 16
+int jh_devwin_create(jh_ctx* ctx, int32_t W, int32_t S, int32_t n_step, uint64_t seed, jh_devwin** out);
+void jh_devwin_destroy(jh_devwin* w);
+int jh_devwin_position(const jh_devwin* w, int64_t* seen, uint64_t* seed, uint64_t* counter);
+/* The whole window as one host block of jh_devwin_state_bytes bytes ({seen, seed, counter} + the device block); blocking, ordered
+ * behind what `stream` holds.  With jh_devenv_get_state / set_state a checkpointed collector resumes bit for bit.                */
+int64_t jh_devwin_state_bytes(const jh_devwin* w);
+int jh_devwin_get_state(jh_devwin* w, void* h_block, jh_stream stream);
+int jh_devwin_set_state(jh_devwin* w, const void* h_block, jh_stream stream);
+/* Rows the next run of T timesteps emits: W * max(0, T - max(0, n_step - seen)) -- every env is at the same timestep. */
+int64_t jh_devroll_q_rows(const jh_devwin* w, int32_t T);
+/* d_params: the bucket of `net` to act with.  d_eps: float64 [W], the actors' epsilons.  The rows are written time-major
+ * (row = (t - t_first) * W + env row: the order in which W lock-step actors feed a ring) into device columns of out_rows =
+ * jh_devroll_q_rows(win, T) rows: state f32 [S], action i64 [1], reward f32 [n_step], next_state f32 [S] (the reset observation where
+ * step t - 1 ended an episode), done u8 [n_step], priority f64 [1].  The caller appends them (jh_store_push_device, jh_per_push_device). */
+int jh_devroll_q_run(jh_rbnet* net, const float* d_params, jh_devenv* env, jh_devwin* win, int32_t T, const double* d_eps, double gamma,
+                     float* d_state, int64_t* d_action, float* d_reward, float* d_next_state, uint8_t* d_done, double* d_priority,
+                     int64_t out_rows, jh_stream stream);
+
 /* N(0,1) draws on the device for NoisyNet layers (core/network/utils.py:58-60 draws torch.randn per forward):
  * counter-based (element i of call c = Box-Muller on splitmix64(seed, c, i)); d_state uint64[4] = {seed, call counter,
  * 0, 0} in DEVICE memory, advanced by the kernel itself, so a replayed hipGraph draws fresh noise every time.        */

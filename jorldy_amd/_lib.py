@@ -325,6 +325,14 @@ _PROTOS = {
     "jh_devenv_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "jh_devenv_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "jh_devroll_run": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "jh_devwin_create": (C.c_int, [_vp, _i32, _i32, _i32, C.c_uint64, _pp]),
+    "jh_devwin_destroy": (None, [_vp]),
+    "jh_devwin_position": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "jh_devwin_state_bytes": (_i64, [_vp]),
+    "jh_devwin_get_state": (C.c_int, [_vp, _vp, _vp]),
+    "jh_devwin_set_state": (C.c_int, [_vp, _vp, _vp]),
+    "jh_devroll_q_rows": (_i64, [_vp, _i32]),
+    "jh_devroll_q_run": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _f64] + [_vp] * 6 + [_i64, _vp]),
     "jh_comm_unique_id": (C.c_int, [_vp]),
     "jh_comm_create": (C.c_int, [_vp, _i32, _i32, _vp, _pp]),
     "jh_comm_destroy": (None, [_vp]),

@@ -153,6 +153,18 @@ struct jh_control {
   std::vector<uint64_t> rng;
 };
 
+// the built-in envs with their state in HBM (jh_devroll.hip creates and steps them; jh_devroll_q.hip steps the CartPole kind)
+struct jh_devenv {
+  jh_ctx* ctx = nullptr;
+  int kind = 0, W = 0, S = 0, A = 0;
+  double* s = nullptr;        // [W][S]
+  int64_t* t = nullptr;       // [W]
+  uint64_t* rng = nullptr;    // [W]
+  double* coupling = nullptr; // [S][A] (control): jh_env::control_coupling evaluated by the host
+  char* scratch = nullptr;    // a run's rows in the store's dtypes, appended by jh_store_push_device
+  size_t scratch_bytes = 0;
+};
+
 void jh_cartpole_obs_rows(const jh_cartpole* e, int r0, int r1, float* h_obs);
 void jh_cartpole_step_rows(jh_cartpole* e, int r0, int r1, const int64_t* h_action, float* h_next_obs, float* h_reward, uint8_t* h_done);
 struct jh_control;

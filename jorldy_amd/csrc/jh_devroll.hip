@@ -27,17 +27,6 @@
 #include "jh_common.h"
 #include "jh_env_dyn.h"
 
-struct jh_devenv {
-  jh_ctx* ctx = nullptr;
-  int kind = 0, W = 0, S = 0, A = 0;
-  double* s = nullptr;        // [W][S]
-  int64_t* t = nullptr;       // [W]
-  uint64_t* rng = nullptr;    // [W]
-  double* coupling = nullptr; // [S][A] (control): jh_env::control_coupling evaluated by the host
-  char* scratch = nullptr;    // a run's rows in the store's dtypes, appended by jh_store_push_device
-  size_t scratch_bytes = 0;
-};
-
 namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 

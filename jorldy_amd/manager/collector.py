@@ -18,6 +18,7 @@ DeviceCollector  the whole T-step loop in one KERNEL (jh_devroll_run) for the bu
 import ctypes as C
 
 import numpy as np
+import torch
 
 from .. import _lib as L
 from .. import ops
@@ -66,7 +67,10 @@ class VecCollector:
 
 DEVICE_ELIGIBLE = ("DeviceCollector runs the PPO agent on the MLP head only (class PPO itself: not its V-MPO / ICM-PPO / RND-PPO subclasses, not PPOConv) "
                    f"with hidden_size % 16 == 0 up to {ops.DEVROLL_MAX_H}, on a device-resident env whose action type is the policy's: ops.DeviceCartPole "
-                   "(discrete_policy_value) or ops.DeviceControl (continuous_policy_value); host and Python envs stay on NativeCollector")
+                   "(discrete_policy_value) or ops.DeviceControl (continuous_policy_value); host and Python envs stay on NativeCollector.  "
+                   "It also runs the Ape-X agent's actors (class ApeX itself: not R2D2) on the MLP head: network dueling with hidden_size % 16 == 0 up to "
+                   f"{ops.DEVROLL_Q_MAX_H['dueling']} or discrete_q_network up to {ops.DEVROLL_Q_MAX_H['q']}, n_step 1 to {ops.DEVROLL_Q_MAX_NSTEP}, no "
+                   "frame_dedup, no grad_sync, on ops.DeviceCartPole")
 
 
 class DeviceCollector:
@@ -74,13 +78,35 @@ class DeviceCollector:
     acting-time capture -- for a PPO agent on a device-resident env (ops.DeviceCartPole / ops.DeviceControl).  Nothing crosses PCIe
     between the timesteps, so W is bounded by memory, not by the host loop.  Protocol of NativeCollector: `run(step)` appends W * step
     transitions to the agent's rollout store and returns (None, 1.0); pass None to `agent.process`.  It does not register as
-    `agent._ride`: the agent uploads its index lists and learning rate itself."""
+    `agent._ride`: the agent uploads its index lists and learning rate itself.
 
-    def __init__(self, env_vec, agent, num_workers=None, mode="sync"):
+    With an Ape-X agent on ops.DeviceCartPole (jh_devroll_q_run): env row i of W is actor i with epsilon_i = epsilon ** (1 + i / (W - 1) *
+    epsilon_alpha) read from the agent at run() time (epsilon_eval for every row when not training); one launch runs Q forward, the draw,
+    env step, the n-step window and the actor-side priorities for T timesteps, and `run(T)` appends the W * max(0, T - max(0, n_step -
+    seen)) emitted rows with their priorities to the agent's PER buffer in time-major order and counts them into agent.num_transitions.
+    `state()` / `set_state()` carry env and window, so a checkpointed collector resumes bit for bit.  The draws come from the collectors'
+    counter-based stream keyed (seed, counter + t, env row), not from numpy's."""
+
+    def __init__(self, env_vec, agent, num_workers=None, mode="sync", seed=0):
+        from ..core.agent.dqn import ApeX
         from ..core.agent.ppo import PPO
         import os
 
         got = f"; got agent {type(agent).__name__}, env {type(env_vec).__name__}"
+        self.window = None
+        if mode == "sync" and type(agent) is ApeX:
+            net = agent._net
+            cap = ops.DEVROLL_Q_MAX_H.get(net.kind, 0)
+            if (not isinstance(env_vec, ops.DeviceCartPole) or net.cnn or net.H % 16 or net.H > cap or not 1 <= agent.n_step <= ops.DEVROLL_Q_MAX_NSTEP
+                    or agent._frame_dedup or agent.grad_sync is not None or (net.Cin, net.A) != (env_vec.state_size, env_vec.action_size)):
+                raise ValueError(DEVICE_ELIGIBLE + got + f" with network kind {net.kind}, head {'cnn' if net.cnn else 'mlp'}, hidden_size {net.H}, n_step {agent.n_step}")
+            assert num_workers in (None, env_vec.W)
+            self.lib = L.load()
+            self.env, self.agent = env_vec, agent
+            self.num_workers = env_vec.W
+            self.window = ops._DeviceWindow(env_vec, agent.n_step, seed)
+            self._eps_key = self._eps = self._out = None
+            return
         if mode != "sync" or type(agent) is not PPO or not isinstance(env_vec, ops._DeviceEnv):
             raise ValueError(DEVICE_ELIGIBLE + got)
         if agent.action_type != env_vec.action_type or agent._net.H > ops.DEVROLL_MAX_H:
@@ -93,7 +119,53 @@ class DeviceCollector:
         self.num_workers = env_vec.W
         self.capture = os.environ.get("JH_COLLECT_CAPTURE", "1") == "1"  # as NativeCollector: the heads / values of acting replace learn()'s two no-grad passes
 
+    def _epsilons(self, training):
+        """float64 [W] on the device: ApeX.set_distributed's schedule over the env rows, computed in double on the host."""
+        agent, W = self.agent, self.env.W
+        key = (float(agent.epsilon), float(agent.epsilon_alpha), float(agent.epsilon_eval), bool(training))
+        if key != self._eps_key:
+            if not training:
+                eps = np.full(W, key[2], np.float64)
+            elif W == 1:
+                eps = np.full(1, key[0], np.float64)
+            else:
+                eps = np.float64(key[0]) ** (1 + (np.arange(W, dtype=np.float64) / (W - 1)) * key[1])
+            self._eps_key, self._eps = key, torch.from_numpy(eps).to(self.env.device)
+        return self._eps
+
+    def _run_apex(self, step, training):
+        agent, mem, env, win = self.agent, self.agent.memory, self.env, self.window
+        S, n, net = env.state_size, agent.n_step, agent._net
+        rows = int(self.lib.jh_devroll_q_rows(win.h, int(step)))
+        if rows > mem.buffer_size:
+            raise ValueError(f"one run of {step} timesteps of {env.W} actors emits {rows} rows, more than the buffer's {mem.buffer_size} slots")
+        if self._out is None or self._out["priority"].numel() < rows:
+            z = lambda shape, dt: torch.empty((max(rows, 1),) + shape, dtype=dt, device=env.device)
+            self._out = {"state": z((S,), torch.float32), "action": z((1,), torch.int64), "reward": z((n, 1), torch.float32),
+                         "next_state": z((S,), torch.float32), "done": z((n, 1), torch.uint8), "priority": z((), torch.float64)}
+        o = self._out
+        L.check(self.lib.jh_devroll_q_run(net.h, L.ptr(net.params), env.h, win.h, int(step), L.ptr(self._epsilons(training)), float(agent.gamma),
+                                          L.ptr(o["state"]), L.ptr(o["action"]), L.ptr(o["reward"]), L.ptr(o["next_state"]), L.ptr(o["done"]),
+                                          L.ptr(o["priority"]), rows, L.stream_ptr()))
+        if rows:
+            # the buffer's own device append: ring position, counters and tree bookkeeping exist once
+            example = {k: np.zeros((1,) + tuple(v.shape[1:]), {torch.float32: np.float32, torch.int64: np.int64, torch.uint8: np.uint8}[v.dtype])
+                       for k, v in o.items() if k != "priority"}
+            mem.store_device({k: v[:rows] for k, v in o.items() if k != "priority"}, example, priorities=o["priority"][:rows])
+            agent.num_transitions += rows
+        return None, 1.0
+
+    def state(self):
+        """-> {"env": the env's state(), "window": the carried window} (Ape-X collectors: what a checkpoint needs to resume bit for bit)."""
+        return {"env": self.env.state(), "window": self.window.state()}
+
+    def set_state(self, st):
+        self.env.set_state(**st["env"])
+        self.window.set_state(st["window"])
+
     def run(self, step=1, training=True):
+        if self.window is not None:
+            return self._run_apex(step, training)
         n_rows = self.env.W * step
         mem, agent = self.agent.memory, self.agent
         S, cont = self.env.state_size, self.env.action_type == "continuous"

@@ -1615,6 +1615,45 @@ class DeviceCartPole(_DeviceEnv):
         super().__init__(0, W, 4, 2, seed, device)
 
 
+DEVROLL_Q_MAX_H = {"q": 1216, "dueling": 816}  # include/jorldy_hip.h: JH_DEVROLL_Q_MAX_H, JH_DEVROLL_Q_MAX_H_DUELING
+DEVROLL_Q_MAX_NSTEP = 16
+
+
+class _DeviceWindow:
+    """jh_devwin_*: the n-step window Ape-X's device-resident actors carry between runs (per env the last n_step states, rewards, dones,
+    q values and actions; the timesteps seen; the exploration stream's seed and counter).  Stepped only by jh_devroll_q_run."""
+
+    def __init__(self, env, n_step, seed):
+        self.lib, self.device = env.lib, env.device
+        self.h = C.c_void_p()
+        L.check(self.lib.jh_devwin_create(L.ctx(self.device.index), env.W, env.state_size, int(n_step), C.c_uint64(int(seed)), C.byref(self.h)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.jh_devwin_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def position(self):
+        """-> (timesteps every env has seen, stream seed, stream counter)."""
+        seen, seed, ctr = C.c_int64(), C.c_uint64(), C.c_uint64()
+        L.check(self.lib.jh_devwin_position(self.h, C.byref(seen), C.byref(seed), C.byref(ctr)))
+        return seen.value, seed.value, ctr.value
+
+    def state(self):
+        """-> the whole window as one uint8 host block (checkpoints)."""
+        out = np.empty(int(self.lib.jh_devwin_state_bytes(self.h)), np.uint8)
+        L.check(self.lib.jh_devwin_get_state(self.h, L.ptr(out), L.stream_ptr()))
+        return out
+
+    def set_state(self, block):
+        block = np.ascontiguousarray(block, dtype=np.uint8)
+        assert block.size == int(self.lib.jh_devwin_state_bytes(self.h)), "a window of another geometry"
+        L.check(self.lib.jh_devwin_set_state(self.h, L.ptr(block), L.stream_ptr()))
+
+
 class DeviceControl(_DeviceEnv):
     """ControlVec(W, state_size, action_size, seed) on the device (S <= 64, A <= 16, continuous)."""
     action_type = "continuous"

@@ -37,11 +37,91 @@ def parse(argv=None):
                                                            "forward is rebuilt in HBM from the plane pool; 7 KB instead of 28 KB per env step over PCIe)")
     ap.add_argument("--device-feed", action="store_true", help="--e2e: the actors' stacks stay in HBM (DeviceActorFeed: plane pool + n-step assembly + "
                                                                 "actor-side priorities on the acting stream) instead of VecNStepApeX + the pinned staging ring")
+    ap.add_argument("--device", type=str, default="", help="W[,W...]: the device-resident actors (manager.DeviceCollector on ops.DeviceCartPole) at config.ape_x.cartpole's "
+                                                           "shapes (dueling, H 512, n_step 3, B 32): rollout alone, rollout + process() at learn_period 4, and the host actors "
+                                                           "(BatchedValueActors + VecNStepApeX + store) at the same widths in the same process")
+    ap.add_argument("--device-steps", type=int, default=64, help="--device: timesteps per rollout-alone launch")
     return ap.parse_args(argv)
 
 
 def main():
-    print(json.dumps(run(parse())))
+    args = parse()
+    print(json.dumps(run_device(args) if args.device else run(args)))
+
+
+def run_device(args):
+    """--device: one JSON-able dict; every figure is wall clock between two device synchronisations, in env steps (= W per timestep) per second."""
+    from jorldy_amd import ops
+    from jorldy_amd.core.agent import Agent
+    from jorldy_amd.manager import BatchedValueActors, DeviceCollector, VecNStepApeX
+
+    n, B, T, gamma = 3, 32, args.device_steps, 0.99
+
+    def agent_of(W):
+        torch.manual_seed(0)
+        np.random.seed(0)
+        a = Agent("ape_x", state_size=4, action_size=2, hidden_size=512, network="dueling", head="mlp", gamma=gamma, buffer_size=max(50000, 2 * W * T), batch_size=B,
+                  start_train_step=0, n_step=n, learn_period=4, num_workers=W, device="cuda")
+        a.memory.first_store = False
+        return a
+
+    def timed(fn, reps, warm):
+        for _ in range(warm):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps
+
+    out = {"workload": f"config.ape_x.cartpole shapes: CartPole, dueling MLP H=512, n_step={n}, B={B}, learn_period 4", "widths": {}}
+    for W in (int(w) for w in args.device.split(",")):
+        res = {}
+        agent = agent_of(W)
+        col = DeviceCollector(ops.DeviceCartPole(W, 0, "cuda"), agent)
+        dt = timed(lambda: col.run(T), args.updates, args.warmup)
+        res["device_rollout_alone"] = {"timesteps_per_launch": T, "ms_per_launch": dt * 1e3, "us_per_timestep": dt / T * 1e6, "env_steps_per_s": W * T / dt}
+        step = [0]
+
+        def tick():  # one launch of 4 timesteps, then process(): one learn() per 4 timesteps
+            col.run(4)
+            step[0] += 4
+            agent.process(None, step[0])
+
+        learned = agent.num_learn
+        dt = timed(tick, args.updates, args.warmup)
+        res["device_rollout_plus_process"] = {"ms_per_iteration": dt * 1e3, "env_steps_per_s": 4 * W / dt, "learner_updates_per_s": 1.0 / dt,
+                                              "learns": agent.num_learn - learned}
+        # the host actors at the same width: one batched forward per timestep, envs and the n-step assembly on the host, rows through the pinned store path
+        agent = agent_of(W)
+        env, actors, asm = ops.CartPoleVec(W, 0), BatchedValueActors(agent, W), VecNStepApeX(W, n, gamma, (4,), np.float32)
+        obs = actors.obs_slab
+
+        def host_step():
+            env.obs(obs)
+            state = obs.copy()
+            o = actors.act(None, training=True)
+            _, r, d = env.step(o["action"][:, 0])
+            got = asm.push(state, o["action"], r.reshape(W, 1), d.reshape(W, 1).astype(np.float32), o["q"])
+            if got is not None:
+                agent.memory.store_soa(got[0], got[1])
+                agent.num_transitions += W
+
+        dt = timed(host_step, 4 * args.updates, 4 * args.warmup)
+        res["host_actors_alone"] = {"us_per_timestep": dt * 1e6, "env_steps_per_s": W / dt}
+        step = [0]
+
+        def host_tick():
+            for _ in range(4):
+                host_step()
+            step[0] += 4
+            agent.process(None, step[0])
+
+        dt = timed(host_tick, args.updates, args.warmup)
+        res["host_actors_plus_process"] = {"ms_per_iteration": dt * 1e3, "env_steps_per_s": 4 * W / dt, "learner_updates_per_s": 1.0 / dt}
+        out["widths"][str(W)] = res
+    return out
 
 
 def run(args, dist=None):
