@@ -1186,6 +1186,27 @@ int jh_devroll_q_run(jh_rbnet* net, const float* d_params, jh_devenv* env, jh_de
                      float* d_state, int64_t* d_action, float* d_reward, float* d_next_state, uint8_t* d_done, double* d_priority,
                      int64_t out_rows, jh_stream stream);
 
+/* ------------------------------------------------------------------ device-resident TD3 / SAC actors (csrc/jh_devroll_ac.hip)
+ * One launch runs T timesteps of all W rows of a JH_DEVENV_CONTROL env with the ONLINE actor of a jh_acnet (TD3, td3.py:132-144 per env
+ * row) or of a jh_sacnet (SAC, sac.py:143-159): actor forward (fp32 MFMA, read in place from the actor's parameter bucket), exploration,
+ * env step with auto-reset, and the replay row.  Draws: the collectors' counter-based stream,
+ * key = seed * 0x100000001B3 + (counter + t) * 0x9E3779B97F4A7C15 + env row * 64 + k, u1 = 1 - u01(2 key + 1), u2 = u01(2 key + 2),
+ * n = sqrt(-2 log u1) cos(2 pi u2) in double; seed and counter are the caller's (counter + T for the next run).
+ *   TD3   timestep t < n_random while training: action_k = 2 u2 - 1; training: clamp(tanh(z_k) + action_noise_std n, -1, 1); else tanh(z_k)
+ *   SAC   mu = clamp(z_k, -5, 5), std = exp(tanh(z_{A+k})); training: tanh(mu + std n); else tanh(mu)
+ * Rows are written time-major (row = t * W + env row: the order in which W lock-step actors feed a ring) into the caller's device columns
+ * of W * T rows: state f32 [S], action f32 [A], reward f32 [1], next_state f32 [S] (the terminal observation where done; the next row's
+ * state is the reset observation), done u8 [1]; the caller appends them (jh_store_push_device).  d_heads != NULL: the raw last-layer
+ * outputs z, f32 [W * T][A] (TD3) | [W * T][2A] (SAC), time-major.  Env row w's output is a function of (actor weights, env state, seed,
+ * counter, w) only.  hidden_size % 16 == 0 up to JH_DEVROLL_AC_MAX_H (both activation tiles of a 16-row workgroup live in the 160 KB of
+ * LDS).  JH_ERR_ARG, nothing written: env kind not control, (S, A) of net and env differ, hidden_size off the rule, T < 1.           */
+#define JH_DEVROLL_AC_MAX_H 1120
+int jh_acnet_devroll_run(jh_acnet* net, jh_devenv* env, int32_t T, int32_t training, int32_t n_random, double action_noise_std, uint64_t seed,
+                         uint64_t counter, float* d_state, float* d_action, float* d_reward, float* d_next_state, uint8_t* d_done, float* d_heads,
+                         jh_stream stream);
+int jh_sacnet_devroll_run(jh_sacnet* net, jh_devenv* env, int32_t T, int32_t training, uint64_t seed, uint64_t counter, float* d_state,
+                          float* d_action, float* d_reward, float* d_next_state, uint8_t* d_done, float* d_heads, jh_stream stream);
+
 /* N(0,1) draws on the device for NoisyNet layers (core/network/utils.py:58-60 draws torch.randn per forward):
  * counter-based (element i of call c = Box-Muller on splitmix64(seed, c, i)); d_state uint64[4] = {seed, call counter,
  * 0, 0} in DEVICE memory, advanced by the kernel itself, so a replayed hipGraph draws fresh noise every time.        */

@@ -197,6 +197,8 @@ class DeterministicActorCritic(BaseAgent):
         self._net.soft_update(self.tau)
 
     def _store(self, transitions):
+        if transitions is None:  # manager.DeviceCollector has appended this step's rows on the device
+            return
         if isinstance(transitions, dict):
             self.memory.store_soa(transitions)
         else:

@@ -52,6 +52,11 @@ static inline TGemm ac_a_pi(const jh_acnet* n, const float* P, int rows) {
 // actor(x)'s three layers on `rows` rows, one launch each -> a_z
 int ac_actor_forward(jh_acnet* n, const float* P, const float* d_x, int rows, hipStream_t st);
 
+// ---- device-resident actors (jh_devroll_ac.hip): T timesteps of every row of a control env with the ONLINE actor, one launch.
+// sac: the last layer is the stacked [mu | log_std]; `who` names the entry in an error
+int ac_devroll_run(const char* who, jh_acnet* n, int sac, jh_devenv* e, int32_t T, int32_t training, int32_t n_random, double action_noise_std, uint64_t seed,
+                   uint64_t counter, float* d_state, float* d_action, float* d_reward, float* d_next_state, uint8_t* d_done, float* d_heads, hipStream_t st);
+
 // ---- critic loss and Polyak average (the kernels: jh_acnet.hip)
 // y = r + (1 - d) * gamma * (min_i q_i' [- alpha * logp']), loss_i = mean((y - q_i)^2), d(loss_i)/d(q_i) = 2 (q_i - y) / B, max_Q = max_b y.
 // The first seven members are the caller's; ac_critic_back fills the rest from the object.

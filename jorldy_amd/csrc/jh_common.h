@@ -262,18 +262,28 @@ static inline int64_t jh_sample_discrete(const jh_pponet* n, const float* z, int
 
 // z = (mu_raw[A], log_std_raw[A]): mu = clamp(mu_raw, -5, 5), std = exp(tanh(log_std_raw)) (policy_value.py:54-56);
 // action = tanh(Normal(mu, std).sample()) when training (Box-Muller on two counter-based uniforms), tanh(mu) otherwise
-JH_HD static inline void jh_sample_continuous_at(int A, uint64_t seed, uint64_t ctr, const float* z, int wq, int training, float* action) {
-  for (int k = 0; k < A; ++k) {
-    const float mu = fminf(fmaxf(z[k], -5.f), 5.f);
-    float v = mu;
-    if (training) {
-      const float sd = expf(tanhf(z[A + k]));
-      const uint64_t key = seed * 0x100000001B3ull + ctr * 0x9E3779B97F4A7C15ull + (uint64_t)wq * 64u + (uint64_t)k;
-      const double u1 = 1.0 - jh_u01_of(key * 2 + 1), u2 = jh_u01_of(key * 2 + 2);  // u1 in (0, 1]
-      v = mu + sd * (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
-    }
-    action[k] = tanhf(v);
+// (per action dimension k, so that a kernel may give every (env row, k) a thread of its own: jh_devroll_ac.hip)
+JH_HD static inline void jh_u01_pair_at(uint64_t seed, uint64_t ctr, int wq, int k, double* u1, double* u2) {
+  const uint64_t key = seed * 0x100000001B3ull + ctr * 0x9E3779B97F4A7C15ull + (uint64_t)wq * 64u + (uint64_t)k;
+  *u1 = 1.0 - jh_u01_of(key * 2 + 1);  // in (0, 1]
+  *u2 = jh_u01_of(key * 2 + 2);
+}
+JH_HD static inline double jh_normal_at(uint64_t seed, uint64_t ctr, int wq, int k) {
+  double u1, u2;
+  jh_u01_pair_at(seed, ctr, wq, k, &u1, &u2);
+  return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+JH_HD static inline float jh_sample_continuous_dim_at(int A, uint64_t seed, uint64_t ctr, const float* z, int wq, int k, int training) {
+  const float mu = fminf(fmaxf(z[k], -5.f), 5.f);
+  float v = mu;
+  if (training) {
+    const float sd = expf(tanhf(z[A + k]));
+    v = mu + sd * (float)jh_normal_at(seed, ctr, wq, k);
   }
+  return tanhf(v);
+}
+JH_HD static inline void jh_sample_continuous_at(int A, uint64_t seed, uint64_t ctr, const float* z, int wq, int training, float* action) {
+  for (int k = 0; k < A; ++k) action[k] = jh_sample_continuous_dim_at(A, seed, ctr, z, wq, k, training);
 }
 static inline void jh_sample_continuous(const jh_pponet* n, const float* z, int wq, int training, float* action) {
   jh_sample_continuous_at(n->A, n->act_seed, n->act_ctr, z, wq, training, action);

@@ -26,14 +26,13 @@
 // workgroup on gfx950 gives H <= 1024 (JH_DEVROLL_MAX_H), 152 KB at S = 64, A = 16.
 #include "jh_common.h"
 #include "jh_env_dyn.h"
+#include "jh_devroll_mlp.h"
 
 namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kRows = 16, kThreads = 256, kWaves = 4, kHeadLd = 40, kActLd = jh_env::kControlMaxA, kMaxTiles = 3;
 constexpr int kPartFloats = kWaves * kMaxTiles * 4 * 64;
-constexpr int kG1 = 8;  // column tiles of layer 1 a wave carries at once
-constexpr int kU2 = 8;  // k chunks of W2 per block of layer 2: 32 MFMAs against one L2 round trip
 
 struct DevRollArgs {
   int W, T, S, H, A, n_out, cont, training, capture;
@@ -75,86 +74,10 @@ __device__ inline Lds carve(char* base, int S, int A, int H) {
 __device__ void forward(const DevRollArgs& a, const Lds& l) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, kq = lane >> 4;
   const int H = a.H, S = a.S, ld = H + 4, tiles = H / 16;
-  // ---- layer 1: lane supplies A[row r][k] and B[k][unit r] for k = 4 ks + kq; holds C[row 4 kq + i][unit r].  A wave takes its column tiles
-  // kG1 at a time: one observation fragment feeds all of them, and their W1 pieces of the NEXT k step are in flight during the MFMAs
-  const int nks = (S + 3) / 4;  // (all four k groups make the same number of trips: the MFMA is wave-wide)
-  for (int g0 = wave; g0 < tiles; g0 += kWaves * kG1) {
-    f32x4 acc[kG1];
-    float bw[kG1], bn[kG1];
-#pragma unroll
-    for (int j = 0; j < kG1; ++j) {
-      acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const int ct = g0 + kWaves * j;
-      bw[j] = (ct < tiles && kq < S) ? a.W1[(size_t)(ct * 16 + r) * S + kq] : 0.f;
-    }
-    for (int ks = 0; ks < nks; ++ks) {
-      const int k = 4 * ks + kq;
-#pragma unroll
-      for (int j = 0; j < kG1; ++j) {
-        const int ct = g0 + kWaves * j;
-        bn[j] = (ct < tiles && k + 4 < S) ? a.W1[(size_t)(ct * 16 + r) * S + k + 4] : 0.f;
-      }
-      const float av = k < S ? (float)l.es[r * S + k] : 0.f;
-#pragma unroll
-      for (int j = 0; j < kG1; ++j) {
-        if (g0 + kWaves * j < tiles) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bw[j], acc[j], 0, 0, 0);  // (uniform)
-        bw[j] = bn[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kG1; ++j) {
-      const int unit = (g0 + kWaves * j) * 16 + r;
-      if (unit < H) {
-        const float b = a.b1[unit];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) l.h1[(4 * kq + i) * ld + unit] = fmaxf(acc[j][i] + b, 0.f);
-      }
-    }
-  }
+  // ---- layers 1 and 2 (jh_devroll_mlp.h, shared with the other rollout kernels)
+  jh_roll::layer1(a.W1, a.b1, l.es, S, H, l.h1, ld);
   __syncthreads();
-  // ---- layer 2: whole K inside the wave.  The wave's work is a flat sequence of (column tile, block of kU2 k chunks); while the
-  // 4 kU2 MFMAs of one block issue (about an L2 round trip), the kU2 16-byte pieces of W2 of the NEXT block -- of the next column tile
-  // at a tile's end -- are in flight
-  {
-    const int nblk = (tiles + kU2 - 1) / kU2, my_tiles = wave < tiles ? (tiles - wave + kWaves - 1) / kWaves : 0;
-    const float* hp = l.h1 + r * ld + kq * 4;
-    float4 cur[kU2], nxt[kU2];
-    auto fetch = [&](int ct, int blk, float4* dst) {
-      const float* wp = a.W2 + (size_t)(ct * 16 + r) * H + kq * 4;
-#pragma unroll
-      for (int u = 0; u < kU2; ++u) {
-        const int c = blk * kU2 + u;
-        dst[u] = c < tiles ? *reinterpret_cast<const float4*>(wp + c * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    };
-    if (my_tiles) fetch(wave, 0, cur);
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    for (int ti = 0; ti < my_tiles; ++ti) {
-      const int ct = wave + kWaves * ti;
-      for (int blk = 0; blk < nblk; ++blk) {
-        const bool last = blk + 1 == nblk;
-        if (!last || ti + 1 < my_tiles) fetch(last ? ct + kWaves : ct, last ? 0 : blk + 1, nxt);
-#pragma unroll
-        for (int u = 0; u < kU2; ++u) {
-          const int c = blk * kU2 + u;
-          if (c < tiles) {  // (uniform)
-            const float4 av = *reinterpret_cast<const float4*>(hp + c * 16);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, cur[u].x, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, cur[u].y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, cur[u].z, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, cur[u].w, acc1, 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kU2; ++u) cur[u] = nxt[u];
-      }
-      const int unit = ct * 16 + r;
-      const float b = a.b2[unit];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) l.h2[(4 * kq + i) * ld + unit] = fmaxf((acc0[i] + acc1[i]) + b, 0.f);
-      acc0 = f32x4{0.f, 0.f, 0.f, 0.f}; acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
+  jh_roll::layer2(a.W2, a.b2, l.h1, ld, H, tiles, l.h2, ld);
   __syncthreads();  // h2 complete; h1 is dead from here on: its space takes the heads' partial tiles
   // ---- heads: output o = 16 q + r is a row of pi / mu, of log_std, or the value row; K split over the waves
   const int nt = (a.n_out + 15) / 16;

@@ -31,6 +31,7 @@
 //   alias x1; nothing aliases x2.
 #include "jh_common.h"
 #include "jh_env_dyn.h"
+#include "jh_devroll_mlp.h"
 
 struct jh_devwin {
   jh_ctx* ctx = nullptr;
@@ -46,7 +47,6 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kRows = 16, kThreads = 256, kWaves = 4, kQLd = 20, kVCol = 16, kTailTiles = 2;
 constexpr int kPartFloats = kWaves * kTailTiles * 4 * 64;
-constexpr int kG1 = 8, kU2 = 8;
 constexpr size_t kLdsMax = 160u << 10;
 constexpr int kHeader = 24;  // seen, seed, counter in front of a saved block
 
@@ -93,83 +93,11 @@ __device__ inline Lds carve(char* base, int S, int H, int N2, int n) {
 __device__ void forward(const QArgs& a, const Lds& l) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, kq = lane >> 4;
   const int H = a.H, S = a.S, ld = H + 4, ld2 = a.N2 + 4, kt = H / 16, ot = a.N2 / 16;
-  // ---- layer 1: lane supplies A[row r][k] and B[k][unit r] for k = 4 ks + kq; holds C[row 4 kq + i][unit r]
-  const int nks = (S + 3) / 4;
-  for (int g0 = wave; g0 < kt; g0 += kWaves * kG1) {
-    f32x4 acc[kG1];
-    float bw[kG1], bn[kG1];
-#pragma unroll
-    for (int j = 0; j < kG1; ++j) {
-      acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const int ct = g0 + kWaves * j;
-      bw[j] = (ct < kt && kq < S) ? a.W1[(size_t)(ct * 16 + r) * S + kq] : 0.f;
-    }
-    for (int ks = 0; ks < nks; ++ks) {
-      const int k = 4 * ks + kq;
-#pragma unroll
-      for (int j = 0; j < kG1; ++j) {
-        const int ct = g0 + kWaves * j;
-        bn[j] = (ct < kt && k + 4 < S) ? a.W1[(size_t)(ct * 16 + r) * S + k + 4] : 0.f;
-      }
-      const float av = k < S ? (float)l.es[r * S + k] : 0.f;
-#pragma unroll
-      for (int j = 0; j < kG1; ++j) {
-        if (g0 + kWaves * j < kt) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bw[j], acc[j], 0, 0, 0);  // (uniform)
-        bw[j] = bn[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kG1; ++j) {
-      const int unit = (g0 + kWaves * j) * 16 + r;
-      if (unit < H) {
-        const float b = a.b1[unit];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) l.x1[(4 * kq + i) * ld + unit] = fmaxf(acc[j][i] + b, 0.f);
-      }
-    }
-  }
+  // ---- layers 1 and 2 (jh_devroll_mlp.h, shared with the other rollout kernels): layer 2 has `ot` output column tiles, H / 16, or 2H / 16
+  // for the stacked a | v layer
+  jh_roll::layer1(a.W1, a.b1, l.es, S, H, l.x1, ld);
   __syncthreads();
-  // ---- layer 2: `ot` output column tiles (H / 16, or 2H / 16 for the stacked a | v layer), each over the whole k range inside one wave
-  {
-    const int nblk = (kt + kU2 - 1) / kU2, my_tiles = wave < ot ? (ot - wave + kWaves - 1) / kWaves : 0;
-    const float* hp = l.x1 + r * ld + kq * 4;
-    float4 cur[kU2], nxt[kU2];
-    auto fetch = [&](int ct, int blk, float4* dst) {
-      const float* wp = a.W2 + (size_t)(ct * 16 + r) * H + kq * 4;
-#pragma unroll
-      for (int u = 0; u < kU2; ++u) {
-        const int c = blk * kU2 + u;
-        dst[u] = c < kt ? *reinterpret_cast<const float4*>(wp + c * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    };
-    if (my_tiles) fetch(wave, 0, cur);
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    for (int ti = 0; ti < my_tiles; ++ti) {
-      const int ct = wave + kWaves * ti;
-      for (int blk = 0; blk < nblk; ++blk) {
-        const bool last = blk + 1 == nblk;
-        if (!last || ti + 1 < my_tiles) fetch(last ? ct + kWaves : ct, last ? 0 : blk + 1, nxt);
-#pragma unroll
-        for (int u = 0; u < kU2; ++u) {
-          const int c = blk * kU2 + u;
-          if (c < kt) {  // (uniform)
-            const float4 av = *reinterpret_cast<const float4*>(hp + c * 16);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, cur[u].x, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, cur[u].y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, cur[u].z, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, cur[u].w, acc1, 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kU2; ++u) cur[u] = nxt[u];
-      }
-      const int unit = ct * 16 + r;
-      const float b = a.b2[unit];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) l.x2[(4 * kq + i) * ld2 + unit] = fmaxf((acc0[i] + acc1[i]) + b, 0.f);
-      acc0 = f32x4{0.f, 0.f, 0.f, 0.f}; acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
+  jh_roll::layer2(a.W2, a.b2, l.x1, ld, H, ot, l.x2, ld2);
   __syncthreads();  // x2 complete; x1 is dead from here on: its space takes the tail's partial tiles
   // ---- tail: column tile 0 = q / l2_a over x2[:, 0 .. H), column tile 1 (dueling) = l2_v over x2[:, H .. 2H); K split over the waves
   const int nt = 1 + a.dueling;

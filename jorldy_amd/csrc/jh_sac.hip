@@ -331,6 +331,13 @@ JH_EXPORT int jh_sacnet_actor_forward(jh_sacnet* s, const float* d_x, int32_t ro
   return rc ? rc : sac_mu_std((int64_t)rows * n->A, n->A, 2 * n->A, n->a_z, d_mu, d_std, jh_s(stream));
 }
 
+// Device-resident acting (sac.py:143-159; the kernel: jh_devroll_ac.hip)
+JH_EXPORT int jh_sacnet_devroll_run(jh_sacnet* s, jh_devenv* env, int32_t T, int32_t training, uint64_t seed, uint64_t counter, float* d_state, float* d_action,
+                                    float* d_reward, float* d_next_state, uint8_t* d_done, float* d_heads, jh_stream stream) {
+  return ac_devroll_run("jh_sacnet_devroll_run", s ? &s->ac : nullptr, 1, env, T, training, 0, 0.0, seed, counter, d_state, d_action, d_reward, d_next_state, d_done,
+                        d_heads, jh_s(stream));
+}
+
 // The critic update of learn() (sac.py:183-225).  d_x = [state; next_state] (2B rows), d_eps [B][A] standard normals: a', logp' come from the
 // ONLINE actor on next_state, which rides in the three grouped levels where TD3's target actor rides.
 // -> d_y [B], d_q [2][B], d_a_next [B][A], d_logp_next [B] (all optional), d_stats {loss_1, loss_2, max_Q, mark}; the critics have taken

@@ -148,6 +148,13 @@ JH_EXPORT int jh_acnet_actor_forward(jh_acnet* n, int32_t which, const float* d_
   return rc ? rc : td3_next_action((int64_t)rows * n->A, n->a_z, nullptr, 0.f, 0.f, d_action, jh_s(stream));
 }
 
+// Device-resident acting (td3.py:132-144 per env row; the kernel: jh_devroll_ac.hip)
+JH_EXPORT int jh_acnet_devroll_run(jh_acnet* n, jh_devenv* env, int32_t T, int32_t training, int32_t n_random, double action_noise_std, uint64_t seed, uint64_t counter,
+                                   float* d_state, float* d_action, float* d_reward, float* d_next_state, uint8_t* d_done, float* d_heads, jh_stream stream) {
+  return ac_devroll_run("jh_acnet_devroll_run", n, 0, env, T, training, n_random, action_noise_std, seed, counter, d_state, d_action, d_reward, d_next_state, d_done,
+                        d_heads, jh_s(stream));
+}
+
 // The critic update of learn() (td3.py:157-178, ddpg.py:128-140).  d_x = [state; next_state] (2B rows), d_noise [B][A] standard normals or
 // NULL (no target noise: DDPG).  -> d_y [B] (optional), d_q [n_critics][B] (optional: the online critics' outputs), d_stats
 // {loss_1, loss_2, max_Q, mark}; the critics' parameters have taken their Adam step on return.

@@ -70,7 +70,9 @@ DEVICE_ELIGIBLE = ("DeviceCollector runs the PPO agent on the MLP head only (cla
                    "(discrete_policy_value) or ops.DeviceControl (continuous_policy_value); host and Python envs stay on NativeCollector.  "
                    "It also runs the Ape-X agent's actors (class ApeX itself: not R2D2) on the MLP head: network dueling with hidden_size % 16 == 0 up to "
                    f"{ops.DEVROLL_Q_MAX_H['dueling']} or discrete_q_network up to {ops.DEVROLL_Q_MAX_H['q']}, n_step 1 to {ops.DEVROLL_Q_MAX_NSTEP}, no "
-                   "frame_dedup, no grad_sync, on ops.DeviceCartPole")
+                   "frame_dedup, no grad_sync, on ops.DeviceCartPole.  It also runs the TD3 and the continuous SAC agents' actors (class TD3 / SAC "
+                   f"itself: not DDPG, not the discrete SAC) with hidden_size % 16 == 0 up to {ops.DEVROLL_AC_MAX_H} on an ops.DeviceControl of the "
+                   "actor's state_size and action_size")
 
 
 class DeviceCollector:
@@ -85,15 +87,36 @@ class DeviceCollector:
     env step, the n-step window and the actor-side priorities for T timesteps, and `run(T)` appends the W * max(0, T - max(0, n_step -
     seen)) emitted rows with their priorities to the agent's PER buffer in time-major order and counts them into agent.num_transitions.
     `state()` / `set_state()` carry env and window, so a checkpointed collector resumes bit for bit.  The draws come from the collectors'
-    counter-based stream keyed (seed, counter + t, env row), not from numpy's."""
+    counter-based stream keyed (seed, counter + t, env row), not from numpy's.
+
+    With a TD3 or a continuous SAC agent on ops.DeviceControl (jh_acnet_devroll_run / jh_sacnet_devroll_run): one launch runs the online
+    actor's forward, the exploration of td3.py:132-144 / sac.py:143-159 per env row, and the env step for T timesteps, and `run(T)` appends
+    the W * T rows to the agent's replay buffer in time-major order; pass None to `agent.process`.  The draws come from the same
+    counter-based stream, keyed (seed, counter + t, env row, action dimension); the collector owns (seed, counter), and `state()` /
+    `set_state()` carry them with the env.  TD3's uniform phase is the first initial_random_step - num_random_step timesteps of a training
+    run.  `capture_heads = True` keeps the actor's raw last-layer outputs of the last run in `_out["heads"]` (time-major, as the rows)."""
 
     def __init__(self, env_vec, agent, num_workers=None, mode="sync", seed=0):
         from ..core.agent.dqn import ApeX
         from ..core.agent.ppo import PPO
+        from ..core.agent.sac import SAC
+        from ..core.agent.td3 import TD3
         import os
 
         got = f"; got agent {type(agent).__name__}, env {type(env_vec).__name__}"
-        self.window = None
+        self.window = self.stream = None
+        if mode == "sync" and type(agent) in (TD3, SAC):
+            net = agent._net
+            if (not isinstance(env_vec, ops.DeviceControl) or net.H % 16 or net.H > ops.DEVROLL_AC_MAX_H
+                    or (net.S, net.A) != (env_vec.state_size, env_vec.action_size)):
+                raise ValueError(DEVICE_ELIGIBLE + got + f" with an actor {net.S} -> {net.A} of hidden_size {net.H}")
+            assert num_workers in (None, env_vec.W)
+            self.lib = L.load()
+            self.env, self.agent = env_vec, agent
+            self.num_workers = env_vec.W
+            self.stream = (int(seed), 0)  # the exploration stream's (seed, counter)
+            self.capture_heads, self._out = False, None
+            return
         if mode == "sync" and type(agent) is ApeX:
             net = agent._net
             cap = ops.DEVROLL_Q_MAX_H.get(net.kind, 0)
@@ -155,17 +178,54 @@ class DeviceCollector:
             agent.num_transitions += rows
         return None, 1.0
 
+    def _run_ac(self, step, training):
+        from ..core.agent.td3 import TD3
+
+        agent, mem, env = self.agent, self.agent.memory, self.env
+        S, A, net, rows = env.state_size, env.action_size, agent._net, env.W * int(step)
+        if rows > mem.buffer_size:
+            raise ValueError(f"one run of {step} timesteps of {env.W} actors emits {rows} rows, more than the buffer's {mem.buffer_size} slots")
+        if self._out is None or self._out["done"].shape[0] < rows:
+            z = lambda shape, dt: torch.empty((rows,) + shape, dtype=dt, device=env.device)
+            self._out = {"state": z((S,), torch.float32), "action": z((A,), torch.float32), "reward": z((1,), torch.float32),
+                         "next_state": z((S,), torch.float32), "done": z((1,), torch.uint8), "heads": None}
+        o, td3 = self._out, type(agent) is TD3
+        if self.capture_heads and (o["heads"] is None or o["heads"].shape[0] < rows):
+            o["heads"] = torch.empty(rows, A if td3 else 2 * A, dtype=torch.float32, device=env.device)
+        seed, ctr = self.stream
+        outs = [L.ptr(o[k]) for k in ("state", "action", "reward", "next_state", "done")] + [L.ptr(o["heads"]) if self.capture_heads else None, L.stream_ptr()]
+        if td3:
+            n_random = min(int(step), max(0, agent.initial_random_step - agent.num_random_step)) if training else 0
+            L.check(self.lib.jh_acnet_devroll_run(net.h, env.h, int(step), int(bool(training)), n_random, float(agent.action_noise_std), seed, ctr, *outs))
+            agent.num_random_step += n_random
+        else:
+            L.check(self.lib.jh_sacnet_devroll_run(net.h, env.h, int(step), int(bool(training)), seed, ctr, *outs))
+        self.stream = (seed, ctr + int(step))
+        cols = {k: v[:rows] for k, v in o.items() if k != "heads"}
+        # the buffer's own device append: ring position and counters exist once
+        example = {k: np.zeros((1,) + tuple(v.shape[1:]), np.uint8 if v.dtype == torch.uint8 else np.float32) for k, v in cols.items()}
+        mem.store_device(cols, example)
+        return None, 1.0
+
     def state(self):
-        """-> {"env": the env's state(), "window": the carried window} (Ape-X collectors: what a checkpoint needs to resume bit for bit)."""
+        """-> what a checkpoint needs to resume bit for bit: {"env": the env's state(), "window": the carried window} (Ape-X collectors) or
+        {"env": ..., "stream": (seed, counter)} (TD3 / SAC collectors)."""
+        if self.stream is not None:
+            return {"env": self.env.state(), "stream": self.stream}
         return {"env": self.env.state(), "window": self.window.state()}
 
     def set_state(self, st):
         self.env.set_state(**st["env"])
-        self.window.set_state(st["window"])
+        if self.stream is not None:
+            self.stream = tuple(int(v) for v in st["stream"])
+        else:
+            self.window.set_state(st["window"])
 
     def run(self, step=1, training=True):
         if self.window is not None:
             return self._run_apex(step, training)
+        if self.stream is not None:
+            return self._run_ac(step, training)
         n_rows = self.env.W * step
         mem, agent = self.agent.memory, self.agent
         S, cont = self.env.state_size, self.env.action_type == "continuous"

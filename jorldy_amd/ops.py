@@ -1654,6 +1654,9 @@ class _DeviceWindow:
         L.check(self.lib.jh_devwin_set_state(self.h, L.ptr(block), L.stream_ptr()))
 
 
+DEVROLL_AC_MAX_H = 1120  # include/jorldy_hip.h: JH_DEVROLL_AC_MAX_H
+
+
 class DeviceControl(_DeviceEnv):
     """ControlVec(W, state_size, action_size, seed) on the device (S <= 64, A <= 16, continuous)."""
     action_type = "continuous"

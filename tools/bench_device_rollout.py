@@ -11,6 +11,10 @@ Every figure is a host clock around `iters` iterations that end in a device sync
 captures learn()'s graph).  Prints one JSON line.
 
     python tools/bench_device_rollout.py [--iters 10] [--warmup 4]
+
+--agent td3 | sac: the device-resident actors of the continuous off-policy agents (csrc/jh_devroll_ac.hip) at config.td3.mujoco / config.sac.mujoco
+shapes (S 11, A 3, H 512; batch 128 / 256) on the synthetic control env at W = 32, 256 and 1024: rollout of T = 4 alone, and rollout of T = 4 + one
+process(), on DeviceCollector and -- in the same process -- on the agent's own act() loop over ops.ControlVec of the same W (VecCollector).
 """
 import argparse
 import json
@@ -70,12 +74,50 @@ def leg(kind, device_side, W, T, iters, warmup):
     return out
 
 
+def leg_ac(name, device_side, W, T, iters, warmup):
+    from jorldy_amd import ops
+    from jorldy_amd.core.agent import Agent
+    from jorldy_amd.manager import DeviceCollector, VecCollector
+
+    S, A = 11, 3
+    torch.manual_seed(0)
+    np.random.seed(0)
+    agent = Agent(name, state_size=S, action_size=A, hidden_size=512, batch_size=128 if name == "td3" else 256, buffer_size=50000, start_train_step=0,
+                  run_step=1_000_000_000, device="cuda")
+    col = DeviceCollector(ops.DeviceControl(W, S, A, 1, "cuda"), agent) if device_side else VecCollector(ops.ControlVec(W, S, A, seed=1), agent)
+    step = 0
+
+    def both():
+        nonlocal step
+        step += T
+        return agent.process(col.run(T)[0], step)
+
+    out = {"collector": type(col).__name__, "agent": name, "W": W, "T": T, "rows_per_iteration": W * T}
+    for key, fn in (("rollout", lambda: col.run(T)), ("rollout_and_learn", both)):
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / iters
+        out[key + "_ms"] = round(dt * 1e3, 4)
+        out[key + "_transitions_per_s"] = round(W * T / dt, 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--agent", choices=("ppo", "td3", "sac"), default="ppo")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X: nothing here is measured without one"
+    if args.agent != "ppo":
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "iters": args.iters, "warmup": args.warmup,
+                          "legs": [leg_ac(args.agent, d, W, 4, args.iters, args.warmup) for W in (32, 256, 1024) for d in (False, True)]}))
+        return
     plan = [("cartpole", False, 8, 128), ("cartpole", True, 8, 128), ("cartpole", True, 256, 128), ("cartpole", True, 1024, 32), ("cartpole", True, 4096, 8),
             ("control", False, 32, 2048), ("control", True, 32, 2048), ("control", True, 1024, 64)]
     print(json.dumps({"device": torch.cuda.get_device_name(0), "iters": args.iters, "warmup": args.warmup,
