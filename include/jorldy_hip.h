@@ -1207,6 +1207,32 @@ int jh_acnet_devroll_run(jh_acnet* net, jh_devenv* env, int32_t T, int32_t train
 int jh_sacnet_devroll_run(jh_sacnet* net, jh_devenv* env, int32_t T, int32_t training, uint64_t seed, uint64_t counter, float* d_state,
                           float* d_action, float* d_reward, float* d_next_state, uint8_t* d_done, float* d_heads, jh_stream stream);
 
+/* ------------------------------------------------------------------ device-resident discrete SAC / DQN actors (csrc/jh_devroll_disc.hip)
+ * One launch runs T timesteps of all W rows of a JH_DEVENV_CARTPOLE env with a jh_rbnet of kind q on the mlp head (head.l -> l -> A
+ * outputs; d_params: the bucket to act with), read in place: forward (fp32 MFMA), the decision, env step with auto-reset, the replay row.
+ * key = seed * 0x100000001B3 + (counter + t) * 0x9E3779B97F4A7C15 + env row; seed and counter are the caller's (counter + T for the next run).
+ *   JH_DEVROLL_DISC_PI   the discrete SAC's actor (sac.py:151-159): training: Categorical(softmax(logits)) by inverse CDF in double on the
+ *                        collectors' uniform at `key` (the first index whose cumulative probability exceeds u * total); else the first index
+ *                        of the largest float32 logit
+ *   JH_DEVROLL_DISC_Q    DQN / Double (dqn.py:100-113), decided PER ENV ROW (the reference draws once for the whole batch): u1, u2 = the
+ *                        uniforms at keys 2 key + 1, 2 key + 2; u1 < epsilon: floor(u2 * A); else the first index of the largest float32 q.
+ *                        `epsilon`: one value for all rows, the caller's epsilon or epsilon_eval; `training` is not read
+ * Rows are written time-major (row = t * W + env row) into the caller's device columns of W * T rows: state f32 [S], action i64 [1],
+ * reward f32 [1], next_state f32 [S] (the terminal observation where done; the next row's state is the reset observation), done u8 [1];
+ * the caller appends them (jh_store_push_device).  d_heads != NULL: the raw last-layer outputs, f32 [W * T][A], time-major.  Env row w's
+ * output is a function of (weights, env state, seed, counter, w) only.  hidden_size % 16 == 0 up to JH_DEVROLL_DISC_MAX_H (both activation
+ * tiles of a 16-row workgroup live in the 160 KB of LDS), 2 <= A <= 64.
+ * flags = JH_DEVROLL_DISC_PROBE: the env is read, not stepped or written, and A need not be the env's -- only d_action and d_heads (both
+ * required) are written, every timestep from the same states; for checking the tail and the draw at action counts no device env has.
+ * JH_ERR_ARG ("bad argument"), nothing written: T < 1, a missing column, env kind not cartpole, a network of another shape than S -> H ->
+ * H -> A with the env's S (and, unless probing, its A), hidden_size off the rule.                                                     */
+#define JH_DEVROLL_DISC_MAX_H 1232
+enum { JH_DEVROLL_DISC_PI = 0, JH_DEVROLL_DISC_Q = 1 };
+enum { JH_DEVROLL_DISC_PROBE = 1 };
+int jh_devroll_disc_run(jh_rbnet* net, const float* d_params, jh_devenv* env, int32_t T, int32_t mode, int32_t training, double epsilon,
+                        uint64_t seed, uint64_t counter, float* d_state, int64_t* d_action, float* d_reward, float* d_next_state, uint8_t* d_done,
+                        float* d_heads, int32_t flags, jh_stream stream);
+
 /* N(0,1) draws on the device for NoisyNet layers (core/network/utils.py:58-60 draws torch.randn per forward):
  * counter-based (element i of call c = Box-Muller on splitmix64(seed, c, i)); d_state uint64[4] = {seed, call counter,
  * 0, 0} in DEVICE memory, advanced by the kernel itself, so a replayed hipGraph draws fresh noise every time.        */

@@ -335,6 +335,7 @@ _PROTOS = {
     "jh_devroll_q_run": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _f64] + [_vp] * 6 + [_i64, _vp]),
     "jh_acnet_devroll_run": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f64, C.c_uint64, C.c_uint64] + [_vp] * 7),
     "jh_sacnet_devroll_run": (C.c_int, [_vp, _vp, _i32, _i32, C.c_uint64, C.c_uint64] + [_vp] * 7),
+    "jh_devroll_disc_run": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f64, C.c_uint64, C.c_uint64] + [_vp] * 6 + [_i32, _vp]),
     "jh_comm_unique_id": (C.c_int, [_vp]),
     "jh_comm_create": (C.c_int, [_vp, _i32, _i32, _vp, _pp]),
     "jh_comm_destroy": (None, [_vp]),

@@ -18,7 +18,10 @@ class DQN(NativeValueNetMixin, BaseAgent):
 
     The network, its backward and the optimizer step run on libjorldy_hip (ops.RainbowNet, jh_rbnet_*): discrete_q_network /
     dueling with an mlp / cnn head, plain Adam or RMSprop.  One backend: any other configuration raises
-    (native_net.NATIVE_ELIGIBLE) instead of switching to library kernels.  learn() is replayed as one hipGraph."""
+    (native_net.NATIVE_ELIGIBLE) instead of switching to library kernels.  learn() is replayed as one hipGraph.
+
+    Class DQN / Double itself on discrete_q_network with the mlp head also acts on the device: manager.DeviceCollector on ops.DeviceCartPole
+    (csrc/jh_devroll_disc.hip) appends its rows to `memory` and process(None, step) learns from them."""
 
     action_type = "discrete"
     _td = dict(double=False, per=False, n_step=0)
@@ -179,6 +182,8 @@ class DQN(NativeValueNetMixin, BaseAgent):
         return self._net.sync_target()
 
     def _store(self, transitions):
+        if transitions is None:  # manager.DeviceCollector has appended this step's rows on the device
+            return
         if isinstance(transitions, dict):
             self.memory.store_soa(transitions)
         else:

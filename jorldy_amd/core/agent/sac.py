@@ -215,6 +215,8 @@ class SACDiscrete(SAC):
       process()     sac.py:281-310: the lr decay reaches the three networks' optimizers, never alpha's; every target_update_period steps the
                     targets are overwritten by their online critics.
       act()         torch.multinomial on the device in training, argmax in evaluation, on the softmax of the native actor's logits.
+                    manager.DeviceCollector on ops.DeviceCartPole runs the same rule inside one kernel for T timesteps of W envs
+                    (csrc/jh_devroll_disc.hip), on the collectors' counter-based stream instead of torch's.
 
     Departures on purpose: log pi is a log-softmax, clamped as Categorical clamps its probabilities (the same entropy wherever float32 pi is a
     normal number, finite beyond); load() as the continuous class (critic 2 from "critic2", targets equal their online critics, the alpha in

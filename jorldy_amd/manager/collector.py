@@ -13,7 +13,8 @@ NativeCollector  the whole T-step loop in one C call (jh_collector_run): acting 
                  observations from device-mapped pinned memory and write the actions back the same
                  way; transitions go directly into the rollout store's pinned staging slab.
 DeviceCollector  the whole T-step loop in one KERNEL (jh_devroll_run) for the built-in envs with their state on the
-                 device (ops.DeviceCartPole / ops.DeviceControl): nothing crosses PCIe between the timesteps.
+                 device (ops.DeviceCartPole / ops.DeviceControl): nothing crosses PCIe between the timesteps.  Also the actors of
+                 Ape-X, TD3 / SAC, the discrete SAC and DQN / Double (jh_devroll_q_run, jh_*_devroll_run, jh_devroll_disc_run).
 """
 import ctypes as C
 
@@ -72,7 +73,10 @@ DEVICE_ELIGIBLE = ("DeviceCollector runs the PPO agent on the MLP head only (cla
                    f"{ops.DEVROLL_Q_MAX_H['dueling']} or discrete_q_network up to {ops.DEVROLL_Q_MAX_H['q']}, n_step 1 to {ops.DEVROLL_Q_MAX_NSTEP}, no "
                    "frame_dedup, no grad_sync, on ops.DeviceCartPole.  It also runs the TD3 and the continuous SAC agents' actors (class TD3 / SAC "
                    f"itself: not DDPG, not the discrete SAC) with hidden_size % 16 == 0 up to {ops.DEVROLL_AC_MAX_H} on an ops.DeviceControl of the "
-                   "actor's state_size and action_size")
+                   "actor's state_size and action_size.  It also runs the discrete SAC's actor and the DQN / Double agents' actors (class SACDiscrete / "
+                   "DQN / Double itself: not Dueling, Multistep, PER or the rest of the family) on the MLP head: network discrete_q_network with "
+                   f"hidden_size % 16 == 0 up to {ops.DEVROLL_DISC_MAX_H}, no frame_dedup, no grad_sync, on an ops.DeviceCartPole of the network's "
+                   "state_size and action_size")
 
 
 class DeviceCollector:
@@ -94,17 +98,39 @@ class DeviceCollector:
     the W * T rows to the agent's replay buffer in time-major order; pass None to `agent.process`.  The draws come from the same
     counter-based stream, keyed (seed, counter + t, env row, action dimension); the collector owns (seed, counter), and `state()` /
     `set_state()` carry them with the env.  TD3's uniform phase is the first initial_random_step - num_random_step timesteps of a training
-    run.  `capture_heads = True` keeps the actor's raw last-layer outputs of the last run in `_out["heads"]` (time-major, as the rows)."""
+    run.  `capture_heads = True` keeps the actor's raw last-layer outputs of the last run in `_out["heads"]` (time-major, as the rows).
+
+    With the discrete SAC or a DQN / Double agent on ops.DeviceCartPole (jh_devroll_disc_run): one launch runs the actor's / the Q network's
+    forward, the decision per env row and the env step for T timesteps, and `run(T)` appends the W * T rows to the agent's replay buffer in
+    time-major order; pass None to `agent.process`, whose own bookkeeping (start_train_step, epsilon decay, target updates) runs on the
+    `step` it is given.  The discrete SAC draws from Categorical(softmax(logits)) on one uniform of the collector's stream keyed (seed,
+    counter + t, env row), or takes the argmax when not training (sac.py:151-159).  DQN / Double: epsilon-greedy (dqn.py:100-113) with ONE
+    epsilon for all rows, agent.epsilon (epsilon_eval when not training) read at run() time -- but decided PER ENV ROW on two uniforms of
+    the stream: the reference draws one np.random.random() for the whole batch, so all of its rows explore together or none does.  A
+    departure on purpose, as for Ape-X's device actors.  `state()` / `set_state()` and `capture_heads` as for TD3 / SAC."""
 
     def __init__(self, env_vec, agent, num_workers=None, mode="sync", seed=0):
-        from ..core.agent.dqn import ApeX
+        from ..core.agent.dqn import DQN, ApeX, Double
         from ..core.agent.ppo import PPO
-        from ..core.agent.sac import SAC
+        from ..core.agent.sac import SAC, SACDiscrete
         from ..core.agent.td3 import TD3
         import os
 
         got = f"; got agent {type(agent).__name__}, env {type(env_vec).__name__}"
-        self.window = self.stream = None
+        self.window = self.stream = self.disc = None
+        if mode == "sync" and type(agent) in (SACDiscrete, DQN, Double) and isinstance(env_vec, ops.DeviceCartPole):
+            net = agent._net
+            if (net.kind != ("pi" if type(agent) is SACDiscrete else "q") or net.cnn or net.H % 16 or net.H > ops.DEVROLL_DISC_MAX_H
+                    or getattr(agent, "_frame_dedup", False) or agent.grad_sync is not None or (net.Cin, net.A) != (env_vec.state_size, env_vec.action_size)):
+                raise ValueError(DEVICE_ELIGIBLE + got + f" with network kind {net.kind}, head {'cnn' if net.cnn else 'mlp'}, hidden_size {net.H}")
+            assert num_workers in (None, env_vec.W)
+            self.lib = L.load()
+            self.env, self.agent = env_vec, agent
+            self.num_workers = env_vec.W
+            self.disc = 0 if type(agent) is SACDiscrete else 1  # JH_DEVROLL_DISC_PI | JH_DEVROLL_DISC_Q
+            self.stream = (int(seed), 0)  # the exploration stream's (seed, counter)
+            self.capture_heads, self._out = False, None
+            return
         if mode == "sync" and type(agent) in (TD3, SAC):
             net = agent._net
             if (not isinstance(env_vec, ops.DeviceControl) or net.H % 16 or net.H > ops.DEVROLL_AC_MAX_H
@@ -207,9 +233,33 @@ class DeviceCollector:
         mem.store_device(cols, example)
         return None, 1.0
 
+    def _run_disc(self, step, training):
+        agent, mem, env = self.agent, self.agent.memory, self.env
+        S, A, net, rows = env.state_size, env.action_size, agent._net, env.W * int(step)
+        if rows > mem.buffer_size:
+            raise ValueError(f"one run of {step} timesteps of {env.W} actors emits {rows} rows, more than the buffer's {mem.buffer_size} slots")
+        if self._out is None or self._out["done"].shape[0] < rows:
+            z = lambda shape, dt: torch.empty((rows,) + shape, dtype=dt, device=env.device)
+            self._out = {"state": z((S,), torch.float32), "action": z((1,), torch.int64), "reward": z((1,), torch.float32),
+                         "next_state": z((S,), torch.float32), "done": z((1,), torch.uint8), "heads": None}
+        o = self._out
+        if self.capture_heads and (o["heads"] is None or o["heads"].shape[0] < rows):
+            o["heads"] = torch.empty(rows, A, dtype=torch.float32, device=env.device)
+        seed, ctr = self.stream
+        eps = 0.0 if self.disc == 0 else float(agent.epsilon if training else agent.epsilon_eval)
+        L.check(self.lib.jh_devroll_disc_run(net.h, L.ptr(net.params), env.h, int(step), self.disc, int(bool(training)), eps, seed, ctr,
+                                             *[L.ptr(o[k]) for k in ("state", "action", "reward", "next_state", "done")],
+                                             L.ptr(o["heads"]) if self.capture_heads else None, 0, L.stream_ptr()))
+        self.stream = (seed, ctr + int(step))
+        cols = {k: v[:rows] for k, v in o.items() if k != "heads"}
+        # the buffer's own device append: ring position and counters exist once
+        example = {k: np.zeros((1,) + tuple(v.shape[1:]), {torch.float32: np.float32, torch.int64: np.int64, torch.uint8: np.uint8}[v.dtype]) for k, v in cols.items()}
+        mem.store_device(cols, example)
+        return None, 1.0
+
     def state(self):
         """-> what a checkpoint needs to resume bit for bit: {"env": the env's state(), "window": the carried window} (Ape-X collectors) or
-        {"env": ..., "stream": (seed, counter)} (TD3 / SAC collectors)."""
+        {"env": ..., "stream": (seed, counter)} (TD3 / SAC, discrete SAC and DQN / Double collectors)."""
         if self.stream is not None:
             return {"env": self.env.state(), "stream": self.stream}
         return {"env": self.env.state(), "window": self.window.state()}
@@ -224,6 +274,8 @@ class DeviceCollector:
     def run(self, step=1, training=True):
         if self.window is not None:
             return self._run_apex(step, training)
+        if self.disc is not None:
+            return self._run_disc(step, training)
         if self.stream is not None:
             return self._run_ac(step, training)
         n_rows = self.env.W * step

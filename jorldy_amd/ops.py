@@ -1655,6 +1655,7 @@ class _DeviceWindow:
 
 
 DEVROLL_AC_MAX_H = 1120  # include/jorldy_hip.h: JH_DEVROLL_AC_MAX_H
+DEVROLL_DISC_MAX_H = 1232  # include/jorldy_hip.h: JH_DEVROLL_DISC_MAX_H
 
 
 class DeviceControl(_DeviceEnv):

@@ -15,6 +15,10 @@ captures learn()'s graph).  Prints one JSON line.
 --agent td3 | sac: the device-resident actors of the continuous off-policy agents (csrc/jh_devroll_ac.hip) at config.td3.mujoco / config.sac.mujoco
 shapes (S 11, A 3, H 512; batch 128 / 256) on the synthetic control env at W = 32, 256 and 1024: rollout of T = 4 alone, and rollout of T = 4 + one
 process(), on DeviceCollector and -- in the same process -- on the agent's own act() loop over ops.ControlVec of the same W (VecCollector).
+
+--agent sac_discrete | dqn: the device-resident actors of the discrete SAC and of DQN (csrc/jh_devroll_disc.hip) at config.sac.cartpole_discrete /
+config.dqn.cartpole shapes (S 4, A 2, H 512; batch 64 / 32) on CartPole, the same legs: DeviceCollector on ops.DeviceCartPole next to the agent's own
+act() loop over ops.CartPoleVec.  DQN's epsilon starts at 0.1, not the config's 1.0: at 1.0 the host act() never runs its network.
 """
 import argparse
 import json
@@ -82,9 +86,17 @@ def leg_ac(name, device_side, W, T, iters, warmup):
     S, A = 11, 3
     torch.manual_seed(0)
     np.random.seed(0)
-    agent = Agent(name, state_size=S, action_size=A, hidden_size=512, batch_size=128 if name == "td3" else 256, buffer_size=50000, start_train_step=0,
-                  run_step=1_000_000_000, device="cuda")
-    col = DeviceCollector(ops.DeviceControl(W, S, A, 1, "cuda"), agent) if device_side else VecCollector(ops.ControlVec(W, S, A, seed=1), agent)
+    common = dict(hidden_size=512, buffer_size=50000, start_train_step=0, run_step=1_000_000_000, device="cuda")
+    if name in ("sac_discrete", "dqn"):  # config.sac.cartpole_discrete / config.dqn.cartpole on the CartPole envs
+        S, A = 4, 2
+        own = (dict(actor="discrete_policy", critic="discrete_q_network", use_dynamic_alpha=True, batch_size=64, target_update_period=500,
+                    optim_config={"actor": "adam", "critic": "adam", "alpha": "adam", "actor_lr": 1.5e-4, "critic_lr": 3e-4, "alpha_lr": 1e-5}) if name == "sac_discrete" else
+               dict(network="discrete_q_network", epsilon_init=0.1, epsilon_min=0.01, explore_ratio=0.2, batch_size=32, target_update_period=500, optim_config={"name": "adam", "lr": 1e-4}))
+        agent = Agent("sac" if name == "sac_discrete" else "dqn", state_size=S, action_size=A, **common, **own)
+        col = DeviceCollector(ops.DeviceCartPole(W, 1, "cuda"), agent) if device_side else VecCollector(ops.CartPoleVec(W, seed=1), agent)
+    else:
+        agent = Agent(name, state_size=S, action_size=A, batch_size=128 if name == "td3" else 256, **common)
+        col = DeviceCollector(ops.DeviceControl(W, S, A, 1, "cuda"), agent) if device_side else VecCollector(ops.ControlVec(W, S, A, seed=1), agent)
     step = 0
 
     def both():
@@ -111,7 +123,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--agent", choices=("ppo", "td3", "sac"), default="ppo")
+    ap.add_argument("--agent", choices=("ppo", "td3", "sac", "sac_discrete", "dqn"), default="ppo")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X: nothing here is measured without one"
     if args.agent != "ppo":
